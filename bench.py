@@ -1,7 +1,13 @@
 """Benchmark of the FuMI meta-training step on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times EXACTLY K steps in one region and prints the headline line; ``--dump-outputs DIR`` then
+writes what the last timed step computed (loss, accuracy, query predictions, every gradient and updated parameter) as float32
+``DIR/<name>.npy``.  ``--full`` adds everything else below: the headline as the median of ``--repeats`` regions, the roofline
+kernels timed with HIP events, the host cost per step, the all-reduce timing (N > 1), the CPU baseline and the other
+configurations (``extra``, ``as_worded``, ``configs4``).
 
 A "step" = one meta-batch through ``FUMI.evaluate(task='train')``: GloVe embedding bag -> class text select ->
 hypernetwork -> T inner SGD steps on the support set -> query loss -> second-order meta-gradients ->
@@ -11,7 +17,7 @@ Workload (configs[1]): 5-way 5-shot, 32 query/class, D=2048 ResNet-152-style emb
 GloVe-300 token text (L=128, V=20000, mean pooling), text_hid 256, 1 inner step, 32 episodes per GPU (weak scaling:
 the global meta-batch is 32*N episodes sharded as contiguous blocks, one RCCL all-reduce of the flat gradient).
 
-Prints ONE JSON line (rank 0).  ``roofline`` is for the dominant kernel (xpanel_bwd: gW0 = sum_b Abar0_b^T [Xs_b;Xq_b], split-bf16 on the
+Prints ONE JSON line (rank 0).  With ``--full``, ``roofline`` is for the dominant kernel (xpanel_bwd: gW0 = sum_b Abar0_b^T [Xs_b;Xq_b], split-bf16 on the
 bf16 matrix pipe since round 2; with the forward X-panel pass the longest kernel of a step), timed with
 HIP events on the launch stream inside the timed region; ``cpu_baseline`` is the oracle restatement of the reference
 path timed on this box's host cores on a bounded sample of the same workload.
@@ -477,6 +483,31 @@ def configs4_leg(dev, steps, warmup, with_cpu, episodes):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, model, last):
+    """What the caller of the timed path holds after its last step, as float32 DIR/<name>.npy: evaluate's (loss, acc, query
+    predictions, targets) and, for every parameter the step trained, its gradient and its value after the Adam step."""
+    import numpy as np
+    loss, acc, preds, targets = last
+    arrays = {"loss": np.float32(float(loss)), "acc": np.float32(float(acc))}
+    if preds is not None:
+        arrays["preds"] = preds.detach().float().cpu().numpy()
+    arrays["targets"] = targets.float().cpu().numpy()
+    for n, p in model.named_parameters():
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad.detach().float().cpu().numpy()
+            arrays[f"param.{n}"] = p.detach().float().cpu().numpy()
+    total = sum(np.asarray(v).nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), np.asarray(v, dtype=np.float32))
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2 ** 20:.1f} MiB) to {d}", file=sys.stderr, flush=True)
+
+
 def visible_gpus():
     """GPUs of this node counted from the KFD topology in sysfs (a node with simd_count > 0 and a non-zero gfx target is a GPU),
     narrowed by HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES when set; None when sysfs cannot tell."""
@@ -527,15 +558,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: repeats, roofline / phase timing, host cost, all-reduce, "
+                         "CPU baseline and the other configurations (the --no-* options below narrow this)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-as-worded", action="store_true", help="skip the Conv4-as-worded leg (runs at N = 1 only)")
     ap.add_argument("--as-worded-steps", type=int, default=10)
     ap.add_argument("--no-configs4", action="store_true", help="skip the ResNet-12 / bf16 leg (BASELINE.json configs[4], N = 1 only)")
     ap.add_argument("--configs4-episodes", type=int, default=C4["B_per_gpu"], help="episodes of the ResNet-12 leg (one GPU's share: 64)")
     ap.add_argument("--configs4-steps", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (EXACTLY --steps steps between two barriers) is repeated this many times back to back; "
-                         "`value` / `ms_per_step` are the MEDIAN repeat's, min / max are reported beside it")
+                         "`value` / `ms_per_step` are the MEDIAN repeat's, min / max are reported beside it (default: 5 with "
+                         "--full, else 1)")
     ap.add_argument("--no-extra", action="store_true", help="skip the per-rank lines of BASELINE.json configs[0], [2], [3] (N = 1 only)")
     ap.add_argument("--no-phase-timing", action="store_true", help="do not record HIP events around the library's phases")
     ap.add_argument("--all-phases", action="store_true",
@@ -592,14 +629,15 @@ def main():
         model.evaluate(args, batches[i % NBATCH], opt, "train")
         if i % 64 == 63:
             torch.cuda.synchronize()
-    if not a.no_phase_timing:
+    phase_timing = a.full and not a.no_phase_timing
+    if phase_timing:
         # an event record is a ~6 us bubble on the stream: the roofline kernel is timed at every 8th step of the timed region
         prof_every = 1 if a.all_phases else max(1, min(PROF_EVERY, a.steps // 16))     # >= 16 samples from a short run too
         ws.set_profiling(True, None if a.all_phases else ["xpanel_bwd", "query"], every=prof_every)
     # the timed region: EXACTLY a.steps steps bracketed by barrier + synchronize on both sides -- repeated a.repeats times back to
     # back (a short region on a freshly started process sees clock and queue jitter of several per cent: the median repeat is the
     # measurement, min and max say how far the repeats spread)
-    reps = max(1, a.repeats)
+    reps = max(1, a.repeats if a.repeats is not None else (5 if a.full else 1))
     times = []
     last = None
     for r_ in range(reps):
@@ -609,7 +647,9 @@ def main():
             last = model.evaluate(args, batches[i % NBATCH], opt, "train")
         barrier()
         times.append(time.perf_counter() - t0)
-    prof = ws.profile() if not a.no_phase_timing else {}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, last)
+    prof = ws.profile() if phase_timing else {}
     ws.set_profiling(False)
     t = torch.tensor(times, device="cpu" if rehearsal else dev, dtype=torch.float64)
     allreduce = None
@@ -623,6 +663,7 @@ def main():
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         ranks_info = [{"rank": int(g_[0]), "device": int(g_[1]), "episodes": int(g_[2])} for g_ in gathered]
+    if world > 1 and a.full:
         # the step's one collective, timed on its own after the timed region: the flat [grads | loss | acc] buffer
         flat = model._flat_grads().flat
         buf = flat.clone() if not rehearsal else flat.cpu()
@@ -648,7 +689,7 @@ def main():
     # what the HOST costs per step (Python + ctypes + launches), measured where it cannot be confused with waiting for the device:
     # bursts of 4 steps enqueued into an EMPTY queue, median of 15
     host_ms = None
-    if world == 1:
+    if world == 1 and a.full:
         burst = []
         for r_ in range(15):
             torch.cuda.synchronize()
@@ -726,9 +767,9 @@ def main():
                                        "timed": f"HIP events around every {prof_every}th launch of the timed region"}
         if allreduce:
             out["allreduce"] = allreduce
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(table)
-        if not a.no_extra and world == 1:
+        if a.full and not a.no_extra and world == 1:
             # BASELINE.json's other embedding-input configurations at their per-rank shapes (one GPU's share), with the library's
             # phases timed in a second loop: configs[0]'s shapes on the GPU, configs[2] (FuMI, BERT text, 5 inner steps), configs[3] (AM3)
             print("[bench] extra legs: configs[0], [2], [3] at per-rank shapes", file=sys.stderr, flush=True)
@@ -739,7 +780,7 @@ def main():
             out["extra"] = {k: bench_configs.run_config(k, dev, steps=100, warmup=10, roofline=True)
                             for k in ("maml_5w1s_b4_t5", "fumi_bert_t5_b32", "am3_b32")}
             batches = None
-        if not a.no_as_worded and world == 1:
+        if a.full and not a.no_as_worded and world == 1:
             print("[bench] as-worded (Conv4, 84x84) leg", file=sys.stderr, flush=True)
             del batches
             torch.cuda.empty_cache()
@@ -749,7 +790,7 @@ def main():
             out["as_worded_t5"] = as_worded(dev, max(2, a.as_worded_steps // 3), 1, 0.0, False, T=5)
             out["as_worded_t5"]["workload"] = out["as_worded_t5"]["workload"].replace("1 inner step", "5 inner steps").replace(
                 "BASELINE.json configs[1] as worded", "BASELINE.json configs[2] as worded, GloVe instead of BERT text rows")
-        if not a.no_configs4 and world == 1:
+        if a.full and not a.no_configs4 and world == 1:
             print("[bench] configs[4] (ResNet-12, bf16, 20-way, 5 inner steps) leg", file=sys.stderr, flush=True)
             torch.cuda.empty_cache()
             out["configs4"] = configs4_leg(dev, a.configs4_steps, 1, not a.no_cpu_baseline, a.configs4_episodes)

@@ -111,7 +111,7 @@ def test_bench_rehearsal_runs_the_two_rank_code_path():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FUMI_BENCH_REHEARSAL="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
                         "--no-cpu-baseline", "--no-as-worded", "--no-configs4", "--no-extra"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -122,3 +122,31 @@ def test_bench_rehearsal_runs_the_two_rank_code_path():
     assert out["world_size"] == 2 and out["allreduce"]["torch_backend"] == "gloo"
     assert sorted(r_["rank"] for r_ in out["ranks"]) == [0, 1] and all(r_["episodes"] == 32 for r_ in out["ranks"])
     assert out["repeats"]["n"] >= 3 and out["repeats"]["ms_per_step_min"] <= out["ms_per_step"] <= out["repeats"]["ms_per_step_max"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): one timed region of exactly K steps, only
+    the headline in the line, and the last step's outputs as float32 .npy files that two runs with the same arguments reproduce."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 7 and out["repeats"]["n"] == 1 and out["repeats"]["of_steps"] == 7 and out["ms_per_step"] > 0
+        assert out["value"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert not {"roofline", "cpu_baseline", "extra", "as_worded", "configs4"} & set(out) and out["host_ms_per_step"] is None
+        got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert {"loss", "acc", "preds", "targets"} <= set(got) and any(k.startswith("grad.") for k in got)
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+        assert sum(v.nbytes for v in got.values()) <= 64 << 20
+        np.testing.assert_allclose(got["loss"], out["final_loss"], rtol=1e-6)
+        outs.append(got)
+    assert set(outs[0]) == set(outs[1])
+    for k, v in outs[0].items():
+        np.testing.assert_allclose(outs[1][k], v, rtol=1e-5, atol=1e-6 * max(float(np.abs(v).max()), 1e-6), err_msg=k)

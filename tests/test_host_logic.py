@@ -443,6 +443,35 @@ def test_bench_self_launches_one_process_per_gpu(monkeypatch, capsys):
     assert e.value.code == 2
 
 
+def test_bench_dump_outputs_writes_what_evaluate_returned(oracle_engine, tmp_path):
+    """`bench.py --dump-outputs DIR`: evaluate's (loss, acc, preds, targets) and every trained parameter's gradient and post-step
+    value, float32, one .npy each, equal to what the step left behind."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from fumi_amd.models.fumi import FUMI
+    name = "fumi_t1"
+    c = cg.FUMI_CASES[name]
+    seed = case_seed(name)
+    ep = cg.make_episodes(seed, c["B"], c["N"], c["K"], c["Q"], c["D"], c["Dt"], blocked=c["blocked"])
+    theta, phi = cg.make_fumi_params(seed, c["D"], c["hid"], c["Dt"], c["Ht"])
+    model = FUMI(n_way=c["N"], im_emb_dim=c["D"], im_hid_dim=c["hid"], text_encoder="BERT", text_emb_dim=c["Dt"],
+                 text_hid_dim=c["Ht"], dropout_rate=0.0, norm_hypernet=c["tanh"])
+    model.load_state_dict(cg.fumi_state_dict(theta, phi))
+    opt = torch.optim.Adam(model.parameters(), lr=3e-5, weight_decay=5e-4)
+    last = model.evaluate(_args(c["T"]), cg.to_batch(ep), opt, "train")
+    bench.dump_outputs(str(tmp_path / "out"), model, last)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"] == np.float32(float(last[0])) and got["acc"] == np.float32(float(last[1]))
+    np.testing.assert_array_equal(got["preds"], last[2].numpy())
+    np.testing.assert_array_equal(got["targets"], last[3].float().numpy())
+    trained = [(n, p) for n, p in model.named_parameters() if p.grad is not None]
+    assert trained and set(got) == {"loss", "acc", "preds", "targets"} | {f"{k}.{n}" for n, _ in trained for k in ("grad", "param")}
+    for n, p in trained:
+        np.testing.assert_array_equal(got[f"grad.{n}"], p.grad.numpy())
+        np.testing.assert_array_equal(got[f"param.{n}"], p.detach().numpy())
+
+
 def test_cli_maml_conv4_plumbing_on_cpu(oracle_engine, tmp_path, monkeypatch):
     """BASELINE.json configs[0] as worded: `main.py --model maml` 5-way 1-shot with the Conv4 encoder, meta-batch 4, on CPU
     (plumbing: flags -> image loader -> Conv4 module -> inner loop -> checkpoint -> test; tiny images keep it to seconds)."""

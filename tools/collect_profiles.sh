@@ -6,12 +6,12 @@ tag=${1:-run}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-echo "[collect] bench.py (default)"; python bench.py > "$out/bench.json" 2> "$out/bench.err"
+echo "[collect] bench.py --full"; python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 echo "[collect] rocprofv3 kernel stats of bench.py"
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_bench" -- python3 "$OLDPWD/bench.py" --no-cpu-baseline > "$out/bench_under_rocprof.json" 2> "$out/bench_under_rocprof.err")
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_bench" -- python3 "$OLDPWD/bench.py" --full --no-cpu-baseline > "$out/bench_under_rocprof.json" 2> "$out/bench_under_rocprof.err")
 echo "[collect] PMC passes (faithful leg)"
 for c in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out/pmc_$c" -- python3 "$OLDPWD/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-phase-timing --no-as-worded > /dev/null 2> "$out/pmc_$c.err")
+  (cd /tmp && rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out/pmc_$c" -- python3 "$OLDPWD/bench.py" --steps 20 --warmup 5 --full --no-cpu-baseline --no-phase-timing --no-as-worded > /dev/null 2> "$out/pmc_$c.err")
 done
 python tools/pmc_summary.py "$out/pmc_FETCH_SIZE" "$out/pmc_WRITE_SIZE" "$out/pmc_traffic.json" > "$out/pmc_summary.txt"
 echo "[collect] other configurations"; python tools/bench_configs.py --roofline > "$out/other_configs_roofline.jsonl" 2> /dev/null

@@ -7,11 +7,11 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 root=$PWD
 parts=${@:-bench stats pmc rn12 rn12pmc}
-HEAD="--steps 20 --warmup 5 --no-cpu-baseline --no-as-worded --no-configs4 --no-extra"
+HEAD="--steps 20 --warmup 5 --full --no-cpu-baseline --no-as-worded --no-configs4 --no-extra"
 for part in $parts; do
   case $part in
-    bench)   # the default line, not under a profiler
-      (timeout -k 10 900 python3 bench.py > "$out/bench.json" 2> "$out/bench.err") || exit 1; echo "[r04] bench done";;
+    bench)   # the --full line, not under a profiler
+      (timeout -k 10 900 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err") || exit 1; echo "[r04] bench done";;
     stats)   # per-kernel table of the headline step
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bench_stats" -- python3 "$root/bench.py" $HEAD > "$out/bench_under_rocprof.json" 2> "$out/bench_stats.err") || exit 1
       cp "$(find "$out/bench_stats" -name '*kernel_stats.csv' | head -1)" "$out/bench_kernel_stats.csv"; echo "[r04] stats done";;

@@ -1,6 +1,6 @@
 # dev: knobs of the backward X-panel kernel (name, ms/step, episodes/s, kernel us)
 run() { name=$1; shift
-  env "$@" python bench.py --steps 400 --warmup 40 --no-cpu-baseline --no-as-worded 2>/dev/null | python3 -c "
+  env "$@" python bench.py --steps 400 --warmup 40 --full --no-cpu-baseline --no-as-worded 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', d['ms_per_step'], d['value'], d['roofline']['avg_us'])"
 }
