@@ -75,25 +75,35 @@ size_t map_el(const RnNet& n, int M, int l) { return (size_t)n.B * M * n.g[l].Pp
 size_t out_el(const RnNet& n, int M, int l) { return (size_t)n.B * M * n.g[l + 1].Pp * n.C[l]; }
 rbf16* ws_h(fumi_ws* ws, size_t n) { return (rbf16*)ws_f(ws, (n + 1) / 2); }
 
-size_t pass_bytes(const RnNet& n, int M, bool bwd) {
+// the maps of a pass: `fwd` = what the forward writes and the backward reads (u, a, out, BN tables), `bwd` = what only the backward
+// writes (du, da, dout).  A first-order tape keeps the forward part; the backward part can be shared by the passes of a lane.
+size_t maps_bytes(const RnNet& n, int M, bool fwd, bool bwd) {
     size_t b = 0;
     for (int l = 0; l < n.nblk; ++l) {
-        b += (bwd ? 12 : 6) * ws_align(map_el(n, M, l) * 2) + (bwd ? 2 : 1) * ws_align(out_el(n, M, l) * 2);
-        b += 4 * ws_align((size_t)n.B * RCF_N * n.C[l] * 4);
+        b += ((fwd ? 6 : 0) + (bwd ? 6 : 0)) * ws_align(map_el(n, M, l) * 2) + ((fwd ? 1 : 0) + (bwd ? 1 : 0)) * ws_align(out_el(n, M, l) * 2);
+        if (fwd) b += 4 * ws_align((size_t)n.B * RCF_N * n.C[l] * 4);
     }
-    return b + 2 * ws_align((size_t)n.B * M * n.F * 4) + 3 * ws_align((size_t)n.B * M * n.N * 4);
+    return b;
 }
-void pass_carve(fumi_ws* ws, const RnNet& n, int M, bool bwd, RnPass& pb) {
+void maps_carve(fumi_ws* ws, const RnNet& n, int M, bool fwd, bool bwd, RnPass& pb) {
     pb.M = M;
     for (int l = 0; l < n.nblk; ++l) {
-        for (int k = 0; k < 4; ++k) pb.u[l][k] = ws_h(ws, map_el(n, M, l));
-        for (int k = 0; k < 2; ++k) pb.a[l][k] = ws_h(ws, map_el(n, M, l));
-        pb.out[l] = ws_h(ws, out_el(n, M, l));
+        if (fwd) {
+            for (int k = 0; k < 4; ++k) pb.u[l][k] = ws_h(ws, map_el(n, M, l));
+            for (int k = 0; k < 2; ++k) pb.a[l][k] = ws_h(ws, map_el(n, M, l));
+            pb.out[l] = ws_h(ws, out_el(n, M, l));
+        }
         for (int k = 0; k < 4; ++k) pb.du[l][k] = bwd ? ws_h(ws, map_el(n, M, l)) : nullptr;
         for (int k = 0; k < 2; ++k) pb.da[l][k] = bwd ? ws_h(ws, map_el(n, M, l)) : nullptr;
         pb.dout[l] = bwd ? ws_h(ws, out_el(n, M, l)) : nullptr;
-        for (int k = 0; k < 4; ++k) pb.coef[l][k] = ws_f(ws, (size_t)n.B * RCF_N * n.C[l]);
+        if (fwd) for (int k = 0; k < 4; ++k) pb.coef[l][k] = ws_f(ws, (size_t)n.B * RCF_N * n.C[l]);
     }
+}
+size_t pass_bytes(const RnNet& n, int M, bool bwd) {
+    return maps_bytes(n, M, true, bwd) + 2 * ws_align((size_t)n.B * M * n.F * 4) + 3 * ws_align((size_t)n.B * M * n.N * 4);
+}
+void pass_carve(fumi_ws* ws, const RnNet& n, int M, bool bwd, RnPass& pb) {
+    maps_carve(ws, n, M, true, bwd, pb);
     pb.f = ws_f(ws, (size_t)n.B * M * n.F); pb.df = ws_f(ws, (size_t)n.B * M * n.F);
     pb.z = ws_f(ws, (size_t)n.B * M * n.N); pb.p = ws_f(ws, (size_t)n.B * M * n.N); pb.dz = ws_f(ws, (size_t)n.B * M * n.N);
 }
@@ -454,15 +464,76 @@ static size_t chunk_bytes(RnNet& n, int Bc, const Rn12Problem& p, RnScratch& sc)
     return b + (1u << 16);
 }
 
-int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
-    // Two LANES: the meta-batch's chunks of episodes are independent until their meta-gradients are added, so odd chunks run on a
-    // second stream (ws->lane, own half of the workspace) beside the even ones on the caller's.  Each lane's kernels alternate between
-    // MFMA-bound (convolutions, weight gradients: 3/4 of the time) and HBM-bound (element-wise: 1/4) and leave partial last rounds
-    // of workgroups; two lanes out of phase fill both (measured with two processes of 4 episodes each against one of 8: 15.9 vs
-    // 14.1 episodes/s; in one process at 24 episodes 2 / 3 / 4 lanes: 14.46 / 14.81 / 14.24 -- two by default, FUMI_RN_LANES=n <= 4).
-    // FUMI_RN_LANES=1 or phase timing: one lane (then the weight gradients fork onto ws->side instead).
+// ---- machinery shared by the meta-steps and the first-order encoder pair ----------------------------------------------------------------
+// Two LANES: the meta-batch's chunks of episodes are independent until their gradients are added, so odd chunks run on a second
+// stream (ws->lane, own part of the workspace) beside the even ones on the caller's.  Each lane's kernels alternate between
+// MFMA-bound (convolutions, weight gradients: 3/4 of the time) and HBM-bound (element-wise: 1/4) and leave partial last rounds of
+// workgroups; two lanes out of phase fill both (measured with two processes of 4 episodes each against one of 8: 15.9 vs 14.1
+// episodes/s; in one process at 24 episodes 2 / 3 / 4 lanes: 14.46 / 14.81 / 14.24 -- two by default, FUMI_RN_LANES=n <= 4).
+// FUMI_RN_LANES=1 or phase timing: one lane (then the weight gradients fork onto ws->side instead).
+constexpr int RN_MAXLANES = 4;
+static int rn_lanes(fumi_ws* ws, int B) {
     static const int lanes_env = getenv("FUMI_RN_LANES") ? atoi(getenv("FUMI_RN_LANES")) : 2;
-    constexpr int MAXLANES = 4;
+    int lanes = (lanes_env >= 2 && !ws->profiling && !g_rn_probe && B >= 2 && ws->side) ? (lanes_env > RN_MAXLANES ? RN_MAXLANES : lanes_env) : 1;
+    return lanes > B ? B : lanes;
+}
+// workspace budget in bytes (fumi_hip_resnet12_set_budget, else FUMI_RN12_BUDGET_GB, else 200 GB)
+static size_t rn_budget() {
+    if (g_rn_budget) return g_rn_budget;
+    const char* e = getenv("FUMI_RN12_BUDGET_GB");
+    return (size_t)((e && atof(e) > 0 ? atof(e) : 200.0) * (double)(1ull << 30));
+}
+// the largest chunk <= Bc whose bytes (all lanes) fit the budget: total(Bc) is close to linear, start from the estimate, step down
+static int rn_fit_chunk(int Bc, size_t budget, const std::function<size_t(int)>& total) {
+    const size_t one = total(1);
+    const long est = (long)(budget / (one ? one : 1)) + 1;
+    if (Bc > est) Bc = (int)(est < 1 ? 1 : est);
+    while (Bc > 1 && total(Bc) > budget) --Bc;
+    return Bc;
+}
+// the lanes start behind everything already on the caller's stream ...
+static int rn_fork_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
+    if (lanes < 2) return FUMI_OK;
+    HIP_TRY(hipEventRecord(ws->ev[2], st));
+    for (int i = 1; i < lanes; ++i) HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
+    return FUMI_OK;
+}
+// ... and the caller's stream waits for them
+static int rn_join_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
+    for (int i = 1; i < lanes; ++i) {
+        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
+        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
+    }
+    return FUMI_OK;
+}
+// parameter slot of n.B episodes = theta (12 nblk tensors, torch layouts) broadcast to every episode
+static int slot_from_theta(hipStream_t st, const RnNet& n, const float* const* theta, float* params) {
+    for (int l = 0; l < n.nblk; ++l)
+        for (int k = 0; k < RN_NCONV; ++k) {
+            const RnLayer& y = n.L[l][k];
+            const float* const* th = theta + 12 * l + 3 * k;
+            TRY(launch_broadcast(st, n.B, (long)y.Cout * y.Cin_real * y.ntaps, th[0], params + y.offW, n.PSZ));
+            TRY(launch_broadcast(st, n.B, y.Cout, th[1], params + y.offG, n.PSZ));
+            TRY(launch_broadcast(st, n.B, y.Cout, th[2], params + y.offB, n.PSZ));
+        }
+    return FUMI_OK;
+}
+// one summed parameter-slab gradient -> the 12 nblk tensors of g_theta
+static int theta_grads_out(hipStream_t st, const RnNet& n, const float* gsum, float* const* g_theta) {
+    for (int l = 0; l < n.nblk; ++l)
+        for (int k = 0; k < RN_NCONV; ++k) {
+            const RnLayer& y = n.L[l][k];
+            float* const* g = g_theta + 12 * l + 3 * k;
+            HIP_TRY(hipMemcpyAsync(g[0], gsum + y.offW, (size_t)y.Cout * y.Cin_real * y.ntaps * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(g[1], gsum + y.offG, (size_t)y.Cout * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(g[2], gsum + y.offB, (size_t)y.Cout * 4, hipMemcpyDeviceToDevice, st));
+        }
+    return FUMI_OK;
+}
+
+int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
+    // chunks of episodes on lanes (rn_lanes)
+    constexpr int MAXLANES = RN_MAXLANES;
     RnCtx cx[MAXLANES];
     for (int i = 0; i < MAXLANES; ++i) { cx[i].ws = ws; cx[i].st = st; }
     RnCtx& c = cx[0];
@@ -473,23 +544,12 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
     const bool grad = p.need_grad != 0, second = grad && p.second_order && p.T > 0;
     if (second && p.T > RN_MAXTAPE) return FUMI_ENOTSUP;
     const int ntape = second ? p.T : 1, nslot = second ? p.T + 1 : 2;
-    int lanes = (lanes_env >= 2 && !ws->profiling && !g_rn_probe && p.B >= 2 && ws->side) ? (lanes_env > MAXLANES ? MAXLANES : lanes_env) : 1;
-    if (lanes > p.B) lanes = p.B;
+    int lanes = rn_lanes(ws, p.B);
     g_rn_tab.valid = false;
     // ---- chunk size: the largest number of episodes whose tapes (one per lane) fit the budget
-    size_t budget = g_rn_budget;
-    if (!budget) {
-        const char* e = getenv("FUMI_RN12_BUDGET_GB");
-        budget = (size_t)((e && atof(e) > 0 ? atof(e) : 200.0) * (double)(1ull << 30));
-    }
+    const size_t budget = rn_budget();
     int Bc = p.chunk > 0 ? (p.chunk < p.B ? p.chunk : p.B) : (p.B + lanes - 1) / lanes;
-    if (p.chunk <= 0) {
-        // the largest chunk whose lanes fit (chunk_bytes is close to linear in Bc: start from the estimate, then step down)
-        const size_t one = chunk_bytes(n, 1, p, c.sc);
-        const long est = (long)(budget / ((size_t)lanes * (one ? one : 1))) + 1;
-        if (Bc > est) Bc = (int)(est < 1 ? 1 : est);
-        while (Bc > 1 && lanes * chunk_bytes(n, Bc, p, c.sc) > budget) --Bc;
-    }
+    if (p.chunk <= 0) Bc = rn_fit_chunk(Bc, budget, [&](int b) { return (size_t)lanes * chunk_bytes(n, b, p, c.sc); });
     if (Bc >= p.B) lanes = 1;                                             // a single chunk
     const size_t region = ws_align(chunk_bytes(n, Bc, p, c.sc));
     if ((rc = ws_reserve(ws, lanes * region))) return rc;
@@ -498,13 +558,8 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
     // (one lane: its weight gradients fork onto ws->side; with two lanes a stream of weight gradients per lane added nothing --
     // 530.5 vs 524.2 ms per 8-episode step -- and they stay in line)
     if (lanes == 1) { c.side = rn_side_stream(ws); c.ev_fork = ws->ev[0]; c.ev_join = ws->ev[1]; }
-    if (lanes > 1) {
-        HIP_TRY(hipEventRecord(ws->ev[2], st));                           // the lanes start behind everything already on the caller's stream
-        for (int i = 1; i < lanes; ++i) {
-            cx[i].n = n; cx[i].st = ws->lanes[i - 1];
-            HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
-        }
-    }
+    TRY(rn_fork_lanes(ws, st, lanes));
+    for (int i = 1; i < lanes; ++i) { cx[i].n = n; cx[i].st = ws->lanes[i - 1]; }
     const size_t F1 = (size_t)n.N * (n.F + 1);
     float* gacc_lane[MAXLANES] = {nullptr, nullptr, nullptr, nullptr};
     fumi_ws* const ws_real = ws;
@@ -561,14 +616,7 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
         HIP_TRY(hipMemsetAsync(G, 0, (size_t)bc * n.PSZ * 4, st));          // (the slab's padding words stay 0 in every vector derived from G)
         HIP_TRY(hipMemsetAsync(P(0), 0, (size_t)bc * n.PSZ * 4, st));
         HIP_TRY(hipMemsetAsync(HV, 0, (size_t)bc * n.PSZ * 4, st));
-        for (int l = 0; l < n.nblk; ++l)
-            for (int k = 0; k < RN_NCONV; ++k) {
-                const RnLayer& y = n.L[l][k];
-                const float* const* th = p.theta + 12 * l + 3 * k;
-                TRY(launch_broadcast(st, bc, (long)y.Cout * y.Cin_real * y.ntaps, th[0], P(0) + y.offW, n.PSZ));
-                TRY(launch_broadcast(st, bc, y.Cout, th[1], P(0) + y.offG, n.PSZ));
-                TRY(launch_broadcast(st, bc, y.Cout, th[2], P(0) + y.offB, n.PSZ));
-            }
+        TRY(slot_from_theta(st, n, p.theta, P(0)));
         TRY(frags_of_slot(st, n, P(0), Fr(0)));
         HIP_TRY(hipMemcpyAsync(Hd(0), p.head + (size_t)b0 * F1, hsz * 4, hipMemcpyDeviceToDevice, st));
         // ---- inner loop on the support set
@@ -625,10 +673,7 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
             first[lane] = false;
         }
     }
-    for (int i = 1; i < lanes; ++i) {                                     // the caller's stream waits for the other lanes
-        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
-        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
-    }
+    TRY(rn_join_lanes(ws, st, lanes));                                    // the caller's stream waits for the other lanes
     float* gacc = gacc_lane[0];
     for (int i = 1; i < lanes; ++i) if (grad && gacc_lane[i]) TRY(launch_axpy(st, n.PSZ, gacc, 1.f, gacc_lane[i], gacc));
     if (p.stats) {
@@ -637,15 +682,7 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
         TRY(launch_reduce_multi(st, sg));
     }
     if (!grad) return FUMI_OK;
-    for (int l = 0; l < n.nblk; ++l)
-        for (int k = 0; k < RN_NCONV; ++k) {
-            const RnLayer& y = n.L[l][k];
-            float* const* g = p.g_theta + 12 * l + 3 * k;
-            HIP_TRY(hipMemcpyAsync(g[0], gacc + y.offW, (size_t)y.Cout * y.Cin_real * y.ntaps * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g[1], gacc + y.offG, (size_t)y.Cout * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g[2], gacc + y.offB, (size_t)y.Cout * 4, hipMemcpyDeviceToDevice, st));
-        }
-    return FUMI_OK;
+    return theta_grads_out(st, n, gacc, p.g_theta);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -685,6 +722,110 @@ int side_reserve(fumi_ws* ws, size_t floats, float** out) {
     return FUMI_OK;
 }
 size_t al64(size_t n) { return (n + 63) / 64 * 64; }
+}  // namespace
+
+// ---- first-order encoder pair (AM3's image encoder): encode with the tape kept, backward from the feature adjoints ---------------------
+// Every episode's support set and query set is one batch-statistics group.  Workspace layout, the same in both calls (a plan from the
+// shapes and the budget, kept in a token by encode so that encode_bwd carves the identical layout):
+//   global:       per-episode gradient slabs [2][B][PSZ] (support, query) and their sum [PSZ]
+//   lane i:       scratch, theta's parameter / fragment slab for Bc episodes (broadcast at encode; encode_bwd reads no theta), the
+//                 backward-only maps (du, da, dout) of a support and a query pass of one chunk; recompute form also: the prepared
+//                 images, forward maps and features of one chunk
+//   tape (taped form only): chunk k's prepared images and the forward maps (u, a, out, BN tables) of its support and query pass
+// TAPED form when the whole meta-batch's tape fits the budget (encode_bwd runs only the backward), else RECOMPUTE (encode keeps no maps;
+// encode_bwd runs each chunk's forward again, then its backward).  An episode's arithmetic does not depend on its chunk (the launch
+// geometry is priced per RN_BREF episodes), and the gradient is ONE sum over all 2 B per-episode slabs in a fixed order, so both
+// forms and every chunking give bit-identical features and gradients.
+namespace {
+struct RnEncPlan { int lanes, Bc, nchunks, taped; size_t glob, lane, tape, total; };
+struct RnEncToken { bool valid; fumi_ws* ws; char* base; int B, S, Qn, Cin, H, W, nblk; int ch[RN_MAXBLK]; RnEncPlan pl; };
+RnEncToken g_rn_enc = {};
+RnEncPlan g_rn_enc_last = {};                         // plan of the last encode (fumi_hip_resnet12_encode_plan)
+
+struct RnEncLane { RnScratch sc; float* params; rbf16* frags; RnPass bs, bq; rbf16* img_s; rbf16* img_q; RnPass fs, fq; float* f; };
+
+size_t enc_tape_bytes(const RnNet& n, int S, int Qn) {
+    return ws_align((size_t)n.B * S * n.g[0].Pp * 16 * 2) + ws_align((size_t)n.B * Qn * n.g[0].Pp * 16 * 2) +
+           maps_bytes(n, S, true, false) + maps_bytes(n, Qn, true, false);
+}
+size_t enc_lane_bytes(RnNet n, int Bc, int S, int Qn, bool recompute) {
+    n.B = Bc;
+    RnScratch sc;
+    size_t b = scratch_sizes(n, S, Qn, sc) + ws_align((size_t)Bc * n.PSZ * 4) + ws_align((size_t)Bc * n.FSZ * 2) +
+               maps_bytes(n, S, false, true) + maps_bytes(n, Qn, false, true);
+    if (recompute) b += enc_tape_bytes(n, S, Qn) + ws_align((size_t)Bc * (S > Qn ? S : Qn) * n.F * 4);
+    return b;
+}
+void enc_plan(fumi_ws* ws, const RnNet& n, int B, int S, int Qn, bool want_tape, RnEncPlan& pl) {
+    const size_t budget = rn_budget();
+    pl.lanes = rn_lanes(ws, B);
+    pl.glob = ws_align((size_t)2 * B * n.PSZ * 4) + ws_align((size_t)n.PSZ * 4);
+    const int Bmax = (B + pl.lanes - 1) / pl.lanes;
+    RnNet nb = n;
+    auto tape_of = [&](int b) { nb.B = b; return ws_align(enc_tape_bytes(nb, S, Qn)); };
+    auto taped_total = [&](int b) { return pl.glob + (size_t)pl.lanes * ws_align(enc_lane_bytes(n, b, S, Qn, false)) +
+                                           (size_t)((B + b - 1) / b) * tape_of(b); };
+    // taped: the largest chunk with which every chunk's tape fits (the backward maps shrink with the chunk, the tape does not)
+    int Bc = Bmax;
+    while (Bc > 1 && taped_total(Bc) > budget) --Bc;
+    pl.taped = want_tape && taped_total(Bc) <= budget;
+    if (!pl.taped) {
+        const size_t room = budget > pl.glob ? budget - pl.glob : 0;
+        Bc = rn_fit_chunk(Bmax, room, [&](int b) { return (size_t)pl.lanes * ws_align(enc_lane_bytes(n, b, S, Qn, true)); });
+    }
+    if (Bc >= B) pl.lanes = 1;                                            // a single chunk
+    pl.Bc = Bc; pl.nchunks = (B + Bc - 1) / Bc;
+    pl.lane = ws_align(enc_lane_bytes(n, Bc, S, Qn, !pl.taped));
+    pl.tape = pl.taped ? tape_of(Bc) : 0;
+    pl.total = pl.glob + (size_t)pl.lanes * pl.lane + (size_t)pl.nchunks * pl.tape + (1u << 16);
+}
+// lane i's buffers (c.n.B = Bc on return)
+int enc_carve_lane(fumi_ws* ws, RnCtx& c, const RnEncPlan& pl, int i, int S, int Qn, RnEncLane& L) {
+    fumi_ws view = *ws;
+    view.off = pl.glob + (size_t)i * pl.lane;
+    RnNet& n = c.n;
+    n.B = pl.Bc;
+    (void)scratch_sizes(n, S, Qn, c.sc);
+    c.sc.cpart = ws_f(&view, c.sc.cpart_n); c.sc.rpart = ws_f(&view, c.sc.rpart_n); c.sc.wpart = ws_f(&view, c.sc.wpart_n);
+    c.sc.rowl = ws_f(&view, c.sc.rowl_n); c.sc.c2 = ws_f(&view, c.sc.c2_n);
+    L.params = ws_f(&view, (size_t)n.B * n.PSZ); L.frags = ws_h(&view, (size_t)n.B * n.FSZ);
+    memset(&L.bs, 0, sizeof(RnPass)); memset(&L.bq, 0, sizeof(RnPass));
+    maps_carve(&view, n, S, false, true, L.bs); maps_carve(&view, n, Qn, false, true, L.bq);
+    L.img_s = L.img_q = nullptr; L.f = nullptr;
+    memset(&L.fs, 0, sizeof(RnPass)); memset(&L.fq, 0, sizeof(RnPass));
+    if (!pl.taped) {
+        L.img_s = ws_h(&view, (size_t)n.B * S * n.g[0].Pp * 16); L.img_q = ws_h(&view, (size_t)n.B * Qn * n.g[0].Pp * 16);
+        maps_carve(&view, n, S, true, false, L.fs); maps_carve(&view, n, Qn, true, false, L.fq);
+        L.f = ws_f(&view, (size_t)n.B * (S > Qn ? S : Qn) * n.F);
+    }
+    return view.off > pl.glob + (size_t)(i + 1) * pl.lane || view.off > ws->cap ? FUMI_ENOMEM : FUMI_OK;
+}
+// chunk k's forward maps: its tape slot (taped form) or its lane's buffers (recompute form)
+int enc_chunk_maps(fumi_ws* ws, const RnNet& n, const RnEncPlan& pl, int k, int S, int Qn, const RnEncLane& L, rbf16** img_s,
+                   rbf16** img_q, RnPass& ps, RnPass& pq) {
+    if (!pl.taped) { *img_s = L.img_s; *img_q = L.img_q; ps = L.fs; pq = L.fq; return FUMI_OK; }
+    fumi_ws view = *ws;
+    const size_t o0 = pl.glob + (size_t)pl.lanes * pl.lane + (size_t)k * pl.tape;
+    view.off = o0;
+    RnNet nb = n; nb.B = pl.Bc;                                           // (every tape slot is laid out for Bc episodes)
+    *img_s = ws_h(&view, (size_t)nb.B * S * n.g[0].Pp * 16); *img_q = ws_h(&view, (size_t)nb.B * Qn * n.g[0].Pp * 16);
+    memset(&ps, 0, sizeof(RnPass)); memset(&pq, 0, sizeof(RnPass));
+    maps_carve(&view, nb, S, true, false, ps); maps_carve(&view, nb, Qn, true, false, pq);
+    return view.off > o0 + pl.tape || view.off > ws->cap ? FUMI_ENOMEM : FUMI_OK;
+}
+void with_bwd_maps(RnPass& p, const RnPass& b) {
+    for (int l = 0; l < RN_MAXBLK; ++l) {
+        for (int k = 0; k < 4; ++k) p.du[l][k] = b.du[l][k];
+        for (int k = 0; k < 2; ++k) p.da[l][k] = b.da[l][k];
+        p.dout[l] = b.dout[l];
+    }
+}
+bool enc_shape_ok(const RnEncToken& t, fumi_ws* ws, int B, int S, int Qn, int Cin, int H, int W, int nblk, const int* channels) {
+    if (!t.valid || t.ws != ws || t.base != ws->base || t.B != B || t.S != S || t.Qn != Qn || t.Cin != Cin || t.H != H || t.W != W ||
+        t.nblk != nblk) return false;
+    for (int l = 0; l < nblk; ++l) if (t.ch[l] != channels[l]) return false;
+    return true;
+}
 }  // namespace
 
 extern "C" {
@@ -883,17 +1024,139 @@ int fumi_hip_resnet12_features(fumi_ws_t* ws, fumi_stream_t stream, int G, int M
     rbf16* img = ws_h(ws, (size_t)G * M * n.g[0].Pp * 16);
     float* params = ws_f(ws, (size_t)G * n.PSZ); rbf16* frags = ws_h(ws, (size_t)G * n.FSZ);
     TRY(launch_rn_img_prep(st, (long)G * M, Cin, n.g[0], x, img));
-    for (int l = 0; l < n.nblk; ++l)
-        for (int k = 0; k < RN_NCONV; ++k) {
-            const RnLayer& y = n.L[l][k];
-            const float* const* th = theta + 12 * l + 3 * k;
-            TRY(launch_broadcast(st, G, (long)y.Cout * y.Cin_real * y.ntaps, th[0], params + y.offW, n.PSZ));
-            TRY(launch_broadcast(st, G, y.Cout, th[1], params + y.offG, n.PSZ));
-            TRY(launch_broadcast(st, G, y.Cout, th[2], params + y.offB, n.PSZ));
-        }
+    TRY(slot_from_theta(st, n, theta, params));
     TRY(frags_of_slot(st, n, params, frags));
     TRY(forward_pass(c, M, img, params, frags, pb, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
     HIP_TRY(hipMemcpyAsync(feats, pb.f, (size_t)G * M * n.F * 4, hipMemcpyDeviceToDevice, st));
+    return FUMI_OK;
+}
+
+// ---- first-order encoder pair ---------------------------------------------------------------------------------------------------------
+int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
+        float* feats_s, float* feats_q, int keep_tape) {
+    if (!ws || !x_s || !x_q || !theta || !feats_s || !feats_q || !channels || B < 1 || S < 1 || Qn < 1) return FUMI_EINVAL;
+    if (nblk < 1 || nblk > RN_MAXBLK) return FUMI_EINVAL;
+    for (int i = 0; i < 12 * nblk; ++i) if (!theta[i]) return FUMI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
+    g_rn_enc.valid = false; g_rn_tab.valid = false;
+    RnCtx c0; c0.ws = ws; c0.st = st;
+    int rc = net_init(c0.n, B, nblk, Cin, 1, H, W, channels);
+    if (rc) return rc;
+    RnEncPlan pl;
+    enc_plan(ws, c0.n, B, S, Qn, keep_tape != 0, pl);
+    if ((rc = ws_reserve(ws, pl.total))) return rc;
+    for (int i = 1; i < pl.lanes; ++i) if (!ws_lane_stream(ws, i)) return FUMI_EHIP;
+    RnCtx cx[RN_MAXLANES]; RnEncLane L[RN_MAXLANES];
+    for (int i = 0; i < pl.lanes; ++i) {
+        cx[i] = c0;
+        cx[i].st = i ? ws->lanes[i - 1] : st;
+        if ((rc = enc_carve_lane(ws, cx[i], pl, i, S, Qn, L[i]))) return rc;
+    }
+    if (pl.lanes == 1) { cx[0].side = rn_side_stream(ws); cx[0].ev_fork = ws->ev[0]; cx[0].ev_join = ws->ev[1]; }
+    const size_t img = (size_t)Cin * H * W;
+    const int F = c0.n.F;
+    auto run = [&]() -> int {
+        TRY(rn_fork_lanes(ws, st, pl.lanes));
+        for (int i = 0; i < pl.lanes; ++i) {                               // theta's slab of each lane (n.B = Bc)
+            TRY(slot_from_theta(cx[i].st, cx[i].n, theta, L[i].params));
+            TRY(frags_of_slot(cx[i].st, cx[i].n, L[i].params, L[i].frags));
+        }
+        for (int k = 0; k < pl.nchunks; ++k) {
+            const int lane = k % pl.lanes, b0 = k * pl.Bc, bc = B - b0 < pl.Bc ? B - b0 : pl.Bc;
+            RnCtx& c = cx[lane];
+            c.n.B = bc;
+            rbf16 *img_s, *img_q; RnPass ps, pq;
+            TRY(enc_chunk_maps(ws, c.n, pl, k, S, Qn, L[lane], &img_s, &img_q, ps, pq));
+            TRY(launch_rn_img_prep(c.st, (long)bc * S, Cin, c.n.g[0], x_s + (size_t)b0 * S * img, img_s));
+            TRY(launch_rn_img_prep(c.st, (long)bc * Qn, Cin, c.n.g[0], x_q + (size_t)b0 * Qn * img, img_q));
+            ps.f = feats_s + (size_t)b0 * S * F; pq.f = feats_q + (size_t)b0 * Qn * F;     // the pooled features land in the caller's tensors
+            TRY(forward_pass(c, S, img_s, L[lane].params, L[lane].frags, ps, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
+            TRY(forward_pass(c, Qn, img_q, L[lane].params, L[lane].frags, pq, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
+        }
+        return rn_join_lanes(ws, st, pl.lanes);
+    };
+    if ((rc = run())) { rn_abandon(ws); return rc; }
+    g_rn_enc_last = pl;
+    if (keep_tape) {
+        RnEncToken& t = g_rn_enc;
+        t.ws = ws; t.base = ws->base; t.B = B; t.S = S; t.Qn = Qn; t.Cin = Cin; t.H = H; t.W = W; t.nblk = nblk;
+        for (int l = 0; l < nblk; ++l) t.ch[l] = channels[l];
+        t.pl = pl; t.valid = true;
+    }
+    return FUMI_OK;
+}
+
+int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
+        const float* dfeats_q, float scale, float* const* g_theta) {
+    if (!ws || !x_s || !x_q || !dfeats_s || !dfeats_q || !g_theta || !channels || nblk < 1 || nblk > RN_MAXBLK) return FUMI_EINVAL;
+    const RnEncToken t = g_rn_enc;
+    if (!enc_shape_ok(t, ws, B, S, Qn, Cin, H, W, nblk, channels)) return FUMI_EINVAL;     // no tape of this shape in this workspace
+    for (int i = 0; i < 12 * nblk; ++i) if (!g_theta[i]) return FUMI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
+    g_rn_enc.valid = false;                                               // the backward pass overwrites the BN tables of the tape
+    const RnEncPlan pl = t.pl;                                            // the layout the forward call left
+    RnCtx c0; c0.ws = ws; c0.st = st;
+    int rc = net_init(c0.n, B, nblk, Cin, 1, H, W, channels);
+    if (rc) return rc;
+    if ((rc = ws_reserve(ws, pl.total))) return rc;
+    if (ws->base != t.base) return FUMI_EINVAL;
+    for (int i = 1; i < pl.lanes; ++i) if (!ws_lane_stream(ws, i)) return FUMI_EHIP;
+    RnCtx cx[RN_MAXLANES]; RnEncLane L[RN_MAXLANES];
+    for (int i = 0; i < pl.lanes; ++i) {
+        cx[i] = c0;
+        cx[i].st = i ? ws->lanes[i - 1] : st;
+        if ((rc = enc_carve_lane(ws, cx[i], pl, i, S, Qn, L[i]))) return rc;
+    }
+    if (pl.lanes == 1) { cx[0].side = rn_side_stream(ws); cx[0].ev_fork = ws->ev[0]; cx[0].ev_join = ws->ev[1]; }
+    fumi_ws gview = *ws; gview.off = 0;
+    const RnNet& n0 = c0.n;
+    // per-episode gradient slabs: every entry but the slab padding is written by the backward (the padding is summed, never read)
+    float* Gs = ws_f(&gview, (size_t)2 * B * n0.PSZ); float* Gq = Gs + (size_t)B * n0.PSZ;
+    float* gsum = ws_f(&gview, (size_t)n0.PSZ);
+    const size_t img = (size_t)Cin * H * W;
+    const int F = n0.F;
+    auto run = [&]() -> int {
+        TRY(rn_fork_lanes(ws, st, pl.lanes));
+        for (int k = 0; k < pl.nchunks; ++k) {
+            const int lane = k % pl.lanes, b0 = k * pl.Bc, bc = B - b0 < pl.Bc ? B - b0 : pl.Bc;
+            RnCtx& c = cx[lane];
+            c.n.B = bc;
+            rbf16 *img_s, *img_q; RnPass ps, pq;
+            TRY(enc_chunk_maps(ws, c.n, pl, k, S, Qn, L[lane], &img_s, &img_q, ps, pq));
+            with_bwd_maps(ps, L[lane].bs); with_bwd_maps(pq, L[lane].bq);
+            ps.df = const_cast<float*>(dfeats_s) + (size_t)b0 * S * F;   // read straight into the average-pool backward
+            pq.df = const_cast<float*>(dfeats_q) + (size_t)b0 * Qn * F;
+            const float* xs = x_s + (size_t)b0 * S * img; const float* xq = x_q + (size_t)b0 * Qn * img;
+            if (!pl.taped) {
+                TRY(launch_rn_img_prep(c.st, (long)bc * S, Cin, c.n.g[0], xs, img_s));
+                ps.f = L[lane].f;
+                TRY(forward_pass(c, S, img_s, L[lane].params, L[lane].frags, ps, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
+            }
+            TRY(backward_pass(c, S, img_s, L[lane].frags, ps, nullptr, Gs + (size_t)b0 * n0.PSZ, nullptr));
+            if (!pl.taped) {
+                TRY(launch_rn_img_prep(c.st, (long)bc * Qn, Cin, c.n.g[0], xq, img_q));
+                pq.f = L[lane].f;
+                TRY(forward_pass(c, Qn, img_q, L[lane].params, L[lane].frags, pq, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
+            }
+            TRY(backward_pass(c, Qn, img_q, L[lane].frags, pq, nullptr, Gq + (size_t)b0 * n0.PSZ, nullptr));
+        }
+        TRY(rn_join_lanes(ws, st, pl.lanes));
+        // one sum over the 2 B slabs (support and query of every episode) in a fixed order, whatever the chunks and lanes were
+        TRY(launch_reduce_batched(st, 1, 2 * B, n0.PSZ, Gs, scale, gsum, 0));
+        return theta_grads_out(st, n0, gsum, g_theta);
+    };
+    if ((rc = run())) { rn_abandon(ws); return rc; }
+    return FUMI_OK;
+}
+
+// plan of the last fumi_hip_resnet12_encode: *taped (1 taped, 0 recompute), *chunk (episodes per chunk), *lanes
+int fumi_hip_resnet12_encode_plan(int* taped, int* chunk, int* lanes) {
+    if (!taped || !chunk || !lanes) return FUMI_EINVAL;
+    *taped = g_rn_enc_last.taped; *chunk = g_rn_enc_last.Bc; *lanes = g_rn_enc_last.lanes;
     return FUMI_OK;
 }
 

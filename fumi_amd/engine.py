@@ -50,6 +50,14 @@ class HipEngine:
         return hip.conv4_encode_bwd(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, dfeats_s, dfeats_q, theta_like,
                                     scale=scale, g_theta=g_theta)
 
+    def resnet12_encode(self, x_s, x_q, theta, keep_tape=False):
+        """ResNet-12 in front of a step with its own workspace (AM3): the tape lives in the device's "encoder" workspace."""
+        return hip.resnet12_encode(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, theta, keep_tape=keep_tape)
+
+    def resnet12_encode_bwd(self, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_theta=None):
+        return hip.resnet12_encode_bwd(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, dfeats_s, dfeats_q, theta_like,
+                                       scale=scale, g_theta=g_theta)
+
     def fumi_conv4_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
                         g_theta=None, g_phi=None, cls_text=None, stats=None):
         """FuMI with the Conv4 encoder at the im_net seam: x_s [B,S,C,H,W], x_q [B,Qn,C,H,W]."""

@@ -29,6 +29,7 @@ SYMBOLS = [
     "fumi_hip_conv4_feature_dim", "fumi_hip_fumi_conv4_step", "fumi_hip_maml_conv4_step", "fumi_hip_conv4_probe", "fumi_hip_conv4_features", "fumi_hip_conv4_set_option",
     "fumi_hip_conv4_encode", "fumi_hip_conv4_encode_bwd", "fumi_hip_am3_step_dx",
     "fumi_hip_resnet12_set_budget", "fumi_hip_fumi_resnet12_step", "fumi_hip_maml_resnet12_step", "fumi_hip_resnet12_features",
+    "fumi_hip_resnet12_encode", "fumi_hip_resnet12_encode_bwd", "fumi_hip_resnet12_encode_plan",
     "fumi_hip_rn12_conv", "fumi_hip_rn12_wgrad", "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
     "fumi_hip_conv3x3_fwd", "fumi_hip_conv3x3_bwd_data", "fumi_hip_conv3x3_bwd_weight",
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
@@ -167,6 +168,10 @@ def lib():
             [c_void_p, c_void_p] + [c_int] * 8 + [PI] + [c_int, c_float, c_int, c_int, c_float, c_int]
             + [c_void_p] * 4 + [PP] + [c_void_p] * 6 + [PP])
         L.fumi_hip_resnet12_features.argtypes = [c_void_p, c_void_p] + [c_int] * 6 + [PI, c_void_p, PP, c_void_p]
+        L.fumi_hip_resnet12_encode.argtypes = ([c_void_p, c_void_p] + [c_int] * 7 + [PI, c_void_p, c_void_p, PP, c_void_p, c_void_p,
+                                                                                  c_int])
+        L.fumi_hip_resnet12_encode_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [PI] + [c_void_p] * 4 + [c_float, PP]
+        L.fumi_hip_resnet12_encode_plan.argtypes = [POINTER(c_int)] * 3
         L.fumi_hip_rn12_conv.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4
         L.fumi_hip_rn12_wgrad.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3
         L.fumi_hip_resnet12_set_option.argtypes = [c_int, c_int]
@@ -882,7 +887,9 @@ def _resnet12_shapes(x_s, y_s, x_q, y_q, theta):
     if len(theta) % 12 or not theta:
         raise FumiHipError("resnet12: theta must hold 12 tensors per block (W1,g1,b1, W2,g2,b2, W3,g3,b3, Ws,gs,bs)")
     nblk = len(theta) // 12
-    _shape(x_q, (B, Qn, Cin, H, W), "x_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
+    _shape(x_q, (B, Qn, Cin, H, W), "x_q")
+    if y_s is not None or y_q is not None:         # (the encoder pair has no labels)
+        _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
     channels, ci = [], Cin
     for l in range(nblk):
         c = int(theta[12 * l].shape[0])
@@ -966,6 +973,53 @@ def resnet12_features(ws, x, theta):
     _check(lib().fumi_hip_resnet12_features(ws.handle, _stream(dev), G, M, Cin, H, W, nblk, _ci(channels), _f32(x, "x"),
                                             _parr(theta, "theta"), _f32(feats, "feats")), "fumi_hip_resnet12_features")
     return feats
+
+
+def _resnet12_encode_shapes(what, x_s, x_q, theta):
+    if x_s.dim() != 5 or x_q.dim() != 5 or x_s.shape[0] != x_q.shape[0] or x_s.shape[2:] != x_q.shape[2:]:
+        raise FumiHipError(f"{what}: x_s [B,S,C,H,W] and x_q [B,Qn,C,H,W] expected")
+    return _resnet12_shapes(x_s, None, x_q, None, theta)
+
+
+def resnet12_encode(ws, x_s, x_q, theta, keep_tape=False):
+    """(feats_s [B,S,F], feats_q [B,Qn,F]) = ResNet-12 of every episode's support / query images (one batch-statistics group each).
+    keep_tape: what the backward needs stays in ``ws`` for ``resnet12_encode_bwd`` -- no other call may use ``ws`` in between."""
+    dev = _dev(x_s)
+    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_encode_shapes("resnet12_encode", x_s, x_q, theta)
+    F = channels[-1]
+    fs = torch.empty(B, S, F, device=dev, dtype=torch.float32)
+    fq = torch.empty(B, Qn, F, device=dev, dtype=torch.float32)
+    _check(lib().fumi_hip_resnet12_encode(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _ci(channels), _f32(x_s, "x_s"),
+                                          _f32(x_q, "x_q"), _parr(theta, "theta"), _f32(fs, "feats_s"), _f32(fq, "feats_q"),
+                                          int(bool(keep_tape))), "fumi_hip_resnet12_encode")
+    return fs, fq
+
+
+def resnet12_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_theta=None):
+    """Gradient of sum <dfeats, ResNet12(x)> w.r.t. the encoder's parameters (summed over episodes, times ``scale``) from what the
+    last ``resnet12_encode(..., keep_tape=True)`` left in ``ws``."""
+    dev = _dev(x_s)
+    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_encode_shapes("resnet12_encode_bwd", x_s, x_q, theta_like)
+    F = channels[-1]
+    _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q")
+    if g_theta is None:
+        g_theta = [torch.empty_like(t) for t in theta_like]
+    elif len(g_theta) != len(theta_like):
+        raise FumiHipError("resnet12_encode_bwd: g_theta must hold one tensor per theta tensor")
+    else:
+        for i, (g, t) in enumerate(zip(g_theta, theta_like)):
+            _shape(g, tuple(t.shape), f"g_theta[{i}]")
+    _check(lib().fumi_hip_resnet12_encode_bwd(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _ci(channels), _f32(x_s, "x_s"),
+                                              _f32(x_q, "x_q"), _f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), float(scale),
+                                              _parr(g_theta, "g_theta")), "fumi_hip_resnet12_encode_bwd")
+    return g_theta
+
+
+def resnet12_encode_plan():
+    """(taped, chunk, lanes) of the last ``resnet12_encode``: taped = True for the taped form, False for the recompute form."""
+    t, c, l = c_int(0), c_int(0), c_int(0)
+    _check(lib().fumi_hip_resnet12_encode_plan(ctypes.byref(t), ctypes.byref(c), ctypes.byref(l)), "fumi_hip_resnet12_encode_plan")
+    return bool(t.value), int(c.value), int(l.value)
 
 
 def _bf16ptr(t, name):

@@ -37,7 +37,8 @@ class AM3(nn.Module):
         self.pooling_strat = pooling_strat
         self.lamda_fixed = lamda_fixed
 
-        self.conv = None
+        self.conv = None                                        # the backbone on raw images (conv4 / resnet12), else None
+        self.backbone = im_encoder if im_encoder in ("conv4", "resnet12") else None
         if im_encoder in ("precomputed", "resnet"):            # "resnet" is the same Linear in the reference (am3.py:44-46)
             self.image_encoder = nn.Linear(im_emb_dim, prototype_dim)
         elif im_encoder == "conv4":
@@ -46,6 +47,14 @@ class AM3(nn.Module):
             # is one batch-statistics group (like the MAML / FuMI Conv4 path); "parity unpinned" (oracle/conv4_ref.py).
             from .conv4 import Conv4
             self.conv = Conv4(image_channels, 64, 4, image_size)
+            self.im_emb_dim = self.conv.feature_dim
+            self.image_encoder = nn.Linear(self.conv.feature_dim, prototype_dim)
+        elif im_encoder == "resnet12":
+            # the same seam with the bf16 ResNet-12 (the reference's `# TODO image encoder if raw images`, am3.py:44-46; AM3 was
+            # published on the TADAM ResNet-12): features [rows, 640] -> the reference's Linear.  "Parity unpinned"
+            # (oracle/resnet12_ref.py).
+            from .resnet12 import CHANNELS, ResNet12
+            self.conv = ResNet12(image_channels, CHANNELS, image_size)
             self.im_emb_dim = self.conv.feature_dim
             self.image_encoder = nn.Linear(self.conv.feature_dim, prototype_dim)
         else:
@@ -188,10 +197,12 @@ class AM3(nn.Module):
         on_device = task != "test" and x_s.is_cuda and num_ways <= 64 and hasattr(eng, "am3_metrics")
         tail = fg.tail if need_grad else torch.empty(3 + num_ways * num_ways, device=x_s.device, dtype=torch.float32)
         img_s = img_q = theta = None
-        if self.conv is not None:           # raw images -> Conv4 features; the tape stays in the encoder's own workspace
+        if self.conv is not None:           # raw images -> backbone features; the tape stays in the encoder's own workspace
+            encode, encode_bwd = ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
+                                  (eng.resnet12_encode, eng.resnet12_encode_bwd))
             img_s, img_q = x_s, x_q
             theta = th_det
-            x_s, x_q = eng.conv4_encode(img_s, img_q, theta, keep_tape=need_grad)
+            x_s, x_q = encode(img_s, img_q, theta, keep_tape=need_grad)
         g_w = fg.split(10)[0] if need_grad else None
         rand_text = self.text_encoder_type == "rand"
         if rand_text:
@@ -210,7 +221,7 @@ class AM3(nn.Module):
                            **({"stats": tail} if on_device else {}),
                            **({"want_dx": True} if (self.conv is not None and need_grad) else {}))
         if self.conv is not None and need_grad:     # ... and backwards from the adjoints of the features (already scaled by 1/B)
-            eng.conv4_encode_bwd(img_s, img_q, out["dx_s"], out["dx_q"], theta, scale=1.0, g_theta=fg.split(10)[1])
+            encode_bwd(img_s, img_q, out["dx_s"], out["dx_q"], theta, scale=1.0, g_theta=fg.split(10)[1])
         if not on_device:
             torch.stack([out["loss"].reshape(()), out["correct"].reshape(()) / (B * Qn),
                          out["lamda_s"].sum() / (B * out["lamda_s"].shape[1])], out=tail[:3])

@@ -42,7 +42,7 @@ _FLAGS = [
     # model
     ("--model", dict(type=str, default="fumi", help="Model to be trained")),
     ("--prototype_dim", dict(type=int, default=64, help="Dimension of latent space")),
-    ("--im_encoder", dict(type=str, default="precomputed", help="Type of vision feature extractor (resnet, precomputed; conv4 / resnet12 = Conv4 / bf16 ResNet-12 on raw images, this engine's extensions at the im_net seam)")),
+    ("--im_encoder", dict(type=str, default="precomputed", help="Type of vision feature extractor (resnet, precomputed; conv4 / resnet12 = Conv4 / bf16 ResNet-12 on raw images for fumi, maml and am3, this engine's extensions at the im_net / image_encoder seam)")),
     ("--im_emb_dim", dict(type=int, default=2048, help="Dimension of image embedding (if precomputed)")),
     ("--im_hid_dim", dict(type=int, nargs="+", default=[256, 64], help="Hidden dimension of image model")),
     ("--text_encoder", dict(type=str, choices=["glove", "w2v", "RNN", "RNNhid", "BERT", "rand"], default="BERT",
@@ -76,8 +76,8 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--synthetic_classes", dict(type=int, default=64, help="[synthetic dataset] number of classes per split")),
     ("--synthetic_vocab", dict(type=int, default=2000, help="[synthetic dataset] vocabulary size for token text")),
     ("--synthetic_seq_len", dict(type=int, default=32, help="[synthetic dataset] token sequence length")),
-    ("--image_size", dict(type=int, default=84, help="[--im_encoder conv4] height = width of the input images")),
-    ("--image_channels", dict(type=int, default=3, help="[--im_encoder conv4] input channels (1-3)")),
+    ("--image_size", dict(type=int, default=84, help="[--im_encoder conv4 / resnet12] height = width of the input images")),
+    ("--image_channels", dict(type=int, default=3, help="[--im_encoder conv4 / resnet12] input channels (conv4: 1-3, resnet12: 1-8)")),
 ]
 
 
@@ -110,7 +110,8 @@ def init_model(args, dictionary, watch=True):
                         text_emb_dim=args.text_emb_dim, text_hid_dim=args.text_hid_dim,
                         prototype_dim=args.prototype_dim, dropout=args.dropout, fine_tune=args.fine_tune,
                         dictionary=dictionary, pooling_strat=args.pooling_strat, lamda_fixed=args.lamda_fixed,
-                        **(dict(image_size=args.image_size, image_channels=args.image_channels) if args.im_encoder == "conv4" else {}))
+                        **(dict(image_size=args.image_size, image_channels=args.image_channels)
+                           if args.im_encoder in ("conv4", "resnet12") else {}))
     if watch:
         wandb.watch(model, log="all")
     model.to(args.device)

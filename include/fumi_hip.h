@@ -305,6 +305,23 @@ int fumi_hip_maml_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
 /* Forward only: feats [G*M, channels[nblk-1]] fp32; batch statistics per group of M images. */
 int fumi_hip_resnet12_features(fumi_ws_t* ws, fumi_stream_t stream, int G, int M, int Cin, int H, int W, int nblk, const int* channels,
         const float* x, const float* const* theta, float* feats);
+/* ResNet-12 as the image encoder in front of a step that lays out its own workspace (AM3 at the seam am3.py:41-46; "parity
+ * unpinned" like the other ResNet-12 rows).  encode: feats_s [B,S,F], feats_q [B,Qn,F] with F = channels[nblk-1]; every episode's
+ * support set and query set is one batch-statistics group; theta in the order above.  keep_tape = 1 leaves in `ws` what the
+ * backward needs, theta's parameter / fragment slab included; encode_bwd (same shapes, same `ws`, no other call on `ws` in between
+ * -- give the encoder its own workspace) consumes it: g_theta (12 nblk pointers, torch layouts) = scale * sum over episodes of
+ * d(<dfeats_s, feats_s> + <dfeats_q, feats_q>)/dtheta.  FUMI_EINVAL without a tape of these shapes.  Two forms, chosen from the
+ * workspace budget (fumi_hip_resnet12_set_budget): TAPED (the forward maps of the whole meta-batch stay resident, encode_bwd runs
+ * the backward only) when they fit, else RECOMPUTE (encode_bwd runs each chunk's forward again); both give bit-identical results. */
+int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
+        float* feats_s, float* feats_q, int keep_tape);
+int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
+        const float* dfeats_q, float scale, float* const* g_theta);
+/* Plan of the last fumi_hip_resnet12_encode: *taped = 1 (taped form) or 0 (recompute form), *chunk = episodes per chunk,
+ * *lanes = streams the chunks were spread over. */
+int fumi_hip_resnet12_encode_plan(int* taped, int* chunk, int* lanes);
 /* The matrix kernels on raw maps (unit parity tests): x, y, dy are bf16 "padded channels-last" [B][M (H+2)(W+2)][C] with zero
  * borders, Wt / dW fp32 [B][Cout][Cin][k][k] (k = 3: ntaps 9, pad 1; k = 1: ntaps 1).  transpose != 0: the input-gradient
  * product (x has Cout channels, y has Cin).  stats (optional) [B][2][C_y]: per-channel sum and sum of squares of the stored y. */
