@@ -649,7 +649,7 @@ __device__ __forceinline__ void wg_colsum(float* lds, int lds_cap, int M, int N,
 //   ds_read_b128 per 16-deep step, a k-major one with 4 ds_read_b32, both conflict-free.  The arena is zeroed once at
 //   kernel start: rows/cols past the logical shape stay zero (K padding must be), M/N padding is never written.
 // ------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int wg_ld(int cols) { return ((cols + 31) & ~31) + 4; }
+__host__ __device__ __forceinline__ constexpr int wg_ld(int cols) { return ((cols + 31) & ~31) + 4; }
 
 // executes a StageTab whose copy `Tl` sits in LDS (wg_stage_tab_to_lds).  The units go round-robin over the waves
 // (unit u -> wave u % nw).  Step A: every LANE works out one of its wave's units (job search, row, source row pointer,

@@ -85,6 +85,22 @@ __device__ __forceinline__ f32x4 drop_relu4(const EpiDims& d, unsigned key, long
 }
 constexpr int QUERY_CALL = 1 << 20;      // "call" id of the query forward (support step t uses t)
 
+// The reference configuration (bench.py configs[1]): one inner step, h = [256, 64], at most 8 classes and 32 support rows (28 in
+// the query kernel: its fused layout at 32 rows is 40776 floats, over QLDS_CAP -- such steps take the adapt kernel), the reverse
+// sweep split in 4 column parts.  query_lds_kernel<true, true, DROP> and reverse_lds_kernel<true, DROP> are instantiated
+// for it: the dimensions, the control flags and the LDS layout are compile-time constants, only S, N and Qn (and, with DROP,
+// the dropout threshold / scale) are read at run time.  Same code, same accumulation order: the outputs are bit-identical to
+// the run-time-shaped instances.
+constexpr int REF_SP = 32, REF_SQ = 28, REF_NP = 8, REF_H0 = 256, REF_H1 = 64, REF_P = 4;
+template <bool FIX, bool DROP>
+__device__ __forceinline__ void fix_dims(EpiDims& d) {
+    if constexpr (FIX) {
+        d.L = 2; d.T = 1; d.H = REF_H1;           // (the widths: dh() below -- a written copy of d.h would go to scratch memory)
+        d.need_grad = 1; d.second_order = 1; d.taped = 1;
+        if constexpr (!DROP) { d.drop_thr = 0; d.mscale = 1.f; }      // (x * 1.f == x: the scale folds away exactly)
+    }
+}
+
 struct EpiParams {                             // meta-parameters of the hidden layers (device pointers)
     const float* W[MAXL];
     const float* b[MAXL];
@@ -240,8 +256,8 @@ __global__ __launch_bounds__(512) void adapt_kernel(EpiDims d, EpiBuf w, EpiPara
 // never changes (needs ceil(S/16)*ceil(h0/64) <= 8 blocks, one per wave).  Global memory only sees the tape (stores,
 // never waited for) and the final state.  Taken when adapt_layout().total <= ALDS_CAP and the block count fits.
 // ------------------------------------------------------------------------------------------------------------
-__host__ __device__ inline int q_r4(int x) { return (x + 3) & ~3; }
-__host__ __device__ inline int q_r16(int x) { return (x + 15) & ~15; }
+__host__ __device__ constexpr int q_r4(int x) { return (x + 3) & ~3; }
+__host__ __device__ constexpr int q_r16(int x) { return (x + 15) & ~15; }
 constexpr int ALDS_CAP = 40000;
 struct ALay { int a[MAXL], dz[MAXL], W[MAXL], bi[MAXL], Wh, G, D, e, cs, bh, total; };
 __host__ __device__ inline void adapt_layout(ALay& y, int L, const int* h, int S, int N) {
@@ -677,7 +693,7 @@ __global__ __launch_bounds__(512) void query_kernel(EpiDims d, EpiBuf w, const f
 // ------------------------------------------------------------------------------------------------------------
 constexpr int QLDS_CAP = 40000;         // floats of dynamic LDS (160 KiB = 40960 less the kernel's static arrays)
 struct QLay { int a[MAXL], W[MAXL], bi[MAXL], Wh, Wh2, Gq, D, lq, b0, cs, pb0, bh, total; };
-__host__ __device__ inline void query_layout(QLay& y, int L, const int* h, int S, int N, bool fused = false) {
+__host__ __device__ constexpr void query_layout(QLay& y, int L, const int* h, int S, int N, bool fused = false) {
     int off = 0;
     for (int i = 0; i < MAXL; ++i) { y.a[i] = y.W[i] = y.bi[i] = 0; }
     for (int i = 0; i < L; ++i) { y.a[i] = off; off += QR * wg_ld(h[i]); }
@@ -693,16 +709,25 @@ __host__ __device__ inline void query_layout(QLay& y, int L, const int* h, int S
     y.bh = off; off += q_r4(N);
     y.total = off;
 }
+constexpr QLay ref_qlay() { QLay y{}; const int h[MAXL] = {REF_H0, REF_H1}; query_layout(y, 2, h, REF_SQ, REF_NP, true); return y; }
 
 // FUSED (one inner step, two layers, S <= 32: the reference configuration): every query tile first runs the episode's inner step on
 // the support rows ITSELF -- redundantly in each of the episode's tiles, which costs nothing on a chip that the 32 one-workgroup
 // adapt launches left 7/8 idle -- so the adapt kernel, its launch and the round trip of the fast weights through memory go away.
 // The support activations borrow the tile's own images (a_0, a_1, lq) before the query rows are staged into them; the updated head
 // is built next to the old one (the backward through the head reads the old); tile 0 writes the tape the reverse sweep reads.
-template <bool FUSED>
-__global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab stg_sup, EpiDims d, EpiBuf w, QLay y, const int64_t* y_q,
+template <bool FUSED, bool FIX = false, bool DROP = true>
+__global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab stg_sup, EpiDims d_arg, EpiBuf w, QLay y_arg, const int64_t* y_q,
                                                         float* logits_q, int64_t* preds_q, float* preds_f, int* status,
                                                         const int64_t* y_s) {
+    static_assert(!FIX || FUSED, "the fixed-shape form is the fused one-step form");
+    // FIX: the reference shape's constants over the arguments (the run-time instances read the arguments themselves)
+    EpiDims d_fix = d_arg; fix_dims<FIX, DROP>(d_fix);
+    const EpiDims& d = FIX ? d_fix : d_arg;
+    auto dh = [&](int i) { return FIX ? (i == 0 ? REF_H0 : REF_H1) : d_arg.h[i]; };
+    QLay y_fix = y_arg;
+    if constexpr (FIX) { constexpr QLay k = ref_qlay(); y_fix = k; }
+    const QLay& y = FIX ? y_fix : y_arg;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float s_loss[QR];
     __shared__ float s_corr[QR];
@@ -713,19 +738,20 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     int qi = 0;
 #define QSTAMP() if (w.trace && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) w.trace[64 + qi++] = __builtin_amdgcn_s_memrealtime();
     QSTAMP()
-    const int S = d.S, N = d.N, L = d.L, H = d.H, h0 = d.h[0], Qn = d.Qn;
+    const int S = d.S, N = d.N, L = d.L, H = d.H, h0 = dh(0), Qn = d.Qn;
     const int r0 = tile * QR, nr = min(QR, Qn - r0);
     const float alpha = d.alpha;
     const int ldq = wg_ld(N), ldG = wg_ld(S), ld0 = wg_ld(h0), ldH = wg_ld(H);
     auto a = [&](int i) { return sm + y.a[i]; };
-    auto lda = [&](int i) { return wg_ld(d.h[i]); };
+    auto lda = [&](int i) { return wg_ld(dh(i)); };
 
     // the row's label is loaded now: inside the chain it would wait for every older store (vmcnt is in order)
     const int my_label = tid < nr ? label(y_q + (long)b * Qn + r0, tid, N, status) : 0;
     // ---- zero the arena (padding must read as zero), then stage everything this tile needs in one batch (plan: host)
     const int my_label_s = (FUSED && tid < S) ? label(y_s + (long)b * S, tid, N, status) : 0;
     if (FUSED && tid < S && tid < QR) s_lab[tid] = my_label_s;
-    wg_stage_tab_to_lds(s_stg2, 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(QLay) + 64));
+    // (FIX: the staging is written out below, the tables are not read)
+    wg_stage_tab_to_lds(s_stg2, FIX ? 0 : 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(QLay) + 64));
     for (int i = tid * 4, tot = y.total; i < tot; i += nt * 4) *(f32x4*)(sm + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads(); QSTAMP()
     int whq = y.Wh;                                                  // the head the query pass uses
@@ -749,12 +775,51 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 qv[i] = *(const f32x4*)(A0q + (long)(qok[i] ? m : 0) * h0 + (qok[i] ? n : 0));
             }
         }
-        wg_stage_rows<20>(&s_stg2[1], b, tile, 0, nr, sm);           // A0_s rows -> a_0, W_1, b_1, the episode's head, b_0, the tile's G rows
+        if constexpr (FIX) {
+            // the same jobs as fixed-address loads, all in flight before the first LDS write.  Sources: the plan's base pointers
+            // (run_episodes adds them in this order); W_1, b_1, b_0 are 16-byte aligned (checked there).  Loads read clamped
+            // in-range addresses, the LDS writes are masked.
+            const float* A0s = stg_sup.base[0] + (long)b * (S + Qn) * REF_H0;
+            const float* W1g = stg_sup.base[1]; const float* b1g = stg_sup.base[2];
+            const float* hdg = stg_sup.base[3] + (long)b * N * (REF_H1 + 1); const float* b0g = stg_sup.base[5];
+            const float* Gg = stg_sup.base[6] + ((long)b * (S + Qn) + r0) * S;
+            constexpr int C4 = REF_H0 / 4;                                   // float4 per row of A0_s / W_1
+            f32x4 va[4], vw[8];
+            float vg[2], vh;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; va[k] = *(const f32x4*)(A0s + (long)(m < S ? m : 0) * REF_H0 + 4 * (f % C4)); }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; vw[k] = *(const f32x4*)(W1g + (long)f * 4); }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {                                    // G: 32 x 32 slots, row m < nr, column c < S
+                const int f = tid + 512 * k, m = f >> 5, c = f & 31;
+                vg[k] = Gg[(m < nr && c < S) ? (long)m * S + c : 0];
+            }
+            {
+                const int m = tid >> 6, c = tid & 63;                        // head: N <= 8 rows of H = 64 (+ bias) at stride H + 1
+                vh = hdg[m < N ? m * (REF_H1 + 1) + c : 0];
+            }
+            const f32x4 vb0 = *(const f32x4*)(b0g + 4 * (tid & 63));
+            const f32x4 vb1 = *(const f32x4*)(b1g + 4 * (tid & 15));
+            const float vbh = hdg[tid < N ? tid * (REF_H1 + 1) + REF_H1 : 0];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; if (m < S) *(f32x4*)(sm + y.a[0] + m * wg_ld(REF_H0) + 4 * (f % C4)) = va[k]; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; *(f32x4*)(sm + y.W[1] + (f / C4) * wg_ld(REF_H0) + 4 * (f % C4)) = vw[k]; }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) { const int f = tid + 512 * k, m = f >> 5, c = f & 31; if (m < nr && c < S) sm[y.Gq + m * wg_ld(REF_SQ) + c] = vg[k]; }
+            if ((tid >> 6) < N) sm[y.Wh + (tid >> 6) * wg_ld(REF_H1) + (tid & 63)] = vh;
+            if (tid < REF_H0 / 4) *(f32x4*)(sm + y.b0 + 4 * tid) = vb0;
+            if (tid < REF_H1 / 4) *(f32x4*)(sm + y.bi[1] + 4 * tid) = vb1;
+            if (tid < N) sm[y.bh + tid] = vbh;
+        } else {
+            wg_stage_rows<20>(&s_stg2[1], b, tile, 0, nr, sm);       // A0_s rows -> a_0, W_1, b_1, the episode's head, b_0, the tile's G rows
+        }
         wg_lds_barrier();
         float* a0 = a(0); float* a1 = a(1); float* W1 = sm + y.W[1]; float* b1 = sm + y.bi[1];
         float* Wh = sm + y.Wh; float* Wh2 = sm + y.Wh2; float* bh = sm + y.bh; float* Dl = sm + y.D; float* csl = sm + y.cs;
         const float* b0l = sm + y.b0; float* e_ = sm + y.lq;
-        const int h1 = d.h[1], ld1 = wg_ld(h1);
+        const int h1 = dh(1), ld1 = wg_ld(h1);
         const long tp = (long)b * w.ntape;                           // tape step 0
         auto store_img = [&](float* dst, long drs, const float* img, int ld, int rows, int cols) {      // LDS image -> global rows
             const int c4n = (cols + 3) >> 2;
@@ -889,7 +954,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     }
     wg_lds_barrier(); QSTAMP()
     for (int i = 1; i < L; ++i) {
-        const int hi = d.h[i], hp = d.h[i - 1];
+        const int hi = dh(i), hp = dh(i - 1);
         float* ai = a(i); const int ldi = lda(i);
         const float* bi = sm + y.bi[i];
         const unsigned keyqi = drop_key(d, b, QUERY_CALL, i);
@@ -963,7 +1028,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     }
     wg_lds_barrier(); QSTAMP()
     for (int i = L - 1; i >= 1; --i) {
-        const int hi = d.h[i], hp = d.h[i - 1];
+        const int hi = dh(i), hp = dh(i - 1);
         const float* zi = a(i); const int ldi = lda(i), ldp = lda(i - 1);
         float* pWi = w.pW[i] + pt * (long)hi * hp;
         wg_lmm_wide<false>(hi, hp, nr, zi, ldi, a(i - 1), ldp, [&](int m, int n, const f32x4& acc, int cnt, auto) {
@@ -1175,7 +1240,7 @@ struct RLay {
     int Wb[MAXL], bb[MAXL], a[MAXL], dz[MAXL], W[MAXL], ab[MAXL];
     int Db, A0bs, b0b, Whb, bhb, Wh, p, e, eb, G, dab0, X0, X1, cs, ldX, total;
 };
-inline void reverse_layout(RLay& y, int L, const int* h, int S, int N, int P) {
+__host__ __device__ constexpr void reverse_layout(RLay& y, int L, const int* h, int S, int N, int P) {
     int off = 0;
     const int RS = q_r4(S), h0c = h[0] / P, H = h[L - 1];
     auto take = [&](int rows, int ld) { const int o = off; off += rows * ld; return o; };
@@ -1196,9 +1261,20 @@ inline void reverse_layout(RLay& y, int L, const int* h, int S, int N, int P) {
     y.b0b = take(1, q_r4(h0c)); y.cs = take(1, q_r4(h0c)); y.bhb = take(1, q_r4(N));
     y.total = off + 64;
 }
+constexpr RLay ref_rlay() { RLay y{}; const int h[MAXL] = {REF_H0, REF_H1}; reverse_layout(y, 2, h, REF_SP, REF_NP, REF_P); return y; }
+static_assert(ref_qlay().total <= QLDS_CAP && ref_rlay().total <= RLDS_CAP, "the reference layouts fit the CU's LDS");
 
-__global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, StageTab stg_step, EpiDims d, EpiBuf w, RLay y,
-                                                          int P, float* loss_b, float* acc_b, float* head_bar) {
+template <bool FIX = false, bool DROP = true>
+__global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, StageTab stg_step, EpiDims d_arg, EpiBuf w, RLay y_arg,
+                                                          int P_arg, float* loss_b, float* acc_b, float* head_bar) {
+    // FIX: the reference shape's constants over the arguments (the run-time instances read the arguments themselves)
+    EpiDims d_fix = d_arg; fix_dims<FIX, DROP>(d_fix);
+    const EpiDims& d = FIX ? d_fix : d_arg;
+    auto dh = [&](int i) { return FIX ? (i == 0 ? REF_H0 : REF_H1) : d_arg.h[i]; };
+    RLay y_fix = y_arg;
+    if constexpr (FIX) { constexpr RLay k = ref_rlay(); y_fix = k; }
+    const RLay& y = FIX ? y_fix : y_arg;
+    const int P = FIX ? REF_P : P_arg;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ StageTab s_stg[2];
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -1208,7 +1284,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
     int ri = 0;
 #define RSTAMP() if (w.trace && tid == 0 && blockIdx.x == 0) w.trace[128 + ri++] = __builtin_amdgcn_s_memrealtime();
     RSTAMP()
-    const int S = d.S, N = d.N, L = d.L, H = d.H, h0 = d.h[0], h0c = h0 / P, c0 = c * h0c, h1 = d.h[1];
+    const int S = d.S, N = d.N, L = d.L, H = d.H, h0 = dh(0), h0c = h0 / P, c0 = c * h0c, h1 = dh(1);
     const float alpha = d.alpha, ms = d.mscale;
     const int ntile = w.ntile;
     if (tid == 0 && c == 0) {
@@ -1220,7 +1296,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
     if (!d.need_grad) return;
 
     const int ldc = wg_ld(h0c), ldN = wg_ld(N), ldS = wg_ld(S), ldH = wg_ld(H), ldX = y.ldX;
-    auto ldh = [&](int i) { return wg_ld(d.h[i]); };
+    auto ldh = [&](int i) { return wg_ld(dh(i)); };
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     auto relu_bwd4 = [&](const f32x4& act, const f32x4& g) {
         f32x4 o;
@@ -1260,7 +1336,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
             wg_stage_rows<8, 1>(&s_stg[1], b, t, c, 0, sm);
             wg_lds_barrier(); RSTAMP()
             // abar_i = 0 ; dab_0 = Dbar * relu'(z_0)
-            for (int i = 1; i < L; ++i) { float* abi = sm + y.ab[i]; const int ldi = ldh(i); ew(d.h[i], [&](int m, int n) { *(f32x4*)(abi + m * ldi + n) = z4; }); }
+            for (int i = 1; i < L; ++i) { float* abi = sm + y.ab[i]; const int ldi = ldh(i); ew(dh(i), [&](int m, int n) { *(f32x4*)(abi + m * ldi + n) = z4; }); }
             ew(h0c, [&](int m, int n) {
                 *(f32x4*)(ab0 + m * ldc + n) = z4;
                 *(f32x4*)(dab0 + m * ldc + n) = relu_bwd4(*(const f32x4*)(a0 + m * ldc + n), *(const f32x4*)(Db + m * ldc + n));
@@ -1327,7 +1403,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
             auto X = [&](int i) { return i ? Xb : Xa; };
             // ---- deeper layers (not split; every part computes them)
             for (int i = 2; i < L; ++i) {
-                const int hi = d.h[i], hp = d.h[i - 1], ldi = ldh(i), ldp = ldh(i - 1);
+                const int hi = dh(i), hp = dh(i - 1), ldi = ldh(i), ldp = ldh(i - 1);
                 const float* dab = X(cur); float* nxt = X(cur ^ 1);
                 const float* bbi = sm + y.bb[i]; float* Wbi = sm + y.Wb[i]; const float* ai = sm + y.a[i];
                 const float* dzi = sm + y.dz[i]; float* abp = sm + y.ab[i - 1];
@@ -1384,13 +1460,13 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
             }
             // ---- reverse of the forward pass
             for (int i = L - 1; i >= 1; --i) {
-                const int hi = d.h[i], ldi = ldh(i);
+                const int hi = dh(i), ldi = ldh(i);
                 float* zb = sm + y.ab[i]; const float* ai = sm + y.a[i];
                 ew(hi, [&](int m, int n) { float* pz = zb + m * ldi + n; *(f32x4*)pz = relu_bwd4(*(const f32x4*)(ai + m * ldi + n), *(const f32x4*)pz); });
                 wg_lds_barrier();
                 float* bbw = sm + y.bb[i];
                 if (i >= 2) {
-                    const int hp = d.h[i - 1], ldp = ldh(i - 1);
+                    const int hp = dh(i - 1), ldp = ldh(i - 1);
                     float* abp = sm + y.ab[i - 1]; float* Wbi = sm + y.Wb[i];
                     wg_lmm_wide<true>(S, hp, hi, zb, ldi, sm + y.W[i], ldp, [&](int m, int n, const f32x4& acc, int, auto) {
                         float* pa = abp + m * ldp + n; *(f32x4*)pa = *(const f32x4*)pa + acc;
@@ -1432,8 +1508,8 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
     if (c == 0) {
         for (int i = 1; i < L; ++i) {
             const float* bbi = sm + y.bb[i];
-            for (int n = tid; n < d.h[i]; n += nt) w.bb[i][(long)b * d.h[i] + n] = bbi[n];
-            if (i >= 2) store_img(w.Wb[i] + (long)b * d.h[i] * d.h[i - 1], d.h[i - 1], sm + y.Wb[i], ldh(i - 1), d.h[i], d.h[i - 1]);
+            for (int n = tid; n < dh(i); n += nt) w.bb[i][(long)b * dh(i) + n] = bbi[n];
+            if (i >= 2) store_img(w.Wb[i] + (long)b * dh(i) * dh(i - 1), dh(i - 1), sm + y.Wb[i], ldh(i - 1), dh(i), dh(i - 1));
         }
         // d loss_b / d head_b = [Whbar | bhbar]
         float* hb = head_bar + (long)b * N * (H + 1);
@@ -1495,6 +1571,9 @@ __global__ void split_head_grad_kernel(int B, int N, int H, const float* head_ba
     const int n = j / (H + 1), c = j % (H + 1);
     if (c < H) gW[n * H + c] = scale * s; else gb[n] = scale * s;
 }
+
+// a kernel as a type: each instance of a launch lambda taking it keeps its own FUMI_SET_DYN_LDS state
+template <auto K> struct KernTag { static constexpr auto fn = K; };
 
 inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
 
@@ -1577,6 +1656,9 @@ extern "C" int fumi_hip_set_trace_buffer(int which, void* p) {
     else return FUMI_EINVAL;
     return FUMI_OK;
 }
+// which fixed-shape kernels the last run_episodes launched: 1 = query_lds_kernel<true, true, *>, 2 = reverse_lds_kernel<true, *>
+static int g_epi_fixed_last = 0;
+extern "C" int fumi_hip_epi_fixed_last() { return g_epi_fixed_last; }
 extern "C" int fumi_hip_set_spin_limit(int polls) { const int old = g_spin_limit; g_spin_limit = polls < 0 ? 0 : polls; return old; }
 
 size_t episode_workspace_bytes(const EpisodeProblem& p) {
@@ -1657,8 +1739,17 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
     static const int fuse_env = getenv("FUMI_EPI_FUSE") ? atoi(getenv("FUMI_EPI_FUSE")) : 1;
     QLay qlf; StageTab tbq, tbs;
     bool fuse_q = fuse_env && !getenv("FUMI_EPI_GLOBAL") && p.T == 1 && p.L == 2 && p.S <= QR && (h0 & 3) == 0 && p.head != nullptr;
+    // the reference shape of a training step: the query and reverse kernels compiled for it (REF_*; FUMI_EPI_FIXED=0: the
+    // run-time-shaped instances).  The layout is the one of S = REF_SP, N = REF_NP: every smaller S, N fits it (zero padding).
+    static const int fixed_env = getenv("FUMI_EPI_FIXED") ? atoi(getenv("FUMI_EPI_FIXED")) : 1;
+    const bool fixed = fixed_env && !getenv("FUMI_EPI_GLOBAL") && p.T == 1 && p.L == 2 && p.h[0] == REF_H0 && p.h[1] == REF_H1 &&
+                       p.S <= REF_SP && p.N <= REF_NP && p.need_grad && p.second_order;
+    bool fixed_q = fixed && fuse_q && p.S <= REF_SQ;
+    g_epi_fixed_last = 0;
+    const bool drop = d.drop_thr != 0;
     if (fuse_q) {
-        query_layout(qlf, p.L, p.h, p.S, p.N, true);
+        if (fixed_q) qlf = ref_qlay();
+        else query_layout(qlf, p.L, p.h, p.S, p.N, true);
         fuse_q = qlf.total <= QLDS_CAP;
     }
     if (fuse_q) {
@@ -1673,6 +1764,9 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
         tbs.add(p.b[0], 0, 0, 0, h0, 1, 1, h0, qlf.b0, h0);
         tbs.add(w.G + S * S, R * S, (long)QR * S, 0, S, -1, QR, p.S, qlf.Gq, wg_ld(p.S));      // the tile's rows of G (its A0 rows: direct loads)
         fuse_q = !tbs.bad && tbs.nunits <= 64 * 8 && h0 <= 256;
+        // (the fixed-shape kernel reads these jobs' base pointers itself: W_1, b_1, b_0 as float4)
+        auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+        fixed_q = fixed_q && a16(p.W[1]) && a16(p.b[1]) && a16(p.b[0]);
     }
     if (!fuse_q) {
         ProfScope ps(ws, st, FUMI_PH_ADAPT);
@@ -1721,10 +1815,18 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
     }
     if (fuse_q) {
         ProfScope ps(ws, st, FUMI_PH_QUERY);
-        FUMI_SET_DYN_LDS(query_lds_kernel<true>, qlf.total * 4);
-        hipLaunchKernelGGL(query_lds_kernel<true>, dim3(w.ntile, p.B), dim3(512), qlf.total * 4, st, tbq, tbs, d, w, qlf, p.y_q,
-                           p.logits_q, p.preds_q, p.preds_f, ws->status, p.y_s);
-        LAUNCH_CHECK();
+        auto launch = [&](auto tag) -> int {
+            constexpr auto kern = decltype(tag)::fn;
+            FUMI_SET_DYN_LDS(kern, qlf.total * 4);
+            hipLaunchKernelGGL(kern, dim3(w.ntile, p.B), dim3(512), qlf.total * 4, st, tbq, tbs, d, w, qlf, p.y_q,
+                               p.logits_q, p.preds_q, p.preds_f, ws->status, p.y_s);
+            LAUNCH_CHECK();
+            return FUMI_OK;
+        };
+        if (fixed_q) g_epi_fixed_last |= 1;
+        if (fixed_q) rc = drop ? launch(KernTag<query_lds_kernel<true, true, true>>{}) : launch(KernTag<query_lds_kernel<true, true, false>>{});
+        else rc = launch(KernTag<query_lds_kernel<true>>{});
+        if (rc) return rc;
     } else {
         ProfScope ps(ws, st, FUMI_PH_QUERY);
         QLay ql; query_layout(ql, p.L, p.h, p.S, p.N);
@@ -1785,6 +1887,9 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
             }
             lds_form = P > 0;
         }
+        // the fixed-shape sweep where the run-time one splits the same way (the sum over the parts depends on P)
+        const bool fixed_r = fixed && lds_form && P == REF_P;
+        if (fixed_r) rl = ref_rlay();
         if (lds_form) {
             const long S = p.S, N = p.N, H = d.H, R = p.S + p.Qn, nt = w.ntile, h0c = h0 / P, h1 = p.h[1];
             ti.init(); tsx.init();
@@ -1815,9 +1920,18 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
             lds_form = !ti.bad && !tsx.bad && ti.nunits <= 64 * 8 && tsx.nunits <= 64 * 8;
         }
         if (lds_form) {
-            FUMI_SET_DYN_LDS(reverse_lds_kernel, rl.total * 4);
-            hipLaunchKernelGGL(reverse_lds_kernel, dim3(8 * ((p.B + 7) / 8) * P), dim3(512), rl.total * 4, st, ti, tsx, d, w, rl, P,
-                               p.loss_b, p.acc_b, p.head_bar);
+            auto launch = [&](auto tag) -> int {
+                constexpr auto kern = decltype(tag)::fn;
+                FUMI_SET_DYN_LDS(kern, rl.total * 4);
+                hipLaunchKernelGGL(kern, dim3(8 * ((p.B + 7) / 8) * P), dim3(512), rl.total * 4, st, ti, tsx, d, w, rl, P,
+                                   p.loss_b, p.acc_b, p.head_bar);
+                LAUNCH_CHECK();
+                return FUMI_OK;
+            };
+            if (fixed_r) g_epi_fixed_last |= 2;
+            if (fixed_r) rc = drop ? launch(KernTag<reverse_lds_kernel<true, true>>{}) : launch(KernTag<reverse_lds_kernel<true, false>>{});
+            else rc = launch(KernTag<reverse_lds_kernel<>>{});
+            if (rc) return rc;
         } else {
             FUMI_SET_DYN_LDS(reverse_kernel, w.lds_reverse * 4);
             hipLaunchKernelGGL(reverse_kernel, dim3(p.B), dim3(512), w.lds_reverse * 4, st, d, w, p.loss_b, p.acc_b, p.head_bar);
