@@ -157,6 +157,30 @@ __device__ __forceinline__ void adam_update1(float g, float& p, float& m, float&
     v = b2 * v + (1.f - b2) * gr * gr;
     p = p - lr_over_bc1 * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
 }
+// torch.optim.AdamW's update of one element (_single_tensor_adam with decoupled weight decay): the parameter shrinks by `decay` =
+// 1 - lr * weight_decay first, then Adam's moments and update on the RAW gradient.  decay, omb1 = 1 - beta1 and omb2 = 1 - beta2 are
+// folded on the host in double, as torch folds them in Python floats (1.f - 0.999f is off by 1.3e-5 of 0.001).  Same discipline.
+__device__ __forceinline__ void adamw_update1(float g, float& p, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2, float omb1,
+                                              float b2, float omb2, float eps, float decay) {
+#pragma clang fp contract(off)
+    p = p * decay;
+    m = m + omb1 * (g - m);
+    v = b2 * v + omb2 * g * g;
+    p = p - lr_over_bc1 * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
+}
+// torch.optim.SGD's update of one element (_single_tensor_sgd, dampening 0, no Nesterov): coupled L2 weight decay, then the momentum
+// buffer -- which IS the decayed gradient on a parameter's first step -- then the parameter.  Same discipline.
+__device__ __forceinline__ void sgd_momentum_update1(float g, float& p, float& buf, float lr, float momentum, float wd, bool first) {
+#pragma clang fp contract(off)
+    const float gr = g + wd * p;
+    buf = first ? gr : momentum * buf + gr;
+    p = p - lr * buf;
+}
+__device__ __forceinline__ void sgd_update1(float g, float& p, float lr, float wd) {                     // momentum == 0: no buffer
+#pragma clang fp contract(off)
+    const float gr = g + wd * p;
+    p = p - lr * gr;
+}
 #endif
 // One embedding-bag request (glove.hip / glove_bag.h): out[r, :] = pool over the L tokens of row r (select form: of the first support
 // row of class r % N of episode r / N) of table rows; a deferred one waits in the workspace for the next FuMI step (glove_flush
@@ -167,18 +191,37 @@ struct GloveArgs {
 };
 struct GlovePending { GloveArgs a; int on, vec; size_t lds; };
 int glove_flush(fumi_ws* ws, hipStream_t st);
-// A deferred Adam step (fumi_hip_adam_step_deferred): tensors by value, coefficients already folded (adam.hip)
+// The update rules of the fused optimizer step (adam.hip; folded form: gemm.hip) and the state streams each of them moves besides
+// the parameter and its gradient: Adam / AdamW two (exp_avg, exp_avg_sq), SGD one (momentum_buffer) or none (momentum == 0).
+enum OptRule { OPT_ADAM = 0, OPT_ADAMW = 1, OPT_SGD_MOMENTUM = 2, OPT_SGD = 3 };
+constexpr int opt_nstate(int rule) { return rule <= OPT_ADAMW ? 2 : rule == OPT_SGD_MOMENTUM ? 1 : 0; }
+// A rule's coefficients, folded on the host in double.  Adam / AdamW: lr = lr / bias_correction1, a = 1 / sqrt(bias_correction2),
+// wd = weight_decay (Adam) or 1 - lr * weight_decay (AdamW), omb1 / omb2 = 1 - beta1 / 1 - beta2 (AdamW; Adam's element function
+// subtracts in fp32 and keeps doing so).  SGD: lr, a = momentum, wd = weight_decay, first = 1 on the step that creates the momentum
+// buffers (they are written, not read).
+struct OptCoef { float lr, a, b1, b2, eps, wd, omb1, omb2; int first; };
+#ifdef __HIPCC__
+template <int RULE>
+__device__ __forceinline__ void opt_update1(float g, float& p, float& s0, float& s1, const OptCoef& c) {
+    if constexpr (RULE == OPT_ADAM) adam_update1(g, p, s0, s1, c.lr, c.a, c.b1, c.b2, c.eps, c.wd);
+    else if constexpr (RULE == OPT_ADAMW) adamw_update1(g, p, s0, s1, c.lr, c.a, c.omb1, c.b2, c.omb2, c.eps, c.wd);
+    else if constexpr (RULE == OPT_SGD_MOMENTUM) sgd_momentum_update1(g, p, s0, c.lr, c.a, c.wd, c.first != 0);
+    else sgd_update1(g, p, c.lr, c.wd);
+}
+#endif
+// A deferred optimizer step (fumi_hip_adam_step_deferred and its siblings): rule, tensors by value (s[i]: state stream i of the
+// rule), coefficients already folded (adam.hip)
 struct AdamPending {
-    int n, on;
-    float* p[32]; const float* g[32]; float* m[32]; float* v[32]; long numel[32];
-    float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, wd;
+    int n, on, rule;
+    float* p[32]; const float* g[32]; float* s[2][32]; long numel[32];
+    OptCoef c;
 };
 // The LAST launch of a training meta-step: the reduction `sg` (whose outputs are the gradients and the step's statistics) with,
-// when the workspace holds them and every gradient tensor of the pending optimizer step is one whole segment of `sg`, the Adam
-// update of each element right behind its gradient and the deferred publication of the statistics -- one launch instead of
+// when the workspace holds them and every gradient tensor of the pending optimizer step is one whole segment of `sg`, the pending
+// rule's update of each element right behind its gradient and the deferred publication of the statistics -- one launch instead of
 // three, same arithmetic in the same order (bit-identical parameters).  Falls back to the separate launches otherwise.
 int launch_reduce_multi_final(fumi_ws* ws, hipStream_t st, ReduceSegs& sg);
-int launch_adam_pending(fumi_ws* ws, hipStream_t st);       // the plain Adam launch of a still pending deferred step (adam.hip)
+int launch_adam_pending(fumi_ws* ws, hipStream_t st);       // the plain launch of a still pending deferred step, any rule (adam.hip)
 // out[n] = scale * sum_m X[m*ld + n]
 int launch_colsum(hipStream_t st, const float* X, int M, int N, long ld, float scale, float* out);
 // several column sums (bias gradients) in TWO launches: partial sums of 128-row chunks for every job, then one

@@ -227,16 +227,17 @@ __global__ void reduce_multi_kernel(ReduceSegs sg) {
     }
 }
 
-// reduce_multi + the optimizer step + the publication of the statistics (launch_reduce_multi_final).  ap[k] != NULL: segment k's
-// outputs are the gradient of a parameter tensor: p / m / v at the same offsets get torch.optim.Adam's update (the expressions of
-// adam_kernel, adam.hip, in the same order: bit-identical).  An output that lies in [pub_src, pub_src + pub_n) is also stored to
-// the pinned host buffer; the lane whose store is the last one (a device counter) stores the sequence word behind it.
-struct AdamSegs { float* p[24]; float* m[24]; float* v[24]; float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, wd; };
-__device__ __forceinline__ void adam1(float g, float& p, float& m, float& v, const AdamSegs& a) {
-    adam_update1(g, p, m, v, a.lr_over_bc1, a.inv_sqrt_bc2, a.b1, a.b2, a.eps, a.wd);
-}
-__global__ void reduce_multi_adam_kernel(ReduceSegs sg, AdamSegs ad, const float* pub_src, int pub_n, float* pub_dst,
-                                         unsigned long long pub_seq, int* pub_cnt) {
+// reduce_multi + the optimizer step + the publication of the statistics (launch_reduce_multi_final).  ad.p[k] != NULL: segment k's
+// outputs are the gradient of a parameter tensor: the parameter and the rule's state streams at the same offsets get the pending
+// rule's update (the expressions of optim_kernel, adam.hip, in the same order: bit-identical).  An output that lies in
+// [pub_src, pub_src + pub_n) is also stored to the pinned host buffer; the lane whose store is the last one (a device counter)
+// stores the sequence word behind it.
+template <int NS> struct OptSegs { float* p[24]; float* s[NS][24]; OptCoef c; };
+template <> struct OptSegs<0> { float* p[24]; OptCoef c; };
+template <int RULE>
+__global__ void reduce_multi_optim_kernel(ReduceSegs sg, OptSegs<opt_nstate(RULE)> ad, const float* pub_src, int pub_n, float* pub_dst,
+                                          unsigned long long pub_seq, int* pub_cnt) {
+    constexpr int NS = opt_nstate(RULE);
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= sg.end[sg.n - 1]) return;
     int k = 0;
@@ -244,42 +245,54 @@ __global__ void reduce_multi_adam_kernel(ReduceSegs sg, AdamSegs ad, const float
     const long u = i - (k ? sg.end[k - 1] : 0);
     const long st = sg.stride[k];
     const int ns = sg.nslab[k];
+    const bool rd0 = NS >= 1 && !(RULE == OPT_SGD_MOMENTUM && ad.c.first);  // (a momentum buffer's first step writes it only)
+    float* s0 = nullptr; float* s1 = nullptr;
+    if constexpr (NS >= 1) s0 = ad.s[0][k];
+    if constexpr (NS >= 2) s1 = ad.s[1][k];
     if (sg.vec[k]) {
         const float* src = sg.src[k] + 4 * u;
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
         int t = 0;
         for (; t + 3 < ns; t += 4) {
             const f32x4 a = *(const f32x4*)(src + t * st), b = *(const f32x4*)(src + (t + 1) * st);
             const f32x4 c = *(const f32x4*)(src + (t + 2) * st), d = *(const f32x4*)(src + (t + 3) * st);
-            s0 += a; s1 += b; s0 += c; s1 += d;
+            a0 += a; a1 += b; a0 += c; a1 += d;
         }
-        for (; t + 1 < ns; t += 2) { s0 += *(const f32x4*)(src + t * st); s1 += *(const f32x4*)(src + (t + 1) * st); }
-        if (t < ns) s0 += *(const f32x4*)(src + t * st);
-        const f32x4 g = sg.scale * (s0 + s1);
+        for (; t + 1 < ns; t += 2) { a0 += *(const f32x4*)(src + t * st); a1 += *(const f32x4*)(src + (t + 1) * st); }
+        if (t < ns) a0 += *(const f32x4*)(src + t * st);
+        const f32x4 g = sg.scale * (a0 + a1);
         *(f32x4*)(sg.dst[k] + 4 * u) = g;
         if (ad.p[k]) {
-            f32x4 pp = *(f32x4*)(ad.p[k] + 4 * u), mm = *(f32x4*)(ad.m[k] + 4 * u), vv = *(f32x4*)(ad.v[k] + 4 * u);
+            f32x4 pp = *(f32x4*)(ad.p[k] + 4 * u), aa = {0.f, 0.f, 0.f, 0.f}, bb = aa;
+            if (rd0) aa = *(f32x4*)(s0 + 4 * u);
+            if constexpr (NS >= 2) bb = *(f32x4*)(s1 + 4 * u);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float pe = pp[e], me = mm[e], ve = vv[e];
-                adam1(g[e], pe, me, ve, ad);
-                pp[e] = pe; mm[e] = me; vv[e] = ve;
+                float pe = pp[e], ae = aa[e], be = bb[e];
+                opt_update1<RULE>(g[e], pe, ae, be, ad.c);
+                pp[e] = pe; aa[e] = ae; bb[e] = be;
             }
-            *(f32x4*)(ad.p[k] + 4 * u) = pp; *(f32x4*)(ad.m[k] + 4 * u) = mm; *(f32x4*)(ad.v[k] + 4 * u) = vv;
+            *(f32x4*)(ad.p[k] + 4 * u) = pp;
+            if constexpr (NS >= 1) *(f32x4*)(s0 + 4 * u) = aa;
+            if constexpr (NS >= 2) *(f32x4*)(s1 + 4 * u) = bb;
         }
     } else {
         const float* src = sg.src[k] + u;
-        float s0 = 0.f, s1 = 0.f;
+        float a0 = 0.f, a1 = 0.f;
         int t = 0;
-        for (; t + 1 < ns; t += 2) { s0 += src[t * st]; s1 += src[(t + 1) * st]; }
-        if (t < ns) s0 += src[t * st];
-        const float g = sg.scale * (s0 + s1);
+        for (; t + 1 < ns; t += 2) { a0 += src[t * st]; a1 += src[(t + 1) * st]; }
+        if (t < ns) a0 += src[t * st];
+        const float g = sg.scale * (a0 + a1);
         float* d = sg.dst[k] + u;
         *d = g;
         if (ad.p[k]) {
-            float pp = ad.p[k][u], mm = ad.m[k][u], vv = ad.v[k][u];
-            adam1(g, pp, mm, vv, ad);
-            ad.p[k][u] = pp; ad.m[k][u] = mm; ad.v[k][u] = vv;
+            float pe = ad.p[k][u], ae = 0.f, be = 0.f;
+            if (rd0) ae = s0[u];
+            if constexpr (NS >= 2) be = s1[u];
+            opt_update1<RULE>(g, pe, ae, be, ad.c);
+            ad.p[k][u] = pe;
+            if constexpr (NS >= 1) s0[u] = ae;
+            if constexpr (NS >= 2) s1[u] = be;
         }
         if (pub_dst && d >= pub_src && d < pub_src + pub_n) {          // (the statistics are single-element segments)
             __hip_atomic_store(pub_dst + (d - pub_src), g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -290,6 +303,22 @@ __global__ void reduce_multi_adam_kernel(ReduceSegs sg, AdamSegs ad, const float
             }
         }
     }
+}
+
+// the folded launch for one rule: seg[k] = index of the pending step's tensor whose gradient segment k is, or -1
+template <int RULE> void launch_reduce_multi_optim(fumi_ws* ws, hipStream_t st, const ReduceSegs& sg, const AdamPending& ap, const int* seg) {
+    constexpr int NS = opt_nstate(RULE);
+    OptSegs<NS> ad; memset(&ad, 0, sizeof(ad));
+    for (int k = 0; k < sg.n; ++k) {
+        if (seg[k] < 0) continue;
+        ad.p[k] = ap.p[seg[k]];
+        if constexpr (NS >= 1) ad.s[0][k] = ap.s[0][seg[k]];
+        if constexpr (NS >= 2) ad.s[1][k] = ap.s[1][seg[k]];
+    }
+    ad.c = ap.c;
+    const long tot = sg.end[sg.n - 1];
+    hipLaunchKernelGGL(reduce_multi_optim_kernel<RULE>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sg, ad, ws->pub_src,
+                       ws->pub_n, ws->pub_dst, ws->pub_seq, ws->status + 48);
 }
 
 __global__ void colsum_kernel(const float* __restrict__ X, int M, int N, long ld, float scale, float* __restrict__ out) {
@@ -380,17 +409,18 @@ int launch_reduce_multi_final(fumi_ws* ws, hipStream_t st, ReduceSegs& sg) {
     static const int fuse_env = getenv("FUMI_ADAM_FUSE") ? atoi(getenv("FUMI_ADAM_FUSE")) : 1;
     // every gradient tensor of the pending step must be exactly one segment (whole tensor, from its first element); no other
     // segment may write into a gradient tensor; a pending publication must read single-element segments of this reduction only
-    AdamSegs ad; memset(&ad, 0, sizeof(ad));
-    bool ok = fuse_env != 0;
+    int seg[24];
+    bool ok = fuse_env != 0 && sg.n <= 24;
     int matched = 0, pub_found = 0;
     for (int k = 0; k < sg.n && ok; ++k) {
         const long cnt = (sg.end[k] - (k ? sg.end[k - 1] : 0)) * (sg.vec[k] ? 4 : 1);
         const float* d = sg.dst[k];
+        seg[k] = -1;
         for (int j = 0; j < ap->n; ++j) {
-            if (d == ap->g[j] && cnt == ap->numel[j]) { ad.p[k] = ap->p[j]; ad.m[k] = ap->m[j]; ad.v[k] = ap->v[j]; ++matched; break; }
+            if (d == ap->g[j] && cnt == ap->numel[j]) { seg[k] = j; ++matched; break; }
             if (d + cnt > ap->g[j] && d < ap->g[j] + ap->numel[j]) { ok = false; break; }            // partial cover: not this way
         }
-        if (ad.p[k] && sg.vec[k] && ((((uintptr_t)ad.p[k] | (uintptr_t)ad.m[k] | (uintptr_t)ad.v[k]) & 15) != 0)) ok = false;
+        if (seg[k] >= 0 && sg.vec[k] && ((((uintptr_t)ap->p[seg[k]] | (uintptr_t)ap->s[0][seg[k]] | (uintptr_t)ap->s[1][seg[k]]) & 15) != 0)) ok = false;
         if (ws->pub_dst && d >= ws->pub_src && d < ws->pub_src + ws->pub_n) { if (cnt == 1 && !sg.vec[k]) ++pub_found; else ok = false; }
     }
     ok = ok && matched == ap->n && (!ws->pub_dst || pub_found == ws->pub_n);
@@ -398,10 +428,13 @@ int launch_reduce_multi_final(fumi_ws* ws, hipStream_t st, ReduceSegs& sg) {
         int rc = launch_reduce_multi(st, sg);
         return rc ? rc : launch_adam_pending(ws, st);
     }
-    ad.lr_over_bc1 = ap->lr_over_bc1; ad.inv_sqrt_bc2 = ap->inv_sqrt_bc2; ad.b1 = ap->b1; ad.b2 = ap->b2; ad.eps = ap->eps; ad.wd = ap->wd;
-    const long tot = sg.end[sg.n - 1];
-    hipLaunchKernelGGL(reduce_multi_adam_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sg, ad, ws->pub_src, ws->pub_n,
-                       ws->pub_dst, ws->pub_seq, ws->status + 48);
+    switch (ap->rule) {
+        case OPT_ADAM: launch_reduce_multi_optim<OPT_ADAM>(ws, st, sg, *ap, seg); break;
+        case OPT_ADAMW: launch_reduce_multi_optim<OPT_ADAMW>(ws, st, sg, *ap, seg); break;
+        case OPT_SGD_MOMENTUM: launch_reduce_multi_optim<OPT_SGD_MOMENTUM>(ws, st, sg, *ap, seg); break;
+        case OPT_SGD: launch_reduce_multi_optim<OPT_SGD>(ws, st, sg, *ap, seg); break;
+        default: return FUMI_EINVAL;
+    }
     ap->on = 0;
     ws->pub_dst = nullptr; ws->pub_src = nullptr;          // (the publication rode along)
     LAUNCH_CHECK();

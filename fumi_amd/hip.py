@@ -23,6 +23,7 @@ SYMBOLS = [
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
     "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
+    "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
     "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_publish_scalars",
     "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics",
@@ -141,6 +142,11 @@ def lib():
         L.fumi_hip_adam_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_flush.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
+        betas = [c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int]       # lr, beta1, beta2 (doubles), eps, wd, step
+        L.fumi_hip_adamw_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + betas
+        L.fumi_hip_adamw_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + betas
+        L.fumi_hip_sgd_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 3 + [c_int]
+        L.fumi_hip_sgd_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 3 + [c_int]
         L.fumi_hip_linear_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int, c_void_p]
         L.fumi_hip_linear_bwd_data.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3
         L.fumi_hip_linear_bwd_weight.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4
@@ -682,10 +688,50 @@ def adam_step_deferred(ws, args, lr, beta1, beta2, eps, weight_decay, step):
 
 
 def adam_flush(ws, device):
-    """Launches a deferred Adam step no meta-step has folded; True when it had to."""
+    """Launches a deferred optimizer step (any rule) no meta-step has folded; True when it had to."""
     launched = c_int(0)
     _check(lib().fumi_hip_adam_flush(ws.handle, _stream(device), ctypes.byref(launched)), "fumi_hip_adam_flush")
     return bool(launched.value)
+
+
+def adamw_step(ws, args, lr, beta1, beta2, eps, weight_decay, step, device):
+    """torch.optim.AdamW's update (decoupled weight decay) on the same fused launch; ``args``: an ``AdamArgs``."""
+    rc = lib().fumi_hip_adamw_step(ws.handle, _stream(device), args.n, args.p, args.g, args.m, args.v, args.numel,
+                                   float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+    _check(rc, "fumi_hip_adamw_step")
+
+
+def adamw_step_deferred(ws, args, lr, beta1, beta2, eps, weight_decay, step):
+    rc = lib().fumi_hip_adamw_step_deferred(ws.handle, args.n, args.p, args.g, args.m, args.v, args.numel,
+                                            float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+    _check(rc, "fumi_hip_adamw_step_deferred")
+
+
+class SgdArgs:
+    """Cached pointer tables of one fused SGD call; ``bufs``: the momentum buffers, or None when momentum == 0."""
+
+    def __init__(self, params, grads, bufs):
+        self.n = len(params)
+        self.p, self.g = _parr(params, "params"), _parr(grads, "grads")
+        self.buf = _parr(bufs, "momentum_buffer") if bufs is not None else None
+        self.numel = (ctypes.c_long * self.n)(*[t.numel() for t in params])
+
+
+def sgd_step(ws, args, lr, momentum, weight_decay, first, device):
+    """torch.optim.SGD's update (dampening 0, no Nesterov) as one fused launch; ``first``: this step creates the momentum buffers."""
+    if (args.buf is None) != (momentum == 0):
+        raise FumiHipError("sgd_step: momentum buffers are needed exactly when momentum != 0")
+    rc = lib().fumi_hip_sgd_step(ws.handle, _stream(device), args.n, args.p, args.g, args.buf, args.numel,
+                                 float(lr), float(momentum), float(weight_decay), int(bool(first)))
+    _check(rc, "fumi_hip_sgd_step")
+
+
+def sgd_step_deferred(ws, args, lr, momentum, weight_decay, first):
+    if (args.buf is None) != (momentum == 0):
+        raise FumiHipError("sgd_step_deferred: momentum buffers are needed exactly when momentum != 0")
+    rc = lib().fumi_hip_sgd_step_deferred(ws.handle, args.n, args.p, args.g, args.buf, args.numel,
+                                          float(lr), float(momentum), float(weight_decay), int(bool(first)))
+    _check(rc, "fumi_hip_sgd_step_deferred")
 
 
 def linear_fwd(ws, x, W, b=None, act=0):
@@ -768,7 +814,7 @@ def gather_rows(ws, table, idx):
 def publish_scalars(ws, src, n, host_pinned, seq, defer=False):
     """One tiny launch on the current stream writes src[:n] and then the 64-bit word ``seq`` (byte offset 56) into the pinned
     host tensor ``host_pinned`` (>= 64 bytes) with system-scope stores: the host polls the word, no copy, no event.
-    ``defer``: the stores ride on the next ``adam_step`` launch of the workspace instead (``publish_flush`` issues them if
+    ``defer``: the stores ride on the next optimizer launch (``adam_step`` / ``adamw_step`` / ``sgd_step``) of the workspace instead (``publish_flush`` issues them if
     none comes)."""
     dev = _dev(src)
     if src.dtype != torch.float32 or not src.is_contiguous() or not host_pinned.is_pinned() or host_pinned.numel() * host_pinned.element_size() < 64:

@@ -1,27 +1,34 @@
-"""Optimizers for the outer loop.  ``Adam`` is torch.optim.Adam (same constructor, ``param_groups``, ``state_dict`` layout:
-``step`` / ``exp_avg`` / ``exp_avg_sq``) whose ``step()`` runs as ONE fused HIP launch over all parameter tensors when they
-are fp32 GPU tensors (csrc/adam.hip); any other configuration (amsgrad, maximize, CPU tensors, sparse grads ...) uses
-torch's own implementation unchanged."""
+"""Optimizers for the outer loop.  ``Adam``, ``AdamW`` and ``SGD`` are torch.optim's classes of the same names (same constructors,
+``param_groups``, ``state_dict`` layouts: ``step`` / ``exp_avg`` / ``exp_avg_sq``; ``momentum_buffer``) whose ``step()`` runs as ONE
+fused HIP launch over all parameter tensors when they are fp32 GPU tensors (csrc/adam.hip); any other configuration (amsgrad,
+maximize, nesterov, dampening, CPU tensors, sparse grads ...) uses torch's own implementation unchanged.  ``_FusedStep`` holds what
+the three share: the cached launch plans, ``step_fused`` / ``defer_step`` / ``finish_deferred`` and the bookkeeping around
+``state_dict`` / pickling; a class adds its rule's flags, state tensors and launch."""
+import copy
+
 import torch
 
 from . import hip
 
+MAX_TENSORS = 32          # one fused launch (csrc/adam.hip: MAXT)
+MAX_FOLDED = 24           # segments of the meta-step's final reduction (csrc/common.h: ReduceSegs)
 
-class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **kw):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
-        self._fused_args = {}
+
+class _FusedStep:
+    """Mixed in FRONT of a torch.optim class (``_torch_cls``).  A subclass provides ``_flags_ok(group, plan)`` (the rule covers this
+    group's options, and they still fit the cached plan if there is one), ``_plan(group, params, grads)`` (creates missing state
+    in torch's layout and returns the cached launch arguments, or None when torch must take the step) and
+    ``_launch(group, plan, device, deferred)``."""
+    _torch_cls = None
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._fused_args = {}                     # the moment tensors were replaced: rebuild the cached pointer tables (and counts)
+        self._fused_args = {}                     # the state tensors were replaced: rebuild the cached pointer tables (and counts)
 
     def _fusable(self, group, params):
-        return (params and not group.get("amsgrad") and not group.get("maximize") and not group.get("capturable")
-                and not group.get("differentiable") and len(params) <= 32
+        return (params and self._flags_ok(group) and len(params) <= MAX_TENSORS
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()
-                        and not p.grad.is_sparse and p.grad.dtype == torch.float32 for p in params)
-                and not isinstance(group["lr"], torch.Tensor))
+                        and not p.grad.is_sparse and p.grad.dtype == torch.float32 for p in params))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -40,29 +47,28 @@ class Adam(torch.optim.Adam):
             self._opt_called = True               # what the lr_scheduler's wrapper around step() records (its order check)
         with torch.no_grad():
             if not self._step_impl():
-                return torch.optim.Adam.step(self)
+                return self._torch_cls.step(self)
         return None
 
     def defer_step(self, device):
         """Registers this step with the device's workspace instead of launching it: the engine folds the update into the last
-        launch of the training meta-step that follows (``fumi_hip_adam_step_deferred``; single process only -- the caller checks).
-        True when registered; the caller then runs the meta-step and ``finish_deferred``.  False (nothing done) when the step
-        has to go the ordinary way: first step (no gradient views yet), several groups, hooks, a non-fusable configuration."""
+        launch of the training meta-step that follows (``fumi_hip_adam_step_deferred`` and its siblings; single process only --
+        the caller checks).  True when registered; the caller then runs the meta-step and ``finish_deferred``.  False (nothing
+        done) when the step has to go the ordinary way: first step (no gradient views yet), several groups, hooks, a
+        non-fusable configuration."""
         if self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(self.param_groups) != 1:
             return False
         group = self.param_groups[0]
         cached = self._fused_args.get(0)
         params = [p for p in group["params"] if p.grad is not None]
-        if cached is None or not params or len(params) > 24:
+        if cached is None or not params or len(params) > MAX_FOLDED:
             return False
         ident = tuple(p.data_ptr() for p in params) + tuple(p.grad.data_ptr() for p in params)
-        if cached.ident != ident or isinstance(group["lr"], torch.Tensor) or group.get("amsgrad") or group.get("maximize"):
+        if cached.ident != ident or not self._flags_ok(group, cached):
             return False
         if hasattr(self.step, "_wrapped_by_lr_sched"):
             self._opt_called = True
-        cached.count += 1
-        b1, b2 = group["betas"]
-        hip.adam_step_deferred(hip.Workspace.get(device), cached, group["lr"], b1, b2, group["eps"], group["weight_decay"], cached.count)
+        self._launch(group, cached, device, True)
         return True
 
     def finish_deferred(self, device):
@@ -74,8 +80,8 @@ class Adam(torch.optim.Adam):
         return super().state_dict()
 
     def _sync_steps(self):
-        """The per-parameter ``step`` tensors (torch.optim.Adam's state layout) are brought up to date lazily: the fused launch only
-        needs the count, and eight tiny tensor increments cost ~5 us of host time a step."""
+        """Per-parameter ``step`` tensors (Adam's and AdamW's state layout) are brought up to date lazily: the fused launch only
+        needs the count, and eight tiny tensor increments cost ~5 us of host time a step.  (SGD keeps no count.)"""
         for args in self._fused_args.values():
             lag = args.count - args.synced
             if lag:
@@ -93,8 +99,11 @@ class Adam(torch.optim.Adam):
         self._sync_steps()                        # pickling / deepcopy read optimizer.state directly
         return super().__getstate__()
 
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._fused_args = {}                     # (pointer tables are not pickled)
+
     def __deepcopy__(self, memo):
-        import copy
         self._sync_steps()
         cls = self.__class__
         new = cls.__new__(cls)
@@ -119,24 +128,117 @@ class Adam(torch.optim.Adam):
                     self._sync_steps()            # (the replaced entry's pending count goes into the `step` tensors first)
                 if not self._fusable(group, params):
                     return self._fall_back()
-                for p in params:
-                    st = self.state[p]
-                    if len(st) == 0:
-                        st["step"] = torch.tensor(0.0, dtype=torch.float32)        # same layout as torch.optim.Adam
-                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                ms = [self.state[p]["exp_avg"] for p in params]
-                vs = [self.state[p]["exp_avg_sq"] for p in params]
-                cached = self._fused_args[gi] = hip.AdamArgs(list(params), grads, ms, vs)
+                cached = self._plan(group, params, grads)
+                if cached is None:
+                    return self._fall_back()
+                self._fused_args[gi] = cached
                 cached.ident = ident
-                cached.steps = [self.state[p]["step"] for p in params]
-                cached.count = cached.synced = int(cached.steps[0])
                 cached.dev = params[0].device
-            elif isinstance(group["lr"], torch.Tensor) or group.get("amsgrad") or group.get("maximize"):
+            elif not self._flags_ok(group, cached):
                 return self._fall_back()
             plans.append((group, cached))
         for group, args in plans:
-            args.count += 1                                                     # (the `step` tensors follow in _sync_steps)
-            b1, b2 = group["betas"]
-            hip.adam_step(hip.Workspace.get(args.dev), args, group["lr"], b1, b2, group["eps"], group["weight_decay"], args.count, args.dev)
+            self._launch(group, args, args.dev, False)
         return True
+
+
+class _AdamRule(_FusedStep):
+    """Adam's and AdamW's state (``step``, ``exp_avg``, ``exp_avg_sq``) and launch; they differ in the kernel's rule only."""
+    _now = _later = None
+
+    def _flags_ok(self, group, plan=None):
+        return not (isinstance(group["lr"], torch.Tensor) or group.get("amsgrad") or group.get("maximize")
+                    or group.get("capturable") or group.get("differentiable"))
+
+    def _plan(self, group, params, grads):
+        for p in params:
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)        # same layout as torch.optim.Adam
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        ms = [self.state[p]["exp_avg"] for p in params]
+        vs = [self.state[p]["exp_avg_sq"] for p in params]
+        plan = hip.AdamArgs(list(params), grads, ms, vs)
+        plan.steps = [self.state[p]["step"] for p in params]
+        plan.count = plan.synced = int(plan.steps[0])
+        return plan
+
+    def _launch(self, group, plan, device, deferred):
+        plan.count += 1                                                         # (the `step` tensors follow in _sync_steps)
+        b1, b2 = group["betas"]
+        ws = hip.Workspace.get(device)
+        if deferred:
+            type(self)._later(ws, plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], plan.count)
+        else:
+            type(self)._now(ws, plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], plan.count, device)
+
+
+class Adam(_AdamRule, torch.optim.Adam):
+    _torch_cls = torch.optim.Adam
+    _now, _later = staticmethod(hip.adam_step), staticmethod(hip.adam_step_deferred)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+        self._fused_args = {}
+
+
+class AdamW(_AdamRule, torch.optim.AdamW):
+    """torch.optim.AdamW (decoupled weight decay, default 1e-2): what --optim adamw / adamw_lin_schedule construct.  A schedule
+    may rewrite ``group["lr"]`` before every step; the value is read at each launch, the deferred form included."""
+    _torch_cls = torch.optim.AdamW
+    _now, _later = staticmethod(hip.adamw_step), staticmethod(hip.adamw_step_deferred)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+        self._fused_args = {}
+
+    def _flags_ok(self, group, plan=None):
+        return super()._flags_ok(group) and bool(group.get("decoupled_weight_decay", True))
+
+
+class SGD(_FusedStep, torch.optim.SGD):
+    """torch.optim.SGD with momentum (dampening 0, no Nesterov) or without.  The step that creates the momentum buffers goes
+    through the fused kernel too (the buffers are written, not read); a group in which only some parameters have a buffer is
+    torch's."""
+    _torch_cls = torch.optim.SGD
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, **kw)
+        self._fused_args = {}
+
+    def _flags_ok(self, group, plan=None):
+        return (not (isinstance(group["lr"], torch.Tensor) or group.get("nesterov") or group.get("dampening") or group.get("maximize")
+                     or group.get("differentiable"))
+                and (plan is None or (group["momentum"] == 0) == (plan.buf is None)))   # (momentum switched on or off: a new plan)
+
+    def _sync_steps(self):
+        pass
+
+    def _plan(self, group, params, grads):
+        bufs, first = None, False
+        if group["momentum"] != 0:
+            have = [self.state[p].get("momentum_buffer") is not None for p in params]
+            if any(have) and not all(have):
+                return None
+            first = not have[0]
+            # (new buffers enter optimizer.state at the launch that fills them: another group may still hand this step to torch)
+            bufs = ([torch.empty_like(p, memory_format=torch.preserve_format) for p in params] if first
+                    else [self.state[p]["momentum_buffer"] for p in params])
+            if not all(b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() for b in bufs):
+                return None
+        plan = hip.SgdArgs(list(params), grads, bufs)
+        plan.first = first
+        plan.new_bufs = list(zip(params, bufs)) if first else None
+        return plan
+
+    def _launch(self, group, plan, device, deferred):
+        ws = hip.Workspace.get(device)
+        if deferred:
+            hip.sgd_step_deferred(ws, plan, group["lr"], group["momentum"], group["weight_decay"], plan.first)
+        else:
+            hip.sgd_step(ws, plan, group["lr"], group["momentum"], group["weight_decay"], plan.first, device)
+        if plan.first:
+            for p, b in plan.new_bufs:
+                self.state[p]["momentum_buffer"] = b
+            plan.first, plan.new_bufs = False, None

@@ -129,17 +129,17 @@ def _linear_warmup_schedule(opt, num_warmup_steps, num_training_steps):
 
 def init_optim(args, model):
     """Optimizer factory (utils.py:277-299); may return an (optimizer, scheduler) tuple."""
+    # torch.optim's classes whose step() is one fused HIP launch on the GPU (and folds into the FuMI meta-step's last launch)
+    from ..optim import SGD, Adam, AdamW
     if args.optim == "adam":
-        from ..optim import Adam            # torch.optim.Adam whose step() is one fused HIP launch on the GPU
         return Adam(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     if args.optim == "SGD":
-        return torch.optim.SGD(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
-                               momentum=args.momentum)
+        return SGD(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay, momentum=args.momentum)
     if args.optim == "adamw":
         # transformers.AdamW(lr) of the pinned 4.5.1: decoupled weight decay, default weight_decay 0.0
-        return torch.optim.AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
+        return AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
     if args.optim == "adamw_lin_schedule":
-        opt = torch.optim.AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
+        opt = AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
         return opt, _linear_warmup_schedule(opt, args.num_warmup_steps, args.epochs)
     raise NotImplementedError()
 

@@ -204,6 +204,29 @@ int fumi_hip_adam_step_deferred(fumi_ws_t* ws, int n_tensors, float* const* para
         const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const long* numel,
         float lr, float beta1, float beta2, float eps, float weight_decay, int step);
 int fumi_hip_adam_flush(fumi_ws_t* ws, fumi_stream_t stream, int* launched);
+/* The reference's other outer optimizers (fumi/utils/utils.py:284-299) on the same fused launch, each in the operation order of
+ * torch's single-tensor implementation.  AdamW = torch.optim.AdamW: every parameter shrinks by 1 - lr * weight_decay first, then
+ * Adam's moments and update on the raw gradient (no coupled L2 term); arguments as fumi_hip_adam_step, except that the betas are
+ * doubles: torch folds 1 - beta in Python floats, and 1 - 0.999f is off by 1.3e-5 of 0.001.  `lr` is a per-call scalar: a schedule
+ * may change it on every step, also in the deferred form. */
+int fumi_hip_adamw_step(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
+        const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const long* numel,
+        float lr, double beta1, double beta2, float eps, float weight_decay, int step);
+/* SGD = torch.optim.SGD(lr, momentum, weight_decay) with dampening 0 and no Nesterov: g += wd * p; buf = g when first_step != 0
+ * (the step that creates the momentum buffers: they are written, not read), else buf = momentum * buf + g; p -= lr * buf.
+ * momentum == 0: there is no buffer, momentum_buf may be NULL and p -= lr * g.  Up to 32 tensors, HOST pointer/size arrays. */
+int fumi_hip_sgd_step(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
+        const float* const* grads, float* const* momentum_buf, const long* numel,
+        float lr, float momentum, float weight_decay, int first_step);
+/* Their deferred forms, as fumi_hip_adam_step_deferred: folded into the last launch of the next meta-step of this workspace
+ * (bit-identical to the immediate form), or launched by fumi_hip_adam_flush, which flushes a pending step of ANY rule.  One step
+ * may be pending per workspace; a later registration replaces an earlier one that was never launched. */
+int fumi_hip_adamw_step_deferred(fumi_ws_t* ws, int n_tensors, float* const* params,
+        const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const long* numel,
+        float lr, double beta1, double beta2, float eps, float weight_decay, int step);
+int fumi_hip_sgd_step_deferred(fumi_ws_t* ws, int n_tensors, float* const* params,
+        const float* const* grads, float* const* momentum_buf, const long* numel,
+        float lr, float momentum, float weight_decay, int first_step);
 /* y[M,N] = act(x[M,K] W[N,K]^T + b[N]);  act: 0 none, 1 relu, 2 tanh.  b may be NULL. */
 int fumi_hip_linear_fwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int N, int K,
         const float* x, const float* W, const float* b, int act, float* y);
@@ -420,9 +443,9 @@ int fumi_hip_gather_rows(fumi_ws_t* ws, fumi_stream_t stream, const void* table,
  * an event (an async copy + event record idles the stream for ~10 us per step).  host_pinned: 64 bytes of page-locked,
  * device-accessible host memory (hipHostMalloc / a pinned torch tensor), 8-byte aligned. */
 int fumi_hip_publish_scalars(fumi_ws_t* ws, fumi_stream_t stream, const float* src, int n, void* host_pinned, uint64_t seq);
-/* Deferred form: the same stores ride on the next fumi_hip_adam_step launch of this workspace (the optimizer step that
- * follows a training meta-step: one launch less); fumi_hip_publish_flush issues them on their own if none came.  At most one
- * publication may be pending per workspace; src must stay valid and unchanged until it has been issued. */
+/* Deferred form: the same stores ride on the next fumi_hip_adam_step / _adamw_step / _sgd_step launch of this workspace (the optimizer
+ * step that follows a training meta-step: one launch less); fumi_hip_publish_flush issues them on their own if none came.  At most
+ * one publication may be pending per workspace; src must stay valid and unchanged until it has been issued. */
 int fumi_hip_publish_scalars_deferred(fumi_ws_t* ws, const float* src, int n, void* host_pinned, uint64_t seq);
 int fumi_hip_publish_flush(fumi_ws_t* ws, fumi_stream_t stream);
 
