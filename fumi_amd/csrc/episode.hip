@@ -1263,6 +1263,18 @@ __host__ __device__ constexpr void reverse_layout(RLay& y, int L, const int* h, 
 }
 constexpr RLay ref_rlay() { RLay y{}; const int h[MAXL] = {REF_H0, REF_H1}; reverse_layout(y, 2, h, REF_SP, REF_NP, REF_P); return y; }
 static_assert(ref_qlay().total <= QLDS_CAP && ref_rlay().total <= RLDS_CAP, "the reference layouts fit the CU's LDS");
+// reverse_lds_kernel<true, *> writes its staged images with one 16-byte LDS store per lane at fixed offsets: every image it stages
+// starts on a 16-byte boundary, the 64-column ones have the row stride of wg_ld(64), and the arena is a whole number of float4
+constexpr bool ref_rlay_ok() {
+    constexpr RLay y = ref_rlay();
+    const int v4[] = {y.Wb[1], y.W[1], y.bb[1], y.a[1], y.dz[1], y.ab[1], y.a[0], y.ab[0], y.dab0, y.Db, y.A0bs, y.Whb, y.Wh, y.b0b};
+    for (int o : v4) if (o & 3) return false;
+    return wg_ld(REF_H0 / REF_P) == 68 && wg_ld(REF_H1) == 68 && wg_ld(REF_NP) == 36 && y.ldX == 68 && (y.total & 3) == 0 &&
+           y.Wb[1] == 0 && y.W[1] == 64 * 68 && y.a[0] - y.ab[1] == REF_SP * 68 && y.Whb - y.X1 == REF_SP * 68 &&
+           y.bhb + q_r4(REF_NP) + 64 == y.total;
+}
+static_assert(ref_rlay_ok(), "the fixed-address staging of the reverse sweep assumes this layout");
+static_assert(REF_SP * REF_NP <= 512 && REF_NP * 16 <= 128, "one lane per staged element of p / e and per float4 of the head");
 
 template <bool FIX = false, bool DROP = true>
 __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, StageTab stg_step, EpiDims d_arg, EpiBuf w, RLay y_arg,
@@ -1317,12 +1329,86 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
         }
     };
 
-    wg_stage_tab_to_lds(s_stg, 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(RLay) + 64));
-    for (int i = tid * 4, tot = y.total; i < tot; i += nt * 4) *(f32x4*)(sm + i) = z4;
-    __syncthreads(); RSTAMP()
-    // adjoints after the query pass = sums of the tiles' partial slabs (this part's columns); G_ss
-    wg_stage_rows<3, 8>(&s_stg[0], b, 0, c, 0, sm);
-    wg_lds_barrier(); RSTAMP()
+    // (FIX: the staging is written out below, the tables are not read)
+    wg_stage_tab_to_lds(s_stg, FIX ? 0 : 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(RLay) + 64));
+    if constexpr (FIX) {
+        // Both stagings of the one round as fixed-address loads: every image is 64 columns wide, so
+        // lane l of the workgroup owns the float4 at row l >> 4 (+32 for the 64-row images), column 4 (l & 15) of each.  The
+        // loads are unconditional from clamped addresses and all issued before the arena is cleared; the tile slabs are
+        // summed in tile order 0, 1, ... exactly as wg_stage_rows<3, 8> does (same bits).  Masked at the LDS write.
+        static_assert(REF_H0 / REF_P == 64 && REF_H1 == 64 && REF_SP <= 32 && REF_NP <= 8, "one float4 per lane and 32-row pass");
+        constexpr int LD = wg_ld(64), LDN = wg_ld(REF_NP);
+        const int r = tid >> 4, c4 = (tid & 15) << 2;
+        const bool rS = r < S;
+        const long rc = rS ? r : 0;
+        const long ntl = ntile;
+        auto sum_tiles = [&](const float* p, long ss) {              // sum over the tiles' partial slabs, in tile order
+            f32x4 tk[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) tk[k] = *(const f32x4*)(p + (k < ntile ? k : 0) * ss);
+            f32x4 t = tk[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) if (k < ntile) t += tk[k];
+            return t;
+        };
+        // -- the adjoints after the query pass (G_ss is not staged: only the last Dbar update read it, see below)
+        const float* pW1 = w.pW[1] + ((long)b * ntl * REF_H1 + r) * REF_H0 + c0 + c4;
+        const f32x4 vWb0 = sum_tiles(pW1, (long)REF_H1 * REF_H0), vWb1 = sum_tiles(pW1 + 32 * REF_H0, (long)REF_H1 * REF_H0);
+        const f32x4 vDb = sum_tiles(w.pD + ((long)b * ntl * S + rc) * REF_H0 + c0 + c4, (long)S * REF_H0);
+        // the small ones share one load: lanes 0..127 the head's rows, 128..143 b0bar, 144..159 bbar_1; 160..167 bhbar (scalars)
+        const int sj = tid < 128 ? 0 : tid < 144 ? 1 : tid < 160 ? 2 : 3;
+        const bool sok = sj == 0 ? r < N : sj < 3;
+        const float* sp = sj == 1 ? w.pb0 + (long)b * ntl * REF_H0 + c0 + c4
+                        : sj == 2 ? w.pb[1] + (long)b * ntl * REF_H1 + c4
+                                  : w.pWh + ((long)b * ntl * N + (sj == 0 && r < N ? r : 0)) * REF_H1 + c4;
+        const long sss = sj == 1 ? REF_H0 : sj == 2 ? REF_H1 : (long)N * REF_H1;
+        const f32x4 vsm = sum_tiles(sp, sss);
+        const int nb = tid - 160;
+        const bool bok = nb >= 0 && nb < N;
+        float vbh;
+        {
+            const float* p = w.pbh + (long)b * ntl * N + (bok ? nb : 0);
+            float tk[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) tk[k] = p[(k < ntile ? k : 0) * (long)N];
+            vbh = tk[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) if (k < ntile) vbh += tk[k];
+        }
+        // -- the tape of the one inner step (one tape slot, two weight slots: T = 1)
+        const f32x4 va0 = *(const f32x4*)(w.ta[0] + ((long)b * S + rc) * REF_H0 + c0 + c4);
+        const float* pWs = w.Wslot[1] + ((long)b * 2 * REF_H1 + r) * REF_H0 + c0 + c4;
+        const f32x4 vW0 = *(const f32x4*)pWs, vW1 = *(const f32x4*)(pWs + 32 * REF_H0);
+        const f32x4 va1 = *(const f32x4*)(w.ta[1] + ((long)b * S + rc) * REF_H1 + c4);
+        const f32x4 vdz = *(const f32x4*)(w.tdz[1] + ((long)b * S + rc) * REF_H1 + c4);
+        const f32x4 vWh = *(const f32x4*)(w.Whslot + ((long)b * 2 * N + (r < N ? r : 0)) * REF_H1 + c4);
+        const bool pok = tid < S * N;
+        const long pi = (long)b * S * N + (pok ? tid : 0);
+        const float vp = w.tp[pi], ve = w.te[pi];
+        // the arena is cleared while the loads travel (K padding must be zero; abar_1 and abar_0 start from zero)
+        for (int i = tid * 4, tot = y.total; i < tot; i += nt * 4) *(f32x4*)(sm + i) = z4;
+        wg_lds_barrier(); RSTAMP()
+        *(f32x4*)(sm + y.Wb[1] + r * LD + c4) = vWb0; *(f32x4*)(sm + y.Wb[1] + (r + 32) * LD + c4) = vWb1;
+        *(f32x4*)(sm + y.W[1] + r * LD + c4) = vW0; *(f32x4*)(sm + y.W[1] + (r + 32) * LD + c4) = vW1;
+        if (rS) {
+            *(f32x4*)(sm + y.Db + r * LD + c4) = vDb;
+            *(f32x4*)(sm + y.a[0] + r * LD + c4) = va0;
+            *(f32x4*)(sm + y.dab0 + r * LD + c4) = relu_bwd4(va0, vDb);         // dab_0 = Dbar * relu'(z_0)
+            *(f32x4*)(sm + y.a[1] + r * LD + c4) = va1;
+            *(f32x4*)(sm + y.dz[1] + r * LD + c4) = vdz;
+        }
+        if (sok) *(f32x4*)(sm + (sj == 0 ? y.Whb + r * LD : sj == 1 ? y.b0b : y.bb[1]) + c4) = vsm;
+        if (bok) sm[y.bhb + nb] = vbh;
+        if (r < N) *(f32x4*)(sm + y.Wh + r * LD + c4) = vWh;
+        if (pok) { const int m = tid / N, n = tid - m * N; sm[y.p + m * LDN + n] = vp; sm[y.e + m * LDN + n] = ve; }
+        wg_lds_barrier(); RSTAMP()
+    } else {
+        for (int i = tid * 4, tot = y.total; i < tot; i += nt * 4) *(f32x4*)(sm + i) = z4;
+        __syncthreads(); RSTAMP()
+        // adjoints after the query pass = sums of the tiles' partial slabs (this part's columns); G_ss
+        wg_stage_rows<3, 8>(&s_stg[0], b, 0, c, 0, sm);
+        wg_lds_barrier(); RSTAMP()
+    }
 
     float* Wb1 = sm + y.Wb[1]; float* Db = sm + y.Db; float* A0bs = sm + y.A0bs; float* b0b = sm + y.b0b;
     float* Whb = sm + y.Whb; float* bhb = sm + y.bhb; float* cs = sm + y.cs;
@@ -1333,6 +1419,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
     if (d.second_order) {
         for (int t = d.T - 1; t >= 0; --t) {
             const int round = d.T - 1 - t;
+            if constexpr (!FIX) {                 // (FIX: the one round's tape, the zero abar_i and dab_0 are in place already)
             wg_stage_rows<8, 1>(&s_stg[1], b, t, c, 0, sm);
             wg_lds_barrier(); RSTAMP()
             // abar_i = 0 ; dab_0 = Dbar * relu'(z_0)
@@ -1342,6 +1429,7 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
                 *(f32x4*)(dab0 + m * ldc + n) = relu_bwd4(*(const f32x4*)(a0 + m * ldc + n), *(const f32x4*)(Db + m * ldc + n));
             });
             wg_lds_barrier(); RSTAMP()
+            }
             // ---- layer 1 (split): this part's share of dzbar_1, abar_0 -= alpha dz_1 Wbar_1
             const float* dz1 = sm + y.dz[1]; const int ld1 = ldh(1);
             wg_lmm<true, true>(S, h1, h0c, dab0, ldc, W1, ldc, [&](int m, int n, const f32x4& acc, int) { *(f32x4*)(Xa + m * ldX + n) = acc; });
@@ -1493,11 +1581,17 @@ __global__ __launch_bounds__(512) void reverse_lds_kernel(StageTab stg_init, Sta
                 float* pA = A0bs + m * ldc + n; *(f32x4*)pA = *(const f32x4*)pA + z;
             });
             wg_lds_barrier();
+            if constexpr (FIX) {
+                // Dbar is read at the top of the NEXT round only and is no output: in the last round (the only one here) its
+                // update -- the [S,S] x [S,h0c] product, the column-sum image it adds and G_ss -- is work nothing reads
+                wg_lcolsum(S, h0c, ab0, ldc, [&](int n, float s_) { b0b[n] += s_; });
+            } else {
             wg_lcolsum(S, h0c, ab0, ldc, [&](int n, float s_) { cs[n] = s_; b0b[n] += s_; });
             wg_lds_barrier();
             wg_lmm_wide<true>(S, h0c, S, G, ldS, ab0, ldc, [&](int m, int n, const f32x4& acc, int, auto) {
                 float* pd = Db + m * ldc + n; *(f32x4*)pd = *(const f32x4*)pd - alpha * (acc + *(const f32x4*)(cs + n));
             });
+            }
             wg_lds_barrier(); RSTAMP()
         }
     }
@@ -1888,7 +1982,10 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
             lds_form = P > 0;
         }
         // the fixed-shape sweep where the run-time one splits the same way (the sum over the parts depends on P)
-        const bool fixed_r = fixed && lds_form && P == REF_P;
+        // (its staging is 16-byte loads at fixed offsets from these arrays)
+        auto a16r = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+        const bool fixed_r = fixed && lds_form && P == REF_P && w.ntile <= 8 && a16r(w.pW[1]) && a16r(w.pD) && a16r(w.pb0) && a16r(w.pWh) &&
+                             a16r(w.pb[1]) && a16r(w.ta[0]) && a16r(w.ta[1]) && a16r(w.tdz[1]) && a16r(w.Wslot[1]) && a16r(w.Whslot);
         if (fixed_r) rl = ref_rlay();
         if (lds_form) {
             const long S = p.S, N = p.N, H = d.H, R = p.S + p.Qn, nt = w.ntile, h0c = h0 / P, h1 = p.h[1];
