@@ -480,6 +480,11 @@ __global__ __launch_bounds__(1024) void am3_head_kernel(int N, int S, int Qn, in
 
 }  // namespace
 
+// decisions of the last am3_step_impl of this process (fumi_hip_am3_step_plan): written on the host beside the launches, never read
+// by them
+struct Am3Plan { int fast_head, nwaves, hgq, imparts, xks, g_fwd_split, g_fwd_rode, h_fwd_split, h_bwd_fused, g_bwd_fused, tx_nparts; };
+static Am3Plan g_am3_last = {};
+
 // dx_s [B,S,D] / dx_q [B,Qn,D] (optional, need_grad): adjoints of the image rows, imbar Wi -- what an image encoder in front of
 // this step (the Conv4 backbone, fumi_hip_conv4_encode_bwd) continues from
 static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
@@ -545,6 +550,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     if (xks > 1) A((size_t)xks * (Rs + Rq) * P);
     int rc = ws_reserve(ws, bytes);
     if (rc) return rc;
+    g_am3_last = Am3Plan{fast_head ? 1 : 0, nwaves, hgq, 1, xks, 0, 0, 0, 0, 0, 0};
     float* im = ws_f(ws, (Rs + Rq) * P);          // image embeddings, [B, S+Qn, P]: an episode's support rows, then its query rows
     float* t1 = ws_f(ws, Rs * Ht);
     float* tx = ws_f(ws, Rs * P);
@@ -575,6 +581,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         if ((rc = launch_xpanel_fwd(st, B, S, Qn, D, P, x_s, x_q, Wi, im, nullptr, nullptr, g_split ? &fa : nullptr, &g_rode, xparts,
                                     fast_head ? &im_nparts : nullptr))) return rc;
         if (im_nparts > 1) { im_src = xparts; im_pstride = (long)(Rs + Rq) * P; }        // the head adds the parts where it reads rows
+        g_am3_last.imparts = im_nparts > 1 ? im_nparts : 1; g_am3_last.g_fwd_split = g_split ? 1 : 0; g_am3_last.g_fwd_rode = g_rode ? 1 : 0;
     }
     {
         ProfScope ps(ws, st, FUMI_PH_HYPER_FWD);
@@ -592,6 +599,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
             if (mlp_fused && Rs < (1 << 30) / Ht &&
                 hyper_fwd_split_args((int)Rs, P, Ht, 1, 2 /* sigmoid */, tx, H0, h0, H1, h1, l1, lamda_s, hfh, ws->hcnt, &fa)) {
                 fa.d.drop_thr = thr; fa.d.drop_key = dkey(2); fa.d.drop_scale = dsc;
+                g_am3_last.h_fwd_split = 1;
                 if ((rc = launch_hyper_fwd_split(st, fa))) return rc;
             } else {
                 g = gemm_args((int)Rs, Ht, P, tx, P, H0, P, l1, Ht); g.bias = h0; g.act = 1;
@@ -684,6 +692,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
                                               &tail_, &ba, l1b)) {
             // txbar += l1bar H0 leaves this launch as per-(row block, chunk) partials that g's backward adds while it stages txbar
             if (txparts && P <= HBW_XDT && (P & 3) == 0) { ba.A0 = H0; ba.xpart = txparts; tx_nparts = Ht / 64; }
+            g_am3_last.h_bwd_fused = 1; g_am3_last.tx_nparts = tx_nparts;
             if ((rc = launch_hyper_bwd_fused(st, ba))) return rc;                      // gH1, gh1, l1bar, gh0, gH0 (row-block slabs)
         } else {
             if ((rc = wgrad(1, Ht, zlb, 1, l1, Ht, g_w[8]))) return rc;                // gH1 = zlbar^T l1
@@ -706,6 +715,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     if (mlp_fused && hyper_bwd_fused_args((int)Rs, Dt, Ht, P, 0, dsc, text_s, t1, nullptr, txb, G1, hbg, nullptr, g_w[3], g_w[4], g_w[5],
                                           &tail_, &ba, t1b)) {
         if (tx_nparts) { ba.hbar_parts = txparts; ba.hbar_nparts = tx_nparts; }
+        g_am3_last.g_bwd_fused = 1;
         if ((rc = launch_hyper_bwd_fused(st, ba))) return rc;                          // gG1, gg1, t1bar, gg0 (row-block slabs)
     } else {
         if (tx_nparts) return FUMI_EINVAL;                                             // (cannot happen: probed above)
@@ -760,6 +770,14 @@ extern "C" int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
     if (need_grad && (!dx_s || !dx_q)) return FUMI_EINVAL;
     return am3_step_impl(ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
                          text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q);
+}
+
+extern "C" int fumi_hip_am3_step_plan(int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    const int v[11] = {g_am3_last.fast_head, g_am3_last.nwaves, g_am3_last.hgq, g_am3_last.imparts, g_am3_last.xks, g_am3_last.g_fwd_split,
+                       g_am3_last.g_fwd_rode, g_am3_last.h_fwd_split, g_am3_last.h_bwd_fused, g_am3_last.g_bwd_fused, g_am3_last.tx_nparts};
+    for (int i = 0; i < n && i < 11; ++i) plan[i] = v[i];
+    return FUMI_OK;
 }
 
 // ---- accuracy and macro precision / recall / F1 from the confusion matrix (what the reference asks sklearn for on the host

@@ -26,7 +26,7 @@ SYMBOLS = [
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
     "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_publish_scalars",
-    "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics",
+    "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics", "fumi_hip_am3_step_plan",
     "fumi_hip_conv4_feature_dim", "fumi_hip_fumi_conv4_step", "fumi_hip_maml_conv4_step", "fumi_hip_conv4_probe", "fumi_hip_conv4_features", "fumi_hip_conv4_set_option",
     "fumi_hip_conv4_encode", "fumi_hip_conv4_encode_bwd", "fumi_hip_am3_step_dx",
     "fumi_hip_resnet12_set_budget", "fumi_hip_fumi_resnet12_step", "fumi_hip_maml_resnet12_step", "fumi_hip_resnet12_features",
@@ -178,6 +178,7 @@ def lib():
                                                                                   c_int])
         L.fumi_hip_resnet12_encode_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [PI] + [c_void_p] * 4 + [c_float, PP]
         L.fumi_hip_resnet12_encode_plan.argtypes = [POINTER(c_int)] * 3
+        L.fumi_hip_am3_step_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_rn12_conv.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4
         L.fumi_hip_rn12_wgrad.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3
         L.fumi_hip_resnet12_set_option.argtypes = [c_int, c_int]
@@ -575,6 +576,17 @@ def am3_step(ws, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed=None, *, need
     else:
         _check(L.fumi_hip_am3_step(*args), "fumi_hip_am3_step")
     return dict(loss=loss, preds=preds, lamda_s=lam, correct=correct, grads=g_w, stats=stats, dx_s=dx_s, dx_q=dx_q)
+
+
+AM3_PLAN_KEYS = ["fast_head", "nwaves", "hgq", "imparts", "xks", "g_fwd_split", "g_fwd_rode", "h_fwd_split", "h_bwd_fused",
+                 "g_bwd_fused", "tx_nparts"]
+
+
+def am3_step_plan():
+    """dict over AM3_PLAN_KEYS: the form the last ``am3_step`` of this process took (fumi_hip_am3_step_plan)."""
+    v = (c_int * len(AM3_PLAN_KEYS))()
+    _check(lib().fumi_hip_am3_step_plan(v, len(AM3_PLAN_KEYS)), "fumi_hip_am3_step_plan")
+    return {k: int(x) for k, x in zip(AM3_PLAN_KEYS, v)}
 
 
 def am3_metrics(ws, n_way, stats):

@@ -165,6 +165,12 @@ int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
  * AM3.evaluate returns per meta-batch (am3.py:203-212 via sklearn on the host, utils.py:319-326), without leaving the device.
  * N <= 64. */
 int fumi_hip_am3_metrics(fumi_ws_t* ws, fumi_stream_t stream, int N, const float* stats, float* out6);
+/* Which form the last fumi_hip_am3_step / _dx of this process took (csrc/am3.hip, am3_step_impl; DESIGN.md "AM3 form tree"): the first
+ * min(n, 11) of  [fast head (1) or generic head (0), waves of the head workgroup, query shares per episode, image-encoder parts the
+ * head adds where it reads (1 = none), contraction parts of the image-encoder pass, g forward in the split form, g forward inside
+ * the X-panel launch, h forward in the split form, h backward fused, g backward fused, partials of txbar += l1bar H0 handed from h's
+ * backward to g's (0 = the GEMM)].  The backward entries are 0 after a call with need_grad = 0.  Recording changes no launch. */
+int fumi_hip_am3_step_plan(int* plan, int n);
 
 /* ---- finer-grained ops (unit parity tests; building blocks of the steps) --------------------------------------- */
 /* out[r,:] = mean (mode 0: sum / #non-PAD tokens) or max (mode 1: over ALL L positions) of table[tok[r,l],:]. */
