@@ -12,7 +12,12 @@ HBM), the per-class image lists (CSR) and the per-class text rows stay on the de
 
 with the class-major order / categorical labels of torchmeta's ConcatTask.  Sampling is reproducible from (seed, step).
 ``zero_copy=True`` hands the FuMI engine ``hip.RowRef``s (table + indices) in place of the gathered image rows: the X-panel
-kernels then read the rows where they lie in the table (fumi_hip_fumi_step_indexed)."""
+kernels then read the rows where they lie in the table (fumi_hip_fumi_step_indexed).
+
+Raw images (--im_encoder conv4 / resnet12): ``images`` is a uint8 pixel table [n_images, C, H, W] that stays uint8 in HBM; the
+same episode kernels draw the indices, and one ``fumi_hip_gather_images`` launch per index list gathers, augments (random crop
+out of the zero-padded image, horizontal flip, colour jitter -- ``augment``) and normalises the pixels into the fp32
+[B, rows, C, H, W] batch the encoders take (csrc/imgather.hip)."""
 import numpy as np
 import torch
 
@@ -21,7 +26,8 @@ from .. import hip
 
 class GpuEpisodeSampler:
     def __init__(self, images, class_of_image, class_text, num_ways, num_shots, num_shots_test, batch_size, seed=123,
-                 length=None, zero_copy=False, row_ids=None, skip_small_classes=None, torchmeta_tasks=False):
+                 length=None, zero_copy=False, row_ids=None, skip_small_classes=None, torchmeta_tasks=False, normalize=None,
+                 augment=None):
         """images [n_images, D] fp32 (moved to the device once), class_of_image [n_images] ints (category of every row, as
         inat_anim.json's annotations give it), class_text [C, Dt] fp32 or [C, L] int64 tokens (one row per class: the text of
         a sample is its class description, data.py:543-549).  row_ids [n_images] ints: the id reported for every table row in
@@ -33,7 +39,26 @@ class GpuEpisodeSampler:
         strict and raises up front.
         torchmeta_tasks=True reproduces torchmeta's task semantics: the class slots of a task get a
         random permutation of the labels 0..N-1 (Categorical) and a class tuple drawn again has the same support / query
-        members (ClassSplitter seeds its shuffle with hash(task) + seed); False keeps label n for slot n."""
+        members (ClassSplitter seeds its shuffle with hash(task) + seed); False keeps label n for slot n.
+        A 4-d uint8 ``images`` [n_images, C, H, W] is a pixel table: normalize=(mean, std), C floats each on the [0, 1] pixel
+        scale (default: 0 and 1), augment=None | dict(pad=, flip=, jitter=) as hip.gather_images takes them."""
+        self.pixels = images.dim() == 4
+        if self.pixels:
+            if images.dtype != torch.uint8:
+                raise ValueError(f"a pixel table [n_images, C, H, W] must be uint8, got {images.dtype}")
+            if zero_copy:
+                raise ValueError("zero_copy=True hands out rows of an fp32 embedding table; a uint8 pixel table is always gathered")
+            C_img = int(images.shape[1])
+            mean, std = normalize if normalize is not None else ((0.0,) * C_img, (1.0,) * C_img)
+            self.mean, self.std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
+            if len(self.mean) != C_img or len(self.std) != C_img or min(self.std) <= 0:
+                raise ValueError(f"normalize needs {C_img} means and {C_img} positive standard deviations")
+            aug = dict(augment or {})
+            self.augment = dict(pad=int(aug.pop("pad", 0)), flip=bool(aug.pop("flip", False)), jitter=aug.pop("jitter", (0, 0, 0)))
+            if aug:
+                raise ValueError(f"unknown augment keys {sorted(aug)}")
+        elif normalize is not None or augment is not None:
+            raise ValueError("normalize / augment apply to a uint8 pixel table [n_images, C, H, W] only")
         coi = np.asarray(class_of_image, dtype=np.int64)
         C = int(class_text.shape[0])
         if coi.min() < 0 or coi.max() >= C or len(coi) != images.shape[0]:
@@ -66,7 +91,7 @@ class GpuEpisodeSampler:
         self.class_ptr_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.class_items_host = order.astype(np.int64)
         self.dev = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.images = images.to(self.dev, torch.float32).contiguous()
+        self.images = images.to(self.dev).contiguous() if self.pixels else images.to(self.dev, torch.float32).contiguous()
         self.class_ptr = torch.from_numpy(self.class_ptr_host).to(self.dev)
         self.class_items = torch.from_numpy(self.class_items_host).to(self.dev)
         self.class_text = class_text.to(self.dev).contiguous()
@@ -92,7 +117,12 @@ class GpuEpisodeSampler:
             y_s, y_q = lab.repeat_interleave(K, dim=1), lab.repeat_interleave(Q, dim=1)
         else:
             cls, it_s, it_q = hip.sample_episodes(self.ws, self.seed, step, B, N, K, Q, self.class_ptr, self.class_items)
-        if self.zero_copy:
+        if self.pixels:
+            img = lambda it, sid: hip.gather_images(self.ws, self.images, it.view(-1), self.mean, self.std, seed=self.seed, step=step,
+                                                    stream_id=sid, **self.augment)
+            x_s = img(it_s, 0).view(B, N * K, *self.images.shape[1:])
+            x_q = img(it_q, 1).view(B, N * Q, *self.images.shape[1:])
+        elif self.zero_copy:
             x_s, x_q = hip.RowRef(self.images, it_s.view(B, N * K)), hip.RowRef(self.images, it_q.view(B, N * Q))
         else:
             x_s = hip.gather_rows(self.ws, self.images, it_s.view(-1)).view(B, N * K, -1)

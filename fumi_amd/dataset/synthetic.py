@@ -76,7 +76,8 @@ def get_synthetic_resident(args, images_per_class=48):
     """``--dataset synthetic-resident``: the same learnable task family as ``synthetic``, but as a FIXED table of image
     embeddings per split (n_classes x images_per_class rows) that lives in HBM and is sampled by the GPU-resident episode
     sampler (fumi_amd/dataset/gpu_sampler.py) -- the shape of the real pipeline (precomputed embeddings + class descriptions)
-    without the files.  Needs a GPU."""
+    without the files.  With ``--im_encoder conv4 | resnet12`` the table holds uint8 pixels ([n, C, H, W], the host loader's image
+    form mapped into 0..255) and the sampler gathers, augments (``--augment``) and normalises them on the device.  Needs a GPU."""
     from .gpu_sampler import GpuEpisodeSampler
     tokens, dictionary = None, None
     if args.text_encoder in ("glove", "w2v"):
@@ -86,6 +87,8 @@ def get_synthetic_resident(args, images_per_class=48):
         dictionary.update({f"tok{i}": i for i in range(1, V)})
     q_eval = int(100 / args.num_ways)
     per = max(images_per_class, args.num_shots + max(args.num_shots_test, q_eval))
+    if getattr(args, "im_encoder", "") in ("conv4", "resnet12"):
+        return _synthetic_resident_images(args, per, tokens, q_eval) + (dictionary,)
 
     def mk(split, q):
         base = SyntheticEpisodes(args.synthetic_classes, args.im_emb_dim, args.text_emb_dim, args.num_ways, args.num_shots, q,
@@ -96,6 +99,76 @@ def get_synthetic_resident(args, images_per_class=48):
         return GpuEpisodeSampler(torch.from_numpy(images.astype(np.float32)).to(args.device), coi, torch.from_numpy(base.text),
                                  args.num_ways, args.num_shots, q, args.batch_size, seed=args.seed + len(split))
     return mk("train", args.num_shots_test), mk("val", q_eval), mk("test", q_eval), dictionary
+
+
+PIXEL_RANGE = 8.0      # the image form's values (prototype N(0, 1) + 2 N(0, 1): sigma 2.24) map affinely from [-8, 8] onto 0..255
+
+
+def synthetic_pixel_table(base, per, rs):
+    """uint8 [n_classes * per, C, H, W] + the class of every image: ``SyntheticEpisodes``' image form (class prototype pattern plus
+    noise) mapped affinely into 0..255 and rounded, one class at a time (the fp32 form of a whole split is never held)."""
+    n_classes = len(base.mu)
+    table = np.empty((n_classes * per,) + tuple(base.image_shape), dtype=np.uint8)
+    for c in range(n_classes):
+        x = base.mu[c] + 2.0 * rs.standard_normal((per, base.D)).astype(np.float32)
+        u = np.clip(np.rint((x + PIXEL_RANGE) * (255.0 / (2 * PIXEL_RANGE))), 0, 255).astype(np.uint8)
+        table[c * per:(c + 1) * per] = u.reshape((per,) + tuple(base.image_shape))
+    return table, np.repeat(np.arange(n_classes), per)
+
+
+def pixel_statistics(table, chunk=4096):
+    """Per-channel mean and standard deviation of a device uint8 table [n, C, H, W] on the [0, 1] pixel scale (computed once, on
+    the device, in float64 sums)."""
+    C = table.shape[1]
+    s1 = torch.zeros(C, dtype=torch.float64, device=table.device)
+    s2 = torch.zeros(C, dtype=torch.float64, device=table.device)
+    for i in range(0, table.shape[0], chunk):
+        x = table[i:i + chunk].to(torch.float64) / 255.0
+        s1 += x.sum(dim=(0, 2, 3))
+        s2 += (x * x).sum(dim=(0, 2, 3))
+    n = table.shape[0] * table.shape[2] * table.shape[3]
+    mean = s1 / n
+    std = (s2 / n - mean * mean).clamp_min(0).sqrt().clamp_min(1e-6)
+    return tuple(mean.tolist()), tuple(std.tolist())
+
+
+def image_normalization(args, train_table):
+    """--image_mean / --image_std, or the train table's own per-channel statistics (used for all three splits)."""
+    C = train_table.shape[1]
+    mean, std = getattr(args, "image_mean", None), getattr(args, "image_std", None)
+    if mean is None or std is None:
+        m, s = pixel_statistics(train_table)
+        mean, std = (m if mean is None else mean), (s if std is None else std)
+    spread = lambda v: tuple(float(x) for x in (list(v) * C if len(v) == 1 else v))      # one value serves every channel
+    mean, std = spread(mean), spread(std)
+    if len(mean) != C or len(std) != C:
+        raise ValueError(f"--image_mean / --image_std need one value or {C} (one per channel)")
+    return mean, std
+
+
+def train_augmentation(args):
+    """--augment for a pixel table: random crop out of the zero-padded image, horizontal flip, colour jitter (three channels only);
+    None without the flag."""
+    if not getattr(args, "augment", False):
+        return None
+    j = float(args.augment_jitter) if args.image_channels == 3 else 0.0
+    return dict(pad=int(args.augment_pad), flip=True, jitter=(j, j, j))
+
+
+def _synthetic_resident_images(args, per, tokens, q_eval):
+    """``--dataset synthetic-resident`` with an image encoder: a uint8 pixel table per split, resident in HBM."""
+    from .gpu_sampler import GpuEpisodeSampler
+    shape = (args.image_channels, args.image_size, args.image_size)
+    tables = {}
+    for split in ("train", "val", "test"):
+        base = SyntheticEpisodes(args.synthetic_classes, args.im_emb_dim, args.text_emb_dim, args.num_ways, args.num_shots, 1,
+                                 args.batch_size, args.seed, split, tokens, image_shape=shape)
+        table, coi = synthetic_pixel_table(base, per, np.random.RandomState(args.seed * 13 + len(split)))
+        tables[split] = (torch.from_numpy(table).to(args.device), coi, torch.from_numpy(base.text))
+    norm = image_normalization(args, tables["train"][0])
+    mk = lambda split, q, aug: GpuEpisodeSampler(*tables[split], args.num_ways, args.num_shots, q, args.batch_size,
+                                                 seed=args.seed + len(split), normalize=norm, augment=aug)
+    return mk("train", args.num_shots_test, train_augmentation(args)), mk("val", q_eval, None), mk("test", q_eval, None)
 
 
 class SyntheticSupervised:

@@ -25,7 +25,7 @@ SYMBOLS = [
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
-    "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_publish_scalars",
+    "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_gather_images", "fumi_hip_publish_scalars",
     "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics", "fumi_hip_am3_step_plan",
     "fumi_hip_conv4_feature_dim", "fumi_hip_fumi_conv4_step", "fumi_hip_maml_conv4_step", "fumi_hip_conv4_probe", "fumi_hip_conv4_features", "fumi_hip_conv4_set_option",
     "fumi_hip_conv4_encode", "fumi_hip_conv4_encode_bwd", "fumi_hip_am3_step_dx",
@@ -154,6 +154,9 @@ def lib():
         L.fumi_hip_sample_episodes_tm.argtypes = ([c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64] + [c_int] * 5 + [c_void_p] * 2
                                                   + [c_int] + [c_void_p] * 4)
         L.fumi_hip_gather_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]
+        L.fumi_hip_gather_images.argtypes = ([c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
+                                              POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int]
+                                             + [c_float] * 3 + [c_void_p])
         L.fumi_hip_publish_scalars.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_uint64]
         L.fumi_hip_publish_scalars_deferred.argtypes = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_uint64]
         L.fumi_hip_publish_flush.argtypes = [c_void_p, c_void_p]
@@ -820,6 +823,37 @@ def gather_rows(ws, table, idx):
     out = torch.empty(idx.numel(), table.shape[1], device=dev, dtype=table.dtype)
     _check(lib().fumi_hip_gather_rows(ws.handle, _stream(dev), ctypes.c_void_p(table.data_ptr()), table.shape[0], row_bytes,
                                       _i64(idx, "idx"), idx.numel(), ctypes.c_void_p(out.data_ptr())), "fumi_hip_gather_rows")
+    return out
+
+
+def gather_images(ws, table, idx, mean, std, *, seed=0, step=0, stream_id=0, pad=0, flip=False, jitter=(0, 0, 0)):
+    """out[i] = normalise(jitter(flip(crop(table[idx[i]])))) (csrc/imgather.hip): ``table`` uint8 [n_images, C, H, W] on the device,
+    ``idx`` int64 (any shape, read flat), ``mean`` / ``std`` C floats of the [0, 1] pixel scale -> float32 [n_idx, C, H, W].
+    ``pad`` > 0: random crop out of the zero-padded image; ``flip``: random horizontal flip; ``jitter``: one amplitude or
+    (brightness, contrast, saturation) in [0, 1] (C == 3).  The draws are a function of (seed, step, stream_id, position in idx)."""
+    dev = _dev(table)
+    if (table.dim() != 4 or table.dtype != torch.uint8 or not table.is_contiguous() or not isinstance(idx, torch.Tensor)
+            or table.device != idx.device or idx.dtype != torch.int64):
+        raise FumiHipError("gather_images: table must be a contiguous uint8 [n_images, C, H, W] device tensor and idx an int64 "
+                           f"tensor on the same device; got {table.dtype} {tuple(table.shape)}")
+    n_images, C, H, W = (int(s) for s in table.shape)
+    if n_images < 1:
+        raise FumiHipError("gather_images: the table is empty")
+    jit = (jitter,) * 3 if isinstance(jitter, (int, float)) else tuple(jitter)
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C or len(jit) != 3:
+        raise FumiHipError(f"gather_images: mean and std need {C} entries each and jitter three")
+    import numpy as np
+    inv = np.float32(1.0) / np.asarray(std, dtype=np.float32)               # the kernel multiplies: 1 / std rounded once, in fp32
+    idx = idx.contiguous()
+    out = torch.empty(idx.numel(), C, H, W, device=dev, dtype=torch.float32)
+    if idx.numel() == 0:
+        return out
+    _check(lib().fumi_hip_gather_images(ws.handle, _stream(dev), c_void_p(table.data_ptr()), n_images, C, H, W, _i64(idx, "idx"),
+                                        idx.numel(), (c_float * C)(*mean), (c_float * C)(*[float(v) for v in inv]),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(stream_id), int(pad),
+                                        int(bool(flip)), float(jit[0]), float(jit[1]), float(jit[2]), _f32(out, "out")),
+           "fumi_hip_gather_images")
     return out
 
 

@@ -6,7 +6,8 @@
 Same flags (fumi_amd/utils/utils.py), same flag validation and error types, same train -> test flow and logged
 metrics.  ``--dataset inat-anim`` reads the reference's files (inat_anim.json + image_embeddings_<model>.hdf5 / .npy) into
 HBM-resident tables (fumi_amd/dataset/inat_anim.py) and raises FileNotFoundError when they are absent; ``--dataset
-synthetic`` / ``synthetic-resident`` have the same batch contract and need no files."""
+synthetic`` / ``synthetic-resident`` have the same batch contract and need no files; ``--dataset image-npy`` reads uint8
+pixels (fumi_amd/dataset/image_table.py) into an HBM-resident table for ``--im_encoder conv4 | resnet12``."""
 import os
 import random
 import sys
@@ -38,6 +39,9 @@ def get_dataset(args):
     if args.dataset == "inat-anim":                # the reference's files (fumi/dataset/data.py) -> HBM-resident tables
         from .dataset.inat_anim import get_inat_anim
         return get_inat_anim(args)
+    if args.dataset == "image-npy":                # uint8 pixels from {split}_images.npy -> HBM-resident tables, sampled on the GPU
+        from .dataset.image_table import get_image_npy
+        return get_image_npy(args)
     raise NotImplementedError()                    # data.py:73-74 ('cub' needs a torchmeta download, 'supervised-inat-anim' is CLIP's)
 
 
@@ -81,6 +85,10 @@ def main(args):
     _check_embedding_flags(args)
 
     train_loader, val_loader, test_loader, dictionary = get_dataset(args)
+    if args.augment and not getattr(train_loader, "pixels", False):
+        # the reference parses --augment and never reads it; here it acts on a resident pixel table only
+        print("--augment is ignored: it applies to a GPU-resident pixel table (--dataset synthetic-resident / image-npy with "
+              "--im_encoder conv4 | resnet12), not to embeddings or the host loader")
     max_test_batches = int(args.num_ep_test / args.batch_size)
     for seed_fn in (torch.manual_seed, np.random.seed, random.seed):
         seed_fn(args.seed)

@@ -18,7 +18,7 @@ from .wandb_compat import wandb
 _FLAGS = [
     ("--wandb_entity", dict(type=str, default="multimodal-image-cls", help="W&B entity")),
     ("--wandb_project", dict(type=str, default="fumi", help="W&B project")),
-    ("--dataset", dict(type=str, default="inat-anim", help="Dataset to use (inat-anim, supervised-inat-anim, synthetic, synthetic-resident)")),
+    ("--dataset", dict(type=str, default="inat-anim", help="Dataset to use (inat-anim, supervised-inat-anim, synthetic, synthetic-resident, image-npy)")),
     ("--data_dir", dict(type=str, default="./data", help="Directory to use for data")),
     ("--checkpoint", dict(type=str, default=None, help="Path to pretrained model (a best.pth.tar file, or a W&B run id when wandb is installed)")),
     ("--log_dir", dict(type=str, default="./results", help="Directory to use for results")),
@@ -78,6 +78,10 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--synthetic_seq_len", dict(type=int, default=32, help="[synthetic dataset] token sequence length")),
     ("--image_size", dict(type=int, default=84, help="[--im_encoder conv4 / resnet12] height = width of the input images")),
     ("--image_channels", dict(type=int, default=3, help="[--im_encoder conv4 / resnet12] input channels (conv4: 1-3, resnet12: 1-8)")),
+    ("--augment_pad", dict(type=int, default=8, help="[--augment on a resident pixel table] zero padding of the random crop (0-64)")),
+    ("--augment_jitter", dict(type=float, default=0.4, help="[--augment on a resident pixel table] amplitude of the brightness / contrast / saturation jitter (0-1; three-channel images)")),
+    ("--image_mean", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel mean on the 0..1 pixel scale (default: the train table's own)")),
+    ("--image_std", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel standard deviation on the 0..1 pixel scale (default: the train table's own)")),
 ]
 
 

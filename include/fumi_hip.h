@@ -442,6 +442,24 @@ int fumi_hip_sample_episodes_tm(fumi_ws_t* ws, fumi_stream_t stream, uint64_t se
         int64_t* items_s, int64_t* items_q);
 int fumi_hip_gather_rows(fumi_ws_t* ws, fumi_stream_t stream, const void* table, int64_t n_rows, int64_t row_bytes,
         const int64_t* idx, int64_t n_idx, void* out);
+/* gather_images (csrc/imgather.hip): out[i] = normalise(jitter(flip(crop(zero_pad(table[idx[i]]))))) -- n_idx images of a device
+ *   table uint8 [n_images, C, H, W] (planar) into float [n_idx, C, H, W], one launch, nothing on the host.  mean / inv_std are
+ *   HOST arrays of C floats.  All draws come from the stream of fumi_hip_sample_episodes: key = its 32-bit (seed, step) key,
+ *   r(c, n) = rand_below(key, i, 0xFF00 + stream_id, c, n) with i the flat output index (stream_id: 0 support, 1 query, < 254).
+ *     crop    ox = r(0, 2 pad + 1), oy = r(1, 2 pad + 1) for pad > 0, else both pad;   flip  fl = flip ? r(2, 2) : 0
+ *     source  sx = (fl ? W - 1 - x : x) + ox - pad, sy = y + oy - pad; byte 0 outside the image (pad, crop, flip: torchvision's order)
+ *     float   v = (float)u * k, k the fp32 nearest to 1 / 255
+ *     jitter  (any amplitude > 0; brightness, contrast, saturation in this order; an amplitude of 0 skips its step)
+ *             f_j = 1 + a_j (2 u_j - 1), u_j = r(3 + j, 1 << 24) 2^-24;  v = clamp01(v f_0);  v = clamp01(m + f_1 (v - m)) with m the
+ *             mean over the H x W output window of g = 0.299 R + 0.587 G + 0.114 B;  v = clamp01(g + f_2 (v - g)), g recomputed
+ *     out     (v - mean[c]) * inv_std[c]
+ *   No FMA contraction: with the jitter off the result is bit-reproducible in float32 (tests/image_gather_ref.py); with it on
+ *   only the order of the gray-mean sum is free, and it is fixed (two calls give the same bits).
+ *   An index outside [0, n_images) sets FUMI_ST_LABEL_RANGE and reads image 0.  C in 1..8, H, W >= 1, 0 <= pad <= 64, amplitudes
+ *   in [0, 1] (FUMI_EINVAL otherwise); jitter with C != 3, or an image of more than ~64 KB, is FUMI_ENOTSUP. */
+int fumi_hip_gather_images(fumi_ws_t* ws, fumi_stream_t stream, const uint8_t* table, int64_t n_images, int C, int H, int W,
+        const int64_t* idx, int64_t n_idx, const float* mean, const float* inv_std, uint64_t seed, uint64_t step, int stream_id,
+        int pad, int flip, float jit_brightness, float jit_contrast, float jit_saturation, float* out);
 
 /* ---- event-free read-back of a step's scalars (replaces outer_loss.detach().cpu().numpy(), fumi/models/fumi.py:195) ----
  * One single-wave launch on `stream` stores src[0..n) (device, fp32, n <= 14) into host_pinned[0..n) and then `seq` into the
