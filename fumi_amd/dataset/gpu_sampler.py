@@ -17,7 +17,9 @@ kernels then read the rows where they lie in the table (fumi_hip_fumi_step_index
 Raw images (--im_encoder conv4 / resnet12): ``images`` is a uint8 pixel table [n_images, C, H, W] that stays uint8 in HBM; the
 same episode kernels draw the indices, and one ``fumi_hip_gather_images`` launch per index list gathers, augments (random crop
 out of the zero-padded image, horizontal flip, colour jitter -- ``augment``) and normalises the pixels into the fp32
-[B, rows, C, H, W] batch the encoders take (csrc/imgather.hip)."""
+[B, rows, C, H, W] batch the encoders take (csrc/imgather.hip).  A table stored at another size than the encoders' (``out_size``) goes
+through ``fumi_hip_gather_images_resized`` instead (csrc/imresize.hip): a fixed source rectangle (resize + centre crop) or a
+random-resized crop per image, resampled with an antialiased bilinear filter, then flip, jitter and normalisation as before."""
 import numpy as np
 import torch
 
@@ -27,7 +29,7 @@ from .. import hip
 class GpuEpisodeSampler:
     def __init__(self, images, class_of_image, class_text, num_ways, num_shots, num_shots_test, batch_size, seed=123,
                  length=None, zero_copy=False, row_ids=None, skip_small_classes=None, torchmeta_tasks=False, normalize=None,
-                 augment=None):
+                 augment=None, out_size=None, resize=None):
         """images [n_images, D] fp32 (moved to the device once), class_of_image [n_images] ints (category of every row, as
         inat_anim.json's annotations give it), class_text [C, Dt] fp32 or [C, L] int64 tokens (one row per class: the text of
         a sample is its class description, data.py:543-549).  row_ids [n_images] ints: the id reported for every table row in
@@ -41,7 +43,10 @@ class GpuEpisodeSampler:
         random permutation of the labels 0..N-1 (Categorical) and a class tuple drawn again has the same support / query
         members (ClassSplitter seeds its shuffle with hash(task) + seed); False keeps label n for slot n.
         A 4-d uint8 ``images`` [n_images, C, H, W] is a pixel table: normalize=(mean, std), C floats each on the [0, 1] pixel
-        scale (default: 0 and 1), augment=None | dict(pad=, flip=, jitter=) as hip.gather_images takes them."""
+        scale (default: 0 and 1), augment=None | dict(pad=, flip=, jitter=) as hip.gather_images takes them.
+        out_size=(Ho, Wo): batches are [B, rows, C, Ho, Wo], resampled by hip.gather_images_resized from resize=dict(rect=(x0, y0, w, h))
+        (one source rectangle for every image; default: the whole image) or resize=dict(scale=(lo, hi), ratio=rmax) (a random-resized
+        crop per image); ``augment`` then holds flip / jitter only (no pad).  Unset: the class behaves as it did without them."""
         self.pixels = images.dim() == 4
         if self.pixels:
             if images.dtype != torch.uint8:
@@ -57,8 +62,25 @@ class GpuEpisodeSampler:
             self.augment = dict(pad=int(aug.pop("pad", 0)), flip=bool(aug.pop("flip", False)), jitter=aug.pop("jitter", (0, 0, 0)))
             if aug:
                 raise ValueError(f"unknown augment keys {sorted(aug)}")
-        elif normalize is not None or augment is not None:
-            raise ValueError("normalize / augment apply to a uint8 pixel table [n_images, C, H, W] only")
+            self.out_size, self.resize = None, None
+            if out_size is not None:
+                self.out_size = (int(out_size[0]), int(out_size[1]))
+                rs = dict(resize or {})
+                if "scale" in rs:
+                    lo, hi = rs.pop("scale")
+                    self.resize = dict(scale=(float(lo), float(hi)), ratio=float(rs.pop("ratio", 1.0)))
+                else:
+                    self.resize = dict(rect=tuple(int(v) for v in rs.pop("rect", (0, 0, int(images.shape[3]), int(images.shape[2])))))
+                if rs:
+                    raise ValueError(f"unknown resize keys {sorted(rs)}")
+                if self.augment["pad"]:
+                    raise ValueError("augment pad= does not apply with out_size: the random-resized crop takes its place")
+                if min(self.out_size) < 1:
+                    raise ValueError(f"out_size must be positive, got {self.out_size}")
+            elif resize is not None:
+                raise ValueError("resize needs out_size=(Ho, Wo)")
+        elif normalize is not None or augment is not None or out_size is not None or resize is not None:
+            raise ValueError("normalize / augment / out_size / resize apply to a uint8 pixel table [n_images, C, H, W] only")
         coi = np.asarray(class_of_image, dtype=np.int64)
         C = int(class_text.shape[0])
         if coi.min() < 0 or coi.max() >= C or len(coi) != images.shape[0]:
@@ -118,10 +140,17 @@ class GpuEpisodeSampler:
         else:
             cls, it_s, it_q = hip.sample_episodes(self.ws, self.seed, step, B, N, K, Q, self.class_ptr, self.class_items)
         if self.pixels:
-            img = lambda it, sid: hip.gather_images(self.ws, self.images, it.view(-1), self.mean, self.std, seed=self.seed, step=step,
-                                                    stream_id=sid, **self.augment)
-            x_s = img(it_s, 0).view(B, N * K, *self.images.shape[1:])
-            x_q = img(it_q, 1).view(B, N * Q, *self.images.shape[1:])
+            if self.out_size is None:
+                img = lambda it, sid: hip.gather_images(self.ws, self.images, it.view(-1), self.mean, self.std, seed=self.seed, step=step,
+                                                        stream_id=sid, **self.augment)
+                shape = tuple(self.images.shape[1:])
+            else:
+                img = lambda it, sid: hip.gather_images_resized(self.ws, self.images, it.view(-1), self.mean, self.std, self.out_size,
+                                                                seed=self.seed, step=step, stream_id=sid, flip=self.augment["flip"],
+                                                                jitter=self.augment["jitter"], **self.resize)
+                shape = (int(self.images.shape[1]),) + self.out_size
+            x_s = img(it_s, 0).view(B, N * K, *shape)
+            x_q = img(it_q, 1).view(B, N * Q, *shape)
         elif self.zero_copy:
             x_s, x_q = hip.RowRef(self.images, it_s.view(B, N * K)), hip.RowRef(self.images, it_q.view(B, N * Q))
         else:

@@ -8,7 +8,9 @@ Per split (train / val / test) under ``--data_dir``:
 
 The table stays uint8 on the device (21 KB per 3 x 84 x 84 image); the GPU-resident episode sampler draws the episodes and
 csrc/imgather.hip gathers, augments (``--augment``: train split only) and normalises a meta-batch without touching the host.
-Decoding and resizing are out of scope: the files hold pixels of the size the encoder is built for (--image_size)."""
+Decoding is out of scope.  Files stored at another size than the encoder is built for (--image_size) are resampled on the device
+(csrc/imresize.hip): the --image_crop_frac centre square for validation, test and un-augmented training, a random-resized crop
+(--augment_scale, --augment_ratio) with --augment."""
 import os
 
 import numpy as np
@@ -57,10 +59,24 @@ def load_image_split(root, split):
     return images, labels, np.ascontiguousarray(text, dtype=np.float32)
 
 
+def check_image_splits(args, splits):
+    """Host-side checks of the loaded splits against the flags (no GPU): the channels and the text width must fit; the stored image
+    size may differ from --image_size (the samplers then resample), but not between the splits' need to resample."""
+    from .synthetic import resize_settings
+    for s, (images, _, text) in splits.items():
+        if images.shape[1] != args.image_channels:
+            raise ValueError(f"{s}_images.npy holds {tuple(images.shape[1:])} images; --image_channels says {args.image_channels}")
+        if text.shape[1] != args.text_emb_dim:
+            raise ValueError(f"{s}_class_text.npy rows are {text.shape[1]} wide; --text_emb_dim is {args.text_emb_dim}")
+    need = {s: resize_settings(args, images.shape[2:]) is not None for s, (images, _, _) in splits.items()}
+    if len(set(need.values())) > 1:
+        raise ValueError(f"the splits are stored at {[tuple(v[0].shape[2:]) for v in splits.values()]}: either all are of "
+                         f"--image_size {args.image_size} or none")
+
+
 def get_image_npy(args):
     """(train, val, test, dictionary) for ``--dataset image-npy``: three GPU-resident samplers over uint8 pixel tables."""
-    from .gpu_sampler import GpuEpisodeSampler
-    from .synthetic import image_normalization, train_augmentation
+    from .synthetic import image_normalization, pixel_samplers
     if getattr(args, "im_encoder", "") not in ("conv4", "resnet12"):
         raise ValueError("--dataset image-npy holds raw pixels: it needs --im_encoder conv4 or resnet12")
     if args.text_encoder != "BERT":
@@ -68,16 +84,8 @@ def get_image_npy(args):
     if args.device.type != "cuda":
         raise RuntimeError("--dataset image-npy keeps the pixel table in HBM and samples on the GPU: no GPU visible")
     splits = {s: load_image_split(args.data_dir, s) for s in ("train", "val", "test")}
-    want = (args.image_channels, args.image_size, args.image_size)
-    for s, (images, _, text) in splits.items():
-        if tuple(images.shape[1:]) != want:
-            raise ValueError(f"{s}_images.npy holds {tuple(images.shape[1:])} images; --image_channels / --image_size say {want} "
-                             "(resizing is not done here)")
-        if text.shape[1] != args.text_emb_dim:
-            raise ValueError(f"{s}_class_text.npy rows are {text.shape[1]} wide; --text_emb_dim is {args.text_emb_dim}")
-    tables = {s: torch.from_numpy(images).to(args.device) for s, (images, _, _) in splits.items()}
-    norm = image_normalization(args, tables["train"])
+    check_image_splits(args, splits)
+    tables = {s: (torch.from_numpy(images).to(args.device), labels, torch.from_numpy(text)) for s, (images, labels, text) in splits.items()}
+    norm = image_normalization(args, tables["train"][0])
     q_eval = int(100 / args.num_ways)                                                   # data.py:163-166,180-183
-    mk = lambda s, q, aug: GpuEpisodeSampler(tables[s], splits[s][1], torch.from_numpy(splits[s][2]), args.num_ways, args.num_shots,
-                                             q, args.batch_size, seed=args.seed + len(s), normalize=norm, augment=aug)
-    return mk("train", args.num_shots_test, train_augmentation(args)), mk("val", q_eval, None), mk("test", q_eval, None), {}
+    return pixel_samplers(args, tables, norm, q_eval) + ({},)

@@ -155,10 +155,59 @@ def train_augmentation(args):
     return dict(pad=int(args.augment_pad), flip=True, jitter=(j, j, j))
 
 
+def center_rect(Hs, Ws, frac):
+    """(x0, y0, w, h): the centred square of side max(1, min(m, round(frac m))), m = min(Hs, Ws)."""
+    m = min(Hs, Ws)
+    side = max(1, min(m, int(round(float(frac) * m))))
+    return (Ws - side) // 2, (Hs - side) // 2, side, side
+
+
+def resize_settings(args, table_hw):
+    """How the samplers of a pixel table stored at ``table_hw`` = (Hs, Ws) resample to --image_size: None when nothing is resampled
+    (the table is of that size and --augment_scale is not given), else dict(out_size=, eval=, train=, augment=) -- the keyword
+    arguments of GpuEpisodeSampler: ``eval`` (validation, test) is the --image_crop_frac centre square; ``train`` is the same
+    without --augment and the random-resized crop (--augment_scale, default 0.08 1.0; --augment_ratio) with it, when ``augment``
+    holds flip and jitter (--augment_pad is not used on this path)."""
+    Hs, Ws = int(table_hw[0]), int(table_hw[1])
+    size = int(args.image_size)
+    scale = getattr(args, "augment_scale", None)
+    if (Hs, Ws) == (size, size) and scale is None:
+        return None
+    rect = dict(rect=center_rect(Hs, Ws, getattr(args, "image_crop_frac", 0.875)))
+    out = dict(out_size=(size, size), eval=rect, train=rect, augment=None)
+    if getattr(args, "augment", False):
+        lo, hi = scale if scale is not None else (0.08, 1.0)
+        j = float(args.augment_jitter) if args.image_channels == 3 else 0.0
+        out["train"] = dict(scale=(float(lo), float(hi)), ratio=float(getattr(args, "augment_ratio", 4.0 / 3.0)))
+        out["augment"] = dict(flip=True, jitter=(j, j, j))
+    return out
+
+
+def pixel_samplers(args, tables, norm, q_eval):
+    """(train, val, test) GpuEpisodeSamplers over tables[split] = (uint8 table on the device, class of every image, class text)."""
+    from .gpu_sampler import GpuEpisodeSampler
+    rs = resize_settings(args, tables["train"][0].shape[2:])
+    for split in ("val", "test"):
+        if (rs is None) != (resize_settings(args, tables[split][0].shape[2:]) is None):
+            raise ValueError(f"the {split} table is stored at {tuple(tables[split][0].shape[2:])}, the train table at "
+                             f"{tuple(tables['train'][0].shape[2:])}: either all are of --image_size or none")
+
+    def mk(split, q, train):
+        kw = {}
+        if rs is None:
+            kw["augment"] = train_augmentation(args) if train else None
+        else:
+            r = resize_settings(args, tables[split][0].shape[2:])
+            kw.update(out_size=r["out_size"], resize=r["train"] if train else r["eval"], augment=r["augment"] if train else None)
+        return GpuEpisodeSampler(*tables[split], args.num_ways, args.num_shots, q, args.batch_size, seed=args.seed + len(split),
+                                 normalize=norm, **kw)
+    return mk("train", args.num_shots_test, True), mk("val", q_eval, False), mk("test", q_eval, False)
+
+
 def _synthetic_resident_images(args, per, tokens, q_eval):
     """``--dataset synthetic-resident`` with an image encoder: a uint8 pixel table per split, resident in HBM."""
-    from .gpu_sampler import GpuEpisodeSampler
-    shape = (args.image_channels, args.image_size, args.image_size)
+    stored = int(getattr(args, "synthetic_table_size", None) or args.image_size)
+    shape = (args.image_channels, stored, stored)
     tables = {}
     for split in ("train", "val", "test"):
         base = SyntheticEpisodes(args.synthetic_classes, args.im_emb_dim, args.text_emb_dim, args.num_ways, args.num_shots, 1,
@@ -166,9 +215,7 @@ def _synthetic_resident_images(args, per, tokens, q_eval):
         table, coi = synthetic_pixel_table(base, per, np.random.RandomState(args.seed * 13 + len(split)))
         tables[split] = (torch.from_numpy(table).to(args.device), coi, torch.from_numpy(base.text))
     norm = image_normalization(args, tables["train"][0])
-    mk = lambda split, q, aug: GpuEpisodeSampler(*tables[split], args.num_ways, args.num_shots, q, args.batch_size,
-                                                 seed=args.seed + len(split), normalize=norm, augment=aug)
-    return mk("train", args.num_shots_test, train_augmentation(args)), mk("val", q_eval, None), mk("test", q_eval, None)
+    return pixel_samplers(args, tables, norm, q_eval)
 
 
 class SyntheticSupervised:

@@ -25,7 +25,7 @@ SYMBOLS = [
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
-    "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_gather_images", "fumi_hip_publish_scalars",
+    "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_gather_images", "fumi_hip_gather_images_resized", "fumi_hip_publish_scalars",
     "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics", "fumi_hip_am3_step_plan",
     "fumi_hip_conv4_feature_dim", "fumi_hip_fumi_conv4_step", "fumi_hip_maml_conv4_step", "fumi_hip_conv4_probe", "fumi_hip_conv4_features", "fumi_hip_conv4_set_option",
     "fumi_hip_conv4_encode", "fumi_hip_conv4_encode_bwd", "fumi_hip_am3_step_dx",
@@ -157,6 +157,9 @@ def lib():
         L.fumi_hip_gather_images.argtypes = ([c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
                                               POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int]
                                              + [c_float] * 3 + [c_void_p])
+        L.fumi_hip_gather_images_resized.argtypes = ([c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p, c_int64,
+                                                      POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64]
+                                                     + [c_int] * 6 + [c_float] * 3 + [c_int] + [c_float] * 3 + [c_void_p])
         L.fumi_hip_publish_scalars.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_uint64]
         L.fumi_hip_publish_scalars_deferred.argtypes = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_uint64]
         L.fumi_hip_publish_flush.argtypes = [c_void_p, c_void_p]
@@ -854,6 +857,51 @@ def gather_images(ws, table, idx, mean, std, *, seed=0, step=0, stream_id=0, pad
                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(stream_id), int(pad),
                                         int(bool(flip)), float(jit[0]), float(jit[1]), float(jit[2]), _f32(out, "out")),
            "fumi_hip_gather_images")
+    return out
+
+
+RESIZE_FIXED, RESIZE_RANDOM = 0, 1
+
+
+def gather_images_resized(ws, table, idx, mean, std, out_size, *, seed=0, step=0, stream_id=0, rect=None, scale=None, ratio=1.0,
+                          flip=False, jitter=(0, 0, 0)):
+    """out[i] = normalise(jitter(flip(resample(rect_i of table[idx[i]])))) (csrc/imresize.hip): ``table`` uint8 [n_images, C, Hs, Ws]
+    on the device, ``out_size`` = (Ho, Wo) -> float32 [n_idx, C, Ho, Wo].  Exactly one of ``rect`` = (x0, y0, w, h), the source
+    rectangle of every image (resize + centre crop), and ``scale`` = (lo, hi) with ``ratio`` = rmax >= 1, a random-resized crop per
+    image (area fraction in [lo, hi], aspect ratio in [1 / rmax, rmax]).  The rectangle is resampled with a separable triangle
+    filter (antialiased bilinear).  ``idx``, ``mean`` / ``std``, ``flip``, ``jitter`` and the draws as in ``gather_images``."""
+    dev = _dev(table)
+    if (table.dim() != 4 or table.dtype != torch.uint8 or not table.is_contiguous() or not isinstance(idx, torch.Tensor)
+            or table.device != idx.device or idx.dtype != torch.int64):
+        raise FumiHipError("gather_images_resized: table must be a contiguous uint8 [n_images, C, Hs, Ws] device tensor and idx an "
+                           f"int64 tensor on the same device; got {table.dtype} {tuple(table.shape)}")
+    n_images, C, Hs, Ws = (int(s) for s in table.shape)
+    if n_images < 1:
+        raise FumiHipError("gather_images_resized: the table is empty")
+    if (rect is None) == (scale is None):
+        raise FumiHipError("gather_images_resized: give either rect=(x0, y0, w, h) or scale=(lo, hi)")
+    Ho, Wo = (int(s) for s in out_size)
+    if Ho < 1 or Wo < 1:
+        raise FumiHipError(f"gather_images_resized: out_size must be positive, got {(Ho, Wo)}")
+    jit = (jitter,) * 3 if isinstance(jitter, (int, float)) else tuple(jitter)
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C or len(jit) != 3:
+        raise FumiHipError(f"gather_images_resized: mean and std need {C} entries each and jitter three")
+    import numpy as np
+    inv = np.float32(1.0) / np.asarray(std, dtype=np.float32)               # the kernel multiplies: 1 / std rounded once, in fp32
+    idx = idx.contiguous()
+    out = torch.empty(idx.numel(), C, Ho, Wo, device=dev, dtype=torch.float32)
+    x0, y0, w, h = (int(v) for v in rect) if rect is not None else (0, 0, Ws, Hs)
+    lo, hi = (float(v) for v in scale) if scale is not None else (1.0, 1.0)
+    if idx.numel() == 0:
+        return out
+    _check(lib().fumi_hip_gather_images_resized(ws.handle, _stream(dev), c_void_p(table.data_ptr()), n_images, C, Hs, Ws, Ho, Wo,
+                                                _i64(idx, "idx"), idx.numel(), (c_float * C)(*mean),
+                                                (c_float * C)(*[float(v) for v in inv]), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(step) & 0xFFFFFFFFFFFFFFFF, int(stream_id),
+                                                RESIZE_FIXED if rect is not None else RESIZE_RANDOM, x0, y0, w, h, lo, hi, float(ratio),
+                                                int(bool(flip)), float(jit[0]), float(jit[1]), float(jit[2]), _f32(out, "out")),
+           "fumi_hip_gather_images_resized")
     return out
 
 

@@ -89,6 +89,10 @@ def main(args):
         # the reference parses --augment and never reads it; here it acts on a resident pixel table only
         print("--augment is ignored: it applies to a GPU-resident pixel table (--dataset synthetic-resident / image-npy with "
               "--im_encoder conv4 | resnet12), not to embeddings or the host loader")
+    if args.augment and getattr(train_loader, "out_size", None) is not None:
+        print(f"--augment on a table stored at {tuple(train_loader.images.shape[2:])}: random-resized crop "
+              f"(area {train_loader.resize['scale']}, ratio up to {train_loader.resize['ratio']:.4g}), flip and jitter; "
+              "--augment_pad is not used")
     max_test_batches = int(args.num_ep_test / args.batch_size)
     for seed_fn in (torch.manual_seed, np.random.seed, random.seed):
         seed_fn(args.seed)

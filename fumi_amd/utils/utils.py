@@ -80,6 +80,10 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--image_channels", dict(type=int, default=3, help="[--im_encoder conv4 / resnet12] input channels (conv4: 1-3, resnet12: 1-8)")),
     ("--augment_pad", dict(type=int, default=8, help="[--augment on a resident pixel table] zero padding of the random crop (0-64)")),
     ("--augment_jitter", dict(type=float, default=0.4, help="[--augment on a resident pixel table] amplitude of the brightness / contrast / saturation jitter (0-1; three-channel images)")),
+    ("--image_crop_frac", dict(type=float, default=0.875, help="[resident pixel table stored at another size than --image_size] validation, test and un-augmented train batches take the centred square of this fraction of the shorter side, resized to --image_size")),
+    ("--augment_scale", dict(type=float, nargs=2, default=None, metavar=("LO", "HI"), help="[--augment on a resident pixel table] random-resized crop: area fraction range (given, or with a table of another size than --image_size: default 0.08 1.0)")),
+    ("--augment_ratio", dict(type=float, default=4.0 / 3.0, help="[--augment, random-resized crop] largest aspect ratio rmax: ratios are drawn from [1 / rmax, rmax]")),
+    ("--synthetic_table_size", dict(type=int, default=None, help="[--dataset synthetic-resident with an image encoder] stored height = width of the pixel table (default: --image_size)")),
     ("--image_mean", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel mean on the 0..1 pixel scale (default: the train table's own)")),
     ("--image_std", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel standard deviation on the 0..1 pixel scale (default: the train table's own)")),
 ]

@@ -460,6 +460,43 @@ int fumi_hip_gather_rows(fumi_ws_t* ws, fumi_stream_t stream, const void* table,
 int fumi_hip_gather_images(fumi_ws_t* ws, fumi_stream_t stream, const uint8_t* table, int64_t n_images, int C, int H, int W,
         const int64_t* idx, int64_t n_idx, const float* mean, const float* inv_std, uint64_t seed, uint64_t step, int stream_id,
         int pad, int flip, float jit_brightness, float jit_contrast, float jit_saturation, float* out);
+/* gather_images_resized (csrc/imresize.hip): the same for a table whose images are not of the size the encoder takes --
+ *   out[i] = normalise(jitter(flip(resample(rect_i of table[idx[i]])))), table uint8 [n_images, C, Hs, Ws], out float [n_idx, C, Ho, Wo].
+ *   rect_i = (x0, y0, w, h) in whole source pixels, 1 <= w <= Ws, 1 <= h <= Hs, inside the image, is resampled to Ho x Wo with a
+ *   separable triangle filter (antialiased bilinear: plain bilinear with clamped edges when the rectangle is not larger than the
+ *   output, an exact copy when it is of the same size).  Every operation below is ONE float32 operation rounded on its own (no FMA
+ *   contraction, no fast-math, correctly rounded / and sqrt), restated in tests/image_resize_ref.py.
+ *   Per axis (x shown: n_in = w, n_out = Wo; y the same with h, Ho):
+ *     scale = (float)n_in / (float)n_out;  s = max(scale, 1);  inv = 1 / s
+ *     output x:  c = scale * ((float)x + 0.5f);  k0 = max(0, (int)(c - s + 0.5f)),  k1 = min(n_in, (int)(c + s + 0.5f))  (truncating)
+ *                w_k = max(0, 1 - |((float)k - c + 0.5f) * inv|) for k = k0 .. k1 - 1;  tot = sum of w_k in ascending k from 0.f
+ *     horizontal t[y'][x] = (sum in ascending k of w_k * (float)u[y0 + y'][x0 + k], accumulated as acc = acc + w_k * v) / tot, for every
+ *     row y' of the rectangle, pixel values as floats in 0..255;  vertical: the same over t, giving r[y][x].
+ *     (The kernel recomputes the horizontal sums of the rows an output pixel needs and drops end taps of weight 0: the same bits.)
+ *   After resampling:  flip  output column x takes r[y][fl ? Wo - 1 - x : x], fl = flip ? r(2, 2) : 0;  v = r * k, k the fp32 nearest
+ *     to 1 / 255;  jitter (counters 3..5) and (v - mean[c]) * inv_std[c] exactly as fumi_hip_gather_images: same formulas, order and
+ *     clamp; the gray mean is taken over the Ho x Wo output, in double, in a fixed order (two calls give the same bits).
+ *   mode FUMI_RESIZE_FIXED: (rect_x0, rect_y0, rect_w, rect_h) for every image; FUMI_EINVAL if it leaves the image.
+ *   mode FUMI_RESIZE_RANDOM: a random-resized crop per image, 0 < scale_min <= scale_max <= 1, ratio_max >= 1 (FUMI_EINVAL
+ *     otherwise), from the same hash r(c, n) = rand_below(key, i, 0xFF00 + stream_id, c, n); counters 0..5 keep their meaning.
+ *     With U(c) = (float)r(c, 1 << 24) * 0x1p-24f:
+ *       a = scale_min + (scale_max - scale_min) * U(6);  q = 1 + (ratio_max - 1) * U(7);  ratio = r(8, 2) ? q : 1 / q
+ *       A = (float)(Hs * Ws);  wf = sqrt(a * A * ratio),  hf = sqrt(a * A / ratio)
+ *       w = clamp((int)rintf(wf), 1, Ws),  h = clamp((int)rintf(hf), 1, Hs)  (ties to even);  x0 = r(9, Ws - w + 1),  y0 = r(10, Hs - h + 1)
+ *     One pass with clamping: torchvision's RandomResizedCrop draws again (up to ten times, then falls back to a centre crop) where
+ *     this clamps, so rectangles near the limits of scale and ratio are a little more frequent here.
+ *   Status and refusals as fumi_hip_gather_images: an index outside [0, n_images) sets FUMI_ST_LABEL_RANGE and reads image 0; C in
+ *   1..8, sizes >= 1, amplitudes in [0, 1] (FUMI_EINVAL otherwise); jitter with C != 3 is FUMI_ENOTSUP.  Size limit (FUMI_ENOTSUP
+ *   beyond it): Hs, Ws, Ho, Wo <= 4096, C Ho Wo max(Ho, Wo) < 2^32, and one workgroup's LDS <= 160 KiB:
+ *     C * (round_up_16(rows * Ws) + 16) + 112 + 4 * (Wo * mx + Ho * my + 4 * (Wo + Ho)) bytes,  rows = rect_h (fixed) | Hs (random),
+ *     mx = floor(2 max(wmax / Wo, 1)) + 2 with wmax = rect_w | Ws, my likewise from rows and Ho.
+ *   A 3 x 160 x 160 rectangle into 3 x 84 x 84 takes 83,008 bytes, a 3 x 224 x 224 one into 84 x 84 takes 158,080. */
+#define FUMI_RESIZE_FIXED 0
+#define FUMI_RESIZE_RANDOM 1
+int fumi_hip_gather_images_resized(fumi_ws_t* ws, fumi_stream_t stream, const uint8_t* table, int64_t n_images, int C,
+        int Hs, int Ws, int Ho, int Wo, const int64_t* idx, int64_t n_idx, const float* mean, const float* inv_std, uint64_t seed,
+        uint64_t step, int stream_id, int mode, int rect_x0, int rect_y0, int rect_w, int rect_h, float scale_min, float scale_max,
+        float ratio_max, int flip, float jit_brightness, float jit_contrast, float jit_saturation, float* out);
 
 /* ---- event-free read-back of a step's scalars (replaces outer_loss.detach().cpu().numpy(), fumi/models/fumi.py:195) ----
  * One single-wave launch on `stream` stores src[0..n) (device, fp32, n <= 14) into host_pinned[0..n) and then `seq` into the

@@ -5,6 +5,8 @@ Times the FuMI Conv4 meta-step at the as-worded shape (5-way 5-shot, Q = 32, B =
   (b) the host loader of ``--dataset synthetic`` (numpy draws the fp32 batch, then a host-to-device copy);
   (c) the GPU-resident uint8 pixel table, sampled and gathered on the device (csrc/imgather.hip), no augmentation;
   (d) the same with the ``--augment`` defaults (pad 8, flip, jitter 0.4);
+  (e) a 3 x 96 x 96 uint8 table resampled on the device (csrc/imresize.hip): the 0.875 centre rectangle resized to 84 x 84;
+  (f) the same with ``--augment``: random-resized crop (area 0.08 - 1, ratio up to 4/3), flip, jitter 0.4;
 and the sampler alone per meta-batch.  The variants alternate inside one process; a figure is the median of the regions with
 its min / max.  ``--resnet12`` adds the sampler alone at the ResNet-12 20-way shape (B = 64, 400 images per episode).
 
@@ -12,9 +14,10 @@ its min / max.  ``--resnet12`` adds the sampler alone at the ResNet-12 20-way sh
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o img -- python tools/bench_image_pipeline.py --profile
 
 ``--profile`` launches only what the trace is read for: the two gather_images calls of a meta-batch (with and without
-augmentation) and, as the yardstick, fumi_hip_gather_rows over the same number of 8 KB fp32 rows.  Effective bandwidth of the image
-gather = n_idx * C*H*W * 5 bytes (1 read as uint8, 4 written as fp32) over the kernel's average duration; of the row gather
-= n_idx * row_bytes * 2."""
+augmentation), the two gather_images_resized calls of rows (e) and (f) and, as the yardstick, fumi_hip_gather_rows over the same
+number of 8 KB fp32 rows.  Effective bandwidth of the image gather = n_idx * C*H*W * 5 bytes (1 read as uint8, 4 written as fp32)
+over the kernel's average duration; of the resized gather = n_idx * (C*h*w + 4*C*Ho*Wo) with h x w the rectangle (row (f): the mean
+rectangle area of the draws, printed); of the row gather = n_idx * row_bytes * 2."""
 import argparse
 import json
 import os
@@ -51,11 +54,20 @@ n_cls, per = 256, 64                                   # 16,384 images = 347 MB 
 table = torch.randint(0, 256, (n_cls * per, Cin, H, W), device=dev, generator=g, dtype=torch.uint8)
 coi = np.repeat(np.arange(n_cls), per)
 text = torch.randn(n_cls, Dt, device=dev, generator=g)
+HS = 96                                                 # rows (e), (f): the table as stored, 16,384 x 3 x 96 x 96 = 453 MB
+table96 = torch.randint(0, 256, (n_cls * per, Cin, HS, HS), device=dev, generator=g, dtype=torch.uint8)
+side = max(1, min(HS, int(round(0.875 * HS))))
+RECT = ((HS - side) // 2, (HS - side) // 2, side, side)
+RRC = dict(scale=(0.08, 1.0), ratio=4.0 / 3.0)
 sync = torch.cuda.synchronize
 
 
 def sampler(aug, b=B, n=N, k=K, q=Q):
     return GpuEpisodeSampler(table, coi, text, n, k, q, b, seed=1, normalize=NORM, augment=aug)
+
+
+def sampler96(resize, aug, b=B, n=N, k=K, q=Q):
+    return GpuEpisodeSampler(table96, coi, text, n, k, q, b, seed=1, normalize=NORM, out_size=(H, W), resize=resize, augment=aug)
 
 
 if opt.profile:
@@ -67,9 +79,14 @@ if opt.profile:
         hip.gather_images(ws, table, it, *NORM, seed=1, step=i, stream_id=0)
         hip.gather_images(ws, table, it, *NORM, seed=1, step=i, stream_id=0, **AUG)
         hip.gather_rows(ws, rows, it_r)
+        hip.gather_images_resized(ws, table96, it, *NORM, (H, W), seed=1, step=i, stream_id=0, rect=RECT)
+        hip.gather_images_resized(ws, table96, it, *NORM, (H, W), seed=1, step=i, stream_id=0, flip=True, jitter=AUG["jitter"], **RRC)
     sync()
+    area = 0.5 * (RRC["scale"][0] + RRC["scale"][1]) * HS * HS              # mean rectangle area of the draws (before clamping)
     print(json.dumps(dict(profile=True, n_idx=n_idx, image_bytes=Cin * H * W, image_gather_bytes=n_idx * Cin * H * W * 5,
-                          row_gather_bytes=n_idx * 2048 * 4 * 2)))
+                          row_gather_bytes=n_idx * 2048 * 4 * 2,
+                          resized_fixed_bytes=n_idx * (Cin * RECT[2] * RECT[3] + 4 * Cin * H * W),
+                          resized_random_bytes=int(n_idx * (Cin * area + 4 * Cin * H * W)))))
     sys.exit(0)
 
 F = hip.conv4_feature_dim(nblk, H, W)
@@ -92,13 +109,17 @@ def step(batch):
 
 
 smp_c, smp_d = sampler(None), sampler(AUG)
+smp_e, smp_f = sampler96(dict(rect=RECT), None), sampler96(RRC, dict(flip=True, jitter=AUG["jitter"]))
 fixed = [smp_c.batch(i) for i in range(2)]                                  # (a): two resident fp32 batches, 1 GB
 host = SyntheticEpisodes(64, 0, Dt, N, K, Q, B, 1, "train", image_shape=(Cin, H, W))
 variants = [("a: resident pre-generated fp32 batches", lambda i: fixed[i % 2], opt.steps),
             ("b: host loader (--dataset synthetic)", host.batch, opt.host_steps),
             ("c: uint8 resident sampler", smp_c.batch, opt.steps),
-            ("d: uint8 resident sampler, --augment", smp_d.batch, opt.steps)]
-alone = [("sampler alone, no augmentation", smp_c.batch), ("sampler alone, --augment", smp_d.batch)]
+            ("d: uint8 resident sampler, --augment", smp_d.batch, opt.steps),
+            ("e: 3 x 96 x 96 uint8 table, centre crop + resize", smp_e.batch, opt.steps),
+            ("f: 3 x 96 x 96 uint8 table, --augment (random-resized crop)", smp_f.batch, opt.steps)]
+alone = [("sampler alone, no augmentation", smp_c.batch), ("sampler alone, --augment", smp_d.batch),
+         ("sampler alone, 96 x 96 table, centre crop + resize", smp_e.batch), ("sampler alone, 96 x 96 table, --augment", smp_f.batch)]
 if opt.resnet12:
     alone += [("sampler alone, ResNet-12 20-way shape (B 64, 400 images / episode)", sampler(None, 64, 20, 5, 15).batch),
               ("sampler alone, ResNet-12 20-way shape, --augment", sampler(AUG, 64, 20, 5, 15).batch)]
