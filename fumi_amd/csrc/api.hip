@@ -512,7 +512,12 @@ int fumi_hip_xpanel_fwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
 
 int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
         const float* x_s, const float* x_q, const float* Abar, float scale, float* gW0) {
-    if (!ws || !x_s || !x_q || !Abar || !gW0 || B < 1 || S < 1 || Qn < 1 || D < 1 || h0 < 1) return FUMI_EINVAL;
+    // a one-sided panel (S == 0 or Qn == 0, not both; the absent side's pointer is not read and may be NULL) is what the two-launch
+    // backward of run_episodes passes
+    if (!ws || !Abar || !gW0 || B < 1 || S < 0 || Qn < 0 || S + Qn < 1 || D < 1 || h0 < 1) return FUMI_EINVAL;
+    if ((S > 0 && !x_s) || (Qn > 0 && !x_q)) return FUMI_EINVAL;
+    if (!x_s) x_s = x_q;                       // (never dereferenced: keeps the launcher's alignment test on the present side)
+    if (!x_q) x_q = x_s;
     HIP_TRY(hipSetDevice(ws->device));
     hipStream_t st = (hipStream_t)stream;
     int kc;

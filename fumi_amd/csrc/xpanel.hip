@@ -1240,7 +1240,29 @@ __global__ __launch_bounds__(512, (NB == 1 && SK == 16) ? 2 : 1) void xpanel_bwd
 inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 unsigned long long* g_trace = nullptr;      // dev tracing only (tools/trace_xpanel.py)
 
+// decisions of the last launch_xpanel_fwd / launch_xpanel_bwd of this process (fumi_hip_xpanel_plan): written on the host beside the
+// launches, never read by one.  Kernel ids -- forward: 1 generic guarded, 2 generic fast, 3 fp32 MFMA, 4 per-tile split, 5 pre-split;
+// backward: 1 64 x 64 guarded, 2 64 x 64 fast, 3 wide fp32, 4 wide split, 5 narrow swapped split.
+struct XpPlan { int fwd_kernel, fwd_ring, fwd_ksplit, fwd_gram_blocks, fwd_rode, bwd_kernel, bwd_nb, bwd_sk, bwd_nsplit, bwd_kchunk, bwd_rode; };
+XpPlan g_xp_last = {};
+inline void xp_plan_fwd(int kernel, int ring, int ksplit, int gram_blocks, int rode) {
+    g_xp_last.fwd_kernel = kernel; g_xp_last.fwd_ring = ring; g_xp_last.fwd_ksplit = ksplit; g_xp_last.fwd_gram_blocks = gram_blocks;
+    g_xp_last.fwd_rode = rode;
+}
+inline void xp_plan_bwd(int kernel, int nb, int sk, int nsplit, int kchunk, int rode) {
+    g_xp_last.bwd_kernel = kernel; g_xp_last.bwd_nb = nb; g_xp_last.bwd_sk = sk; g_xp_last.bwd_nsplit = nsplit; g_xp_last.bwd_kchunk = kchunk;
+    g_xp_last.bwd_rode = rode;
+}
+
 }  // namespace
+
+extern "C" int fumi_hip_xpanel_plan(int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    const int v[11] = {g_xp_last.fwd_kernel, g_xp_last.fwd_ring, g_xp_last.fwd_ksplit, g_xp_last.fwd_gram_blocks, g_xp_last.fwd_rode,
+                       g_xp_last.bwd_kernel, g_xp_last.bwd_nb, g_xp_last.bwd_sk, g_xp_last.bwd_nsplit, g_xp_last.bwd_kchunk, g_xp_last.bwd_rode};
+    for (int i = 0; i < n && i < 11; ++i) plan[i] = v[i];
+    return FUMI_OK;
+}
 
 void set_xpanel_trace(void* p) { g_trace = (unsigned long long*)p; }
 
@@ -1299,6 +1321,7 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
     if (rows && rows->table) { p.table = rows->table; p.idx_s = rows->idx_s; p.idx_q = rows->idx_q; p.n_rows = rows->n_rows; p.x_s = p.x_q = rows->table; }
     const int tiles_m = (S + Qn + 63) / 64, tiles_n = (h0 + p.gcols + 63) / 64;
     const int nper = (B + 7) / 8;
+    const int gram_tiles = tiles_n - h0 / 64;        // (plan record: 64-column tiles that hold a Gram column; the pre-split form counts 32s)
     const bool aligned = al16(p.x_s) && al16(p.x_q) && al16(W0);
     static const int use_sb = getenv("FUMI_XP_SB") ? atoi(getenv("FUMI_XP_SB")) : 1;
     const int ks = xpanel_fwd_ksplit(B, S, Qn, D, h0, G != nullptr);
@@ -1338,6 +1361,7 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         } else {
             hipLaunchKernelGGL((xpanel_fwd_ps_kernel<2, false>), dim3(nwg), dim3(256), 0, st, p, Wp, Xp, A0, G, tm, tg, cbg, none, g_trace);
         }
+        xp_plan_fwd(5, 2, p.ksplit, cbg, rider_done && *rider_done);
     } else if (aligned && D % SBK == 0 && use_sb) {
         static const int sbn = getenv("FUMI_XP_SBN") ? atoi(getenv("FUMI_XP_SBN")) : 2;          // ring depth (tuning knob)
         static const int ride = getenv("FUMI_XP_RIDER") ? atoi(getenv("FUMI_XP_RIDER")) : 1;     // 0: never carry the hypernetwork forward
@@ -1349,13 +1373,20 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         }
         else if (sbn <= 2) hipLaunchKernelGGL((xpanel_fwd_sb_kernel<2, false>), grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, none);
         else hipLaunchKernelGGL((xpanel_fwd_sb_kernel<4, false>), grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, none);
+        xp_plan_fwd(4, sbn <= 2 ? 2 : 4, p.ksplit, gram_tiles, rider_done && *rider_done);
     } else if (aligned && D % FBK == 0) {
         if (nst == 1) hipLaunchKernelGGL(xpanel_fwd_kernel<1>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
         else if (nst == 2) hipLaunchKernelGGL(xpanel_fwd_kernel<2>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
         else hipLaunchKernelGGL(xpanel_fwd_kernel<3>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
+        xp_plan_fwd(3, nst == 1 ? 1 : nst == 2 ? 2 : 3, p.ksplit, gram_tiles, 0);
     }
-    else if (aligned && D % BK == 0) hipLaunchKernelGGL(xpanel_fwd_generic_kernel<true>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, 0);
-    else hipLaunchKernelGGL(xpanel_fwd_generic_kernel<false>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, 0);
+    else if (aligned && D % BK == 0) {
+        hipLaunchKernelGGL(xpanel_fwd_generic_kernel<true>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, 0);
+        xp_plan_fwd(2, 2, p.ksplit, gram_tiles, 0);
+    } else {
+        hipLaunchKernelGGL(xpanel_fwd_generic_kernel<false>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, 0);
+        xp_plan_fwd(1, 2, p.ksplit, gram_tiles, 0);
+    }
     LAUNCH_CHECK();
     if (p.ksplit > 1) {
         if (parts_unreduced) { *parts_unreduced = p.ksplit; return FUMI_OK; }      // the consumer adds the parts where it reads them
@@ -1428,6 +1459,7 @@ int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         FUMI_SET_DYN_LDS((xpanel_bwd256_sb_kernel<false, 2, 1, 16, true>), lds_sb);
         hipLaunchKernelGGL((xpanel_bwd256_sb_kernel<false, 2, 1, 16, true>), dim3(8 * ((nsplit + 7) / 8) * tm), dim3(512), lds_sb, st,
                            p, Abar, slabs, kchunk, nsplit, 1, tm, none);
+        xp_plan_bwd(5, 1, 16, nsplit, kchunk, 0);
         LAUNCH_CHECK();
         return FUMI_OK;
     }
@@ -1456,6 +1488,7 @@ int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
             if (ridden) { if (NB == 2) BSB_LAUNCH(true, 2, 16); else if (SKv == 32) BSB_LAUNCH(true, 1, 32); else BSB_LAUNCH(true, 1, 16); *rider_done = 1; }
             else { if (NB == 2) BSB_LAUNCH(false, 2, 16); else if (SKv == 32) BSB_LAUNCH(false, 1, 32); else BSB_LAUNCH(false, 1, 16); }
 #undef BSB_LAUNCH
+            xp_plan_bwd(4, NB, SKv, nsplit, kchunk, ridden);
             LAUNCH_CHECK();
             return FUMI_OK;
         }
@@ -1471,12 +1504,14 @@ int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
             hipLaunchKernelGGL(xpanel_bwd256_kernel<false>, dim3(nwg), dim3(512), lds_bytes, st, p, Abar, slabs,
                                kchunk, nsplit, tn, tm, none);
         }
+        xp_plan_bwd(3, 1, 32, nsplit, kchunk, rider_done && *rider_done);
         LAUNCH_CHECK();
         return FUMI_OK;
     }
     const dim3 grid((D + 63) / 64, (h0 + 63) / 64, nsplit);
     if (fast) hipLaunchKernelGGL(xpanel_bwd_kernel<true>, grid, dim3(256), 0, st, p, Abar, slabs, kchunk);
     else hipLaunchKernelGGL(xpanel_bwd_kernel<false>, grid, dim3(256), 0, st, p, Abar, slabs, kchunk);
+    xp_plan_bwd(fast ? 2 : 1, 1, 32, nsplit, kchunk, 0);
     LAUNCH_CHECK();
     return FUMI_OK;
 }

@@ -21,7 +21,7 @@ SYMBOLS = [
     "fumi_hip_set_spin_limit", "fumi_hip_set_trace_buffer",
     "fumi_hip_set_profiling", "fumi_hip_set_profiling_every", "fumi_hip_get_profile", "fumi_hip_phase_name",
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
-    "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd",
+    "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
@@ -139,6 +139,7 @@ def lib():
         L.fumi_hip_class_text_select.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3
         L.fumi_hip_xpanel_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5
         L.fumi_hip_xpanel_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [c_float, c_void_p]
+        L.fumi_hip_xpanel_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_adam_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_flush.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
@@ -659,26 +660,57 @@ def class_text_select(ws, text_s, y_s, n_way):
     return out
 
 
-def xpanel_fwd(ws, x_s, x_q, W0):
-    """A0 [B,S+Qn,h0], G [B,S+Qn,S] (support rows first)."""
+def _out(out, shape, dev, name):
+    """A caller-supplied output tensor (tests place it inside a guarded buffer), or a fresh one."""
+    if out is None:
+        return torch.empty(*shape, device=dev, dtype=torch.float32)
+    if tuple(out.shape) != tuple(shape) or out.device != dev:
+        raise FumiHipError(f"{name}: expected shape {tuple(shape)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def xpanel_fwd(ws, x_s, x_q, W0, out=None):
+    """A0 [B,S+Qn,h0], G [B,S+Qn,S] (support rows first).  ``out``: (A0, G) tensors to write instead of fresh ones."""
     dev = _dev(x_s)
     B, S, D = x_s.shape
     Qn, h0 = x_q.shape[1], W0.shape[0]
-    A0 = torch.empty(B, S + Qn, h0, device=dev, dtype=torch.float32)
-    G = torch.empty(B, S + Qn, S, device=dev, dtype=torch.float32)
+    A0 = _out(out[0] if out is not None else None, (B, S + Qn, h0), dev, "A0")
+    G = _out(out[1] if out is not None else None, (B, S + Qn, S), dev, "G")
     _check(lib().fumi_hip_xpanel_fwd(ws.handle, _stream(dev), B, S, Qn, D, h0, _f32(x_s, "x_s"), _f32(x_q, "x_q"),
                                      _f32(W0, "W0"), _f32(A0, "A0"), _f32(G, "G")), "fumi_hip_xpanel_fwd")
     return A0, G
 
 
-def xpanel_bwd(ws, x_s, x_q, Abar, scale=1.0):
-    dev = _dev(x_s)
-    B, S, D = x_s.shape
-    Qn, h0 = x_q.shape[1], Abar.shape[2]
-    gW0 = torch.empty(h0, D, device=dev, dtype=torch.float32)
-    _check(lib().fumi_hip_xpanel_bwd(ws.handle, _stream(dev), B, S, Qn, D, h0, _f32(x_s, "x_s"), _f32(x_q, "x_q"),
+def xpanel_bwd(ws, x_s, x_q, Abar, scale=1.0, out=None):
+    """gW0 [h0, D].  ``x_s`` or ``x_q`` (not both) may be None: a one-sided panel over the rows of the other (Abar [B, rows, h0]).
+    ``out``: the tensor to write instead of a fresh one."""
+    if x_s is None and x_q is None:
+        raise FumiHipError("xpanel_bwd: x_s and x_q are both None")
+    dev = _dev(x_s if x_s is not None else x_q)
+    B, D = (x_s if x_s is not None else x_q).shape[0::2]
+    S = x_s.shape[1] if x_s is not None else 0
+    Qn = x_q.shape[1] if x_q is not None else 0
+    h0 = Abar.shape[2]
+    gW0 = _out(out, (h0, D), dev, "gW0")
+    ps = _f32(x_s, "x_s") if x_s is not None else c_void_p(None)
+    pq = _f32(x_q, "x_q") if x_q is not None else c_void_p(None)
+    _check(lib().fumi_hip_xpanel_bwd(ws.handle, _stream(dev), B, S, Qn, D, h0, ps, pq,
                                      _f32(Abar, "Abar"), float(scale), _f32(gW0, "gW0")), "fumi_hip_xpanel_bwd")
     return gW0
+
+
+XPANEL_PLAN_KEYS = ("fwd_kernel", "fwd_ring", "fwd_ksplit", "fwd_gram_blocks", "fwd_rode",
+                    "bwd_kernel", "bwd_nb", "bwd_sk", "bwd_nsplit", "bwd_kchunk", "bwd_rode")
+XPANEL_FWD_KERNELS = {1: "generic", 2: "generic_fast", 3: "fp32", 4: "split", 5: "presplit"}
+XPANEL_BWD_KERNELS = {1: "guarded64", 2: "fast64", 3: "wide_fp32", 4: "wide_split", 5: "narrow_split"}
+
+
+def xpanel_plan():
+    """dict over XPANEL_PLAN_KEYS: the kernel form the last forward and the last backward X-panel launch of this process took
+    (fumi_hip_xpanel_plan; the kernel ids are named by XPANEL_FWD_KERNELS / XPANEL_BWD_KERNELS)."""
+    v = (c_int * len(XPANEL_PLAN_KEYS))()
+    _check(lib().fumi_hip_xpanel_plan(v, len(XPANEL_PLAN_KEYS)), "fumi_hip_xpanel_plan")
+    return {k: int(x) for k, x in zip(XPANEL_PLAN_KEYS, v)}
 
 
 class AdamArgs:

@@ -196,6 +196,12 @@ int fumi_hip_xpanel_fwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
         const float* x_s, const float* x_q, const float* W0, float* A0, float* G);
 int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
         const float* x_s, const float* x_q, const float* Abar, float scale, float* gW0);
+/* bwd also takes a one-sided panel: S == 0 (x_s may be NULL) or Qn == 0 (x_q may be NULL), not both.
+ * Which kernel form the last fwd / bwd X-panel launch of this process took, up to 11 ints:
+ *   [fwd kernel (1 generic guarded, 2 generic fast, 3 fp32 MFMA, 4 per-tile split, 5 pre-split), ring depth, ksplit, Gram column
+ *    blocks, rider rode, bwd kernel (1 64x64 guarded, 2 64x64 fast, 3 wide fp32, 4 wide split, 5 narrow swapped split), NB, SK,
+ *    nsplit, kchunk, rider rode].  Host-side record only: no launch reads it. */
+int fumi_hip_xpanel_plan(int* plan, int n);
 /* One fused launch of torch.optim.Adam's update (coupled L2 weight decay, bias correction; fumi/utils/utils.py:280-283) for
  * up to 32 tensors.  Pointer/size arrays are HOST arrays; `step` is the 1-based step count. */
 int fumi_hip_adam_step(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
