@@ -478,24 +478,58 @@ __global__ __launch_bounds__(1024) void am3_head_kernel(int N, int S, int Qn, in
     }
 }
 
+// ---- text_encoder = 'rand' (am3.py:118-121): the text prototypes drawn on the device.  Element e = row * P + col of tx is
+// (float)(mix(key ^ (unsigned)e) >> 8) * 2^-23 - 1: uniform on the 2^24-point grid of [-1, 1), every value and every step exact in
+// fp32.  A pure function of (key, e): no atomics, the same bits on every launch.  Four elements per thread where `out` is 16-byte
+// aligned (vec), the n % 4 tail (or everything, vec = 0) one element per thread.
+__device__ __forceinline__ float am3_draw_one(unsigned key, unsigned long long e) {
+    unsigned x = key ^ (unsigned)e;
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return (float)(x >> 8) * 1.1920928955078125e-07f - 1.f;
+}
+__global__ __launch_bounds__(256) void am3_draw_rows_kernel(float* __restrict__ out, unsigned long long n, unsigned key, int vec) {
+    const unsigned long long gid = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    const unsigned long long n4 = vec ? n >> 2 : 0;
+    for (unsigned long long i = gid; i < n4; i += stride) {
+        const unsigned long long e = 4 * i;
+        float4 v;
+        v.x = am3_draw_one(key, e); v.y = am3_draw_one(key, e + 1); v.z = am3_draw_one(key, e + 2); v.w = am3_draw_one(key, e + 3);
+        reinterpret_cast<float4*>(out)[i] = v;
+    }
+    for (unsigned long long e = 4 * n4 + gid; e < n; e += stride) out[e] = am3_draw_one(key, e);
+}
+
 }  // namespace
 
 // decisions of the last am3_step_impl of this process (fumi_hip_am3_step_plan): written on the host beside the launches, never read
 // by them
-struct Am3Plan { int fast_head, nwaves, hgq, imparts, xks, g_fwd_split, g_fwd_rode, h_fwd_split, h_bwd_fused, g_bwd_fused, tx_nparts; };
+struct Am3Plan { int fast_head, nwaves, hgq, imparts, xks, g_fwd_split, g_fwd_rode, h_fwd_split, h_bwd_fused, g_bwd_fused, tx_nparts, text_form; };
 static Am3Plan g_am3_last = {};
 
 // dx_s [B,S,D] / dx_q [B,Qn,D] (optional, need_grad): adjoints of the image rows, imbar Wi -- what an image encoder in front of
 // this step (the Conv4 backbone, fumi_hip_conv4_encode_bwd) continues from
-static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
+//
+// text_form (fumi_hip_am3_step_tx, am3.py:118-126 with text_encoder = 'rand'): 0 = text_s [B*S,Dt] goes through g; 1 = text_s holds the
+// prototype-space rows [B*S,P] themselves; 2 = the step draws those rows into tx_out (am3_draw_rows_kernel, dkey(3)).  In forms 1 and 2
+// g is not part of the step: w[2..5] / g_w[2..5] are never touched, dropout acts in h only (dkey(2), the mask form 0 draws for h), and
+// the backward ends at h's weights -- nothing consumes txbar, so neither l1bar H0 nor any of g's products is formed.
+static int am3_step_impl(int text_form, float* tx_out, fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
         float dropout_p, uint64_t seed,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
         float* stats, float* dx_s, float* dx_q) {
-    if (!ws || !x_s || !y_s || !x_q || !y_q || !text_s || !w || !loss || !preds_q || !lamda_s || !correct) return FUMI_EINVAL;
+    const bool tf = text_form != 0;
+    if (!ws || !x_s || !y_s || !x_q || !y_q || !w || !loss || !preds_q || !lamda_s || !correct) return FUMI_EINVAL;
+    if (tf ? (text_form == 2) != (text_s == nullptr) || (!text_s && !tx_out) : !text_s) return FUMI_EINVAL;
+    if (tf && ws->text_grad) { ws->text_grad = nullptr; return FUMI_EINVAL; }       // no text adjoint exists in this form: disarm, refuse
+    if (tf) Dt = P;
     if (B < 1 || N < 1 || S < 1 || Qn < 1 || D < 1 || Dt < 1 || Ht < 1 || P < 1 || lamda_fixed < -1 || lamda_fixed > 1) return FUMI_EINVAL;
-    for (int i = 0; i < 10; ++i) if (!w[i] || (need_grad && (!g_w || !g_w[i]))) return FUMI_EINVAL;
+    for (int i = 0; i < 10; ++i) {
+        if (tf && i >= 2 && i < 6) continue;                                         // g's slots may be NULL and are never touched
+        if (!w[i] || (need_grad && (!g_w || !g_w[i]))) return FUMI_EINVAL;
+    }
     if (dropout_p < 0.f || dropout_p >= 1.f) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
@@ -506,7 +540,8 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         auto mix = [](unsigned x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; };
         return mix(mix((unsigned)(seed & 0xffffffffULL) ^ (0x9E3779B9U * tag)) ^ (unsigned)(seed >> 32));
     };
-    const float *Wi = w[0], *bi = w[1], *G0 = w[2], *g0 = w[3], *G1 = w[4], *g1 = w[5], *H0 = w[6], *h0 = w[7], *H1 = w[8], *h1 = w[9];
+    const float *Wi = w[0], *bi = w[1], *H0 = w[6], *h0 = w[7], *H1 = w[8], *h1 = w[9];
+    const float *G0 = tf ? nullptr : w[2], *g0 = tf ? nullptr : w[3], *G1 = tf ? nullptr : w[4], *g1 = tf ? nullptr : w[5];
     const long Rs = (long)B * S, Rq = (long)B * Qn;
     // fast head: N <= 64 classes, P <= 512, and the episode's support side fits LDS next to the per-wave adjoint slabs
     int nwaves = 16;
@@ -525,17 +560,18 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
 
     size_t bytes = 0;
     auto A = [&](size_t n) { bytes += ws_align(n * sizeof(float)); };
-    A((Rs + Rq) * P); A(Rs * Ht); A(Rs * P); A(Rs * Ht); A(2 * B); A((size_t)B * N * N + B);
-    const size_t wslab_n = (size_t)((Rs + 127) / 128) * ((size_t)Ht + 2 * (size_t)Ht * P + (size_t)Ht * Dt) + 64;   // text weight-gradient slabs
-    const size_t cpart_n = (size_t)((Rs + 127) / 128) * (size_t)(2 * ((Ht + 3) & ~3) + ((P + 3) & ~3) + 4)
+    // (the text-rows forms have no t1 / tx / t1bar, and of the weight-gradient slabs and column-sum partials only h's)
+    A((Rs + Rq) * P); if (!tf) { A(Rs * Ht); A(Rs * P); } A(Rs * Ht); A(2 * B); A((size_t)B * N * N + B);
+    const size_t wslab_n = (size_t)((Rs + 127) / 128) * ((size_t)Ht + (tf ? 1 : 2) * (size_t)Ht * P + (tf ? 0 : (size_t)Ht * Dt)) + 64;   // text weight-gradient slabs
+    const size_t cpart_n = (size_t)((Rs + 127) / 128) * (size_t)((tf ? 1 : 2) * ((Ht + 3) & ~3) + (tf ? 0 : (P + 3) & ~3) + 4)
                          + (size_t)((Rs + Rq + 127) / 128) * (size_t)((P + 3) & ~3) + 64;       // ColsumJobs partial sums
-    if (need_grad) { A((Rs + Rq) * P); A(Rs * P); A(Rs); A(Rs * Ht); A(Rs * Ht); A((size_t)xns * P * D); A(cpart_n); A(wslab_n); }
+    if (need_grad) { A((Rs + Rq) * P); A(Rs * P); A(Rs); A(Rs * Ht); if (!tf) A(Rs * Ht); A((size_t)xns * P * D); A(cpart_n); A(wslab_n); }
     // the text MLPs g (text -> Ht -> P) and h (P -> Ht -> 1) on the hypernetwork kernels (hyper_fwd.h / hyper_bwd.h): both layers of
     // a forward in one launch, a whole backward in one launch of independent (row block, column chunk) workgroups
     static const int mlp_fused = getenv("FUMI_AM3_MLP") ? atoi(getenv("FUMI_AM3_MLP")) : 1;      // 0: one GEMM launch per product
-    const size_t hfg_n = hyper_fwd_workspace_floats((int)Rs, Ht, P), hfh_n = hyper_fwd_workspace_floats((int)Rs, Ht, 1);
-    const size_t hbh_n = hyper_bwd_fused_workspace_floats((int)Rs, P, Ht, 1), hbg_n = hyper_bwd_fused_workspace_floats((int)Rs, 0, Ht, P);
-    const size_t txp_n = (need_grad && (Ht & 63) == 0) ? (size_t)((Rs + 15) / 16) * (Ht / 64) * 16 * P : 0;   // partials of txbar += l1bar H0
+    const size_t hfg_n = tf ? 0 : hyper_fwd_workspace_floats((int)Rs, Ht, P), hfh_n = hyper_fwd_workspace_floats((int)Rs, Ht, 1);
+    const size_t hbh_n = hyper_bwd_fused_workspace_floats((int)Rs, P, Ht, 1), hbg_n = tf ? 0 : hyper_bwd_fused_workspace_floats((int)Rs, 0, Ht, P);
+    const size_t txp_n = (!tf && need_grad && (Ht & 63) == 0) ? (size_t)((Rs + 15) / 16) * (Ht / 64) * 16 * P : 0;   // partials of txbar += l1bar H0
     if (mlp_fused) { A(hfg_n); A(hfh_n); if (need_grad) { A(hbh_n); A(hbg_n); A(txp_n); } }
     // query shares per episode of the head kernel: enough workgroups for the chip, >= 2 rows per wave, counters available
     static const int hgq_env = getenv("FUMI_AM3_GQ") ? atoi(getenv("FUMI_AM3_GQ")) : 0;
@@ -550,10 +586,11 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     if (xks > 1) A((size_t)xks * (Rs + Rq) * P);
     int rc = ws_reserve(ws, bytes);
     if (rc) return rc;
-    g_am3_last = Am3Plan{fast_head ? 1 : 0, nwaves, hgq, 1, xks, 0, 0, 0, 0, 0, 0};
+    g_am3_last = Am3Plan{fast_head ? 1 : 0, nwaves, hgq, 1, xks, 0, 0, 0, 0, 0, 0, text_form};
     float* im = ws_f(ws, (Rs + Rq) * P);          // image embeddings, [B, S+Qn, P]: an episode's support rows, then its query rows
-    float* t1 = ws_f(ws, Rs * Ht);
-    float* tx = ws_f(ws, Rs * P);
+    float* t1 = tf ? nullptr : ws_f(ws, Rs * Ht);
+    float* txw = tf ? nullptr : ws_f(ws, Rs * P);
+    const float* tx = tf ? (text_s ? text_s : tx_out) : txw;     // the text prototypes every later phase reads
     float* l1 = ws_f(ws, Rs * Ht);
     float* lc = ws_f(ws, 2 * B);                  // per-episode loss | correct
     float* confb = ws_f(ws, (size_t)B * N * N + B);       // per-episode confusion counts | lamda sums
@@ -574,9 +611,9 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         ProfScope ps(ws, st, FUMI_PH_XPANEL_FWD);
         float* xparts = xks > 1 ? ws_f(ws, (size_t)xks * (Rs + Rq) * P) : nullptr;
         // the text MLP g (independent of the images) rides at the front of this launch when it can (hyper_fwd.h)
-        hfg = mlp_fused ? ws_f(ws, hfg_n) : nullptr;
-        g_split = mlp_fused && Rs < (1 << 30) / Ht &&
-                  hyper_fwd_split_args((int)Rs, Dt, Ht, P, 0, text_s, G0, g0, G1, g1, t1, tx, hfg, ws->hcnt, &fa);
+        hfg = (mlp_fused && !tf) ? ws_f(ws, hfg_n) : nullptr;
+        g_split = !tf && mlp_fused && Rs < (1 << 30) / Ht &&
+                  hyper_fwd_split_args((int)Rs, Dt, Ht, P, 0, text_s, G0, g0, G1, g1, t1, txw, hfg, ws->hcnt, &fa);
         if (g_split) { fa.d.drop_thr = thr; fa.d.drop_key = dkey(1); fa.d.drop_scale = dsc; }
         if ((rc = launch_xpanel_fwd(st, B, S, Qn, D, P, x_s, x_q, Wi, im, nullptr, nullptr, g_split ? &fa : nullptr, &g_rode, xparts,
                                     fast_head ? &im_nparts : nullptr))) return rc;
@@ -586,13 +623,22 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     {
         ProfScope ps(ws, st, FUMI_PH_HYPER_FWD);
         float* hfh = mlp_fused ? ws_f(ws, hfh_n) : nullptr;
-        if (g_split) {
+        if (text_form == 2) {                  // the rows are drawn here; everything after reads tx_out
+            const unsigned long long n = (unsigned long long)Rs * P;
+            const int vec = ((uintptr_t)tx_out & 15) == 0;
+            const unsigned long long work = vec ? (n + 3) / 4 : n;
+            const unsigned blocks = (unsigned)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
+            hipLaunchKernelGGL(am3_draw_rows_kernel, dim3(blocks), dim3(256), 0, st, tx_out, n, dkey(3), vec);
+            LAUNCH_CHECK();
+        } else if (tf) {
+            if (tx_out && tx_out != text_s) HIP_TRY(hipMemcpyAsync(tx_out, text_s, (size_t)Rs * P * sizeof(float), hipMemcpyDeviceToDevice, st));
+        } else if (g_split) {
             if (!g_rode && (rc = launch_hyper_fwd_split(st, fa))) return rc;
         } else {
             g = gemm_args((int)Rs, Ht, Dt, text_s, Dt, G0, Dt, t1, Ht); g.bias = g0; g.act = 1;
             g.drop_thr = thr; g.drop_key = dkey(1); g.drop_scale = dsc;
             if ((rc = launch_gemm(st, g, 0, 0))) return rc;
-            g = gemm_args((int)Rs, P, Ht, t1, Ht, G1, Ht, tx, P); g.bias = g1;
+            g = gemm_args((int)Rs, P, Ht, t1, Ht, G1, Ht, txw, P); g.bias = g1;
             if ((rc = launch_gemm(st, g, 0, 0))) return rc;
         }
         if (lamda_fixed < 0) {
@@ -614,7 +660,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     if (need_grad) {
         cpart = nullptr;
         imb = ws_f(ws, (Rs + Rq) * P); txb = ws_f(ws, Rs * P); zlb = ws_f(ws, Rs);
-        l1b = ws_f(ws, Rs * Ht); t1b = ws_f(ws, Rs * Ht); slabs = ws_f(ws, (size_t)xns * P * D);
+        l1b = ws_f(ws, Rs * Ht); t1b = tf ? nullptr : ws_f(ws, Rs * Ht); slabs = ws_f(ws, (size_t)xns * P * D);
         cpart = ws_f(ws, cpart_n);
         wslabs = ws_f(ws, wslab_n);
     }
@@ -685,7 +731,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
                                  g_w[3], g_w[4], g_w[5], &dummy, &probe, t1b)) txparts = cand;
     }
     float* hbh = (mlp_fused && need_grad) ? ws_f(ws, hbh_n) : nullptr;
-    float* hbg = (mlp_fused && need_grad) ? ws_f(ws, hbg_n) : nullptr;
+    float* hbg = (mlp_fused && need_grad && !tf) ? ws_f(ws, hbg_n) : nullptr;
     if (lamda_fixed < 0) {
         // h network: lam = sigmoid(l1 H1^T + h1), l1 = relu(tx H0^T + h0)
         if (mlp_fused && hyper_bwd_fused_args((int)Rs, P, Ht, 1, 0, dsc, tx, l1, nullptr, zlb, H1, hbh, g_w[6], g_w[7], g_w[8], g_w[9],
@@ -703,7 +749,7 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
             if ((rc = wgrad(Ht, P, l1b, Ht, tx, P, g_w[6]))) return rc;                // gH0 = l1bar^T tx
             cj.add(l1b, (int)Rs, Ht, Ht, g_w[7]);
         }
-        if (!tx_nparts) {
+        if (!tx_nparts && !tf) {                                                        // (text-rows forms: nothing consumes txbar)
             g = gemm_args((int)Rs, P, Ht, l1b, Ht, H0, P, txb, P); g.accumulate = 1;   // txbar += l1bar H0
             if ((rc = launch_gemm(st, g, 0, 1))) return rc;
         }
@@ -711,26 +757,28 @@ static int am3_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         HIP_TRY(hipMemsetAsync(g_w[6], 0, (size_t)Ht * P * 4, st)); HIP_TRY(hipMemsetAsync(g_w[7], 0, (size_t)Ht * 4, st));
         HIP_TRY(hipMemsetAsync(g_w[8], 0, (size_t)Ht * 4, st)); HIP_TRY(hipMemsetAsync(g_w[9], 0, 4, st));
     }
-    // g network: tx = t1 G1^T + g1, t1 = relu(text G0^T + g0)
-    if (mlp_fused && hyper_bwd_fused_args((int)Rs, Dt, Ht, P, 0, dsc, text_s, t1, nullptr, txb, G1, hbg, nullptr, g_w[3], g_w[4], g_w[5],
-                                          &tail_, &ba, t1b)) {
-        if (tx_nparts) { ba.hbar_parts = txparts; ba.hbar_nparts = tx_nparts; }
-        g_am3_last.g_bwd_fused = 1;
-        if ((rc = launch_hyper_bwd_fused(st, ba))) return rc;                          // gG1, gg1, t1bar, gg0 (row-block slabs)
-    } else {
-        if (tx_nparts) return FUMI_EINVAL;                                             // (cannot happen: probed above)
-        if ((rc = wgrad(P, Ht, txb, P, t1, Ht, g_w[4]))) return rc;                    // gG1 = txbar^T t1
-        cj.add(txb, (int)Rs, P, P, g_w[5]);
-        g = gemm_args((int)Rs, Ht, P, txb, P, G1, Ht, t1b, Ht);                        // t1bar = (txbar G1) * relu'(t1) * dropout scale
-        g.mask = t1; g.alpha = dsc;
-        if ((rc = launch_gemm(st, g, 0, 1))) return rc;
-        cj.add(t1b, (int)Rs, Ht, Ht, g_w[3]);
-    }
-    if ((rc = wgrad(Ht, Dt, t1b, Ht, text_s, Dt, g_w[2]))) return rc;                  // gG0 = t1bar^T text (800 x 768: 128-row slabs)
-    if (float* tg = ws->text_grad) {                  // armed by fumi_hip_want_text_grad: d loss / d text_s = t1bar G0  [B*S,Dt]
-        ws->text_grad = nullptr;                      // (t1bar carries grad_scale and the dropout scale already)
-        g = gemm_args((int)Rs, Dt, Ht, t1b, Ht, G0, Dt, tg, Dt);
-        if ((rc = launch_gemm(st, g, 0, 1))) return rc;
+    // g network (not part of the graph in the text-rows forms: no product of its backward, no text adjoint): tx = t1 G1^T + g1, t1 = relu(text G0^T + g0)
+    if (!tf) {
+        if (mlp_fused && hyper_bwd_fused_args((int)Rs, Dt, Ht, P, 0, dsc, text_s, t1, nullptr, txb, G1, hbg, nullptr, g_w[3], g_w[4], g_w[5],
+                                              &tail_, &ba, t1b)) {
+            if (tx_nparts) { ba.hbar_parts = txparts; ba.hbar_nparts = tx_nparts; }
+            g_am3_last.g_bwd_fused = 1;
+            if ((rc = launch_hyper_bwd_fused(st, ba))) return rc;                          // gG1, gg1, t1bar, gg0 (row-block slabs)
+        } else {
+            if (tx_nparts) return FUMI_EINVAL;                                             // (cannot happen: probed above)
+            if ((rc = wgrad(P, Ht, txb, P, t1, Ht, g_w[4]))) return rc;                    // gG1 = txbar^T t1
+            cj.add(txb, (int)Rs, P, P, g_w[5]);
+            g = gemm_args((int)Rs, Ht, P, txb, P, G1, Ht, t1b, Ht);                        // t1bar = (txbar G1) * relu'(t1) * dropout scale
+            g.mask = t1; g.alpha = dsc;
+            if ((rc = launch_gemm(st, g, 0, 1))) return rc;
+            cj.add(t1b, (int)Rs, Ht, Ht, g_w[3]);
+        }
+        if ((rc = wgrad(Ht, Dt, t1b, Ht, text_s, Dt, g_w[2]))) return rc;                  // gG0 = t1bar^T text (800 x 768: 128-row slabs)
+        if (float* tg = ws->text_grad) {                  // armed by fumi_hip_want_text_grad: d loss / d text_s = t1bar G0  [B*S,Dt]
+            ws->text_grad = nullptr;                      // (t1bar carries grad_scale and the dropout scale already)
+            g = gemm_args((int)Rs, Dt, Ht, t1b, Ht, G0, Dt, tg, Dt);
+            if ((rc = launch_gemm(st, g, 0, 1))) return rc;
+        }
     }
     pb.reset();
     // image encoder: gWi = imbar_s^T Xs + imbar_q^T Xq (split over the contraction), gbi = colsum(imbar)
@@ -757,7 +805,7 @@ extern "C" int fumi_hip_am3_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
         float* stats) {
-    return am3_step_impl(ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
+    return am3_step_impl(0, nullptr, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
                          text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr);
 }
 
@@ -768,15 +816,38 @@ extern "C" int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
         float* stats, float* dx_s, float* dx_q) {
     if (need_grad && (!dx_s || !dx_q)) return FUMI_EINVAL;
-    return am3_step_impl(ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
+    return am3_step_impl(0, nullptr, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
                          text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q);
+}
+
+// The text-rows forms (text_encoder = 'rand'): text_s [B*S,P] or NULL (drawn into tx_out); Dt is not used.
+extern "C" int fumi_hip_am3_step_tx(fumi_ws_t* ws, fumi_stream_t stream,
+        int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
+        float dropout_p, uint64_t seed,
+        const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
+        const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
+        float* stats, float* tx_out) {
+    return am3_step_impl(text_s ? 1 : 2, tx_out, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed,
+                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr);
+}
+
+extern "C" int fumi_hip_am3_step_tx_dx(fumi_ws_t* ws, fumi_stream_t stream,
+        int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
+        float dropout_p, uint64_t seed,
+        const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
+        const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
+        float* stats, float* tx_out, float* dx_s, float* dx_q) {
+    if (need_grad && (!dx_s || !dx_q)) return FUMI_EINVAL;
+    return am3_step_impl(text_s ? 1 : 2, tx_out, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed,
+                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q);
 }
 
 extern "C" int fumi_hip_am3_step_plan(int* plan, int n) {
     if (!plan || n < 0) return FUMI_EINVAL;
-    const int v[11] = {g_am3_last.fast_head, g_am3_last.nwaves, g_am3_last.hgq, g_am3_last.imparts, g_am3_last.xks, g_am3_last.g_fwd_split,
-                       g_am3_last.g_fwd_rode, g_am3_last.h_fwd_split, g_am3_last.h_bwd_fused, g_am3_last.g_bwd_fused, g_am3_last.tx_nparts};
-    for (int i = 0; i < n && i < 11; ++i) plan[i] = v[i];
+    const int v[12] = {g_am3_last.fast_head, g_am3_last.nwaves, g_am3_last.hgq, g_am3_last.imparts, g_am3_last.xks, g_am3_last.g_fwd_split,
+                       g_am3_last.g_fwd_rode, g_am3_last.h_fwd_split, g_am3_last.h_bwd_fused, g_am3_last.g_bwd_fused, g_am3_last.tx_nparts,
+                       g_am3_last.text_form};
+    for (int i = 0; i < n && i < 12; ++i) plan[i] = v[i];
     return FUMI_OK;
 }
 

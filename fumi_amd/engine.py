@@ -12,6 +12,7 @@ _ENGINE = None
 class HipEngine:
     name = "hip-gfx950"
     folds_optimizer_step = True        # fumi_step consumes a deferred Adam step / publication (fumi_hip_adam_step_deferred)
+    am3_rand_native = True             # am3_step_tx: AM3's text_encoder='rand' as a form of the step (no g, rows drawn on the device)
 
     def _ws(self, t):
         return hip.Workspace.get(t.device if isinstance(t, torch.Tensor) and t.is_cuda else hip._dev(t))
@@ -41,6 +42,12 @@ class HipEngine:
                  dropout_p=0.0, seed=0, stats=None, want_dx=False):
         return hip.am3_step(self._ws(x_s), x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed, need_grad=need_grad,
                             grad_scale=grad_scale, g_w=g_w, dropout_p=dropout_p, seed=seed, stats=stats, want_dx=want_dx)
+
+    def am3_step_tx(self, x_s, y_s, x_q, y_q, text_rows, w, n_way, lamda_fixed, need_grad, grad_scale, g_w=None,
+                    dropout_p=0.0, seed=0, stats=None, want_dx=False):
+        """The AM3 step on prototype-space text rows [B,S,P] (None: drawn on the device from ``seed``); w[2:6] / g_w[2:6] may be None."""
+        return hip.am3_step_tx(self._ws(x_s), x_s, y_s, x_q, y_q, text_rows, w, n_way, lamda_fixed, need_grad=need_grad,
+                               grad_scale=grad_scale, g_w=g_w, dropout_p=dropout_p, seed=seed, stats=stats, want_dx=want_dx)
 
     def conv4_encode(self, x_s, x_q, theta, keep_tape=False):
         """Conv4 in front of a step with its own workspace (AM3): the tape lives in the device's "encoder" workspace."""

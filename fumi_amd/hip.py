@@ -35,6 +35,7 @@ SYMBOLS = [
     "fumi_hip_conv3x3_fwd", "fumi_hip_conv3x3_bwd_data", "fumi_hip_conv3x3_bwd_weight",
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
     "fumi_hip_want_text_grad",
+    "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT = 1, 2, 4
@@ -128,6 +129,8 @@ def lib():
         L.fumi_hip_am3_step.argtypes = (
             [c_void_p, c_void_p] + [c_int] * 10 + [c_float, c_float, ctypes.c_uint64] + [c_void_p] * 5 + [PP] + [c_void_p] * 4 + [PP, c_void_p])
         L.fumi_hip_am3_step_dx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p, c_void_p]
+        L.fumi_hip_am3_step_tx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p]
+        L.fumi_hip_am3_step_tx_dx.argtypes = L.fumi_hip_am3_step_tx.argtypes + [c_void_p, c_void_p]
         L.fumi_hip_am3_metrics.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
         L.fumi_hip_glove_bag.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int,
                                          c_int, c_void_p]
@@ -585,12 +588,94 @@ def am3_step(ws, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed=None, *, need
     return dict(loss=loss, preds=preds, lamda_s=lam, correct=correct, grads=g_w, stats=stats, dx_s=dx_s, dx_q=dx_q)
 
 
+def _parr_opt(tensors, name):
+    """``_parr`` for a list with ``None`` entries (NULL in the table): the text-rows form of the AM3 step never touches g's slots."""
+    key = (name,) + tuple(0 if t is None else t.data_ptr() for t in tensors)
+    arr = _PARR_CACHE.get(key)
+    if arr is not None:
+        for t in tensors:
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+                arr = None
+                break
+    if arr is None:
+        arr = (c_void_p * len(tensors))()
+        for i, t in enumerate(tensors):
+            arr[i] = None if t is None else _f32(t, f"{name}[{i}]").value
+        if len(_PARR_CACHE) > 256:
+            _PARR_CACHE.clear()
+        _PARR_CACHE[key] = arr
+    return arr
+
+
+def am3_step_tx(ws, x_s, y_s, x_q, y_q, text_rows, w, n_way, lamda_fixed=None, *, need_grad=True, grad_scale=None, g_w=None,
+                dropout_p=0.0, seed=0, stats=None, want_dx=False):
+    """The text-rows form of the AM3 step (fumi/models/am3.py:118-126 then :160-200, ``text_encoder='rand'``): the text prototypes are
+    rows of the prototype space, g is not applied and dropout acts in h only.  ``text_rows``: fp32 [B, S, P], or ``None`` -- then the
+    step draws them uniformly on [-1, 1) from ``seed`` on the device.  ``w`` / ``g_w`` keep the AM3_KEYS layout; entries 2..5 (g) may
+    be ``None`` and are never read or written.  Returns what ``am3_step`` returns plus ``"tx"``, the rows the step used."""
+    dev = _dev(x_s)
+    L = lib()
+    B, S, D = x_s.shape
+    Qn = x_q.shape[1]
+    if len(w) != 10:
+        raise FumiHipError("am3_step_tx: w must hold the 10 entries of AM3_KEYS (entries 2..5 may be None)")
+    for i, k in enumerate(AM3_KEYS):
+        if w[i] is None and not 2 <= i < 6:
+            raise FumiHipError(f"am3_step_tx: w[{k}] is None (only the g entries 2..5 may be)")
+    P, Ht = int(w[0].shape[0]), int(w[6].shape[0])
+    shapes = [(P, D), (P,), None, None, None, None, (Ht, P), (Ht,), (1, Ht), (1,)]
+    for t, shp, k in zip(w, shapes, AM3_KEYS):
+        if shp is None:
+            if t is not None:
+                _f32(t, f"w[{k}]")
+        else:
+            _shape(t, shp, f"w[{k}]")
+    _shape(x_q, (B, Qn, D), "x_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
+    if text_rows is not None:
+        _shape(text_rows, (B, S, P), "text_rows")
+        tx = torch.empty_like(text_rows)
+    else:
+        tx = torch.empty(B, S, P, device=dev, dtype=torch.float32)
+    if need_grad:
+        if g_w is None:
+            g_w = [None if (t is None or 2 <= i < 6) else torch.empty_like(t) for i, t in enumerate(w)]
+        elif len(g_w) != 10:
+            raise FumiHipError("am3_step_tx: g_w must hold 10 entries (entries 2..5 may be None)")
+        for g, t, shp, k in zip(g_w, w, shapes, AM3_KEYS):
+            if shp is not None:
+                if g is None:
+                    raise FumiHipError(f"am3_step_tx: g_w[{k}] is None (only the g entries 2..5 may be)")
+                _shape(g, shp, f"g_w[{k}]")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    lam = torch.empty(B, S, device=dev, dtype=torch.float32)
+    lf = -1 if lamda_fixed is None else int(lamda_fixed)
+    if grad_scale is None:
+        grad_scale = 1.0 / B
+    args = [ws.handle, _stream(dev), B, n_way, S, Qn, D, P, Ht, P, lf, int(bool(need_grad)), float(grad_scale),
+            float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"),
+            _f32(text_rows, "text_rows") if text_rows is not None else None,
+            _parr_opt(w, "w_tx"), c_void_p(loss.data_ptr()), c_void_p(preds.data_ptr()), c_void_p(lam.data_ptr()),
+            c_void_p(correct.data_ptr()), _parr_opt(g_w, "g_w_tx") if need_grad else None,
+            _f32(stats, "stats") if stats is not None else None, c_void_p(tx.data_ptr())]
+    dx_s = dx_q = None
+    if want_dx and need_grad:
+        dx_s, dx_q = torch.empty_like(x_s), torch.empty_like(x_q)
+        _check(L.fumi_hip_am3_step_tx_dx(*args, _f32(dx_s, "dx_s"), _f32(dx_q, "dx_q")), "fumi_hip_am3_step_tx_dx")
+    else:
+        _check(L.fumi_hip_am3_step_tx(*args), "fumi_hip_am3_step_tx")
+    return dict(loss=loss, preds=preds, lamda_s=lam, correct=correct, grads=g_w, stats=stats, dx_s=dx_s, dx_q=dx_q, tx=tx)
+
+
 AM3_PLAN_KEYS = ["fast_head", "nwaves", "hgq", "imparts", "xks", "g_fwd_split", "g_fwd_rode", "h_fwd_split", "h_bwd_fused",
-                 "g_bwd_fused", "tx_nparts"]
+                 "g_bwd_fused", "tx_nparts", "text_form"]
 
 
 def am3_step_plan():
-    """dict over AM3_PLAN_KEYS: the form the last ``am3_step`` of this process took (fumi_hip_am3_step_plan)."""
+    """dict over AM3_PLAN_KEYS: the form the last ``am3_step`` / ``am3_step_tx`` of this process took (fumi_hip_am3_step_plan);
+    ``text_form``: 0 = g applied, 1 = prototype-space rows given, 2 = rows drawn on the device."""
     v = (c_int * len(AM3_PLAN_KEYS))()
     _check(lib().fumi_hip_am3_step_plan(v, len(AM3_PLAN_KEYS)), "fumi_hip_am3_step_plan")
     return {k: int(x) for k, x in zip(AM3_PLAN_KEYS, v)}

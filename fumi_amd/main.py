@@ -156,9 +156,11 @@ def check_supported(args):
     family = args.model if args.model in ("maml", "fumi", "clip") else "am3"      # unknown names are AM3, like utils.init_model
     # (--fine_tune with --text_encoder RNN / RNNhid trains the bi-LSTM like the reference, fumi/models/fumi.py:65-67 / am3.py:74-76:
     # every meta-step hands back the adjoint of its text input, csrc/textenc.hip runs the LSTM's backward)
-    if family == "am3" and args.text_encoder == "rand" and args.dropout > 0 and not args.evaluate:
-        # fumi/models/am3.py:118-126 applies dropout inside h only; the engine's AM3 step draws the masks of g and h together and
-        # `rand` replaces g by an identity, so training this combination needs --dropout 0 (the CLI default is 0.25)
+    if (family == "am3" and args.text_encoder == "rand" and args.dropout > 0 and not args.evaluate
+            and not getattr(eng, "am3_rand_native", False)):
+        # fumi/models/am3.py:118-126 applies dropout inside h only.  The engine's text-rows form of the step (am3_step_tx) does that;
+        # an engine without it runs `rand` through an identity in g's place, whose hidden layer the step's dropout would hit too: there
+        # training this combination needs --dropout 0 (the CLI default is 0.25)
         raise NotImplementedError("--model am3 --text_encoder rand trains only with --dropout 0 on this engine "
                                   "(the step's dropout would also hit the identity that stands in for g)")
 

@@ -165,7 +165,12 @@ class AM3(nn.Module):
         elif self.training:
             self.eval()
         drop_p = float(self.dropout) if (train and self.dropout > 0) else 0.0       # nn.Dropout of g / h, train mode only
-        drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) + 7919 * fdist.world()[0] if drop_p > 0 else 0
+        eng = _engine.get_engine()
+        # text_encoder='rand' as a form of the step (am3_step_tx): the step draws the text prototypes from the seed, g is not applied,
+        # dropout acts in h only.  An engine without the form takes the identity route below (_rand_g).
+        rand_text = self.text_encoder_type == "rand"
+        rand_native = rand_text and getattr(eng, "am3_rand_native", False)
+        drop_seed = (int(torch.randint(0, 2 ** 62, (1,)).item()) + 7919 * fdist.world()[0]) if (drop_p > 0 or rand_native) else 0
         (s_idx, s_text, s_im), s_y = batch['train']
         (q_idx, _, q_im), q_y = batch['test']
         B, Qn = q_im.shape[0], q_im.shape[1]
@@ -187,10 +192,11 @@ class AM3(nn.Module):
         if lstm_ft:
             tok = to(s_text)
             text, lstm_tape = self.text_encoder.forward_train(tok)
+        elif rand_native:
+            text = None                           # drawn inside the step
         else:
             text = self._encode_text(to(s_text))
         w_det, th_det, fg = self._step_params(need_grad, num_ways)
-        eng = _engine.get_engine()
         # train / val on the GPU: the step also leaves [loss, correct, mean lamda, confusion counts] in the buffer's tail, one
         # all-reduce covers gradients and statistics, and accuracy / macro P / R / F1 come from one small kernel -- the reference
         # moves the predictions to the host and calls sklearn every meta-batch (utils.py:319-326): a blocking copy per step
@@ -204,8 +210,11 @@ class AM3(nn.Module):
             theta = th_det
             x_s, x_q = encode(img_s, img_q, theta, keep_tape=need_grad)
         g_w = fg.split(10)[0] if need_grad else None
-        rand_text = self.text_encoder_type == "rand"
-        if rand_text:
+        if rand_native:                      # g's slots are never read or written: its flat-buffer segments stay as they are
+            w_det = w_det[:2] + [None] * 4 + w_det[6:]
+            if need_grad:
+                g_w = list(g_w[:2]) + [None] * 4 + list(g_w[6:])
+        elif rand_text:
             if drop_p > 0:
                 raise NotImplementedError("text_encoder='rand' with dropout > 0 in training: the step's dropout would also "
                                           "hit the identity that stands in for g (the reference applies it to h only)")
@@ -215,11 +224,12 @@ class AM3(nn.Module):
         if lstm_ft:
             g_text = torch.empty_like(text)
             eng.want_text_grad(x_s.device, g_text)
-        out = eng.am3_step(x_s, y_s, x_q, y_q, text, w_det, num_ways,
-                           self.lamda_fixed, need_grad=need_grad, grad_scale=1.0 / B,
-                           g_w=g_w, dropout_p=drop_p, seed=drop_seed,
-                           **({"stats": tail} if on_device else {}),
-                           **({"want_dx": True} if (self.conv is not None and need_grad) else {}))
+        out = (eng.am3_step_tx if rand_native else eng.am3_step)(
+            x_s, y_s, x_q, y_q, text, w_det, num_ways,
+            self.lamda_fixed, need_grad=need_grad, grad_scale=1.0 / B,
+            g_w=g_w, dropout_p=drop_p, seed=drop_seed,
+            **({"stats": tail} if on_device else {}),
+            **({"want_dx": True} if (self.conv is not None and need_grad) else {}))
         if self.conv is not None and need_grad:     # ... and backwards from the adjoints of the features (already scaled by 1/B)
             encode_bwd(img_s, img_q, out["dx_s"], out["dx_q"], theta, scale=1.0, g_theta=fg.split(10)[1])
         if not on_device:

@@ -161,15 +161,42 @@ int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
         const float* const* w,
         float* loss, int64_t* preds_q, float* lamda_s, float* correct,
         float* const* g_w, float* stats, float* dx_s, float* dx_q);
+/* ---- AM3 step on text rows (am3.py:118-126 with text_encoder = 'rand', then :160-200) ---------------------------------------
+ * The same step with the text prototypes handed over as rows of the prototype space: tx = text rows, g is not applied,
+ * l1 = dropout(relu(tx H0^T + h0)), lamda = sigmoid(l1 H1^T + h1); prototypes, loss, predictions, stats, dx and lamda_fixed as above.
+ * Arguments as fumi_hip_am3_step / _dx except:
+ *   text_s   [B*S, P] the rows themselves, or NULL: the step draws them, element e = row * P + col is
+ *            (float)(mix(key3 ^ (uint32)e) >> 8) * 2^-23 - 1 with mix the 32-bit hash of the dropout masks and key3 the step's key of
+ *            tag 3 for `seed` -- uniform on the 2^24-point grid of [-1, 1), exact in fp32, the same bits on every call;
+ *   tx_out   [B*S, P] receives the rows the step used (optional when text_s is given, required when it is NULL);
+ *   w / g_w  keep the 10-entry layout; entries 2..5 (G0, g0, G1, g1) may be NULL and are never read or written.  Dt is not used.
+ * dropout_p > 0 acts in h only, with the mask fumi_hip_am3_step draws for h at the same seed (tag 2, element row * Ht + col).
+ * The backward forms gWi, gbi, gH0, gh0, gH1, gh1 (h's as zeros under a fixed lamda) and nothing of g or of the text rows; with
+ * fumi_hip_want_text_grad armed the call disarms it and returns FUMI_EINVAL. */
+int fumi_hip_am3_step_tx(fumi_ws_t* ws, fumi_stream_t stream,
+        int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
+        float dropout_p, uint64_t seed,
+        const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
+        const float* const* w,
+        float* loss, int64_t* preds_q, float* lamda_s, float* correct,
+        float* const* g_w, float* stats, float* tx_out);
+int fumi_hip_am3_step_tx_dx(fumi_ws_t* ws, fumi_stream_t stream,
+        int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
+        float dropout_p, uint64_t seed,
+        const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
+        const float* const* w,
+        float* loss, int64_t* preds_q, float* lamda_s, float* correct,
+        float* const* g_w, float* stats, float* tx_out, float* dx_s, float* dx_q);
 /* out6 = [loss, accuracy, macro F1, macro precision, macro recall, mean lamda] from `stats` (fumi_hip_am3_step): what
  * AM3.evaluate returns per meta-batch (am3.py:203-212 via sklearn on the host, utils.py:319-326), without leaving the device.
  * N <= 64. */
 int fumi_hip_am3_metrics(fumi_ws_t* ws, fumi_stream_t stream, int N, const float* stats, float* out6);
-/* Which form the last fumi_hip_am3_step / _dx of this process took (csrc/am3.hip, am3_step_impl; DESIGN.md "AM3 form tree"): the first
- * min(n, 11) of  [fast head (1) or generic head (0), waves of the head workgroup, query shares per episode, image-encoder parts the
+/* Which form the last fumi_hip_am3_step / _dx / _tx / _tx_dx of this process took (csrc/am3.hip, am3_step_impl; DESIGN.md "AM3 form
+ * tree"): the first min(n, 12) of  [fast head (1) or generic head (0), waves of the head workgroup, query shares per episode, image-encoder parts the
  * head adds where it reads (1 = none), contraction parts of the image-encoder pass, g forward in the split form, g forward inside
  * the X-panel launch, h forward in the split form, h backward fused, g backward fused, partials of txbar += l1bar H0 handed from h's
- * backward to g's (0 = the GEMM)].  The backward entries are 0 after a call with need_grad = 0.  Recording changes no launch. */
+ * backward to g's (0 = the GEMM), text form (0 = g applied, 1 = prototype-space rows given, 2 = rows drawn; in forms 1 and 2 the four g
+ * entries are 0)].  The backward entries are 0 after a call with need_grad = 0.  Recording changes no launch. */
 int fumi_hip_am3_step_plan(int* plan, int n);
 
 /* ---- finer-grained ops (unit parity tests; building blocks of the steps) --------------------------------------- */
