@@ -28,6 +28,7 @@ struct fumi_ws {
     float* text_grad;    // armed by fumi_hip_want_text_grad: the next FuMI step with need_grad also writes d loss / d class text rows here
     int* acnt;           // [FUMI_ACNT] arrival counters of the split adapt kernel (reset by the query kernel of the same step)
     int* hcnt;           // [FUMI_HCNT] arrival counters of hyper_fwd_split_kernel, zero between launches
+    double* clip_parts;  // partial sums of squares of the gradient norm (adam.hip), own allocation made at the first clipped step or norm
     float* side_buf; size_t side_cap;   // small allocation that survives slab rewinds (ResNet-12 chunk loop: heads of the whole meta-batch)
     unsigned short* w0p; size_t w0p_cap;   // the layer-0 weight as three bf16 planes in MFMA fragment order (xpanel.hip), own allocation
     int profiling;       // bit p: record HIP events around phase p (bench only)

@@ -24,6 +24,7 @@ SYMBOLS = [
     "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
+    "fumi_hip_grad_norm", "fumi_hip_adam_step_clipped", "fumi_hip_adamw_step_clipped", "fumi_hip_sgd_step_clipped",
     "fumi_hip_linear_fwd", "fumi_hip_linear_bwd_data", "fumi_hip_linear_bwd_weight",
     "fumi_hip_sample_episodes", "fumi_hip_sample_episodes_tm", "fumi_hip_gather_rows", "fumi_hip_gather_images", "fumi_hip_gather_images_resized", "fumi_hip_publish_scalars",
     "fumi_hip_publish_scalars_deferred", "fumi_hip_publish_flush", "fumi_hip_am3_metrics", "fumi_hip_am3_step_plan",
@@ -151,6 +152,11 @@ def lib():
         L.fumi_hip_adamw_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + betas
         L.fumi_hip_sgd_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 3 + [c_int]
         L.fumi_hip_sgd_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 3 + [c_int]
+        clip = [c_float, c_void_p]                                                         # max_norm, clip_out (device {norm, coef})
+        L.fumi_hip_grad_norm.argtypes = [c_void_p, c_void_p, c_int, PP, POINTER(ctypes.c_long), c_void_p]
+        L.fumi_hip_adam_step_clipped.argtypes = L.fumi_hip_adam_step.argtypes + clip
+        L.fumi_hip_adamw_step_clipped.argtypes = L.fumi_hip_adamw_step.argtypes + clip
+        L.fumi_hip_sgd_step_clipped.argtypes = L.fumi_hip_sgd_step.argtypes + clip
         L.fumi_hip_linear_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int, c_void_p]
         L.fumi_hip_linear_bwd_data.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3
         L.fumi_hip_linear_bwd_weight.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4
@@ -799,7 +805,8 @@ def xpanel_plan():
 
 
 class AdamArgs:
-    """Cached pointer tables of one fused Adam call (rebuilt only when a tensor is reallocated)."""
+    """Cached pointer tables of one fused Adam call (rebuilt only when a tensor is reallocated).  Any number of tensors: the
+    unclipped entry points take up to 32, the clipped ones up to 256 (``MAX_CLIPPED_TENSORS``)."""
 
     def __init__(self, params, grads, exp_avg, exp_avg_sq):
         self.key = tuple(t.data_ptr() for t in params + grads + exp_avg + exp_avg_sq)
@@ -867,6 +874,53 @@ def sgd_step_deferred(ws, args, lr, momentum, weight_decay, first):
     rc = lib().fumi_hip_sgd_step_deferred(ws.handle, args.n, args.p, args.g, args.buf, args.numel,
                                           float(lr), float(momentum), float(weight_decay), int(bool(first)))
     _check(rc, "fumi_hip_sgd_step_deferred")
+
+
+MAX_CLIPPED_TENSORS = 256        # csrc/adam.hip: CLIP_MAX_TENSORS
+
+
+def grad_norm(ws, grads, out=None):
+    """Global L2 norm of the fp32 GPU tensors ``grads`` (up to 256) as a one-element device tensor; nothing is read back
+    (fumi_hip_grad_norm)."""
+    grads = list(grads)
+    dev = _dev(grads[0])
+    if out is None:
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+    numel = (ctypes.c_long * len(grads))(*[t.numel() for t in grads])
+    rc = lib().fumi_hip_grad_norm(ws.handle, _stream(dev), len(grads), _parr(grads, "grads"), numel, _f32(out, "out"))
+    _check(rc, "fumi_hip_grad_norm")
+    return out
+
+
+def _clip_out(t):
+    if t.numel() != 2:
+        raise FumiHipError("clip_out: expected two floats (norm, coef)")
+    return _f32(t, "clip_out")
+
+
+def adam_step_clipped(ws, args, lr, beta1, beta2, eps, weight_decay, step, max_norm, clip_out, device):
+    """clip_grad_norm_(max_norm) and ``adam_step`` without leaving the device; ``clip_out`` receives (norm, coef), the gradients
+    are left as they are.  ``args``: an ``AdamArgs`` of up to 256 tensors."""
+    rc = lib().fumi_hip_adam_step_clipped(ws.handle, _stream(device), args.n, args.p, args.g, args.m, args.v, args.numel,
+                                          float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                          float(max_norm), _clip_out(clip_out))
+    _check(rc, "fumi_hip_adam_step_clipped")
+
+
+def adamw_step_clipped(ws, args, lr, beta1, beta2, eps, weight_decay, step, max_norm, clip_out, device):
+    rc = lib().fumi_hip_adamw_step_clipped(ws.handle, _stream(device), args.n, args.p, args.g, args.m, args.v, args.numel,
+                                           float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                           float(max_norm), _clip_out(clip_out))
+    _check(rc, "fumi_hip_adamw_step_clipped")
+
+
+def sgd_step_clipped(ws, args, lr, momentum, weight_decay, first, max_norm, clip_out, device):
+    if (args.buf is None) != (momentum == 0):
+        raise FumiHipError("sgd_step_clipped: momentum buffers are needed exactly when momentum != 0")
+    rc = lib().fumi_hip_sgd_step_clipped(ws.handle, _stream(device), args.n, args.p, args.g, args.buf, args.numel,
+                                         float(lr), float(momentum), float(weight_decay), int(bool(first)),
+                                         float(max_norm), _clip_out(clip_out))
+    _check(rc, "fumi_hip_sgd_step_clipped")
 
 
 def linear_fwd(ws, x, W, b=None, act=0):

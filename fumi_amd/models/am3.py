@@ -15,6 +15,7 @@ from .. import dist as fdist
 from .. import engine as _engine
 from .. import lazy
 from ..flatgrad import FlatGrads, ParamWatch
+from ..optim import clip_log
 from ..utils import utils as utils
 from ..utils.average_meter import AverageMeter
 from ..utils.wandb_compat import wandb
@@ -288,7 +289,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
                 wandb.log({"val/acc": val_acc, "val/f1": val_f1, "val/prec": val_prec, "val/rec": val_rec,
-                           "val/loss": val_loss, "val/avg_lamda": val_lamda}, step=batch_idx)
+                           "val/loss": val_loss, "val/avg_lamda": val_lamda, **clip_log(opt)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}, train/avg_lamda: {tlam}"

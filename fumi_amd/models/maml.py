@@ -12,6 +12,7 @@ from .. import dist as fdist
 from .. import lazy
 from .. import engine as _engine
 from ..flatgrad import FlatGrads
+from ..optim import clip_log
 from ..meta import MetaLinear, MetaModule, MetaSequential
 from ..utils import utils as utils
 from ..utils.average_meter import AverageMeter
@@ -108,7 +109,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 is_best = val_loss < best_loss
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
-                wandb.log({"val/acc": val_acc, "val/loss": val_loss}, step=batch_idx)
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **clip_log(optimizer)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": optimizer.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {train_loss}, train/acc: {train_acc}"

@@ -3,8 +3,14 @@
 fused HIP launch over all parameter tensors when they are fp32 GPU tensors (csrc/adam.hip); any other configuration (amsgrad,
 maximize, nesterov, dampening, CPU tensors, sparse grads ...) uses torch's own implementation unchanged.  ``_FusedStep`` holds what
 the three share: the cached launch plans, ``step_fused`` / ``defer_step`` / ``finish_deferred`` and the bookkeeping around
-``state_dict`` / pickling; a class adds its rule's flags, state tensors and launch."""
+``state_dict`` / pickling; a class adds its rule's flags, state tensors and launch.
+
+``max_grad_norm=<float>`` (keyword of all three) clips the global gradient norm ahead of every step, as
+``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` would: on the fused route without leaving the device and without writing
+``p.grad`` (csrc/adam.hip: norm launches, finish launch, the rule on ``g * coef``); ``optimizer.clip_stats`` is the device tensor
+``(norm, coef)`` of the last step.  The value lives on the optimizer object, not in ``param_groups``: ``state_dict`` stays torch's."""
 import copy
+import math
 
 import torch
 
@@ -12,6 +18,26 @@ from . import hip
 
 MAX_TENSORS = 32          # one fused launch (csrc/adam.hip: MAXT)
 MAX_FOLDED = 24           # segments of the meta-step's final reduction (csrc/common.h: ReduceSegs)
+MAX_CLIPPED = hip.MAX_CLIPPED_TENSORS      # a clipped step walks its tensors in chunks of MAX_TENSORS (csrc/adam.hip: CLIP_MAX_TENSORS)
+
+
+def _checked_max_norm(v):
+    if v is None:
+        return None
+    v = float(v)
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"max_grad_norm must be a finite number greater than 0, got {v}")
+    return v
+
+
+def clip_log(optimizer):
+    """``{"train/grad_norm", "train/clip_coef"}`` of the last clipped step for the training loops' validation points (the one host
+    read of ``clip_stats``); empty when the optimizer does not clip or has not stepped."""
+    stats = getattr(optimizer, "clip_stats", None)
+    if getattr(optimizer, "max_grad_norm", None) is None or stats is None:
+        return {}
+    norm, coef = stats.tolist()
+    return {"train/grad_norm": norm, "train/clip_coef": coef}
 
 
 class _FusedStep:
@@ -20,22 +46,45 @@ class _FusedStep:
     in torch's layout and returns the cached launch arguments, or None when torch must take the step) and
     ``_launch(group, plan, device, deferred)``."""
     _torch_cls = None
+    max_grad_norm = None                          # (class defaults: an optimizer pickled before the option existed has neither)
+    _clip_stats = None
+
+    @property
+    def clip_stats(self):
+        """Device tensor ``(norm, coef)`` of the last step taken with ``max_grad_norm`` set (None before it): the global gradient
+        norm and the factor the step applied.  Reading it is the caller's host read; the step makes none."""
+        return self._clip_stats
+
+    def _torch_step(self, closure=None):
+        """torch's own step, preceded by torch's own clip when ``max_grad_norm`` is set (which scales ``p.grad`` in place)."""
+        if self.max_grad_norm is None:
+            return self._torch_cls.step(self, closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if params:
+            norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+            self._clip_stats = torch.stack([norm, torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)]).to(torch.float32)
+        self._torch_cls.step(self)
+        return loss
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._fused_args = {}                     # the state tensors were replaced: rebuild the cached pointer tables (and counts)
 
     def _fusable(self, group, params):
-        return (params and self._flags_ok(group) and len(params) <= MAX_TENSORS
+        return (params and self._flags_ok(group) and len(params) <= (MAX_TENSORS if self.max_grad_norm is None else MAX_CLIPPED)
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()
                         and not p.grad.is_sparse and p.grad.dtype == torch.float32 for p in params))
 
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
-            return super().step(closure)
+            return self._torch_step(closure)
         if not self._step_impl():
-            return super().step(closure)
+            return self._torch_step()
         return None
 
     def step_fused(self):
@@ -47,7 +96,7 @@ class _FusedStep:
             self._opt_called = True               # what the lr_scheduler's wrapper around step() records (its order check)
         with torch.no_grad():
             if not self._step_impl():
-                return self._torch_cls.step(self)
+                return self._torch_step()
         return None
 
     def defer_step(self, device):
@@ -55,7 +104,9 @@ class _FusedStep:
         launch of the training meta-step that follows (``fumi_hip_adam_step_deferred`` and its siblings; single process only --
         the caller checks).  True when registered; the caller then runs the meta-step and ``finish_deferred``.  False (nothing
         done) when the step has to go the ordinary way: first step (no gradient views yet), several groups, hooks, a
-        non-fusable configuration."""
+        non-fusable configuration, or ``max_grad_norm`` (the norm needs every gradient element before the first update)."""
+        if self.max_grad_norm is not None:
+            return False
         if self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(self.param_groups) != 1:
             return False
         group = self.param_groups[0]
@@ -88,6 +139,13 @@ class _FusedStep:
                 torch._foreach_add_(args.steps, lag)
                 args.synced = args.count
 
+    def _clip_out(self, device):
+        """The optimizer's own two-float device tensor the clipped launches write (norm, coef) to."""
+        t = self._clip_stats
+        if t is None or t.device != device or t.dtype != torch.float32 or t.numel() != 2 or not t.is_contiguous():
+            t = self._clip_stats = torch.zeros(2, device=device, dtype=torch.float32)
+        return t
+
     def _fall_back(self):
         """torch's own step is about to run for EVERY group and will increment every `step` tensor itself: bring the tensors
         up to date and forget the cached plans, so the next fused step reads its counts from the tensors again."""
@@ -97,7 +155,7 @@ class _FusedStep:
 
     def __getstate__(self):
         self._sync_steps()                        # pickling / deepcopy read optimizer.state directly
-        return super().__getstate__()
+        return dict(super().__getstate__(), max_grad_norm=self.max_grad_norm)
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -109,12 +167,14 @@ class _FusedStep:
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            setattr(new, k, {} if k == "_fused_args" else copy.deepcopy(v, memo))
+            setattr(new, k, {} if k == "_fused_args" else None if k == "_clip_stats" else copy.deepcopy(v, memo))
         return new
 
     def _step_impl(self):
         """True when every group went through the fused launch; False (nothing done) when torch's implementation must run."""
         groups = [(g, [p for p in g["params"] if p.grad is not None]) for g in self.param_groups]
+        if self.max_grad_norm is not None and len(groups) != 1:
+            return self._fall_back()              # (one norm over every group: a launch per group would clip each on its own)
         plans = []
         for gi, (group, params) in enumerate(groups):
             if not params:
@@ -144,7 +204,7 @@ class _FusedStep:
 
 class _AdamRule(_FusedStep):
     """Adam's and AdamW's state (``step``, ``exp_avg``, ``exp_avg_sq``) and launch; they differ in the kernel's rule only."""
-    _now = _later = None
+    _now = _later = _clipped = None
 
     def _flags_ok(self, group, plan=None):
         return not (isinstance(group["lr"], torch.Tensor) or group.get("amsgrad") or group.get("maximize")
@@ -168,7 +228,10 @@ class _AdamRule(_FusedStep):
         plan.count += 1                                                         # (the `step` tensors follow in _sync_steps)
         b1, b2 = group["betas"]
         ws = hip.Workspace.get(device)
-        if deferred:
+        if self.max_grad_norm is not None:
+            type(self)._clipped(ws, plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], plan.count, self.max_grad_norm,
+                                self._clip_out(device), device)
+        elif deferred:
             type(self)._later(ws, plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], plan.count)
         else:
             type(self)._now(ws, plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], plan.count, device)
@@ -176,22 +239,24 @@ class _AdamRule(_FusedStep):
 
 class Adam(_AdamRule, torch.optim.Adam):
     _torch_cls = torch.optim.Adam
-    _now, _later = staticmethod(hip.adam_step), staticmethod(hip.adam_step_deferred)
+    _now, _later, _clipped = staticmethod(hip.adam_step), staticmethod(hip.adam_step_deferred), staticmethod(hip.adam_step_clipped)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **kw):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
         self._fused_args = {}
+        self.max_grad_norm = _checked_max_norm(max_grad_norm)
 
 
 class AdamW(_AdamRule, torch.optim.AdamW):
     """torch.optim.AdamW (decoupled weight decay, default 1e-2): what --optim adamw / adamw_lin_schedule construct.  A schedule
     may rewrite ``group["lr"]`` before every step; the value is read at each launch, the deferred form included."""
     _torch_cls = torch.optim.AdamW
-    _now, _later = staticmethod(hip.adamw_step), staticmethod(hip.adamw_step_deferred)
+    _now, _later, _clipped = staticmethod(hip.adamw_step), staticmethod(hip.adamw_step_deferred), staticmethod(hip.adamw_step_clipped)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
         self._fused_args = {}
+        self.max_grad_norm = _checked_max_norm(max_grad_norm)
 
     def _flags_ok(self, group, plan=None):
         return super()._flags_ok(group) and bool(group.get("decoupled_weight_decay", True))
@@ -203,9 +268,10 @@ class SGD(_FusedStep, torch.optim.SGD):
     torch's."""
     _torch_cls = torch.optim.SGD
 
-    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=None, **kw):
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, **kw)
         self._fused_args = {}
+        self.max_grad_norm = _checked_max_norm(max_grad_norm)
 
     def _flags_ok(self, group, plan=None):
         return (not (isinstance(group["lr"], torch.Tensor) or group.get("nesterov") or group.get("dampening") or group.get("maximize")
@@ -234,7 +300,10 @@ class SGD(_FusedStep, torch.optim.SGD):
 
     def _launch(self, group, plan, device, deferred):
         ws = hip.Workspace.get(device)
-        if deferred:
+        if self.max_grad_norm is not None:
+            hip.sgd_step_clipped(ws, plan, group["lr"], group["momentum"], group["weight_decay"], plan.first, self.max_grad_norm,
+                                 self._clip_out(device), device)
+        elif deferred:
             hip.sgd_step_deferred(ws, plan, group["lr"], group["momentum"], group["weight_decay"], plan.first)
         else:
             hip.sgd_step(ws, plan, group["lr"], group["momentum"], group["weight_decay"], plan.first, device)

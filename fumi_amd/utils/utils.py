@@ -86,6 +86,7 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--synthetic_table_size", dict(type=int, default=None, help="[--dataset synthetic-resident with an image encoder] stored height = width of the pixel table (default: --image_size)")),
     ("--image_mean", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel mean on the 0..1 pixel scale (default: the train table's own)")),
     ("--image_std", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel standard deviation on the 0..1 pixel scale (default: the train table's own)")),
+    ("--max_grad_norm", dict(type=float, default=None, help="clip the global L2 norm of the outer gradient to this value before every optimizer step (torch.nn.utils.clip_grad_norm_ semantics, computed on the device; default: no clipping)")),
 ]
 
 
@@ -139,15 +140,16 @@ def init_optim(args, model):
     """Optimizer factory (utils.py:277-299); may return an (optimizer, scheduler) tuple."""
     # torch.optim's classes whose step() is one fused HIP launch on the GPU (and folds into the FuMI meta-step's last launch)
     from ..optim import SGD, Adam, AdamW
+    clip = dict(max_grad_norm=getattr(args, "max_grad_norm", None))        # --max_grad_norm (additive; None: no clipping)
     if args.optim == "adam":
-        return Adam(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+        return Adam(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay, **clip)
     if args.optim == "SGD":
-        return SGD(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay, momentum=args.momentum)
+        return SGD(params=model.parameters(), lr=args.lr, weight_decay=args.weight_decay, momentum=args.momentum, **clip)
     if args.optim == "adamw":
         # transformers.AdamW(lr) of the pinned 4.5.1: decoupled weight decay, default weight_decay 0.0
-        return AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
+        return AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0, **clip)
     if args.optim == "adamw_lin_schedule":
-        opt = AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0)
+        opt = AdamW(params=model.parameters(), lr=args.lr, weight_decay=0.0, **clip)
         return opt, _linear_warmup_schedule(opt, args.num_warmup_steps, args.epochs)
     raise NotImplementedError()
 

@@ -266,6 +266,28 @@ int fumi_hip_adamw_step_deferred(fumi_ws_t* ws, int n_tensors, float* const* par
 int fumi_hip_sgd_step_deferred(fumi_ws_t* ws, int n_tensors, float* const* params,
         const float* const* grads, float* const* momentum_buf, const long* numel,
         float lr, float momentum, float weight_decay, int first_step);
+/* The global L2 norm of up to 256 gradient tensors, as torch.nn.utils.clip_grad_norm_ forms it (norm_type 2): squares summed in
+ * double in a fixed order (one partial per workgroup in a buffer the workspace owns, added in index order by a second launch; no
+ * floating-point atomics: equal inputs give equal bits), *norm_out = (float)sqrt(sum).  norm_out is a DEVICE float; grads / numel
+ * are HOST arrays.  A tensor of no elements may have a NULL pointer. */
+int fumi_hip_grad_norm(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, const float* const* grads, const long* numel,
+        float* norm_out);
+/* Clipped forms of the three steps: clip_grad_norm_(params, max_norm) followed by the rule, without leaving the device and
+ * without writing the gradients -- the norm as above, coef = min(1, max_norm / (norm + 1e-6)) in fp32 (a NaN norm gives a NaN
+ * coef, an infinite one 0), then the rule on g * coef (one rounded fp32 multiply per element: the parameters and state are bit
+ * for bit those of the unclipped entry point on gradients scaled by coef).  Arguments as the unclipped sibling, then max_norm
+ * (finite and > 0, else FUMI_EINVAL) and clip_out, a DEVICE buffer of two floats that receives {norm, coef} (required).  Up to
+ * 256 tensors (FUMI_ENOTSUP beyond), walked in chunks of 32: separate launches ordered by the stream alone.  There is no deferred
+ * form: the norm needs every gradient element before the first update. */
+int fumi_hip_adam_step_clipped(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
+        const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const long* numel,
+        float lr, float beta1, float beta2, float eps, float weight_decay, int step, float max_norm, float* clip_out);
+int fumi_hip_adamw_step_clipped(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
+        const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const long* numel,
+        float lr, double beta1, double beta2, float eps, float weight_decay, int step, float max_norm, float* clip_out);
+int fumi_hip_sgd_step_clipped(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
+        const float* const* grads, float* const* momentum_buf, const long* numel,
+        float lr, float momentum, float weight_decay, int first_step, float max_norm, float* clip_out);
 /* y[M,N] = act(x[M,K] W[N,K]^T + b[N]);  act: 0 none, 1 relu, 2 tanh.  b may be NULL. */
 int fumi_hip_linear_fwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int N, int K,
         const float* x, const float* W, const float* b, int act, float* y);
