@@ -1,0 +1,165 @@
+// Classification head of the supervised pre-training step: F.cross_entropy(feats W^T + b, y), mean over the
+// M rows, with its backward, for a head over hundreds of classes.
+//
+//   launch 1, one workgroup per tile of 16 rows:
+//       Z = feats_tile W^T + b          [16, C] on the f32 MFMA (wg_mm), kept in LDS
+//       per row: first arg-max, log-sum-exp, NLL; the tile's loss / correct sums go to part[tile]
+//       training form: Z <- dlogits = grad_scale / M * (softmax(Z) - onehot) in place, also written to memory for launch 2,
+//                      dfeats_tile = dlogits W      (wg_mm, A read from LDS)
+//   launch 2, one workgroup per [16 classes x 128 features] block of gW, each over ALL M rows (no sum across workgroups):
+//       gW = dlogits^T feats,  gb = colsum(dlogits) (the workgroups of the first feature block);
+//       one further workgroup adds part[0..ntile) in index order: loss = sum / M, correct = count.
+//   The forward form (no gradient pointers) is launch 1 without its backward half and launch 2 with that last workgroup alone: the
+//   same instructions produce loss, correct and preds in both forms.
+// Every sum has a fixed order (MFMA chains over k, butterflies inside a 16-lane group, index-ordered loops across tiles): equal
+// inputs give equal bits.  No floating-point atomics; the only atomic is the OR into the status word.
+// A label outside [0, C) sets FUMI_ST_LABEL_RANGE; its row adds nothing to the loss, the count or the gradients (the divisor stays M).
+#include "common.h"
+
+namespace {
+
+constexpr int CH_TM = 16;          // rows per workgroup of launch 1
+constexpr int CH_NB = 128;         // output columns of one wg_mm call: 8 MFMA tiles = one pass of 4 waves x 2 tiles
+constexpr int CH_MM = 16384;       // floats of LDS the products stage their operands in
+constexpr int CH_MAXTILE = 4096 / CH_TM;
+
+struct ClsHead {
+    int M, F, C, ldz, ntile, train;
+    float gs;                      // grad_scale / M
+};
+
+__global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, const float* __restrict__ feats, const int64_t* __restrict__ y,
+                                                            const float* __restrict__ W, const float* __restrict__ bias,
+                                                            int64_t* __restrict__ preds, float* __restrict__ part,
+                                                            float* __restrict__ dlog, float* __restrict__ dfeats, int* status) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int tid = threadIdx.x;
+    const int M = d.M, F = d.F, C = d.C, ldz = d.ldz;
+    const int m0 = blockIdx.x * CH_TM, rows = min(CH_TM, M - m0);
+    float* Z = sm;                               // [16, ldz]
+    float* rl = Z + CH_TM * ldz;                 // [16] row losses, [16] row hits
+    float* mm = rl + 64;
+    const float* ft = feats + (long)m0 * F;
+
+    for (int c0 = 0; c0 < C; c0 += CH_NB) {
+        const int nb = min(CH_NB, C - c0);
+        wg_mm(mm, CH_MM, rows, nb, F, ft, F, 1, W + (long)c0 * F, 1, F,
+              [&](int m, int n, float acc) { Z[m * ldz + c0 + n] = acc + bias[c0 + n]; });
+    }
+    __syncthreads();
+
+    {   // 16 lanes per row
+        const int row = tid >> 4, l = tid & 15;
+        float loss = 0.f, hit = 0.f;
+        if (row < rows) {
+            float* z = Z + row * ldz;
+            float mx = -INFINITY; int arg = C;
+            for (int c = l; c < C; c += 16) { const float v = z[c]; if (v > mx) { mx = v; arg = c; } }
+            for (int o = 8; o > 0; o >>= 1) {
+                const float v2 = __shfl_xor(mx, o, 64); const int a2 = __shfl_xor(arg, o, 64);
+                if (v2 > mx || (v2 == mx && a2 < arg)) { mx = v2; arg = a2; }           // first arg-max (torch.max)
+            }
+            if (arg >= C) arg = 0;                                                       // (a row of NaNs)
+            float s = 0.f;
+            for (int c = l; c < C; c += 16) s += expf(z[c] - mx);
+            for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            long yv = y[m0 + row];
+            const bool ok = yv >= 0 && yv < C;
+            if (!ok) { if (l == 0) atomicOr(status, FUMI_ST_LABEL_RANGE); yv = 0; }
+            loss = ok ? mx + logf(s) - z[yv] : 0.f;
+            hit = (ok && arg == (int)yv) ? 1.f : 0.f;
+            if (l == 0 && preds) preds[m0 + row] = arg;
+            if (d.train) {
+                const float inv = 1.f / s, gs = ok ? d.gs : 0.f;
+                float* dl = dlog + (long)(m0 + row) * C;
+                for (int c = l; c < C; c += 16) {
+                    const float g = gs * (expf(z[c] - mx) * inv - (c == (int)yv ? 1.f : 0.f));
+                    z[c] = g; dl[c] = g;
+                }
+            }
+        }
+        if (l == 0) { rl[row] = loss; rl[16 + row] = hit; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float a = 0.f, c = 0.f;
+        for (int r = 0; r < CH_TM; ++r) { a += rl[r]; c += rl[16 + r]; }
+        part[blockIdx.x] = a; part[CH_MAXTILE + blockIdx.x] = c;
+    }
+    if (!d.train) return;
+    // dfeats_tile [rows, F] = dlogits_tile [rows, C] W [C, F]
+    for (int f0 = 0; f0 < F; f0 += CH_NB) {
+        const int nb = min(CH_NB, F - f0);
+        wg_mm(mm, CH_MM, rows, nb, C, Z, ldz, 1, W + f0, F, 1,
+              [&](int m, int n, float acc) { dfeats[(long)(m0 + m) * F + f0 + n] = acc; });
+    }
+}
+
+__global__ __launch_bounds__(256) void cls_head_wgrad_kernel(ClsHead d, int nfb, const float* __restrict__ feats,
+                                                             const float* __restrict__ dlog, const float* __restrict__ part,
+                                                             float* __restrict__ loss, float* __restrict__ correct,
+                                                             float* __restrict__ gW, float* __restrict__ gb) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int tid = threadIdx.x;
+    const int M = d.M, F = d.F, C = d.C;
+    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles, in index order
+        if (tid == 0) {
+            float a = 0.f, c = 0.f;
+            for (int t = 0; t < d.ntile; ++t) { a += part[t]; c += part[CH_MAXTILE + t]; }
+            loss[0] = a / (float)M; correct[0] = c;
+        }
+        return;
+    }
+    const int cb = blockIdx.x / nfb, fb = blockIdx.x - cb * nfb;
+    const int c0 = cb * CH_TM, f0 = fb * CH_NB;
+    const int nc = min(CH_TM, C - c0), nf = min(CH_NB, F - f0);
+    // gW[c0 + m, f0 + n] = sum_k dlog[k, c0 + m] feats[k, f0 + n]
+    wg_mm(sm, CH_MM, nc, nf, M, dlog + c0, 1, C, feats + f0, F, 1,
+          [&](int m, int n, float acc) { gW[(long)(c0 + m) * F + f0 + n] = acc; });
+    if (fb != 0) return;
+    __syncthreads();
+    {   // gb[c0 + c] = sum_k dlog[k, c0 + c]: 16 strided partial sums per class, added in index order
+        const int c = tid & 15, j = tid >> 4;
+        float s = 0.f;
+        if (c < nc) for (int k = j; k < M; k += 16) s += dlog[(long)k * C + c0 + c];
+        sm[j * 16 + c] = s;
+        __syncthreads();
+        if (j == 0 && c < nc) {
+            float a = 0.f;
+            for (int i = 0; i < 16; ++i) a += sm[i * 16 + c];
+            gb[c0 + c] = a;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb) {
+    if (!ws || !feats || !y || !W || !b || !loss || !correct || M < 1 || F < 1 || C < 1) return FUMI_EINVAL;
+    const int ngrad = (dfeats ? 1 : 0) + (gW ? 1 : 0) + (gb ? 1 : 0);
+    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
+    if (M > 4096 || F % 32 != 0 || F < 32 || F > 2048 || C < 2 || C > 1024) return FUMI_ENOTSUP;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
+    const int train = ngrad == 3;
+    ClsHead d;
+    d.M = M; d.F = F; d.C = C; d.ldz = ((C + 15) & ~15) + 4; d.ntile = (M + CH_TM - 1) / CH_TM; d.train = train;
+    d.gs = grad_scale / (float)M;
+    int rc = ws_reserve(ws, ws_align((size_t)2 * CH_MAXTILE * 4) + (train ? ws_align((size_t)M * C * 4) : 0));
+    if (rc) return rc;
+    float* part = ws_f(ws, 2 * CH_MAXTILE);
+    float* dlog = train ? ws_f(ws, (size_t)M * C) : nullptr;
+    const size_t lds1 = ((size_t)CH_TM * d.ldz + 64 + CH_MM) * 4, lds2 = train ? (size_t)CH_MM * 4 : 0;   // the forward form's one workgroup only adds the tile sums
+    FUMI_SET_DYN_LDS(cls_head_rows_kernel, lds1);
+    hipLaunchKernelGGL(cls_head_rows_kernel, dim3(d.ntile), dim3(256), lds1, st, d, feats, y, W, b, preds, part, dlog, dfeats,
+                       ws->status);
+    LAUNCH_CHECK();
+    const int nfb = (F + CH_NB - 1) / CH_NB, ncb = (C + CH_TM - 1) / CH_TM;
+    FUMI_SET_DYN_LDS(cls_head_wgrad_kernel, lds2);
+    hipLaunchKernelGGL(cls_head_wgrad_kernel, dim3((train ? ncb * nfb : 0) + 1), dim3(256), lds2, st, d, nfb, feats, dlog, part, loss,
+                       correct, gW, gb);
+    LAUNCH_CHECK();
+    return FUMI_OK;
+}

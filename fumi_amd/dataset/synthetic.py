@@ -201,7 +201,24 @@ def pixel_samplers(args, tables, norm, q_eval):
             kw.update(out_size=r["out_size"], resize=r["train"] if train else r["eval"], augment=r["augment"] if train else None)
         return GpuEpisodeSampler(*tables[split], args.num_ways, args.num_shots, q, args.batch_size, seed=args.seed + len(split),
                                  normalize=norm, **kw)
+    if getattr(args, "model", "") == "pretrain":       # supervised batches over the train table, the episodic val / test samplers
+        return supervised_pixel_source(args, tables["train"], norm, rs), mk("val", q_eval, False), mk("test", q_eval, False)
     return mk("train", args.num_shots_test, True), mk("val", q_eval, False), mk("test", q_eval, False)
+
+
+def supervised_pixel_source(args, table, norm, rs):
+    """``--model pretrain``: SupervisedPixelBatches over table = (uint8 table on the device, class of every image, class text) with the
+    gather arguments the episodic train sampler would get (``rs`` = resize_settings of the table); the class ids are the rows of
+    the class text."""
+    from .supervised_pixels import SupervisedPixelBatches
+    images, labels, text = table
+    if rs is None:
+        kw = dict(augment=train_augmentation(args))
+    else:
+        kw = dict(out_size=rs["out_size"], resize=rs["train"], augment=rs["augment"])
+    src = SupervisedPixelBatches(images, labels, args.pretrain_batch, seed=args.seed + len("train"), normalize=norm, **kw)
+    src.n_classes = int(text.shape[0])
+    return src
 
 
 def _synthetic_resident_images(args, per, tokens, q_eval):

@@ -129,6 +129,14 @@ class HipEngine:
     def linear(self, x, W, b=None, act=0):
         return hip.linear_fwd(self._ws(x), x.contiguous(), W.contiguous(), b, act)
 
+    def cls_head_step(self, feats, y, W, b, need_grad=True, grad_scale=1.0, dfeats=None, gW=None, gb=None):
+        """Fused classification head of supervised pre-training: mean cross-entropy of feats @ W.T + b, its predictions and gradients."""
+        return hip.cls_head_step(self._ws(feats), feats, y, W, b, need_grad=need_grad, grad_scale=grad_scale, dfeats=dfeats, gW=gW,
+                                 gb=gb)
+
+    def proto_reduce(self, x, y, n_way):
+        return hip.proto_reduce(self._ws(x), x, y, n_way)
+
     def sgd_axpy(self, p, step_size, g):
         return hip.sgd_axpy(self._ws(p), p, step_size, g)
 

@@ -37,6 +37,7 @@ SYMBOLS = [
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
     "fumi_hip_want_text_grad",
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
+    "fumi_hip_cls_head_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT = 1, 2, 4
@@ -217,6 +218,7 @@ def lib():
         L.fumi_hip_lstm_bidir_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_int64, PP, c_int, c_void_p, c_void_p, PP]
         L.fumi_hip_want_text_grad.argtypes = [c_void_p, c_void_p]
         L.fumi_hip_proto_reduce.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3
+        L.fumi_hip_cls_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_float] + [c_void_p] * 6
         _lib = L
     return _lib
 
@@ -1501,6 +1503,34 @@ def proto_reduce(ws, x, y, n_way):
     _check(lib().fumi_hip_proto_reduce(ws.handle, _stream(dev), B, S, int(n_way), P, _f32(x, "x"), _i64(y, "y"), _f32(out, "out")),
            "fumi_hip_proto_reduce")
     return out
+
+
+def cls_head_step(ws, feats, y, W, b, *, need_grad=True, grad_scale=1.0, dfeats=None, gW=None, gb=None, want_preds=True):
+    """The fused classification head (csrc/clshead.hip): F.cross_entropy(feats @ W.T + b, y), mean over the M rows.  Returns a dict
+    of GPU tensors: loss [1], correct [1] (count, float), preds [M] (first arg-max; None without want_preds) and, with need_grad,
+    dfeats [M,F], gW [C,F], gb [C] = gradients of grad_scale * loss (written into the tensors given, else into new ones)."""
+    dev = _dev(feats)
+    if feats.dim() != 2 or W.dim() != 2:
+        raise FumiHipError("cls_head_step: feats [M,F] and W [C,F] expected")
+    M, F = (int(v) for v in feats.shape)
+    C = int(W.shape[0])
+    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y, (M,), "y")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
+    if need_grad:
+        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
+        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
+        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
+        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
+        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
+    else:
+        dfeats = gW = gb = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_cls_head_step(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y, "y"), _f32(W, "W"), _f32(b, "b"),
+                                        float(grad_scale), _f32(loss, "loss"), _f32(correct, "correct"),
+                                        _i64(preds, "preds") if want_preds else None, *grads), "fumi_hip_cls_head_step")
+    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
 
 
 CLIP_KEYS = ["text_fc.weight", "text_fc.bias", "text_fc2.weight", "text_fc2.bias",

@@ -18,12 +18,15 @@ import torch
 from . import dist as fdist
 from . import engine as _engine
 from . import hip
-from .models import am3, clip, fumi, maml
+from .models import am3, clip, fumi, maml, pretrain
 from .utils import utils
 from .utils.wandb_compat import wandb
 
 
 def get_dataset(args):
+    if args.model == "pretrain" and args.dataset not in ("synthetic-resident", "image-npy"):
+        raise ValueError(f"--model pretrain trains on a GPU-resident uint8 pixel table: --dataset synthetic-resident or image-npy, "
+                         f"not {args.dataset} (embeddings and host loaders have no pixels for the backbone)")
     if args.model == "clip" and args.dataset == "synthetic":        # the CLIP baseline consumes supervised mini-batches
         from .dataset.synthetic import get_synthetic_supervised
         return get_synthetic_supervised(args)
@@ -48,7 +51,9 @@ def get_dataset(args):
 # embedding width each image model produces (fumi/main.py:34-44: the three ValueErrors, same messages)
 _EMBEDDING_DIMS = {"resnet-152": ("Resnet-152", 2048), "resnet-34": ("Resnet-34", 512)}
 # names the test metrics are logged and printed under, in the order the test loops return them
-_TEST_METRICS = {"maml": ("loss", "acc"), "fumi": ("loss", "acc"), "am3": ("loss", "acc", "f1", "prec", "rec", "avg_lamda")}
+_TEST_METRICS = {"maml": ("loss", "acc"), "fumi": ("loss", "acc"), "am3": ("loss", "acc", "f1", "prec", "rec", "avg_lamda"),
+                 "pretrain": ("loss", "acc")}
+_FAMILIES = ("maml", "fumi", "clip", "pretrain")                                  # unknown names are AM3, like utils.init_model
 
 
 def _check_embedding_flags(args):
@@ -73,8 +78,8 @@ def _restore(args, model, optimizer):
 
 def main(args):
     check_supported(args)
-    family = args.model if args.model in ("maml", "fumi", "clip") else "am3"      # unknown names are AM3, like utils.init_model
-    mod = {"maml": maml, "fumi": fumi, "am3": am3, "clip": clip}[family]
+    family = args.model if args.model in _FAMILIES else "am3"
+    mod = {"maml": maml, "fumi": fumi, "am3": am3, "clip": clip, "pretrain": pretrain}[family]
     results_path = f"{args.log_dir}/results"
     os.makedirs(results_path, exist_ok=True)
     os.environ["FUMI_LOG_DIR"] = args.log_dir        # where the local W&B stand-in keeps run directories
@@ -97,8 +102,12 @@ def main(args):
     for seed_fn in (torch.manual_seed, np.random.seed, random.seed):
         seed_fn(args.seed)
 
+    if family == "pretrain":
+        args.n_classes = int(train_loader.n_classes)                     # the head's width: the classes of the train table
     model = utils.init_model(args, dictionary)
     print(model)
+    if getattr(args, "encoder_checkpoint", None):                        # the backbone of a --model pretrain checkpoint
+        model = utils.load_encoder_checkpoint(model, args.device, args.encoder_checkpoint)
     optimizer = utils.init_optim(args, model)
     if args.checkpoint:
         model = _restore(args, model, optimizer)
@@ -153,7 +162,21 @@ def check_supported(args):
             ("--disable_cuda was given" if args.disable_cuda else "no GPU is visible (torch.cuda.is_available() is False)")
             + ": fumi_amd has no CPU execution path -- every step runs on the MI355X library "
               "(fumi_amd/lib/libfumi_hip.so).  Run the reference itself for a CPU run.")
-    family = args.model if args.model in ("maml", "fumi", "clip") else "am3"      # unknown names are AM3, like utils.init_model
+    family = args.model if args.model in _FAMILIES else "am3"
+    raw = args.im_encoder in ("conv4", "resnet12")
+    if family == "pretrain":
+        if not raw:
+            raise ValueError("--model pretrain trains an image backbone: it needs --im_encoder conv4 or resnet12")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("--model pretrain runs on one rank: per-rank batch-statistics groups and the gradient "
+                                      "all-reduce of the supervised step are not implemented (WORLD_SIZE > 1)")
+        if args.pretrain_bn_group < 1 or args.pretrain_batch < 1 or args.pretrain_batch % (2 * args.pretrain_bn_group) != 0:
+            raise ValueError(f"--pretrain_batch {args.pretrain_batch} must be a multiple of 2 * --pretrain_bn_group "
+                             f"{args.pretrain_bn_group}: the encoder normalises groups of that many images, half of them on "
+                             f"each side of its call")
+    if getattr(args, "encoder_checkpoint", None) and (family == "clip" or not raw):
+        raise ValueError("--encoder_checkpoint loads a Conv4 / ResNet-12 backbone: it needs --model fumi, maml or am3 with "
+                         "--im_encoder conv4 or resnet12")
     # (--fine_tune with --text_encoder RNN / RNNhid trains the bi-LSTM like the reference, fumi/models/fumi.py:65-67 / am3.py:74-76:
     # every meta-step hands back the adjoint of its text input, csrc/textenc.hip runs the LSTM's backward)
     if (family == "am3" and args.text_encoder == "rand" and args.dropout > 0 and not args.evaluate

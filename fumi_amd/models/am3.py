@@ -84,6 +84,10 @@ class AM3(nn.Module):
         self._flat = None
         self._pcache = None
 
+    def backbone_module(self):
+        """The Conv4 / ResNet12 on raw images (--encoder_checkpoint loads a pre-trained one into it), else None."""
+        return self.conv
+
     def _w(self):
         return [self.image_encoder.weight, self.image_encoder.bias, self.g[0].weight, self.g[0].bias, self.g[3].weight,
                 self.g[3].bias, self.h[0].weight, self.h[0].bias, self.h[3].weight, self.h[3].bias]

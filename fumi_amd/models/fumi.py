@@ -112,6 +112,10 @@ class FUMI(nn.Module):
         self._flat = None
         self._pcache = None
 
+    def backbone_module(self):
+        """The Conv4 / ResNet12 at the im_net seam (--encoder_checkpoint loads a pre-trained one into it), else None."""
+        return self.im_net if self.im_encoder in ("conv4", "resnet12") else None
+
     # ---- parameter views handed to the engine --------------------------------------------------------------------
     def _theta(self):
         if self.im_encoder in ("conv4", "resnet12"):

@@ -49,6 +49,10 @@ class PureImageNetwork(MetaModule):
     def forward(self, inputs, params=None):
         return self.net(inputs, params=self.get_subdict(params, 'net'))
 
+    def backbone_module(self):
+        """The Conv4 / ResNet12 in front of lin_final (--encoder_checkpoint loads a pre-trained one into it), else None."""
+        return self.net.features if self.im_encoder in ("conv4", "resnet12") else None
+
     def _params(self):
         if self.im_encoder in ("conv4", "resnet12"):
             return self.net.features.theta() + [self.net.lin_final.weight, self.net.lin_final.bias]

@@ -1,0 +1,178 @@
+"""Supervised pre-training of the image backbone (``--model pretrain``).
+
+The few-shot recipes this code base follows (AM3's own paper, every ResNet-12 baseline since) train the backbone first as a plain
+classifier over all training classes and carry those weights into the episodic model.  ``Pretrain`` is that classifier: the same
+``Conv4`` / ``ResNet12`` module AM3 builds, under the same attribute name (``conv``, so ``state_dict`` keys ``conv.*``), and
+``classifier = nn.Linear(feature_dim, n_classes)``.
+
+A training step runs on the engine's first-order encoder pair and the fused classification head (csrc/clshead.hip): the M images
+of a batch are laid out as B = M / (2 R) episodes of R "support" and R "query" images, the first half of the batch on the support
+side, so that the unchanged encode call normalises every R consecutive images by their own batch statistics (R =
+``--pretrain_bn_group``); ``cls_head_step`` takes all M feature rows, ``encode_bwd`` the two halves of its ``dfeats``.
+Validation and test are few-shot nearest-centroid classification on backbone features over the episodic batches the pixel samplers
+produce: the checkpoint with the best few-shot validation loss wins.  ``--encoder_checkpoint`` (fumi_amd/utils/utils.py) loads the
+``conv.*`` tensors of such a checkpoint into ``--model fumi | maml | am3``."""
+import os
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import engine as _engine
+from .. import lazy
+from ..flatgrad import FlatGrads, ParamWatch
+from ..optim import clip_log
+from ..utils import utils as utils
+from ..utils.average_meter import AverageMeter
+from ..utils.wandb_compat import wandb
+
+
+class Pretrain(nn.Module):
+    def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None):
+        super().__init__()
+        self.backbone = im_encoder
+        if im_encoder == "conv4":
+            from .conv4 import Conv4
+            self.conv = Conv4(image_channels, 64, 4, image_size)
+        elif im_encoder == "resnet12":
+            from .resnet12 import CHANNELS, ResNet12
+            self.conv = ResNet12(image_channels, CHANNELS, image_size)
+        else:
+            raise NameError(f"{im_encoder} not allowed as image encoder of --model pretrain (conv4, resnet12)")
+        self.n_classes = int(n_classes)
+        self.bn_group = int(bn_group)          # R: images per batch-statistics group of a training step
+        self.num_ways = num_ways               # N of the validation / test episodes (None: read from the labels)
+        self.classifier = nn.Linear(self.conv.feature_dim, self.n_classes)
+        self._flat = None
+        self._pcache = None
+
+    def backbone_module(self):
+        return self.conv
+
+    def _step_params(self, need_grad):
+        """(detached classifier weight and bias, detached backbone tensors, flat gradient buffer | None), the same objects from step
+        to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
+        c = self._pcache
+        if c is None or not c[0].valid():
+            w, th = [self.classifier.weight, self.classifier.bias], self.conv.theta()
+            c = self._pcache = (ParamWatch(self, w + th), [p.detach() for p in w], [p.detach() for p in th])
+            self._flat = None
+        fg = None
+        if need_grad:
+            fg = self._flat
+            if fg is None:
+                fg = self._flat = FlatGrads([self.classifier.weight, self.classifier.bias] + self.conv.theta(), extra=2)
+        return c[1], c[2], fg
+
+    def _apply(self, fn, recurse=True):
+        self._pcache = None
+        return super()._apply(fn, recurse)
+
+    def _encoders(self, eng):
+        return ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
+                (eng.resnet12_encode, eng.resnet12_encode_bwd))
+
+    def train_step(self, x, y, optimizer=None, scheduler=None):
+        """One supervised step on x [M, C, H, W] fp32, y [M] int64; returns the head's output dict (loss, correct, preds, gradients).
+        The gradients are left attached to the parameters; with an optimizer its fused step follows."""
+        eng = _engine.get_engine()
+        M, R = int(x.shape[0]), self.bn_group
+        if M % (2 * R) != 0:
+            raise ValueError(f"a batch of {M} images does not split into groups of 2 * {R} (--pretrain_batch must be a multiple of "
+                             f"2 * --pretrain_bn_group)")
+        B, half = M // (2 * R), M // 2
+        w, theta, fg = self._step_params(True)
+        encode, encode_bwd = self._encoders(eng)
+        x = x.contiguous()
+        x_s, x_q = x[:half].view(B, R, *x.shape[1:]), x[half:].view(B, R, *x.shape[1:])
+        f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
+        feats = torch.cat((f_s.view(half, -1), f_q.view(half, -1)))                 # [M, F], the images' order
+        g_w, g_theta = fg.split(2)
+        out = eng.cls_head_step(feats, y, w[0], w[1], need_grad=True, grad_scale=1.0, gW=g_w[0], gb=g_w[1])
+        df = out["dfeats"]
+        encode_bwd(x_s, x_q, df[:half].view(B, R, -1), df[half:].view(B, R, -1), theta, scale=1.0, g_theta=g_theta)
+        torch.cat((out["loss"], out["correct"] / M), out=fg.tail)
+        if optimizer is not None:
+            optimizer.zero_grad()
+        fg.attach()
+        if optimizer is not None:
+            getattr(optimizer, "step_fused", optimizer.step)()
+            if scheduler:
+                scheduler.step()
+        return out
+
+    def few_shot(self, batch, device):
+        """(loss, acc) of nearest-centroid classification on backbone features over one episodic meta-batch: class means of the support
+        features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min."""
+        eng = _engine.get_engine()
+        (_, _, s_im), s_y = batch['train']
+        (_, _, q_im), q_y = batch['test']
+        to = lambda t: t.to(device).contiguous()
+        x_s, x_q, y_s, y_q = to(s_im).float(), to(q_im).float(), to(s_y), to(q_y)
+        _, theta, _ = self._step_params(False)
+        f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
+        N = int(self.num_ways) if self.num_ways else int(y_s.max().item()) + 1
+        protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
+        d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]
+        loss = F.cross_entropy(-d2.reshape(-1, N), y_q.reshape(-1))
+        acc = (d2.argmin(-1) == y_q).float().mean()
+        return torch.stack((loss, acc))
+
+    def evaluate(self, batch, optimizer, scheduler, device, task="train"):
+        """``train``: one supervised step on batch = (x, y), returns (loss, acc) of the batch; ``val`` / ``test``: few-shot
+        nearest-centroid (loss, acc) of one episodic meta-batch."""
+        device = torch.device(device) if not isinstance(device, torch.device) else device
+        if task == "train" and torch.is_grad_enabled():
+            if not self.training:
+                self.train()
+            x, y = batch
+            self.train_step(x.to(device).float(), y.to(device), optimizer, scheduler)
+            return lazy.scalars(self._flat.tail, 2)
+        if self.training:
+            self.eval()
+        with torch.no_grad():
+            loss, acc = self.few_shot(batch, device).cpu().numpy()
+        return loss, acc
+
+
+def training_run(args, model, optimizer, train_loader, val_loader, max_test_batches):
+    """The structure of am3.training_run: validation at batch 0 and every --eval_freq, the usual checkpoint dictionary, patience,
+    reload of the best checkpoint (best few-shot validation loss) at the end."""
+    best_loss, best_acc = test_loop(args, model, val_loader, max_test_batches)
+    print(f"\ninitial loss: {best_loss}, acc: {best_acc}")
+    best_batch_idx = 0
+    opt, scheduler = optimizer if type(optimizer) == tuple else (optimizer, None)
+    try:
+        for batch_idx, batch in enumerate(train_loader):
+            tl, ta = model.evaluate(batch=batch, optimizer=opt, scheduler=scheduler, device=args.device, task="train")
+            wandb.log({"train/acc": ta, "train/loss": tl, "num_images": (batch_idx + 1) * args.pretrain_batch}, step=batch_idx)
+            if batch_idx % args.eval_freq == 0:
+                val_loss, val_acc = test_loop(args, model, val_loader, max_test_batches)
+                is_best = val_loss < best_loss
+                if is_best:
+                    best_loss, best_batch_idx = val_loss, batch_idx
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **clip_log(opt)}, step=batch_idx)
+                utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
+                                       "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
+                print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"
+                      f"\nval/loss: {val_loss}, val/acc: {val_acc}")
+            if (batch_idx > args.epochs - 1) or (args.patience > 0 and batch_idx - best_batch_idx > args.patience):
+                break
+    except KeyboardInterrupt:
+        pass
+    best_file = os.path.join(wandb.run.dir, "best.pth.tar")
+    if os.path.exists(best_file):
+        model, _ = utils.load_checkpoint(model, opt, args.device, best_file)
+    return model
+
+
+def test_loop(args, model, test_dataloader, max_num_batches):
+    """(mean loss, mean acc) of the few-shot evaluation over max_num_batches + 1 episodic meta-batches."""
+    m_loss, m_acc = AverageMeter(), AverageMeter()
+    for batch_idx, batch in enumerate(test_dataloader):
+        loss, acc = model.evaluate(batch=batch, optimizer=None, scheduler=None, device=args.device, task="test")
+        m_loss.update(loss); m_acc.update(acc)
+        if batch_idx > max_num_batches - 1:
+            break
+    _engine.check_status(args.device)
+    return m_loss.avg, m_acc.avg

@@ -87,6 +87,9 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--image_mean", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel mean on the 0..1 pixel scale (default: the train table's own)")),
     ("--image_std", dict(type=float, nargs="+", default=None, help="[resident pixel table] per-channel standard deviation on the 0..1 pixel scale (default: the train table's own)")),
     ("--max_grad_norm", dict(type=float, default=None, help="clip the global L2 norm of the outer gradient to this value before every optimizer step (torch.nn.utils.clip_grad_norm_ semantics, computed on the device; default: no clipping)")),
+    ("--pretrain_batch", dict(type=int, default=128, help="[--model pretrain] images per supervised training step (a multiple of 2 * --pretrain_bn_group)")),
+    ("--pretrain_bn_group", dict(type=int, default=64, help="[--model pretrain] images per batch-statistics group of a training step")),
+    ("--encoder_checkpoint", dict(type=str, default=None, help="[--model fumi / maml / am3 with --im_encoder conv4 / resnet12] a --model pretrain checkpoint whose backbone (conv.*) is loaded into the model's image encoder before training")),
 ]
 
 
@@ -112,6 +115,10 @@ def init_model(args, dictionary, watch=True):
                           norm_hypernet=args.norm_hypernet, fine_tune=args.fine_tune, init_bias=args.hypernet_bias_init,
                           **(dict(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels)
                              if args.im_encoder in ("conv4", "resnet12") else {}))
+    elif args.model == "pretrain":
+        from ..models import pretrain
+        model = pretrain.Pretrain(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
+                                  n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways)
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:
@@ -179,6 +186,39 @@ def load_checkpoint(model, optimizer, device, checkpoint_file):
     print(f"Loaded {checkpoint_file}, trained to epoch {checkpoint['batch_idx']} "
           f"with best loss (acc for CLIP) {checkpoint['best_loss']}")
     return model, optimizer
+
+
+def load_backbone_state(model, state_dict):
+    """Copy the ``conv.*`` tensors of a ``--model pretrain`` state_dict into the model's backbone module (``backbone_module()``: the
+    Conv4 / ResNet12 of FuMI, MAML, AM3 or Pretrain).  Every backbone tensor must be present with the same shape (ValueError naming
+    the tensor otherwise); the classifier and anything else in the state_dict is ignored, nothing else in the model changes.  The
+    model's cached parameter views (``_pcache``) are dropped so that the first step sees the loaded weights."""
+    get = getattr(model, "backbone_module", None)
+    bb = get() if get is not None else None
+    if bb is None:
+        raise ValueError("--encoder_checkpoint needs a model with an image backbone (--im_encoder conv4 or resnet12)")
+    own = bb.state_dict()
+    for name, dst in own.items():
+        src = state_dict.get("conv." + name)
+        if src is None:
+            raise ValueError(f"--encoder_checkpoint: the checkpoint has no backbone tensor conv.{name}")
+        if tuple(src.shape) != tuple(dst.shape):
+            raise ValueError(f"--encoder_checkpoint: backbone tensor conv.{name} is {tuple(src.shape)} in the checkpoint, "
+                             f"{tuple(dst.shape)} in the model")
+    with torch.no_grad():
+        for name, dst in own.items():
+            dst.copy_(state_dict["conv." + name])
+    if hasattr(model, "_pcache"):
+        model._pcache = None
+    return sorted("conv." + n for n in own)
+
+
+def load_encoder_checkpoint(model, device, checkpoint_file):
+    """--encoder_checkpoint: the backbone of a ``--model pretrain`` checkpoint file into ``model`` (``load_backbone_state``)."""
+    checkpoint = torch.load(checkpoint_file, map_location=device, weights_only=False)
+    names = load_backbone_state(model, checkpoint["state_dict"])
+    print(f"Loaded the backbone ({len(names)} tensors) of {checkpoint_file}, pre-trained to batch {checkpoint.get('batch_idx')}")
+    return model
 
 
 # ---- classification metrics of AM3 (utils.py:319-326) on host integers ------------------------------------------------

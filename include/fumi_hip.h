@@ -427,6 +427,19 @@ int fumi_hip_ce_fwd_bwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int N, const
         int64_t* preds);
 /* get_prototypes (fumi/utils/utils.py:331-376): out[b,n,:] = sum_{s: y[b,s]==n} x[b,s,:] / max(count, 1)  -> [B,N,P] */
 int fumi_hip_proto_reduce(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int N, int P, const float* x, const int64_t* y, float* out);
+/* The classification head of supervised pre-training (csrc/clshead.hip), fused: F.cross_entropy(feats W^T + b, y)
+ * with mean reduction over the M rows and its backward, in two launches.  feats [M,F], y [M], W [C,F], b [C];  loss [1] = mean NLL,
+ * correct [1] = number of rows whose first arg-max equals the label (float), preds [M] = first arg-max (may be NULL);
+ * dfeats [M,F], gW [C,F], gb [C] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training form) or all
+ * three NULL (forward form: loss, correct and preds are bit-identical to the training form's).  fp32 with fp32 accumulation on
+ * v_mfma_f32_16x16x4_f32; the logits of a 16-row tile stay in LDS from the product through the softmax to dlogits and dfeats =
+ * dlogits W, only dlogits goes to memory (workspace) for gW = dlogits^T feats and gb = colsum(dlogits).  Every sum has a fixed order
+ * and there are no floating-point atomics: two calls on the same inputs give the same bits.
+ * A label outside [0,C) sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or the gradients, the divisor stays M.
+ * 1 <= M <= 4096, F % 32 == 0, 32 <= F <= 2048, 2 <= C <= 1024: FUMI_ENOTSUP / FUMI_EINVAL otherwise, before any launch. */
+int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
 
 
 /* ---- beside the episodic path -------------------------------------------------------------------------------
