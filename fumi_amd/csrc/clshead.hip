@@ -14,6 +14,13 @@
 // Every sum has a fixed order (MFMA chains over k, butterflies inside a 16-lane group, index-ordered loops across tiles): equal
 // inputs give equal bits.  No floating-point atomics; the only atomic is the OR into the status word.
 // A label outside [0, C) sets FUMI_ST_LABEL_RANGE; its row adds nothing to the loss, the count or the gradients (the divisor stays M).
+//
+// Soft-target form (fumi_hip_cls_head_step_soft): label smoothing eps and a two-label mix (mixup / CutMix),
+//   t[m,c] = (1 - eps) (lam [c == y_a[m]] + u [c == y_b[m]]) + eps / C,  u = 1 - lam in fp32,
+//   loss = mean_m (lse_m - sum_c t[m,c] z[m,c]),  dlogits = grad_scale / M * (softmax - t).
+// The rows kernel is a template on SOFT: the per-row part reads z[y_b] too and, for eps > 0, forms sum_c z[c] by the strided loop and
+// butterfly of the log-sum-exp; everything else, launch 2 included, is the hard form's code.  With y_b = y_a, lam = 1, eps = 0 every
+// extra operation is exact (a product by 1, a sum with 0), so that call returns the hard form's bits.
 #include "common.h"
 
 namespace {
@@ -28,7 +35,13 @@ struct ClsHead {
     float gs;                      // grad_scale / M
 };
 
-__global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, const float* __restrict__ feats, const int64_t* __restrict__ y,
+struct ClsSoft {                   // the soft target of a row: t[c] = base + wa [c == y_a] + wb [c == y_b]
+    const int64_t* yb;
+    float wa, wb, base;            // (1 - eps) lam, (1 - eps) (1 - lam), eps / C
+};
+
+template <bool SOFT>
+__global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, ClsSoft sf, const float* __restrict__ feats, const int64_t* __restrict__ y,
                                                             const float* __restrict__ W, const float* __restrict__ bias,
                                                             int64_t* __restrict__ preds, float* __restrict__ part,
                                                             float* __restrict__ dlog, float* __restrict__ dfeats, int* status) {
@@ -63,17 +76,30 @@ __global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, const flo
             float s = 0.f;
             for (int c = l; c < C; c += 16) s += expf(z[c] - mx);
             for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            long yv = y[m0 + row];
-            const bool ok = yv >= 0 && yv < C;
-            if (!ok) { if (l == 0) atomicOr(status, FUMI_ST_LABEL_RANGE); yv = 0; }
-            loss = ok ? mx + logf(s) - z[yv] : 0.f;
+            long yv = y[m0 + row], yw = SOFT ? sf.yb[m0 + row] : 0;
+            const bool ok = yv >= 0 && yv < C && yw >= 0 && yw < C;
+            if (!ok) { if (l == 0) atomicOr(status, FUMI_ST_LABEL_RANGE); yv = 0; yw = 0; }
+            if (SOFT) {
+                float tz = sf.wa * z[yv] + sf.wb * z[yw];                                // sum_c t[c] z[c]
+                if (sf.base > 0.f) {
+                    float sz = 0.f;
+                    for (int c = l; c < C; c += 16) sz += z[c];
+                    for (int o = 8; o > 0; o >>= 1) sz += __shfl_xor(sz, o, 64);
+                    tz += sf.base * sz;
+                }
+                loss = ok ? mx + logf(s) - tz : 0.f;
+            } else {
+                loss = ok ? mx + logf(s) - z[yv] : 0.f;
+            }
             hit = (ok && arg == (int)yv) ? 1.f : 0.f;
             if (l == 0 && preds) preds[m0 + row] = arg;
             if (d.train) {
                 const float inv = 1.f / s, gs = ok ? d.gs : 0.f;
                 float* dl = dlog + (long)(m0 + row) * C;
                 for (int c = l; c < C; c += 16) {
-                    const float g = gs * (expf(z[c] - mx) * inv - (c == (int)yv ? 1.f : 0.f));
+                    const float t = SOFT ? sf.base + (c == (int)yv ? sf.wa : 0.f) + (c == (int)yw ? sf.wb : 0.f)
+                                         : (c == (int)yv ? 1.f : 0.f);
+                    const float g = gs * (expf(z[c] - mx) * inv - t);
                     z[c] = g; dl[c] = g;
                 }
             }
@@ -134,8 +160,9 @@ __global__ __launch_bounds__(256) void cls_head_wgrad_kernel(ClsHead d, int nfb,
 
 }  // namespace
 
-extern "C" int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
-        const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
+// both entries: yb == nullptr is the hard form
+static int cls_head_launch(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C, const float* feats, const int64_t* y,
+        const ClsSoft* soft, const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb) {
     if (!ws || !feats || !y || !W || !b || !loss || !correct || M < 1 || F < 1 || C < 1) return FUMI_EINVAL;
     const int ngrad = (dfeats ? 1 : 0) + (gW ? 1 : 0) + (gb ? 1 : 0);
@@ -152,9 +179,15 @@ extern "C" int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M
     float* part = ws_f(ws, 2 * CH_MAXTILE);
     float* dlog = train ? ws_f(ws, (size_t)M * C) : nullptr;
     const size_t lds1 = ((size_t)CH_TM * d.ldz + 64 + CH_MM) * 4, lds2 = train ? (size_t)CH_MM * 4 : 0;   // the forward form's one workgroup only adds the tile sums
-    FUMI_SET_DYN_LDS(cls_head_rows_kernel, lds1);
-    hipLaunchKernelGGL(cls_head_rows_kernel, dim3(d.ntile), dim3(256), lds1, st, d, feats, y, W, b, preds, part, dlog, dfeats,
-                       ws->status);
+    if (soft) {
+        FUMI_SET_DYN_LDS(cls_head_rows_kernel<true>, lds1);
+        hipLaunchKernelGGL(cls_head_rows_kernel<true>, dim3(d.ntile), dim3(256), lds1, st, d, *soft, feats, y, W, b, preds, part, dlog,
+                           dfeats, ws->status);
+    } else {
+        FUMI_SET_DYN_LDS(cls_head_rows_kernel<false>, lds1);
+        hipLaunchKernelGGL(cls_head_rows_kernel<false>, dim3(d.ntile), dim3(256), lds1, st, d, ClsSoft{nullptr, 1.f, 0.f, 0.f}, feats, y,
+                           W, b, preds, part, dlog, dfeats, ws->status);
+    }
     LAUNCH_CHECK();
     const int nfb = (F + CH_NB - 1) / CH_NB, ncb = (C + CH_TM - 1) / CH_TM;
     FUMI_SET_DYN_LDS(cls_head_wgrad_kernel, lds2);
@@ -162,4 +195,20 @@ extern "C" int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M
                        correct, gW, gb);
     LAUNCH_CHECK();
     return FUMI_OK;
+}
+
+extern "C" int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb) {
+    return cls_head_launch(ws, stream, M, F, C, feats, y, nullptr, W, b, grad_scale, loss, correct, preds, dfeats, gW, gb);
+}
+
+extern "C" int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
+        const float* W, const float* b, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb) {
+    if (!(smoothing >= 0.f && smoothing < 1.f) || !(lam >= 0.f && lam <= 1.f) || (!y_b && lam != 1.f)) return FUMI_EINVAL;
+    const float u = 1.f - lam, keep = 1.f - smoothing;
+    const ClsSoft soft{y_b ? y_b : y_a, keep * lam, keep * u, smoothing / (float)C};
+    return cls_head_launch(ws, stream, M, F, C, feats, y_a, &soft, W, b, grad_scale, loss, correct, preds, dfeats, gW, gb);
 }

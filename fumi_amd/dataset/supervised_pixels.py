@@ -8,9 +8,18 @@ the pixels go through ``hip.gather_images`` / ``hip.gather_images_resized`` with
 
     batch(step) -> (x fp32 [M, C, H, W], y int64 [M])      y = the class id of the train table, dense 0..n_classes-1
 
-The permutation schedule (``epoch_permutation`` / ``batch_indices``) is host code and runs without a GPU."""
+With ``mix=dict(mixup_alpha=, cutmix_alpha=, prob=)`` (``--mixup_alpha`` / ``--cutmix_alpha`` / ``--mix_prob``) the
+gathered batch is blended with a permutation of itself by ``hip.mix_images`` under the draw ``mix_draw`` makes for the step:
+
+    batch(step) -> (x_mixed, y_a, y_b = y_a[partner], lam)      a step that draws "no mixing": the unmixed x, y_b = y_a, lam = 1
+
+The permutation schedule (``epoch_permutation`` / ``batch_indices``) and ``mix_draw`` are host code and run without a GPU."""
+import math
+
 import numpy as np
 import torch
+
+MIXUP, CUTMIX = 0, 1
 
 
 def epoch_permutation(n, seed, epoch):
@@ -31,12 +40,52 @@ def batch_indices(n, batch, seed, step):
     return epoch_permutation(n, seed, epoch)[k * batch:(k + 1) * batch]
 
 
+def _mix_key(seed, step):
+    """Seed words of the mixing stream of (seed, step); the leading word keeps it apart from ``epoch_permutation``'s torch stream and
+    from any other numpy stream keyed by the same pair."""
+    return [0x6D697875, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF]
+
+
+def mix_draw(seed, step, M, H, W, mixup_alpha, cutmix_alpha, prob):
+    """(mode, lam, box, partner): what batch ``step`` is mixed with, from numpy.random.Generator(PCG64(_mix_key(seed, step))).
+      mode     None with probability 1 - prob (and when both alphas are 0), else MIXUP or CUTMIX: the one whose alpha is > 0, one half
+               each when both are
+      lam      ~ Beta(alpha, alpha) of the chosen mode; for CutMix recomputed from the box as 1 - area / (H W); 1.0 without mixing
+      box      (bx0, by0, bx1, by1), CutMix as in its paper: r = sqrt(1 - lam), int(W r) columns by int(H r) rows around a uniform
+               centre, clipped to the image; (0, 0, 0, 0) otherwise
+      partner  int64 [M], a permutation of range(M) (the identity without mixing)
+    The draws are made in this order: mix or not, mode, lam, centre x, centre y, partner."""
+    M, H, W = int(M), int(H), int(W)
+    rng = np.random.Generator(np.random.PCG64(_mix_key(seed, step)))
+    a_mix, a_cut = float(mixup_alpha), float(cutmix_alpha)
+    mixes = rng.random() < float(prob)
+    if not mixes or (a_mix <= 0 and a_cut <= 0):
+        return None, 1.0, (0, 0, 0, 0), np.arange(M, dtype=np.int64)
+    if a_mix > 0 and a_cut > 0:
+        mode = MIXUP if rng.random() < 0.5 else CUTMIX
+    else:
+        mode = MIXUP if a_mix > 0 else CUTMIX
+    alpha = a_mix if mode == MIXUP else a_cut
+    lam = min(1.0, max(0.0, float(rng.beta(alpha, alpha))))
+    box = (0, 0, 0, 0)
+    if mode == CUTMIX:
+        r = math.sqrt(1.0 - lam)
+        cut_w, cut_h = int(W * r), int(H * r)
+        cx, cy = int(rng.integers(W)), int(rng.integers(H))
+        clip = lambda v, hi: min(max(v, 0), hi)
+        box = (clip(cx - cut_w // 2, W), clip(cy - cut_h // 2, H), clip(cx + cut_w // 2, W), clip(cy + cut_h // 2, H))
+        lam = 1.0 - (box[2] - box[0]) * (box[3] - box[1]) / float(H * W)
+    return mode, lam, box, rng.permutation(M).astype(np.int64)
+
+
 class SupervisedPixelBatches:
     pixels = True                    # (what main.py asks a train loader before it reports --augment as ignored)
 
-    def __init__(self, images_u8, labels, batch, seed=123, normalize=None, augment=None, out_size=None, resize=None, length=None):
+    def __init__(self, images_u8, labels, batch, seed=123, normalize=None, augment=None, out_size=None, resize=None, length=None,
+                 mix=None):
         """images_u8 uint8 [n, C, H, W] (moved to the device once), labels [n] ints in [0, n_classes); normalize / augment / out_size /
-        resize as ``GpuEpisodeSampler`` takes them for a pixel table.  length: batches an iteration yields (None: endless)."""
+        resize as ``GpuEpisodeSampler`` takes them for a pixel table.  length: batches an iteration yields (None: endless).
+        mix: None | dict(mixup_alpha=, cutmix_alpha=, prob=) as ``mix_draw`` takes them."""
         from .. import hip
         if images_u8.dim() != 4 or images_u8.dtype != torch.uint8:
             raise ValueError(f"a pixel table [n_images, C, H, W] must be uint8, got {images_u8.dtype} {tuple(images_u8.shape)}")
@@ -67,6 +116,15 @@ class SupervisedPixelBatches:
                 raise ValueError("augment pad= does not apply with out_size: the random-resized crop takes its place")
         elif resize is not None:
             raise ValueError("resize needs out_size=(Ho, Wo)")
+        self.mix = None
+        if mix is not None:
+            m = dict(mix)
+            self.mix = dict(mixup_alpha=float(m.pop("mixup_alpha", 0.0)), cutmix_alpha=float(m.pop("cutmix_alpha", 0.0)),
+                            prob=float(m.pop("prob", 1.0)))
+            if m:
+                raise ValueError(f"unknown mix keys {sorted(m)}")
+            if self.mix["mixup_alpha"] < 0 or self.mix["cutmix_alpha"] < 0 or not 0.0 <= self.mix["prob"] <= 1.0:
+                raise ValueError("mix needs mixup_alpha >= 0, cutmix_alpha >= 0 and prob in [0, 1]")
         self.M, self.seed, self.length = int(batch), int(seed), length
         self.n = int(images_u8.shape[0])
         if self.n < self.M:
@@ -86,7 +144,8 @@ class SupervisedPixelBatches:
             self._epoch = (epoch, epoch_permutation(self.n, self.seed, epoch).to(self.dev))
         return self._epoch[1][k * self.M:(k + 1) * self.M].contiguous()
 
-    def batch(self, step):
+    def gather(self, step):
+        """(x, y) of batch ``step``, unmixed."""
         from .. import hip
         idx = self.indices(step)
         if self.out_size is None:
@@ -95,6 +154,17 @@ class SupervisedPixelBatches:
             x = hip.gather_images_resized(self.ws, self.images, idx, self.mean, self.std, self.out_size, seed=self.seed, step=step,
                                           stream_id=0, flip=self.augment["flip"], jitter=self.augment["jitter"], **self.resize)
         return x, self.labels[idx]
+
+    def batch(self, step):
+        x, y = self.gather(step)
+        if self.mix is None:
+            return x, y
+        from .. import hip
+        mode, lam, box, partner = mix_draw(self.seed, step, self.M, x.shape[2], x.shape[3], **self.mix)
+        if mode is None:
+            return x, y, y, 1.0
+        partner = torch.from_numpy(partner).to(self.dev)
+        return hip.mix_images(self.ws, x, partner, mode=mode, lam=lam, box=box), y, y[partner], lam
 
     def __iter__(self):
         i = 0

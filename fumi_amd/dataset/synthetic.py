@@ -216,6 +216,8 @@ def supervised_pixel_source(args, table, norm, rs):
         kw = dict(augment=train_augmentation(args))
     else:
         kw = dict(out_size=rs["out_size"], resize=rs["train"], augment=rs["augment"])
+    if getattr(args, "mixup_alpha", 0.0) > 0 or getattr(args, "cutmix_alpha", 0.0) > 0:
+        kw["mix"] = dict(mixup_alpha=args.mixup_alpha, cutmix_alpha=args.cutmix_alpha, prob=getattr(args, "mix_prob", 1.0))
     src = SupervisedPixelBatches(images, labels, args.pretrain_batch, seed=args.seed + len("train"), normalize=norm, **kw)
     src.n_classes = int(text.shape[0])
     return src

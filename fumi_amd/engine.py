@@ -134,6 +134,16 @@ class HipEngine:
         return hip.cls_head_step(self._ws(feats), feats, y, W, b, need_grad=need_grad, grad_scale=grad_scale, dfeats=dfeats, gW=gW,
                                  gb=gb)
 
+    def cls_head_step_soft(self, feats, y_a, W, b, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,
+                           gW=None, gb=None):
+        """The same head against the soft target of label smoothing and a two-label mix (mixup / CutMix)."""
+        return hip.cls_head_step_soft(self._ws(feats), feats, y_a, W, b, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
+                                      grad_scale=grad_scale, dfeats=dfeats, gW=gW, gb=gb)
+
+    def mix_images(self, x, partner, mode, lam=1.0, box=(0, 0, 0, 0)):
+        """mixup (mode 0) / CutMix (mode 1) of a gathered image batch with its rows ``partner``."""
+        return hip.mix_images(self._ws(x), x, partner, mode=mode, lam=lam, box=box)
+
     def proto_reduce(self, x, y, n_way):
         return hip.proto_reduce(self._ws(x), x, y, n_way)
 

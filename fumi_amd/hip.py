@@ -38,6 +38,7 @@ SYMBOLS = [
     "fumi_hip_want_text_grad",
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
     "fumi_hip_cls_head_step",
+    "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT = 1, 2, 4
@@ -219,6 +220,10 @@ def lib():
         L.fumi_hip_want_text_grad.argtypes = [c_void_p, c_void_p]
         L.fumi_hip_proto_reduce.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3
         L.fumi_hip_cls_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_float] + [c_void_p] * 6
+        L.fumi_hip_cls_head_step_soft.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
+                                                  + [c_float] + [c_void_p] * 6)
+        L.fumi_hip_mix_images.argtypes = ([c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_float] + [c_int] * 4
+                                          + [c_void_p])
         _lib = L
     return _lib
 
@@ -1531,6 +1536,62 @@ def cls_head_step(ws, feats, y, W, b, *, need_grad=True, grad_scale=1.0, dfeats=
                                         float(grad_scale), _f32(loss, "loss"), _f32(correct, "correct"),
                                         _i64(preds, "preds") if want_preds else None, *grads), "fumi_hip_cls_head_step")
     return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+
+
+def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,
+                       gW=None, gb=None, want_preds=True):
+    """``cls_head_step`` against the soft target t = (1 - smoothing) (lam onehot(y_a) + (1 - lam) onehot(y_b)) + smoothing / C
+    (fumi_hip_cls_head_step_soft: label smoothing, mixup / CutMix labels).  ``y_b`` None: y_b = y_a, and lam must be 1.  ``correct``
+    counts against y_a.  The same dict as ``cls_head_step``."""
+    dev = _dev(feats)
+    if feats.dim() != 2 or W.dim() != 2:
+        raise FumiHipError("cls_head_step_soft: feats [M,F] and W [C,F] expected")
+    M, F = (int(v) for v in feats.shape)
+    C = int(W.shape[0])
+    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y_a, (M,), "y_a")
+    if y_b is not None:
+        _shape(y_b, (M,), "y_b")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
+    if need_grad:
+        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
+        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
+        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
+        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
+        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
+    else:
+        dfeats = gW = gb = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_cls_head_step_soft(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
+                                             _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
+                                             _f32(W, "W"), _f32(b, "b"), float(grad_scale), _f32(loss, "loss"),
+                                             _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
+           "fumi_hip_cls_head_step_soft")
+    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+
+
+MIX_MIXUP, MIX_CUTMIX = 0, 1
+
+
+def mix_images(ws, x, partner, *, mode, lam=1.0, box=(0, 0, 0, 0)):
+    """The blend of a gathered batch ``x`` float32 [M, C, H, W] with its rows ``partner`` int64 [M] (csrc/immix.hip), a new tensor:
+    ``mode`` MIX_MIXUP: lam x[i] + (1 - lam) x[partner[i]];  MIX_CUTMIX: x[partner[i]] inside ``box`` = (bx0, by0, bx1, by1) (columns
+    bx0..bx1-1 of rows by0..by1-1), x[i] elsewhere.  A partner outside [0, M) sets ST_LABEL_RANGE and leaves its row unmixed."""
+    dev = _dev(x)
+    if (x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or not isinstance(partner, torch.Tensor)
+            or partner.device != x.device or partner.dtype != torch.int64):
+        raise FumiHipError("mix_images: x must be a contiguous float32 [M, C, H, W] device tensor and partner an int64 tensor on the "
+                           f"same device; got {x.dtype} {tuple(x.shape)}")
+    M, C, H, W = (int(s) for s in x.shape)
+    _shape(partner, (M,), "partner")
+    if len(box) != 4:
+        raise FumiHipError("mix_images: box is (bx0, by0, bx1, by1)")
+    partner = partner.contiguous()
+    out = torch.empty_like(x)
+    _check(lib().fumi_hip_mix_images(ws.handle, _stream(dev), M, C, H, W, _f32(x, "x"), _i64(partner, "partner"),
+                                     int(mode), float(lam), *(int(v) for v in box), _f32(out, "out")), "fumi_hip_mix_images")
+    return out
 
 
 CLIP_KEYS = ["text_fc.weight", "text_fc.bias", "text_fc2.weight", "text_fc2.bias",

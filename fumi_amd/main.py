@@ -174,6 +174,17 @@ def check_supported(args):
             raise ValueError(f"--pretrain_batch {args.pretrain_batch} must be a multiple of 2 * --pretrain_bn_group "
                              f"{args.pretrain_bn_group}: the encoder normalises groups of that many images, half of them on "
                              f"each side of its call")
+    eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
+                                                                    ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
+    if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):
+        raise ValueError("--label_smoothing, --mixup_alpha, --cutmix_alpha and --mix_prob regularise the supervised classifier: "
+                         "they need --model pretrain")
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"--label_smoothing {eps} must lie in [0, 1)")
+    if a_mix < 0 or a_cut < 0:
+        raise ValueError(f"--mixup_alpha {a_mix} and --cutmix_alpha {a_cut} must not be negative (0 turns the mix off)")
+    if not 0.0 <= p_mix <= 1.0:
+        raise ValueError(f"--mix_prob {p_mix} must lie in [0, 1]")
     if getattr(args, "encoder_checkpoint", None) and (family == "clip" or not raw):
         raise ValueError("--encoder_checkpoint loads a Conv4 / ResNet-12 backbone: it needs --model fumi, maml or am3 with "
                          "--im_encoder conv4 or resnet12")

@@ -28,8 +28,11 @@ from ..utils.wandb_compat import wandb
 
 
 class Pretrain(nn.Module):
-    def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None):
+    def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0):
         super().__init__()
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+        self.label_smoothing = float(label_smoothing)     # eps of the training target; evaluation has none
         self.backbone = im_encoder
         if im_encoder == "conv4":
             from .conv4 import Conv4
@@ -72,9 +75,11 @@ class Pretrain(nn.Module):
         return ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
                 (eng.resnet12_encode, eng.resnet12_encode_bwd))
 
-    def train_step(self, x, y, optimizer=None, scheduler=None):
+    def train_step(self, x, y, optimizer=None, scheduler=None, y_b=None, lam=1.0):
         """One supervised step on x [M, C, H, W] fp32, y [M] int64; returns the head's output dict (loss, correct, preds, gradients).
-        The gradients are left attached to the parameters; with an optimizer its fused step follows."""
+        The gradients are left attached to the parameters; with an optimizer its fused step follows.  y_b [M] int64 and lam: the second
+        label of every row and the weight of the first (a mixup / CutMix batch); with them, or with label_smoothing > 0, the head runs
+        in its soft-target form, and ``correct`` counts against y."""
         eng = _engine.get_engine()
         M, R = int(x.shape[0]), self.bn_group
         if M % (2 * R) != 0:
@@ -88,7 +93,11 @@ class Pretrain(nn.Module):
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         feats = torch.cat((f_s.view(half, -1), f_q.view(half, -1)))                 # [M, F], the images' order
         g_w, g_theta = fg.split(2)
-        out = eng.cls_head_step(feats, y, w[0], w[1], need_grad=True, grad_scale=1.0, gW=g_w[0], gb=g_w[1])
+        if self.label_smoothing > 0 or y_b is not None:
+            out = eng.cls_head_step_soft(feats, y, w[0], w[1], y_b=y_b, lam=float(lam), smoothing=self.label_smoothing, need_grad=True,
+                                         grad_scale=1.0, gW=g_w[0], gb=g_w[1])
+        else:
+            out = eng.cls_head_step(feats, y, w[0], w[1], need_grad=True, grad_scale=1.0, gW=g_w[0], gb=g_w[1])
         df = out["dfeats"]
         encode_bwd(x_s, x_q, df[:half].view(B, R, -1), df[half:].view(B, R, -1), theta, scale=1.0, g_theta=g_theta)
         torch.cat((out["loss"], out["correct"] / M), out=fg.tail)
@@ -119,14 +128,18 @@ class Pretrain(nn.Module):
         return torch.stack((loss, acc))
 
     def evaluate(self, batch, optimizer, scheduler, device, task="train"):
-        """``train``: one supervised step on batch = (x, y), returns (loss, acc) of the batch; ``val`` / ``test``: few-shot
-        nearest-centroid (loss, acc) of one episodic meta-batch."""
+        """``train``: one supervised step on batch = (x, y) or, from a mixing batch source, (x, y_a, y_b, lam); returns (loss, acc) of
+        the batch (acc against y_a); ``val`` / ``test``: few-shot nearest-centroid (loss, acc) of one episodic meta-batch."""
         device = torch.device(device) if not isinstance(device, torch.device) else device
         if task == "train" and torch.is_grad_enabled():
             if not self.training:
                 self.train()
-            x, y = batch
-            self.train_step(x.to(device).float(), y.to(device), optimizer, scheduler)
+            if len(batch) == 4:
+                x, y, y_b, lam = batch
+                self.train_step(x.to(device).float(), y.to(device), optimizer, scheduler, y_b=y_b.to(device), lam=lam)
+            else:
+                x, y = batch
+                self.train_step(x.to(device).float(), y.to(device), optimizer, scheduler)
             return lazy.scalars(self._flat.tail, 2)
         if self.training:
             self.eval()

@@ -91,11 +91,17 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--pretrain_bn_group", dict(type=int, default=64, help="[--model pretrain] images per batch-statistics group of a training step")),
     ("--encoder_checkpoint", dict(type=str, default=None, help="[--model fumi / maml / am3 with --im_encoder conv4 / resnet12] a --model pretrain checkpoint whose backbone (conv.*) is loaded into the model's image encoder before training")),
 ]
+_PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain; a list of their own, after _ENGINE_FLAGS
+    ("--label_smoothing", dict(type=float, default=0.0, help="[--model pretrain] label smoothing eps of the training loss, in [0, 1)")),
+    ("--mixup_alpha", dict(type=float, default=0.0, help="[--model pretrain] mixup: lam ~ Beta(alpha, alpha) per training batch (0: off)")),
+    ("--cutmix_alpha", dict(type=float, default=0.0, help="[--model pretrain] CutMix: box area fraction 1 - lam, lam ~ Beta(alpha, alpha) per training batch (0: off; with --mixup_alpha too, one of the two per batch)")),
+    ("--mix_prob", dict(type=float, default=1.0, help="[--model pretrain] probability that a training batch is mixed at all")),
+]
 
 
 def parser():
     p = argparse.ArgumentParser(description="Multimodal image classification")
-    for flag, kw in _FLAGS + _ENGINE_FLAGS:
+    for flag, kw in _FLAGS + _ENGINE_FLAGS + _PRETRAIN_MIX_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -118,7 +124,8 @@ def init_model(args, dictionary, watch=True):
     elif args.model == "pretrain":
         from ..models import pretrain
         model = pretrain.Pretrain(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
-                                  n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways)
+                                  n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways,
+                                  label_smoothing=getattr(args, "label_smoothing", 0.0))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

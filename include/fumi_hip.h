@@ -440,6 +440,30 @@ int fumi_hip_proto_reduce(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int
 int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
         const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* The same head against a soft target: label smoothing `smoothing` = eps and a mix of two labels per row, what
+ * mixup and CutMix train on.  With u = 1 - lam computed in fp32,
+ *     t[m,c] = (1 - eps) * (lam * [c == y_a[m]] + u * [c == y_b[m]]) + eps / C
+ *     loss = mean_m (lse_m - sum_c t[m,c] z[m,c]),   dlogits = grad_scale / M * (softmax - t);
+ * dfeats, gW, gb follow from dlogits as above, correct counts the rows whose first arg-max equals y_a, preds is unchanged.
+ * y_b == NULL means y_b = y_a (label smoothing alone; lam must be 1).  The same two launches, LDS image, shapes, fixed summation
+ * orders and forward form as fumi_hip_cls_head_step; sum_c z[m,c] (needed for eps > 0) is formed by the strided loop and butterfly of
+ * the log-sum-exp.  With y_b == NULL, lam = 1, smoothing = 0 all six outputs are bit-identical to fumi_hip_cls_head_step.
+ * A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or the gradients.
+ * FUMI_EINVAL before any launch: smoothing outside [0, 1), lam outside [0, 1], y_b == NULL with lam != 1. */
+int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
+        const float* W, const float* b, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
+ * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
+ *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
+ *   mode 1, CutMix:  out[i][:, r, c] = x[partner[i]][:, r, c] for by0 <= r < by1, bx0 <= c < bx1 and x[i] elsewhere (a copy);
+ *                    lam is ignored.
+ * A row that is its own partner is copied.  A partner outside [0, M) sets FUMI_ST_LABEL_RANGE and its row is copied unmixed; no
+ * read leaves x.  128-bit loads and stores when C H W % 4 == 0 and both pointers are 16-byte aligned, single floats otherwise.
+ * FUMI_EINVAL: M, C, H or W < 1, mode not 0 or 1, lam outside [0, 1], a box outside the image or with bx1 < bx0 or by1 < by0 (mode 1). */
+int fumi_hip_mix_images(fumi_ws_t* ws, fumi_stream_t stream, int M, int C, int H, int W, const float* x, const int64_t* partner,
+        int mode, float lam, int bx0, int by0, int bx1, int by1, float* out);
 
 
 /* ---- beside the episodic path -------------------------------------------------------------------------------
