@@ -736,7 +736,9 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     StageTab& s_stg = s_stg2[0];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
     int qi = 0;
-#define QSTAMP() if (w.trace && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) w.trace[64 + qi++] = __builtin_amdgcn_s_memrealtime();
+    // (FIX: the last tile of episode 0 stamps too, at 192; QSTAMPF: the phases of the fused inner step)
+#define QSTAMP() if (w.trace && tid == 0 && blockIdx.y == 0 && (blockIdx.x == 0 || (FIX && blockIdx.x + 1 == gridDim.x))) w.trace[(blockIdx.x == 0 ? 64 : 192) + qi++] = __builtin_amdgcn_s_memrealtime();
+#define QSTAMPF() if constexpr (FIX) { QSTAMP() }
     QSTAMP()
     const int S = d.S, N = d.N, L = d.L, H = d.H, h0 = dh(0), Qn = d.Qn;
     const int r0 = tile * QR, nr = min(QR, Qn - r0);
@@ -744,6 +746,17 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     const int ldq = wg_ld(N), ldG = wg_ld(S), ld0 = wg_ld(h0), ldH = wg_ld(H);
     auto a = [&](int i) { return sm + y.a[i]; };
     auto lda = [&](int i) { return wg_ld(dh(i)); };
+    // wg_lcolsum on lanes t0 .. t0 + Nc - 1 (FIX: a column sum beside a product that occupies the first waves); same chains, same order
+    auto colsum_at = [&](int t0, int M, int Nc, const float* X, int ld, auto&& f) {
+        const int n = tid - t0;
+        if (n >= 0 && n < Nc) {
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            int m = 0;
+            for (; m + 3 < M; m += 4) { s0 += X[m * ld + n]; s1 += X[(m + 1) * ld + n]; s2 += X[(m + 2) * ld + n]; s3 += X[(m + 3) * ld + n]; }
+            for (; m < M; ++m) s0 += X[m * ld + n];
+            f(n, (s0 + s1) + (s2 + s3));
+        }
+    };
 
     // the row's label is loaded now: inside the chain it would wait for every older store (vmcnt is in order)
     const int my_label = tid < nr ? label(y_q + (long)b * Qn + r0, tid, N, status) : 0;
@@ -752,6 +765,37 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     if (FUSED && tid < S && tid < QR) s_lab[tid] = my_label_s;
     // (FIX: the staging is written out below, the tables are not read)
     wg_stage_tab_to_lds(s_stg2, FIX ? 0 : 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(QLay) + 64));
+    // FIX: every staging load -- the support set's images and the tile's own A0 / G rows -- is issued HERE, as fixed-address
+    // loads, and travels under the arena clear.  Sources: the plan's base pointers (run_episodes adds them in this order);
+    // W_1, b_1, b_0 are 16-byte aligned (checked there).  Loads read clamped in-range addresses, the LDS writes are masked.
+    f32x4 fq[4], fva[4], fvw[8], fvb0, fvb1;
+    float fvg[2], fvh, fvbh;
+    if constexpr (FIX) {
+        const float* A0s = stg_sup.base[0] + (long)b * (S + Qn) * REF_H0;
+        const float* A0q = A0s + (long)(S + r0) * REF_H0;
+        const float* W1g = stg_sup.base[1]; const float* b1g = stg_sup.base[2];
+        const float* hdg = stg_sup.base[3] + (long)b * N * (REF_H1 + 1); const float* b0g = stg_sup.base[5];
+        const float* Gg = stg_sup.base[6] + ((long)b * (S + Qn) + r0) * S;
+        constexpr int C4 = REF_H0 / 4;                                   // float4 per row of A0 / W_1
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; fva[k] = *(const f32x4*)(A0s + (long)(m < S ? m : 0) * REF_H0 + 4 * (f % C4)); }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; fvw[k] = *(const f32x4*)(W1g + (long)f * 4); }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {                                    // G: 32 x 32 slots, row m < nr, column c < S
+            const int f = tid + 512 * k, m = f >> 5, c = f & 31;
+            fvg[k] = Gg[(m < nr && c < S) ? (long)m * S + c : 0];
+        }
+        {
+            const int m = tid >> 6, c = tid & 63;                        // head: N <= 8 rows of H = 64 (+ bias) at stride H + 1
+            fvh = hdg[m < N ? m * (REF_H1 + 1) + c : 0];
+        }
+        fvb0 = *(const f32x4*)(b0g + 4 * (tid & 63));
+        fvb1 = *(const f32x4*)(b1g + 4 * (tid & 15));
+        fvbh = hdg[tid < N ? tid * (REF_H1 + 1) + REF_H1 : 0];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; fq[k] = *(const f32x4*)(A0q + (long)(m < nr ? m : 0) * REF_H0 + (m < nr ? 4 * (f % C4) : 0)); }
+    }
     for (int i = tid * 4, tot = y.total; i < tot; i += nt * 4) *(f32x4*)(sm + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads(); QSTAMP()
     int whq = y.Wh;                                                  // the head the query pass uses
@@ -765,6 +809,10 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
         // the tile's own A0 rows are requested NOW (4 float4 per thread: h0 <= 256) and written into a_0 when the support rows
         // are done with it: their latency disappears behind the inner step
         f32x4 qv[4]; bool qok[4];
+        if constexpr (FIX) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { qok[i] = (tid + 512 * i) / (REF_H0 / 4) < nr; qv[i] = fq[i]; }
+        } else
         {
             const float* A0q = w.A0 + ((long)b * (S + Qn) + S + r0) * h0;
             const int c4n = h0 >> 2;
@@ -776,46 +824,33 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
             }
         }
         if constexpr (FIX) {
-            // the same jobs as fixed-address loads, all in flight before the first LDS write.  Sources: the plan's base pointers
-            // (run_episodes adds them in this order); W_1, b_1, b_0 are 16-byte aligned (checked there).  Loads read clamped
-            // in-range addresses, the LDS writes are masked.
-            const float* A0s = stg_sup.base[0] + (long)b * (S + Qn) * REF_H0;
-            const float* W1g = stg_sup.base[1]; const float* b1g = stg_sup.base[2];
-            const float* hdg = stg_sup.base[3] + (long)b * N * (REF_H1 + 1); const float* b0g = stg_sup.base[5];
-            const float* Gg = stg_sup.base[6] + ((long)b * (S + Qn) + r0) * S;
-            constexpr int C4 = REF_H0 / 4;                                   // float4 per row of A0_s / W_1
-            f32x4 va[4], vw[8];
-            float vg[2], vh;
+            // the loads issued in front of the arena clear land.  a_0 = relu(A0_s + b_0) (phase 1 below, D_0 = 0) is computed
+            // from the registers on their way to LDS: lane tid's four float4 are all at column 4 (tid & 63), the column of its
+            // float4 of b_0 -- the same sum of the same two values, then the same mask, as the pass over the LDS image
+            constexpr int C4 = REF_H0 / 4;
+            const unsigned key0 = drop_key(d, b, 0, 0);
+            float* ta0 = w.ta[0] + (long)b * w.ntape * S * REF_H0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; va[k] = *(const f32x4*)(A0s + (long)(m < S ? m : 0) * REF_H0 + 4 * (f % C4)); }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; vw[k] = *(const f32x4*)(W1g + (long)f * 4); }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {                                    // G: 32 x 32 slots, row m < nr, column c < S
-                const int f = tid + 512 * k, m = f >> 5, c = f & 31;
-                vg[k] = Gg[(m < nr && c < S) ? (long)m * S + c : 0];
+            for (int k = 0; k < 4; ++k) {
+                const int f = tid + 512 * k, m = f / C4, n = 4 * (f % C4);
+                if (m < S) {
+                    const f32x4 v = drop_relu4(d, key0, (long)m * REF_H0 + n, fva[k] + fvb0);
+                    *(f32x4*)(sm + y.a[0] + m * wg_ld(REF_H0) + n) = v;
+                    if (lead) *(f32x4*)(ta0 + (long)m * REF_H0 + n) = v;
+                }
             }
-            {
-                const int m = tid >> 6, c = tid & 63;                        // head: N <= 8 rows of H = 64 (+ bias) at stride H + 1
-                vh = hdg[m < N ? m * (REF_H1 + 1) + c : 0];
-            }
-            const f32x4 vb0 = *(const f32x4*)(b0g + 4 * (tid & 63));
-            const f32x4 vb1 = *(const f32x4*)(b1g + 4 * (tid & 15));
-            const float vbh = hdg[tid < N ? tid * (REF_H1 + 1) + REF_H1 : 0];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { const int f = tid + 512 * k, m = f / C4; if (m < S) *(f32x4*)(sm + y.a[0] + m * wg_ld(REF_H0) + 4 * (f % C4)) = va[k]; }
+            for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; *(f32x4*)(sm + y.W[1] + (f / C4) * wg_ld(REF_H0) + 4 * (f % C4)) = fvw[k]; }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { const int f = tid + 512 * k; *(f32x4*)(sm + y.W[1] + (f / C4) * wg_ld(REF_H0) + 4 * (f % C4)) = vw[k]; }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) { const int f = tid + 512 * k, m = f >> 5, c = f & 31; if (m < nr && c < S) sm[y.Gq + m * wg_ld(REF_SQ) + c] = vg[k]; }
-            if ((tid >> 6) < N) sm[y.Wh + (tid >> 6) * wg_ld(REF_H1) + (tid & 63)] = vh;
-            if (tid < REF_H0 / 4) *(f32x4*)(sm + y.b0 + 4 * tid) = vb0;
-            if (tid < REF_H1 / 4) *(f32x4*)(sm + y.bi[1] + 4 * tid) = vb1;
-            if (tid < N) sm[y.bh + tid] = vbh;
+            for (int k = 0; k < 2; ++k) { const int f = tid + 512 * k, m = f >> 5, c = f & 31; if (m < nr && c < S) sm[y.Gq + m * wg_ld(REF_SQ) + c] = fvg[k]; }
+            if ((tid >> 6) < N) sm[y.Wh + (tid >> 6) * wg_ld(REF_H1) + (tid & 63)] = fvh;
+            if (tid < REF_H0 / 4) *(f32x4*)(sm + y.b0 + 4 * tid) = fvb0;
+            if (tid < REF_H1 / 4) *(f32x4*)(sm + y.bi[1] + 4 * tid) = fvb1;
+            if (tid < N) sm[y.bh + tid] = fvbh;
         } else {
             wg_stage_rows<20>(&s_stg2[1], b, tile, 0, nr, sm);       // A0_s rows -> a_0, W_1, b_1, the episode's head, b_0, the tile's G rows
         }
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         float* a0 = a(0); float* a1 = a(1); float* W1 = sm + y.W[1]; float* b1 = sm + y.bi[1];
         float* Wh = sm + y.Wh; float* Wh2 = sm + y.Wh2; float* bh = sm + y.bh; float* Dl = sm + y.D; float* csl = sm + y.cs;
         const float* b0l = sm + y.b0; float* e_ = sm + y.lq;
@@ -832,6 +867,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
             store_img(w.Wslot[1] + (long)b * w.nslot * ((long)h1 * h0), h0, W1, ld0, h1, h0);
             store_img(w.Whslot + (long)b * w.nslot * N * H, H, Wh, ldH, N, H);
         }
+        if constexpr (!FIX)
         {   // 1. a_0 = relu(A0_s + b_0)   (D_0 = 0)
             const unsigned key0 = drop_key(d, b, 0, 0);
             float* ta0 = w.ta[0] + tp * S * h0;
@@ -844,7 +880,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 if (lead) *(f32x4*)(ta0 + (long)m * h0 + n) = v;
             }
         }
-        wg_lds_barrier();
+        if constexpr (!FIX) wg_lds_barrier();
         {   // 2. a_1
             const unsigned key1 = drop_key(d, b, 0, 1);
             float* ta1 = w.ta[1] + tp * S * h1;
@@ -856,12 +892,12 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 if (lead_r) wg_st4(ta1 + (long)m * h1 + n, o, cnt);
             });
         }
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         // 3. head logits (into e_), soft-max, e = (p - onehot) / S
         wg_lmm<true, true>(S, N, H, a1, ld1, Wh, ldH, [&](int m, int n, const f32x4& acc, int) {
             *(f32x4*)(e_ + m * ldq + n) = acc + *(const f32x4*)(bh + n);
         });
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         {
             float* tpp = w.tp + tp * S * N; float* tee = w.te + tp * S * N;
             const int G = N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64;
@@ -886,13 +922,15 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 if (rok) for (int n = gl; n < ldq - 4; n += G) if (n >= N) row[n] = 0.f;      // K padding of e
             }
         }
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         // 4. updated head next to the old one: Wh' = Wh - alpha e^T a_1,  bh' = bh - alpha colsum(e)
         wg_lmm_wide<false>(N, H, S, e_, ldq, a1, ld1, [&](int m, int n, const f32x4& acc, int, auto) {
             *(f32x4*)(Wh2 + m * ldH + n) = *(const f32x4*)(Wh + m * ldH + n) - alpha * acc;
         });
+        if constexpr (FIX) colsum_at(64, S, N, e_, ldq, [&](int n, float s_) { bh[n] -= alpha * s_; });      // (wave 1: wave 0 has the product)
+        else
         wg_lcolsum(S, N, e_, ldq, [&](int n, float s_) { bh[n] -= alpha * s_; });
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         {   // 5. dz_1 = (e Wh) * relu'(a_1), in place of a_1 (reads the OLD head)
             float* tdl = w.tdz[1] + tp * S * h1;
             wg_lmm_wide<true>(S, H, N, e_, ldq, Wh, ldH, [&](int m, int n, const f32x4& acc, int cnt, auto) {
@@ -905,7 +943,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 if (lead_r) wg_st4(tdl + (long)m * h1 + n, o, cnt);
             });
         }
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         // 6. dz_0 = (dz_1 W_1) * relu'(a_0) = D_1
         wg_lmm_wide<true>(S, h0, h1, a1, ld1, W1, ld0, [&](int m, int n, const f32x4& acc, int cnt, auto) {
             const f32x4 act = *(const f32x4*)(a0 + m * ld0 + n);
@@ -914,7 +952,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
             for (int c = 0; c < 4; ++c) o[c] = (c < cnt && act[c] > 0.f) ? acc[c] * d.mscale : 0.f;
             *(f32x4*)(Dl + m * ld0 + n) = o;
         });
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         // 7. W_1' = W_1 - alpha dz_1^T a_0 in place, b_1' = b_1 - alpha colsum(dz_1), colsum(D_1)
         wg_lmm_wide<false>(h1, h0, S, a1, ld1, a0, ld0, [&](int m, int n, const f32x4& acc, int, auto) {
             float* pw = W1 + m * ld0 + n;
@@ -922,7 +960,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
         });
         wg_lcolsum(S, h1, a1, ld1, [&](int n, float s_) { b1[n] -= alpha * s_; });
         wg_lcolsum(S, h0, Dl, ld0, [&](int n, float s_) { csl[n] = s_; });
-        wg_lds_barrier();
+        wg_lds_barrier(); QSTAMPF()
         whq = y.Wh2;
         // the query rows replace the support rows in a_0 (rows past the tile: zeros); a_1 and the logits image are cleared
         {
@@ -933,8 +971,15 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
                 if (m < QR) *(f32x4*)(a0 + m * ld0 + n) = qok[i] ? qv[i] : z4s;
             }
         }
+        if constexpr (FIX) {
+            // rows under nr are overwritten whole by the query pass (its epilogues write every float4 of a row up to the width, the
+            // padding columns were never written), rows from S on are still zero from the arena clear: rows nr .. S - 1 are left
+            for (int i = tid + nr * (ld1 >> 2); i < S * (ld1 >> 2); i += nt) { const int m = i / (ld1 >> 2); *(f32x4*)(a1 + m * ld1 + ((i - m * (ld1 >> 2)) << 2)) = z4s; }
+            for (int i = tid + nr * (ldq >> 2); i < S * (ldq >> 2); i += nt) { const int m = i / (ldq >> 2); *(f32x4*)(e_ + m * ldq + ((i - m * (ldq >> 2)) << 2)) = z4s; }
+        } else {
         for (int i = tid; i < QR * (ld1 >> 2); i += nt) { const int m = i / (ld1 >> 2); *(f32x4*)(a1 + m * ld1 + ((i - m * (ld1 >> 2)) << 2)) = z4s; }
         for (int i = tid; i < QR * (ldq >> 2); i += nt) { const int m = i / (ldq >> 2); *(f32x4*)(e_ + m * ldq + ((i - m * (ldq >> 2)) << 2)) = z4s; }
+        }
         wg_lds_barrier(); QSTAMP()
     } else {
         wg_stage_rows<20>(&s_stg, b, tile, 0, nr, sm);
@@ -990,7 +1035,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
         for (int n = 0; n < N; ++n) row[n] = (expf(row[n] - mx) * inv - (n == yy ? 1.f : 0.f)) / (float)Qn;
     }
     wg_lds_barrier(); QSTAMP()
-    if (tid == 0) {
+    if (tid == (FIX ? 256 : 0)) {                                  // (FIX: wave 4; wave 0 has the product of the phase behind)
         float ls = 0.f, cs_ = 0.f;
         for (int m = 0; m < nr; ++m) { ls += s_loss[m]; cs_ += s_corr[m]; }
         w.ploss[(long)b * w.ntile + tile] = ls;
@@ -1063,6 +1108,7 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     });
     (void)z4;
     QSTAMP()
+#undef QSTAMPF
 #undef QSTAMP
 }
 

@@ -38,8 +38,11 @@ def main():
     print("form: query", "fixed-shape" if fx & 1 else "run-time-shaped", "| reverse", "fixed-shape" if fx & 2 else "run-time-shaped",
           "(FUMI_EPI_FIXED=%s)" % os.environ.get("FUMI_EPI_FIXED", "1"))
     t = tr.cpu()
-    for name, lo in (("query_lds", 64), ("reverse_lds", 128)):
+    # (192: the fixed-shape query kernel's last tile of episode 0, stamped when there is more than one tile)
+    for name, lo in (("query_lds", 64), ("reverse_lds", 128), ("query_lds last tile", 192)):
         d = phases(t[lo:lo + 64])
+        if not d:
+            continue
         print(f"{name} phase durations (us):", [round(x, 2) for x in d], "total", round(sum(d), 1))
 
 
