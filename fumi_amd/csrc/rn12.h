@@ -52,6 +52,12 @@ struct RnConvArgs {
     // slab loads, tiles per image (tpi > 0: the tiles restart at every image)
     int tiles, ncg, xcd, slab_rows, glds, tpi;
 };
+// what a launch decides from its shape (rn_conv_plan / rn_wgrad_plan: host arithmetic only, shared by the launch and the query)
+struct RnConvPlan { int NF, MW, BKS, S16, tiles, tpi, ncg, xcd, glds, slab_rows, lds; };
+struct RnWgradPlan { int NTAP, nsplit, ci_tiles, co_tiles, xcd, reduce, lds; };
+enum { RN_RED_ROWS = 1, RN_RED_SPLIT4 = 2, RN_RED_TAPS9 = 3 };      // rn_wgrad_reduce_kernel<false>, <true>, rn_wgrad_reduce9_kernel
+int rn_conv_plan(int B, int Cout, long npix, const RnGeom& g, int nsrc, const int* Cin, const int* ntaps, RnConvPlan* p);
+int rn_wgrad_plan(int B, int npair, int Cin, int Cout, int ntaps, int nsplit, long npix, const RnGeom& g, RnWgradPlan* p);
 int rn_conv_tiles(long npix, const RnGeom& g);          // upper bound of the statistics slabs per episode (sizing)
 size_t rn_conv_lds_bytes(const RnGeom& g, int Cout);
 // nt_out (optional): the number of statistics slabs per episode the launch wrote (its pixel tiles: 128 or 256 pixels each)
@@ -68,9 +74,9 @@ int launch_rn_wgrad(hipStream_t st, const RnWgradArgs& a);
 // G[b][(co * Cin_real + ci) * ntaps + tap] = sum_split part   (torch OIHW), b-stride gstride
 int launch_rn_wgrad_reduce(hipStream_t st, int B, int nsplit, int ntaps, int Cout, int Cin, int Cin_real, const float* part,
                            float* G, long gstride);
-// fp32 OIHW master -> bf16 fragment copies (fwd always, bwd when bwd != NULL)
+// fp32 OIHW master -> bf16 fragment copies (fwd always, bwd when bwd != NULL); sf / sb: the MFMA form of each copy (-1: by channel count)
 int launch_rn_wprep(hipStream_t st, int B, int Cout, int Cin, int Cin_real, int ntaps, const float* W, long wstride,
-                    rbf16* fwd, rbf16* bwd, long fstride);
+                    rbf16* fwd, rbf16* bwd, long fstride, int sf = -1, int sb = -1);
 
 // ---- rn12_ew.hip -------------------------------------------------------------------------------------------------------------------
 // per (episode, channel) coefficient table of one BN and pass: [B][RCF_N][C]

@@ -1165,48 +1165,101 @@ int fumi_hip_resnet12_encode_plan(int* taped, int* chunk, int* lanes) {
 // transpose != 0: the input-gradient product (x has Cout channels, y has Cin).  stats (optional) [B][2][Cy]: sum, sum of squares.
 int fumi_hip_rn12_conv(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cin, int Cout, int ntaps, int transpose,
         const void* x, const float* Wt, void* y, float* stats) {
-    if (!ws || !x || !Wt || !y || B < 1 || M < 1 || (ntaps != 9 && ntaps != 1)) return FUMI_EINVAL;
+    if (!ws || !x || !Wt || !y || B < 1 || M < 1 || H < 1 || W < 1 || (ntaps != 9 && ntaps != 1)) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    const long npix = (long)M * rn_geom(H, W).Pp;
+    const int Cy = transpose ? Cin : Cout, Cx = transpose ? Cout : Cin;
+    const long long xs = npix * Cx, wst = (long long)Cout * Cin * ntaps;
+    RnConvPlan plan;                                                   // (every refusal before the clear: a refused call launches nothing)
+    TRY(rn_conv_plan(B, Cy, npix, rn_geom(H, W), 1, &Cx, &ntaps, &plan));
+    if (transpose && (Cx & 31)) return FUMI_EINVAL;
     HIP_TRY(hipSetDevice(ws->device));
+    HIP_TRY(hipMemsetAsync(y, 0, (size_t)B * npix * Cy * 2, st));      // the kernel writes interior pixels only (nothing reads the border of a conv output)
+    return fumi_hip_rn12_conv_multi(ws, stream, B, M, H, W, Cy, 1, &Cx, &ntaps, &x, &xs, &Wt, &wst, transpose, nullptr, 0, y, npix * Cy, stats);
+}
+
+// The general form (every launch the engine issues: conv_bn / conv_plain): out = sum over 1..4 sources of conv_{ntaps[s]}(x[s], Wt[s]),
+// source s with Cin[s] channels and an episode stride x_stride[s] >= npix Cin[s] (elements); Wt[s] fp32 OIHW [Cout][Cin[s]][k][k], or
+// with transpose != 0 the forward layer's [Cin[s]][Cout][k][k] whose backward-data copy is multiplied; w_stride[s] = 0: one weight
+// set shared by all episodes.  dot (optional, stride dot_stride): the second statistic is sum(out * dot) instead of sum(out^2).
+// y (stride y_stride >= npix Cout) is NOT cleared: interior pixels are written, the border is the caller's.  stats (optional)
+// [B][2][Cout].  Nothing is launched when an argument is refused.
+int fumi_hip_rn12_conv_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cout, int nsrc, const int* Cin,
+        const int* ntaps, const void* const* x, const long long* x_stride, const float* const* Wt, const long long* w_stride,
+        int transpose, const void* dot, long long dot_stride, void* y, long long y_stride, float* stats) {
+    if (!ws || !Cin || !ntaps || !x || !x_stride || !Wt || !w_stride || !y || M < 1 || H < 1 || W < 1) return FUMI_EINVAL;
     const RnGeom g = rn_geom(H, W);
     const long npix = (long)M * g.Pp;
-    const int Cy = transpose ? Cin : Cout, Cx = transpose ? Cout : Cin;
-    const long fe = (long)ntaps * Cin * Cout;
+    RnConvPlan plan;
+    TRY(rn_conv_plan(B, Cout, npix, g, nsrc, Cin, ntaps, &plan));       // (every refusal of launch_rn_conv, before anything is launched)
+    if (y_stride < npix * Cout || (dot && dot_stride < npix * Cout)) return FUMI_EINVAL;
+    size_t fel[4] = {0, 0, 0, 0}, need = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        if (!x[s] || !Wt[s] || x_stride[s] < npix * Cin[s] || w_stride[s] < 0) return FUMI_EINVAL;
+        if (transpose && (Cin[s] & 31)) return FUMI_EINVAL;              // (launch_rn_wprep: the layer's forward copy needs Cout % 32 == 0)
+        fel[s] = (size_t)ntaps[s] * Cin[s] * Cout;
+        if (w_stride[s] && (size_t)w_stride[s] < fel[s]) return FUMI_EINVAL;
+        need += (transpose ? 2 : 1) * ws_align((w_stride[s] ? B : 1) * fel[s] * 2);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
     const int tiles = rn_conv_tiles(npix, g);
-    int rc = ws_reserve(ws, 2 * ws_align((size_t)B * fe * 2) + ws_align((size_t)B * tiles * 2 * Cy * 4));
+    int rc = ws_reserve(ws, need + ws_align((size_t)B * tiles * 2 * Cout * 4));
     if (rc) return rc;
-    rbf16* ff = ws_h(ws, (size_t)B * fe); rbf16* fb = ws_h(ws, (size_t)B * fe); float* part = ws_f(ws, (size_t)B * tiles * 2 * Cy);
-    TRY(launch_rn_wprep(st, B, Cout, Cin, Cin, ntaps, Wt, (long)Cout * Cin * ntaps, ff, transpose ? fb : nullptr, fe));
     RnConvArgs a; memset(&a, 0, sizeof(a));
-    a.B = B; a.nsrc = 1; a.Cout = Cy; a.npix = npix; a.g = g;
-    a.src[0].in = (const rbf16*)x; a.src[0].in_stride = npix * Cx; a.src[0].frag = transpose ? fb : ff; a.src[0].frag_stride = fe;
-    a.src[0].Cin = Cx; a.src[0].ntaps = ntaps;
-    a.src[1] = a.src[2] = a.src[3] = a.src[0];
-    a.out = (rbf16*)y; a.out_stride = npix * Cy; a.stats = stats ? part : nullptr;
-    HIP_TRY(hipMemsetAsync(y, 0, (size_t)B * npix * Cy * 2, st));      // the kernel writes interior pixels only (nothing reads the border of a conv output)
+    a.B = B; a.nsrc = nsrc; a.Cout = Cout; a.npix = npix; a.g = g;
+    for (int s = 0; s < nsrc; ++s) {
+        const int Bw = w_stride[s] ? B : 1;
+        rbf16* ff = ws_h(ws, Bw * fel[s]); rbf16* fb = transpose ? ws_h(ws, Bw * fel[s]) : nullptr;
+        // the copy that is multiplied is laid out in the LAUNCH's form (one form for all sources)
+        if (transpose) TRY(launch_rn_wprep(st, Bw, Cin[s], Cout, Cout, ntaps[s], Wt[s], (long)w_stride[s], ff, fb, (long)fel[s], -1, plan.S16));
+        else TRY(launch_rn_wprep(st, Bw, Cout, Cin[s], Cin[s], ntaps[s], Wt[s], (long)w_stride[s], ff, nullptr, (long)fel[s], plan.S16, -1));
+        a.src[s] = src_of((const rbf16*)x[s], (long)x_stride[s], transpose ? fb : ff, w_stride[s] ? (long)fel[s] : 0, Cin[s], ntaps[s]);
+    }
+    for (int s = nsrc; s < 4; ++s) a.src[s] = a.src[0];
+    float* part = ws_f(ws, (size_t)B * tiles * 2 * Cout);
+    a.out = (rbf16*)y; a.out_stride = (long)y_stride; a.stats = stats ? part : nullptr;
+    a.dot = (const rbf16*)dot; a.dot_stride = (long)dot_stride;
     int nt = 0;
     TRY(launch_rn_conv(st, a, &nt));
-    if (stats) TRY(launch_reduce_batched(st, B, nt, 2L * Cy, part, 1.f, stats, 2L * Cy));
+    if (stats) TRY(launch_reduce_batched(st, B, nt, 2L * Cout, part, 1.f, stats, 2L * Cout));
     return FUMI_OK;
 }
 
 // dW [B][Cout][Cin][k][k] fp32 = sum_p dy[p][co] x[p + off][ci]   (x, dy: raw bf16 maps as above)
 int fumi_hip_rn12_wgrad(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cin, int Cout, int ntaps,
         const void* x, const void* dy, float* dW) {
-    if (!ws || !x || !dy || !dW || B < 1 || M < 1 || (ntaps != 9 && ntaps != 1)) return FUMI_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(ws->device));
+    if (M < 1 || H < 1 || W < 1) return FUMI_EINVAL;
+    const long npix = (long)M * rn_geom(H, W).Pp;
+    return fumi_hip_rn12_wgrad_multi(ws, stream, B, M, H, W, Cin, Cin, Cout, ntaps, 1, 0, x, dy, nullptr, nullptr, npix * Cin, npix * Cout,
+                                     dW, (long long)Cout * Cin * ntaps);
+}
+
+// The general form (wgrad() of the engine): dW [B][Cout][Cin_real][k][k] (stride dw_stride) = sum over npair (x, dy) pairs; the maps
+// have Cin >= Cin_real channels (the image layer: 16 for 3) and episode strides x_stride / dy_stride; nsplit = 0: rn_wgrad_nsplit's
+// split of the pixel axis, else that many slabs.
+int fumi_hip_rn12_wgrad_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cin, int Cin_real, int Cout, int ntaps,
+        int npair, int nsplit, const void* x0, const void* dy0, const void* x1, const void* dy1, long long x_stride, long long dy_stride,
+        float* dW, long long dw_stride) {
+    if (!ws || !x0 || !dy0 || !dW || M < 1 || H < 1 || W < 1 || Cin < 16 || Cout < 32 || Cin_real < 1 || Cin_real > Cin) return FUMI_EINVAL;
+    if (nsplit < 0 || nsplit > 512 || (npair == 2 && (!x1 || !dy1))) return FUMI_EINVAL;
     const RnGeom g = rn_geom(H, W);
     RnWgradArgs a; memset(&a, 0, sizeof(a));
-    a.B = B; a.npair = 1; a.Cin = Cin; a.Cout = Cout; a.ntaps = ntaps; a.npix = (long)M * g.Pp; a.g = g;
-    a.nsplit = rn_wgrad_nsplit(B, a.npix, Cin, Cout);
+    a.B = B; a.npair = npair; a.Cin = Cin; a.Cout = Cout; a.ntaps = ntaps; a.npix = (long)M * g.Pp; a.g = g;
+    RnWgradPlan plan;
+    a.nsplit = nsplit ? nsplit : (B >= 1 ? rn_wgrad_nsplit(B, a.npix, Cin, Cout) : 1);
+    TRY(rn_wgrad_plan(B, npair, Cin, Cout, ntaps, a.nsplit, a.npix, g, &plan));       // (every refusal of launch_rn_wgrad, before anything is launched)
+    if (x_stride < a.npix * Cin || dy_stride < a.npix * Cout || dw_stride < (long long)Cout * Cin_real * ntaps) return FUMI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
     const int Ci32 = (Cin + 31) / 32 * 32;
     int rc = ws_reserve(ws, ws_align((size_t)B * a.nsplit * ntaps * Cout * Ci32 * 4));
     if (rc) return rc;
     a.part = ws_f(ws, (size_t)B * a.nsplit * ntaps * Cout * Ci32);
-    a.x[0] = (const rbf16*)x; a.dy[0] = (const rbf16*)dy; a.x_stride = a.npix * Cin; a.dy_stride = a.npix * Cout;
+    a.x[0] = (const rbf16*)x0; a.dy[0] = (const rbf16*)dy0; a.x[1] = (const rbf16*)x1; a.dy[1] = (const rbf16*)dy1;
+    a.x_stride = (long)x_stride; a.dy_stride = (long)dy_stride;
     TRY(launch_rn_wgrad(st, a));
-    return launch_rn_wgrad_reduce(st, B, a.nsplit, ntaps, Cout, Cin, Cin, a.part, dW, (long)Cout * Cin * ntaps);
+    return launch_rn_wgrad_reduce(st, B, a.nsplit, ntaps, Cout, Cin, Cin_real, a.part, dW, (long)dw_stride);
 }
 
 }  // extern "C"

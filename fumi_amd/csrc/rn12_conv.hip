@@ -74,16 +74,20 @@ inline int rn_slab_span(const RnGeom& g, int mt) {
     return best;
 }
 
+// rows of a tile's slab image (span + halo on both sides, in the 8-row granule of the LDS-direct loads) and the LDS bytes of an
+// instance: slab + two weight tiles of BKS k-steps, or the epilogue's statistics [4 waves][32 NF][2] floats.  The ONE statement of
+// both: the kernel's layout (ConvCfg), the host-side choice of the instance and the host query all read these.
+inline int conv_slab_rows(const RnGeom& g, int MW) { return (rn_slab_span(g, 128 * MW) + 2 * g.halo + 7) / 8 * 8; }
+inline int conv_lds_bytes(const RnGeom& g, int NF, int MW, int BKS) {
+    const int main_ = conv_slab_rows(g, MW) * 128 + 2 * BKS * NF * 1024, epi = 4 * 32 * NF * 2 * 4;
+    return (main_ > epi ? main_ : epi) + 16;
+}
 template <int NF, int MW, int BKS>
 struct ConvCfg {
     static constexpr int MT = 128 * MW, NT = 32 * NF;
     static constexpr int BT = BKS * NF * 1024;                                   // bytes of one weight tile (BKS k-steps of one tap)
-    static int slab_rows(const RnGeom& g) { return (rn_slab_span(g, MT) + 2 * g.halo + 7) / 8 * 8; }
-    static int lds_bytes(const RnGeom& g) {
-        const int main_ = slab_rows(g) * 128 + 2 * BT;
-        const int epi = 4 * NT * 2 * 4;                                          // the epilogue's statistics: [4 waves][NT][2] floats
-        return (main_ > epi ? main_ : epi) + 16;
-    }
+    static int slab_rows(const RnGeom& g) { return conv_slab_rows(g, MW); }
+    static int lds_bytes(const RnGeom& g) { return conv_lds_bytes(g, NF, MW, BKS); }
 };
 
 // (Weight tiles: two buffers, the next tile requested while this one is multiplied, s_waitcnt vmcnt(0) + one barrier per tile.  A
@@ -503,48 +507,16 @@ bool rn_use_s16(int Cin) {
     return on && (Cin & 31) == 0;
 }
 
-template <int NF, int MW, int BKS, bool S16>
-int conv_launch2(hipStream_t st, const RnConvArgs& a, int* nt_out) {
-    typedef ConvCfg<NF, MW, BKS> C;
-    const int lds = C::lds_bytes(a.g);
-    if (lds > 160 * 1024) return FUMI_ENOTSUP;
-    FUMI_SET_DYN_LDS((rn_conv_kernel<NF, MW, BKS, S16>), lds);
-    RnConvArgs k = a;
-    const long NC = a.npix / a.g.Pp * ((long)a.g.H * a.g.W);
-    k.tiles = (int)((NC + C::MT - 1) / C::MT); k.ncg = a.Cout / C::NT; k.slab_rows = C::slab_rows(a.g); k.tpi = 0;
-    if (rn_per_image(a.g, C::MT)) {
-        k.tpi = (a.g.H * a.g.W + C::MT - 1) / C::MT;
-        k.tiles = (int)(a.npix / a.g.Pp) * k.tpi;
-    }
-    const int groups = k.ncg * a.B;
-    static const int xcd_env = getenv("FUMI_RN_XCD") ? atoi(getenv("FUMI_RN_XCD")) : 1;
-    k.xcd = xcd_env && groups >= 8 && groups % 8 == 0;
-    static const int glds_env = getenv("FUMI_RN_GLDS") ? atoi(getenv("FUMI_RN_GLDS")) : 1;
-    k.glds = glds_env; k.trace = g_rn_trace;
-    const dim3 grid((unsigned)((long)k.tiles * groups));
-    hipLaunchKernelGGL((rn_conv_kernel<NF, MW, BKS, S16>), grid, dim3(256), lds, st, k);
-    LAUNCH_CHECK();
-    if (nt_out) *nt_out = k.tiles;
-    return FUMI_OK;
-}
-template <int NF, int MW, int BKS>
-int conv_launch(hipStream_t st, const RnConvArgs& a, int* nt_out) {
-    bool s16 = true;
-    for (int s = 0; s < a.nsrc; ++s) s16 = s16 && rn_use_s16(a.src[s].Cin);
-    return s16 ? conv_launch2<NF, MW, BKS, true>(st, a, nt_out) : conv_launch2<NF, MW, BKS, false>(st, a, nt_out);
-}
-
 // tile shape for a layer: 256-pixel tiles (each wave 64 pixels: every weight fragment feeds two MFMAs, 0.7 KiB of LDS reads per MFMA
 // instead of 1.2) whenever two workgroups still fit a CU's LDS -- with 4-k-step weight tiles, else with 2-k-step ones
-template <int NF>
-int conv_dispatch(hipStream_t st, const RnConvArgs& a, int* nt_out) {
+void conv_tile_shape(int NF, int Cout, long npix, const RnGeom& g, int* MW, int* BKS) {
     // dev knobs: FUMI_RN_MW = 1 | 2 forces the pixels per wave (32 | 64), FUMI_RN_BKS = 2 | 4 the k-steps per weight tile (also
     // when that leaves one workgroup per CU)
     static const int force = getenv("FUMI_RN_MW") ? atoi(getenv("FUMI_RN_MW")) : 0;
     static const int fbks = getenv("FUMI_RN_BKS") ? atoi(getenv("FUMI_RN_BKS")) : 0;
     // (the tile shape is chosen from per-episode quantities -- priced for RN_BREF episodes per chunk, the production chunk -- so that an
     // episode's results do not depend on how many episodes share its chunk)
-    const long tiles256 = (a.npix + 255) / 256 * (a.Cout / (32 * NF)) * RN_BREF;
+    const long tiles256 = (npix + 255) / 256 * (Cout / (32 * NF)) * RN_BREF;
     const int two = 80 * 1024 - 256;                                  // two workgroups per CU
     // (Round 4, the 10 x 10 maps on 128-pixel tiles -- three workgroups per CU at 42 KB / 166 registers: 640 -> 640 303 vs 341 us on one
     // stream (972 TFLOP/s), nothing in the two-lane step (16.72-16.83 vs 16.73-16.76 episodes/s); 21 x 21 and above lose (354 vs 308).)
@@ -563,15 +535,42 @@ int conv_dispatch(hipStream_t st, const RnConvArgs& a, int* nt_out) {
     // with two fragment sets in registers (reads of k-step ks + 1 under the MFMAs of ks, a full
     // tile as straight-line code): hipcc waits with lgkmcnt(0) around every LDS-direct load and shuffles accumulators between AGPRs
     // and VGPRs -- 1 685 us at 160 -> 160, four times the two-workgroup kernel.)
+    *MW = 2;
     if (force != 1 && (tiles256 >= 256 || force == 2)) {
-        if (fbks == 4 && ConvCfg<NF, 2, 4>::lds_bytes(a.g) <= 160 * 1024) return conv_launch<NF, 2, 4>(st, a, nt_out);
-        if (fbks == 2 && ConvCfg<NF, 2, 2>::lds_bytes(a.g) <= 160 * 1024) return conv_launch<NF, 2, 2>(st, a, nt_out);
+        if (fbks == 4 && conv_lds_bytes(g, NF, 2, 4) <= 160 * 1024) { *BKS = 4; return; }
+        if (fbks == 2 && conv_lds_bytes(g, NF, 2, 2) <= 160 * 1024) { *BKS = 2; return; }
         // (NF = 5 with 4-k-step tiles and two register sets of weight loads spills: 2-k-step tiles there)
-        if (NF < 5 && ConvCfg<NF, 2, 4>::lds_bytes(a.g) <= two) return conv_launch<NF, 2, 4>(st, a, nt_out);
-        if (ConvCfg<NF, 2, 2>::lds_bytes(a.g) <= two) return conv_launch<NF, 2, 2>(st, a, nt_out);
+        if (NF < 5 && conv_lds_bytes(g, NF, 2, 4) <= two) { *BKS = 4; return; }
+        if (conv_lds_bytes(g, NF, 2, 2) <= two) { *BKS = 2; return; }
     }
-    if (fbks == 2) return conv_launch<NF, 1, 2>(st, a, nt_out);
-    return conv_launch<NF, 1, 4>(st, a, nt_out);
+    *MW = 1; *BKS = fbks == 2 ? 2 : 4;
+}
+
+// the launch of one instance with the geometry rn_conv_plan chose for it
+template <int NF, int MW, int BKS, bool S16>
+int conv_launch2(hipStream_t st, const RnConvArgs& a, const RnConvPlan& p, int* nt_out) {
+    FUMI_SET_DYN_LDS((rn_conv_kernel<NF, MW, BKS, S16>), p.lds);
+    RnConvArgs k = a;
+    k.tiles = p.tiles; k.ncg = p.ncg; k.slab_rows = p.slab_rows; k.tpi = p.tpi; k.xcd = p.xcd; k.glds = p.glds; k.trace = g_rn_trace;
+    const dim3 grid((unsigned)((long)k.tiles * k.ncg * a.B));
+    hipLaunchKernelGGL((rn_conv_kernel<NF, MW, BKS, S16>), grid, dim3(256), p.lds, st, k);
+    LAUNCH_CHECK();
+    if (nt_out) *nt_out = k.tiles;
+    return FUMI_OK;
+}
+template <int NF>
+int conv_dispatch(hipStream_t st, const RnConvArgs& a, const RnConvPlan& p, int* nt_out) {
+    switch (p.MW * 100 + p.BKS * 10 + p.S16) {
+        case 241: return conv_launch2<NF, 2, 4, true>(st, a, p, nt_out);
+        case 240: return conv_launch2<NF, 2, 4, false>(st, a, p, nt_out);
+        case 221: return conv_launch2<NF, 2, 2, true>(st, a, p, nt_out);
+        case 220: return conv_launch2<NF, 2, 2, false>(st, a, p, nt_out);
+        case 141: return conv_launch2<NF, 1, 4, true>(st, a, p, nt_out);
+        case 140: return conv_launch2<NF, 1, 4, false>(st, a, p, nt_out);
+        case 121: return conv_launch2<NF, 1, 2, true>(st, a, p, nt_out);
+        case 120: return conv_launch2<NF, 1, 2, false>(st, a, p, nt_out);
+    }
+    return FUMI_EINVAL;
 }
 
 // NF (32-column blocks per workgroup) for an output width: the widest of {5, 4, 3, 2, 1} that divides it
@@ -866,21 +865,57 @@ size_t rn_conv_lds_bytes(const RnGeom& g, int Cout) {
     }
 }
 
+// decisions of the last launch_rn_conv / launch_rn_wgrad (+ its reduce) of this process (fumi_hip_rn12_conv_plan): written on the host
+// beside the launches, never read by one
+RnConvPlan g_rn_conv_last = {};
+RnWgradPlan g_rn_wgrad_last = {};
+
+// Every decision of a convolution launch from its shape alone: no HIP call.  launch_rn_conv launches what this returns, and
+// fumi_hip_rn12_conv_query reports it for a shape.  ntaps may be NULL (the query: taps do not enter the choice).
+int rn_conv_plan(int B, int Cout, long npix, const RnGeom& g, int nsrc, const int* Cin, const int* ntaps, RnConvPlan* p) {
+    if (npix >= (1L << 31) - 4096) return FUMI_ENOTSUP;            // (pixel indices are 32-bit inside the kernels)
+    for (int s = 0; s < nsrc && s < 4; ++s)
+        if (npix * Cin[s] * 2 >= (1L << 32) - 65536) return FUMI_ENOTSUP;      // (byte offsets within an episode's map: 32-bit)
+    if (B < 1 || nsrc < 1 || nsrc > 4 || Cout < 32 || (Cout & 31) || npix < 1) return FUMI_EINVAL;
+    if (g.H < 1 || g.W < 1 || npix % g.Pp) return FUMI_EINVAL;
+    if (npix * Cout >= (1L << 31) - 65536) return FUMI_ENOTSUP;                        // (element offsets within an episode's output map: 32-bit)
+    for (int s = 0; s < nsrc; ++s)
+        if (Cin[s] < 16 || (Cin[s] & 15) || (ntaps && ntaps[s] != 9 && ntaps[s] != 1)) return FUMI_EINVAL;
+    p->NF = conv_nf(Cout);
+    conv_tile_shape(p->NF, Cout, npix, g, &p->MW, &p->BKS);
+    p->S16 = 1;
+    for (int s = 0; s < nsrc; ++s) p->S16 = p->S16 && rn_use_s16(Cin[s]);
+    p->lds = conv_lds_bytes(g, p->NF, p->MW, p->BKS);
+    if (p->lds > 160 * 1024) return FUMI_ENOTSUP;
+    const int MT = 128 * p->MW;
+    const long NC = npix / g.Pp * ((long)g.H * g.W);
+    p->tiles = (int)((NC + MT - 1) / MT); p->ncg = Cout / (32 * p->NF); p->slab_rows = conv_slab_rows(g, p->MW); p->tpi = 0;
+    if (rn_per_image(g, MT)) {
+        p->tpi = (g.H * g.W + MT - 1) / MT;
+        p->tiles = (int)(npix / g.Pp) * p->tpi;
+    }
+    const int groups = p->ncg * B;
+    static const int xcd_env = getenv("FUMI_RN_XCD") ? atoi(getenv("FUMI_RN_XCD")) : 1;
+    p->xcd = xcd_env && groups >= 8 && groups % 8 == 0;
+    static const int glds_env = getenv("FUMI_RN_GLDS") ? atoi(getenv("FUMI_RN_GLDS")) : 1;
+    p->glds = glds_env;
+    return FUMI_OK;
+}
+
 int launch_rn_conv(hipStream_t st, const RnConvArgs& a, int* nt_out) {
-    if (a.npix >= (1L << 31) - 4096) return FUMI_ENOTSUP;            // (pixel indices are 32-bit inside the kernels)
-    for (int s = 0; s < a.nsrc; ++s)
-        if (a.npix * a.src[s].Cin * 2 >= (1L << 32) - 65536) return FUMI_ENOTSUP;      // (byte offsets within an episode's map: 32-bit)
-    if (a.B < 1 || a.nsrc < 1 || a.nsrc > 4 || a.Cout < 32 || (a.Cout & 31) || a.npix < 1) return FUMI_EINVAL;
-    if (a.npix * a.Cout >= (1L << 31) - 65536) return FUMI_ENOTSUP;                        // (element offsets within an episode's output map: 32-bit)
-    for (int s = 0; s < a.nsrc; ++s)
-        if (!a.src[s].in || !a.src[s].frag || a.src[s].Cin < 16 || (a.src[s].Cin & 15) || (a.src[s].ntaps != 9 && a.src[s].ntaps != 1))
-            return FUMI_EINVAL;
-    switch (conv_nf(a.Cout)) {
-        case 5: return conv_dispatch<5>(st, a, nt_out);
-        case 4: return conv_dispatch<4>(st, a, nt_out);
-        case 3: return conv_dispatch<3>(st, a, nt_out);
-        case 2: return conv_dispatch<2>(st, a, nt_out);
-        default: return conv_dispatch<1>(st, a, nt_out);
+    int Cin[4] = {0, 0, 0, 0}, ntaps[4] = {0, 0, 0, 0};
+    for (int s = 0; s < a.nsrc && s < 4; ++s) { Cin[s] = a.src[s].Cin; ntaps[s] = a.src[s].ntaps; }
+    RnConvPlan p;
+    const int rc = rn_conv_plan(a.B, a.Cout, a.npix, a.g, a.nsrc, Cin, ntaps, &p);
+    if (rc) return rc;
+    for (int s = 0; s < a.nsrc; ++s) if (!a.src[s].in || !a.src[s].frag) return FUMI_EINVAL;
+    g_rn_conv_last = p;
+    switch (p.NF) {
+        case 5: return conv_dispatch<5>(st, a, p, nt_out);
+        case 4: return conv_dispatch<4>(st, a, p, nt_out);
+        case 3: return conv_dispatch<3>(st, a, p, nt_out);
+        case 2: return conv_dispatch<2>(st, a, p, nt_out);
+        default: return conv_dispatch<1>(st, a, p, nt_out);
     }
 }
 
@@ -923,20 +958,36 @@ int rn_wgrad_nsplit(int B_chunk, long npix, int Cin, int Cout) {
     return (int)ns;
 }
 
-int launch_rn_wgrad(hipStream_t st, const RnWgradArgs& a) {
-    if (a.B < 1 || a.npair < 1 || a.npair > 2 || (a.Cin & 15) || (a.Cout & 31) || a.nsplit < 1 || (a.ntaps != 9 && a.ntaps != 1))
+// the reduce kernel for a split: nine taps side by side, else a four-way split of long slab lists, else four rows per workgroup
+static int rn_wgrad_reduce_kind(int ntaps, int nsplit) { return ntaps == 9 ? RN_RED_TAPS9 : (nsplit >= 16 ? RN_RED_SPLIT4 : RN_RED_ROWS); }
+
+// Every decision of a weight-gradient launch and of the reduce behind it from the shape and the split: no HIP call.
+int rn_wgrad_plan(int B, int npair, int Cin, int Cout, int ntaps, int nsplit, long npix, const RnGeom& g, RnWgradPlan* p) {
+    if (B < 1 || npair < 1 || npair > 2 || (Cin & 15) || (Cout & 31) || nsplit < 1 || (ntaps != 9 && ntaps != 1))
         return FUMI_EINVAL;
-    if (a.npix * (a.Cin > a.Cout ? a.Cin : a.Cout) * 2 >= (1L << 32) - 65536) return FUMI_ENOTSUP;   // (32-bit byte offsets inside the kernel)
-    const int Ci32 = (a.Cin + 31) / 32 * 32;
-    const int ci_tiles = (Ci32 + 63) / 64, co_tiles = (a.Cout + 63) / 64;
-    const int hs = a.ntaps == 9 ? a.g.halo : 0;
+    if (npix * (Cin > Cout ? Cin : Cout) * 2 >= (1L << 32) - 65536) return FUMI_ENOTSUP;   // (32-bit byte offsets inside the kernel)
+    const int Ci32 = (Cin + 31) / 32 * 32;
+    p->NTAP = ntaps; p->nsplit = nsplit;
+    p->ci_tiles = (Ci32 + 63) / 64; p->co_tiles = (Cout + 63) / 64;
+    const int hs = ntaps == 9 ? g.halo : 0;
     const int stage = (WG_PK + (WG_PK + 2 * hs + 7) / 8 * 8) * 128;
-    const int lds = stage + 64;
-    if (lds > 160 * 1024) return FUMI_ENOTSUP;
-    const int groups = a.nsplit * a.B;
+    p->lds = stage + 64;
+    if (p->lds > 160 * 1024) return FUMI_ENOTSUP;
+    const int groups = nsplit * B;
     static const int xcd_env = getenv("FUMI_RN_XCD") ? atoi(getenv("FUMI_RN_XCD")) : 1;
-    const int xcd = xcd_env && groups >= 8 && groups % 8 == 0;
-    const dim3 grid((unsigned)((long)co_tiles * ci_tiles * groups));
+    p->xcd = xcd_env && groups >= 8 && groups % 8 == 0;
+    p->reduce = rn_wgrad_reduce_kind(ntaps, nsplit);
+    return FUMI_OK;
+}
+
+int launch_rn_wgrad(hipStream_t st, const RnWgradArgs& a) {
+    RnWgradPlan p;
+    const int rc = rn_wgrad_plan(a.B, a.npair, a.Cin, a.Cout, a.ntaps, a.nsplit, a.npix, a.g, &p);
+    if (rc) return rc;
+    const int reduce_last = g_rn_wgrad_last.reduce;
+    g_rn_wgrad_last = p; g_rn_wgrad_last.reduce = reduce_last;          // (the reduce launch records its own kernel)
+    const int Ci32 = (a.Cin + 31) / 32 * 32, ci_tiles = p.ci_tiles, co_tiles = p.co_tiles, lds = p.lds, xcd = p.xcd;
+    const dim3 grid((unsigned)((long)co_tiles * ci_tiles * a.nsplit * a.B));
     if (a.ntaps == 9) {
         FUMI_SET_DYN_LDS(rn_wgrad_kernel<9>, lds);
         hipLaunchKernelGGL(rn_wgrad_kernel<9>, grid, dim3(256), lds, st, a, ci_tiles, Ci32, xcd);
@@ -952,10 +1003,12 @@ int launch_rn_wgrad_reduce(hipStream_t st, int B, int nsplit, int ntaps, int Cou
                            float* G, long gstride) {
     const int Ci32 = (Cin + 31) / 32 * 32;
     const int cib = (Cin_real + 63) / 64, rows = ntaps * Cout;
-    if (ntaps == 9)
+    const int kind = rn_wgrad_reduce_kind(ntaps, nsplit);                 // (the function rn_wgrad_plan reports)
+    g_rn_wgrad_last.reduce = kind;
+    if (kind == RN_RED_TAPS9)
         hipLaunchKernelGGL(rn_wgrad_reduce9_kernel, dim3((unsigned)(Cout * cib), B), dim3(256), 0, st, nsplit, Cout, Ci32, Cin_real, part, G,
                            gstride);
-    else if (nsplit >= 16)
+    else if (kind == RN_RED_SPLIT4)
         hipLaunchKernelGGL(rn_wgrad_reduce_kernel<true>, dim3((unsigned)(rows * cib), B), dim3(256), 0, st, nsplit, ntaps, Cout, Ci32,
                            Cin_real, part, G, gstride);
     else
@@ -965,12 +1018,50 @@ int launch_rn_wgrad_reduce(hipStream_t st, int B, int nsplit, int ntaps, int Cou
     return FUMI_OK;
 }
 
+// sf / sb: the fragment order of the forward / the backward-data copy -- 1: 16x16x32, 0: 32x32x16, -1: what the layer's own channel
+// count selects (rn_use_s16).  A launch takes ONE form for all of its sources (16x16x32 only when every source allows it), so a copy
+// that is multiplied beside a source of another channel count must be laid out in the launch's form: the caller passes it.
 int launch_rn_wprep(hipStream_t st, int B, int Cout, int Cin, int Cin_real, int ntaps, const float* W, long wstride,
-                    rbf16* fwd, rbf16* bwd, long fstride) {
+                    rbf16* fwd, rbf16* bwd, long fstride, int sf, int sb) {
     if ((Cout & 31) || (Cin & 15) || (bwd && (Cin & 31))) return FUMI_EINVAL;
+    if (sf < 0) sf = rn_use_s16(Cin) ? 1 : 0;
+    if (sb < 0) sb = rn_use_s16(Cout) ? 1 : 0;
+    if ((sf && (Cin & 31)) || (bwd && sb && (Cout & 31))) return FUMI_EINVAL;
     const long nel = (long)ntaps * Cin * Cout;
     hipLaunchKernelGGL(rn_wprep_kernel, dim3((unsigned)((nel + 255) / 256), B), dim3(256), 0, st, Cout, Cin, Cin_real, ntaps, W, wstride,
-                       fwd, bwd, fstride, rn_use_s16(Cin) ? 1 : 0, rn_use_s16(Cout) ? 1 : 0);
+                       fwd, bwd, fstride, sf, sb);
     LAUNCH_CHECK();
+    return FUMI_OK;
+}
+
+// ---- the plan record and the host query (include/fumi_hip.h) -----------------------------------------------------------------------
+extern "C" int fumi_hip_rn12_conv_plan(int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    const RnConvPlan& c = g_rn_conv_last; const RnWgradPlan& w = g_rn_wgrad_last;
+    const int v[17] = {c.NF, c.MW, c.BKS, c.S16, c.tiles, c.tpi, c.ncg, c.xcd, c.glds, c.slab_rows, c.lds,
+                       w.NTAP, w.nsplit, w.ci_tiles, w.co_tiles, w.xcd, w.reduce};
+    for (int i = 0; i < n && i < 17; ++i) plan[i] = v[i];
+    return FUMI_OK;
+}
+extern "C" int fumi_hip_rn12_conv_query(int B, int M, int H, int W, int Cout, int nsrc, const int* Cin, int* plan, int n) {
+    if (!plan || n < 0 || !Cin || M < 1 || H < 1 || W < 1) return FUMI_EINVAL;
+    const RnGeom g = rn_geom(H, W);
+    RnConvPlan c;
+    const int rc = rn_conv_plan(B, Cout, (long)M * g.Pp, g, nsrc, Cin, nullptr, &c);
+    if (rc) return rc;
+    const int v[11] = {c.NF, c.MW, c.BKS, c.S16, c.tiles, c.tpi, c.ncg, c.xcd, c.glds, c.slab_rows, c.lds};
+    for (int i = 0; i < n && i < 11; ++i) plan[i] = v[i];
+    return FUMI_OK;
+}
+extern "C" int fumi_hip_rn12_wgrad_query(int B, int M, int H, int W, int Cin, int Cout, int ntaps, int npair, int nsplit, int* plan, int n) {
+    if (!plan || n < 0 || M < 1 || H < 1 || W < 1 || nsplit < 0 || nsplit > 512) return FUMI_EINVAL;
+    const RnGeom g = rn_geom(H, W);
+    const long npix = (long)M * g.Pp;
+    RnWgradPlan w;
+    if (B < 1 || Cin < 16 || Cout < 32) return FUMI_EINVAL;
+    const int rc = rn_wgrad_plan(B, npair, Cin, Cout, ntaps, nsplit ? nsplit : rn_wgrad_nsplit(B, npix, Cin, Cout), npix, g, &w);
+    if (rc) return rc;
+    const int v[6] = {w.NTAP, w.nsplit, w.ci_tiles, w.co_tiles, w.xcd, w.reduce};
+    for (int i = 0; i < n && i < 6; ++i) plan[i] = v[i];
     return FUMI_OK;
 }

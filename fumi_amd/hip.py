@@ -32,7 +32,8 @@ SYMBOLS = [
     "fumi_hip_conv4_encode", "fumi_hip_conv4_encode_bwd", "fumi_hip_am3_step_dx",
     "fumi_hip_resnet12_set_budget", "fumi_hip_fumi_resnet12_step", "fumi_hip_maml_resnet12_step", "fumi_hip_resnet12_features",
     "fumi_hip_resnet12_encode", "fumi_hip_resnet12_encode_bwd", "fumi_hip_resnet12_encode_plan",
-    "fumi_hip_rn12_conv", "fumi_hip_rn12_wgrad", "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
+    "fumi_hip_rn12_conv", "fumi_hip_rn12_wgrad", "fumi_hip_rn12_conv_multi", "fumi_hip_rn12_wgrad_multi",
+    "fumi_hip_rn12_conv_plan", "fumi_hip_rn12_conv_query", "fumi_hip_rn12_wgrad_query", "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
     "fumi_hip_conv3x3_fwd", "fumi_hip_conv3x3_bwd_data", "fumi_hip_conv3x3_bwd_weight",
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
     "fumi_hip_want_text_grad",
@@ -199,6 +200,13 @@ def lib():
         L.fumi_hip_am3_step_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_rn12_conv.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4
         L.fumi_hip_rn12_wgrad.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3
+        LL = ctypes.c_longlong
+        L.fumi_hip_rn12_conv_multi.argtypes = ([c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_int), POINTER(c_int), POINTER(c_void_p),
+                                               POINTER(LL), POINTER(c_void_p), POINTER(LL), c_int, c_void_p, LL, c_void_p, LL, c_void_p])
+        L.fumi_hip_rn12_wgrad_multi.argtypes = [c_void_p, c_void_p] + [c_int] * 10 + [c_void_p] * 4 + [LL, LL, c_void_p, LL]
+        L.fumi_hip_rn12_conv_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_rn12_conv_query.argtypes = [c_int] * 6 + [POINTER(c_int), POINTER(c_int), c_int]
+        L.fumi_hip_rn12_wgrad_query.argtypes = [c_int] * 9 + [POINTER(c_int), c_int]
         L.fumi_hip_resnet12_set_option.argtypes = [c_int, c_int]
         L.fumi_hip_rn12_probe.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, POINTER(c_size_t),
                                           POINTER(c_int)]
@@ -1369,6 +1377,61 @@ def rn12_wgrad(ws, x, dy, H, W, k):
     _check(lib().fumi_hip_rn12_wgrad(ws.handle, _stream(dev), B, M, H, W, Cin, Cout, k * k, _bf16ptr(x, "x"), _bf16ptr(dy, "dy"),
                                      _f32(dW, "dW")), "fumi_hip_rn12_wgrad")
     return dW
+
+
+RN12_CONV_KEYS = ("nf", "mw", "bks", "s16", "tiles", "tpi", "ncg", "xcd", "glds", "slab_rows", "lds")
+RN12_WGRAD_KEYS = ("ntap", "nsplit", "ci_tiles", "co_tiles", "xcd", "reduce")
+RN12_REDUCE_KERNELS = {1: "rn_wgrad_reduce_kernel<false>", 2: "rn_wgrad_reduce_kernel<true>", 3: "rn_wgrad_reduce9_kernel"}
+
+
+def rn12_conv_multi(ws, B, M, H, W, Cout, srcs, y, y_stride, transpose=False, dot=None, dot_stride=0, stats=None):
+    """fumi_hip_rn12_conv_multi on raw buffers.  srcs: 1..4 of (x, x_stride, Cin, Wt, w_stride, ntaps) with x a flat bf16 tensor that
+    starts at episode 0 and Wt fp32 (w_stride 0: shared); y a flat bf16 tensor (NOT cleared), stats [B, 2, Cout] fp32 or None."""
+    n = len(srcs)
+    dev = _dev(y)
+    LL = ctypes.c_longlong
+    cin = (c_int * max(n, 1))(*[int(s[2]) for s in srcs])
+    taps = (c_int * max(n, 1))(*[int(s[5]) for s in srcs])
+    xs = (c_void_p * max(n, 1))(*[_bf16ptr(s[0], "x").value for s in srcs])
+    xst = (LL * max(n, 1))(*[int(s[1]) for s in srcs])
+    wp = (c_void_p * max(n, 1))(*[_f32(s[3], "Wt").value for s in srcs])
+    wst = (LL * max(n, 1))(*[int(s[4]) for s in srcs])
+    _check(lib().fumi_hip_rn12_conv_multi(ws.handle, _stream(dev), B, M, H, W, Cout, n, cin, taps, xs, xst, wp, wst, int(bool(transpose)),
+                                          _bf16ptr(dot, "dot") if dot is not None else None, int(dot_stride), _bf16ptr(y, "y"),
+                                          int(y_stride), _f32(stats, "stats") if stats is not None else None),
+           "fumi_hip_rn12_conv_multi")
+
+
+def rn12_wgrad_multi(ws, B, M, H, W, Cin, Cin_real, Cout, ntaps, pairs, x_stride, dy_stride, dW, dw_stride, nsplit=0):
+    """fumi_hip_rn12_wgrad_multi on raw buffers.  pairs: 1..2 of (x, dy) flat bf16 tensors that start at episode 0; dW flat fp32."""
+    dev = _dev(dW)
+    p = [(_bf16ptr(x, "x"), _bf16ptr(dy, "dy")) for x, dy in pairs[:2]] + [(None, None)] * (2 - min(len(pairs), 2))
+    _check(lib().fumi_hip_rn12_wgrad_multi(ws.handle, _stream(dev), B, M, H, W, Cin, Cin_real, Cout, ntaps, len(pairs), int(nsplit),
+                                           p[0][0], p[0][1], p[1][0], p[1][1], int(x_stride), int(dy_stride), _f32(dW, "dW"),
+                                           int(dw_stride)), "fumi_hip_rn12_wgrad_multi")
+
+
+def rn12_conv_plan():
+    """(conv, wgrad): what the last convolution launch and the last weight-gradient launch of this process decided
+    (fumi_hip_rn12_conv_plan; keys RN12_CONV_KEYS / RN12_WGRAD_KEYS)."""
+    v = (c_int * 17)()
+    _check(lib().fumi_hip_rn12_conv_plan(v, 17), "fumi_hip_rn12_conv_plan")
+    return dict(zip(RN12_CONV_KEYS, v[:11])), dict(zip(RN12_WGRAD_KEYS, v[11:]))
+
+
+def rn12_conv_query(B, M, H, W, Cout, Cins):
+    """The decisions launch_rn_conv takes for a shape (under this process's knobs): host arithmetic only, no GPU."""
+    v = (c_int * 11)()
+    cin = (c_int * max(len(Cins), 1))(*[int(c) for c in Cins])
+    _check(lib().fumi_hip_rn12_conv_query(B, M, H, W, Cout, len(Cins), cin, v, 11), "fumi_hip_rn12_conv_query")
+    return dict(zip(RN12_CONV_KEYS, v[:]))
+
+
+def rn12_wgrad_query(B, M, H, W, Cin, Cout, ntaps, npair=1, nsplit=0):
+    """The decisions launch_rn_wgrad and launch_rn_wgrad_reduce take for a shape: host arithmetic only, no GPU."""
+    v = (c_int * 6)()
+    _check(lib().fumi_hip_rn12_wgrad_query(B, M, H, W, Cin, Cout, ntaps, npair, nsplit, v, 6), "fumi_hip_rn12_wgrad_query")
+    return dict(zip(RN12_WGRAD_KEYS, v[:]))
 
 
 def resnet12_set_option(key, value):

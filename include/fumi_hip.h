@@ -413,6 +413,28 @@ int fumi_hip_rn12_conv(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H,
         const void* x, const float* Wt, void* y, float* stats);
 int fumi_hip_rn12_wgrad(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cin, int Cout, int ntaps,
         const void* x, const void* dy, float* dW);
+/* The general forms (every launch the engine issues; tests/rn12_conv_forms.py).  conv_multi: y = sum over nsrc (1..4) sources of
+ * conv_{ntaps[s]}(x[s], Wt[s]); source s has Cin[s] channels and x_stride[s] elements between episodes (>= the map: the gap is never
+ * read); Wt[s] fp32 OIHW [Cout][Cin[s]][k][k], with transpose != 0 the forward layer's [Cin[s]][Cout][k][k]; w_stride[s] = 0 shares
+ * one weight set over the episodes.  dot (optional): the second statistic is sum(y * dot).  y is NOT cleared (interior pixels are
+ * written).  wgrad_multi: npair = 1 | 2 (x, dy) pairs are added; the maps have Cin >= Cin_real channels, dW is
+ * [B][Cout][Cin_real][k][k] with dw_stride elements between episodes; nsplit = 0: the launcher's own split of the pixel axis.
+ * FUMI_EINVAL (nothing launched): Cout % 32, Cin % 16, nsrc outside 1..4, ntaps not 1 | 9, npair outside 1..2, a stride shorter
+ * than its map. */
+int fumi_hip_rn12_conv_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cout, int nsrc, const int* Cin,
+        const int* ntaps, const void* const* x, const long long* x_stride, const float* const* Wt, const long long* w_stride,
+        int transpose, const void* dot, long long dot_stride, void* y, long long y_stride, float* stats);
+int fumi_hip_rn12_wgrad_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int Cin, int Cin_real, int Cout, int ntaps,
+        int npair, int nsplit, const void* x0, const void* dy0, const void* x1, const void* dy1, long long x_stride, long long dy_stride,
+        float* dW, long long dw_stride);
+/* What the last convolution launch and the last weight-gradient launch (+ reduce) of this process decided -- a host-side record
+ * written beside the launches, never read by one: plan[0..10] = NF, MW, BKS, S16, tiles per episode, tiles per image (0: flat tiles),
+ * column groups, XCD-grouped ids, LDS-direct slab loads, slab rows, LDS bytes; plan[11..16] = NTAP, nsplit, ci tiles, co tiles,
+ * XCD-grouped ids, reduce kernel (1 rows, 2 four-way split, 3 nine-tap).  The two queries return the same decisions for a shape
+ * without any HIP call (conv: plan[0..10]; wgrad: plan[0..5] = entries 11..16; nsplit = 0: the launcher's own split). */
+int fumi_hip_rn12_conv_plan(int* plan, int n);
+int fumi_hip_rn12_conv_query(int B, int M, int H, int W, int Cout, int nsrc, const int* Cin, int* plan, int n);
+int fumi_hip_rn12_wgrad_query(int B, int M, int H, int W, int Cin, int Cout, int ntaps, int npair, int nsplit, int* plan, int n);
 /* The three 3x3 / pad 1 / stride 1 convolution products on 64 -> 64 channels (the set is closed under differentiation: the
  * second-order sweep uses nothing else).  Dense channels-last tensors x, y, dy [M,H,W,64]; weights W, dW [64,64,3,3] (OIHW). */
 int fumi_hip_conv3x3_fwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int H, int W, const float* x, const float* Wt, float* y);

@@ -94,12 +94,11 @@ def test_conv_products_match_torch(B, Mi, H, W, Cin, Cout, k, dev, ws):
     assert rel(yi, ref) <= BF
     s_ref = torch.stack([yi.sum((1, 3, 4)), (yi * yi).sum((1, 3, 4))], 1)          # statistics of the STORED values
     assert rel(st.cpu(), s_ref) <= 1e-5
-    if Cin % 32:
-        return
     dy = bf(torch.randn(B, Mi, Cout, H, W, generator=g))
-    ref = torch.stack([F.conv2d(dy[b], bf(Wt[b]).flip(2, 3).transpose(0, 1), None, padding=k // 2) for b in range(B)])
-    dx = hip.rn12_conv(ws, to_cl(dy).to(dev), Wt.to(dev), H, W, transpose=True)
-    assert rel(from_cl(dx.cpu(), Mi, H, W)[..., 1:-1, 1:-1], ref) <= BF
+    if Cin % 32 == 0:                # (the input-gradient product alone: launch_rn_wprep refuses a backward copy at Cin % 32 != 0)
+        ref = torch.stack([F.conv2d(dy[b], bf(Wt[b]).flip(2, 3).transpose(0, 1), None, padding=k // 2) for b in range(B)])
+        dx = hip.rn12_conv(ws, to_cl(dy).to(dev), Wt.to(dev), H, W, transpose=True)
+        assert rel(from_cl(dx.cpu(), Mi, H, W)[..., 1:-1, 1:-1], ref) <= BF
     dW = hip.rn12_wgrad(ws, to_cl(x).to(dev), to_cl(dy).to(dev), H, W, k)
     ref = torch.stack([M.conv_bwd_weight(x[b].double(), dy[b].double(), k) for b in range(B)]).float()
     assert rel(dW.cpu(), ref) <= 1e-5
