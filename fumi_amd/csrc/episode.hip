@@ -766,8 +766,8 @@ __global__ __launch_bounds__(512) void query_lds_kernel(StageTab stg, StageTab s
     // (FIX: the staging is written out below, the tables are not read)
     wg_stage_tab_to_lds(s_stg2, FIX ? 0 : 2, (int)(2 * sizeof(StageTab) + sizeof(EpiDims) + sizeof(EpiBuf) + sizeof(QLay) + 64));
     // FIX: every staging load -- the support set's images and the tile's own A0 / G rows -- is issued HERE, as fixed-address
-    // loads, and travels under the arena clear.  Sources: the plan's base pointers (run_episodes adds them in this order);
-    // W_1, b_1, b_0 are 16-byte aligned (checked there).  Loads read clamped in-range addresses, the LDS writes are masked.
+    // loads, and travels under the arena clear.  Sources: the plan's base pointers (stage_fused_query adds them in this order);
+    // W_1, b_1, b_0 are 16-byte aligned (plan_query checks). Loads read clamped in-range addresses, the LDS writes are masked.
     f32x4 fq[4], fva[4], fvw[8], fvb0, fvb1;
     float fvg[2], fvh, fvbh;
     if constexpr (FIX) {
@@ -1712,9 +1712,6 @@ __global__ void split_head_grad_kernel(int B, int N, int H, const float* head_ba
     if (c < H) gW[n * H + c] = scale * s; else gb[n] = scale * s;
 }
 
-// a kernel as a type: each instance of a launch lambda taking it keeps its own FUMI_SET_DYN_LDS state
-template <auto K> struct KernTag { static constexpr auto fn = K; };
-
 inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
 
 struct Carver {      // computes the layout twice: once to size the workspace, once to hand out pointers
@@ -1738,18 +1735,16 @@ void carve(Carver& c, const EpisodeProblem& p, EpiBuf& w) {
         auto r16 = [](int x) { return (x + 15) & ~15; };
         auto need = [&](int M, int N_, int K) { return (long)(r16(M) + 4 + r16(N_) + 4) * (r16(K) + 4); };
         const int S_ = p.S, N_ = p.N, H_ = p.h[p.L - 1], h0_ = p.h[0], R_ = QR;
-        long a = need(S_, h0_, S_), q = need(R_, h0_, S_), r = need(S_, h0_, S_);
-        a = std::max({a, need(S_, N_, H_), need(S_, H_, N_), need(N_, H_, S_)});
+        long s = need(S_, h0_, S_), q = need(R_, h0_, S_);      // s: adapt and reverse run the same products on the support rows
+        s = std::max({s, need(S_, N_, H_), need(S_, H_, N_), need(N_, H_, S_)});
         q = std::max({q, need(R_, N_, H_), need(N_, H_, R_), need(R_, H_, N_), need(S_, h0_, R_)});
-        r = std::max({r, need(S_, N_, H_), need(S_, H_, N_), need(N_, H_, S_)});
         for (int i = 1; i < p.L; ++i) {
             const int hi = p.h[i], hp = p.h[i - 1];
-            a = std::max({a, need(S_, hi, hp), need(S_, hp, hi), need(hi, hp, S_)});
+            s = std::max({s, need(S_, hi, hp), need(S_, hp, hi), need(hi, hp, S_)});
             q = std::max({q, need(R_, hi, hp), need(R_, hp, hi), need(hi, hp, R_)});
-            r = std::max({r, need(S_, hi, hp), need(S_, hp, hi), need(hi, hp, S_)});
         }
         const long cap = 38000;               // 152 KB of the CU's 160 KB
-        w.lds_adapt = (int)std::min(a, cap); w.lds_query = (int)std::min(q, cap); w.lds_reverse = (int)std::min(r, cap);
+        w.lds_adapt = w.lds_reverse = (int)std::min(s, cap); w.lds_query = (int)std::min(q, cap);
     }
     const size_t nt = w.ntile;
     w.A0 = c.take(B * (S + Qn) * h0); w.G = c.take(B * (S + Qn) * S);
@@ -1784,6 +1779,258 @@ void carve(Carver& c, const EpisodeProblem& p, EpiBuf& w) {
     }
 }
 
+// slabs of the backward X-panel pass that the workspace holds: the larger of its one-launch and two-launch splits (the
+// two-launch form has more, shorter slabs)
+size_t bwd_slab_count(const EpisodeProblem& p) {
+    int kc, nsq = 0, kcq, nss = 0, kcs;
+    const int ns = xpanel_bwd_nsplit(p.B, p.S, p.Qn, p.D, p.h[0], &kc);
+    if (xpanel_bwd_two_part_ok(p.D, p.h[0])) xpanel_bwd_two_part_split(p.B, p.S, p.Qn, p.D, p.h[0], &nsq, &kcq, &nss, &kcs);
+    return (size_t)std::max(ns, nsq + nss);
+}
+
+// ---- The plan of one run_episodes call: which kernel form each phase takes, with the layout and the
+// staging tables of that form.  plan_episodes decides, on the host and without a HIP call; launch_* only launch.
+// dev/test knobs, read once per process (GLOBAL: take the generic kernels)
+struct EpiKnobs { int overlap, fuse, fixed, adapt_p; bool global; };
+const EpiKnobs& epi_knobs() {
+    const auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 1; };
+    static const EpiKnobs k = {num("FUMI_EPI_OVERLAP"), num("FUMI_EPI_FUSE"), num("FUMI_EPI_FIXED"), num("FUMI_ADAPT_P"),
+                               getenv("FUMI_EPI_GLOBAL") != nullptr};
+    return k;
+}
+
+enum class AdaptForm { none, lds, global };                  // none: the inner step runs inside the fused query kernel
+enum class QueryForm { fused_fixed, fused, lds, global };
+enum class ReverseForm { lds_fixed, lds, global };
+struct EpiPlan {
+    AdaptForm adapt; int AP; ALay al; StageTab stg_adapt;
+    QueryForm query; QLay ql; StageTab stg, stg_sup;         // (stg_sup: the fused forms' table; the other of the two is empty)
+    ReverseForm reverse; int P; RLay rl; StageTab stg_init, stg_step;
+    bool two_part; int nsq, kcq, nss, kcs;                   // backward X-panel pass in two launches, and its two splits
+    bool drop;
+    int fixed_last;                                          // what fumi_hip_epi_fixed_last() reports
+};
+
+inline bool a16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+inline bool stage_ok(const StageTab& tb) { return !tb.bad && tb.nunits <= 64 * 8; }     // wg_stage_rows: one unit per lane and wave
+
+// ---- staging tables (source = base + episode*sb + tile*st), one builder per kernel form; false: the table does not fit, take
+// the next form.  The order of the add calls fixes ubase / nunits, which the kernels index.
+bool stage_fused_query(StageTab& tb, const EpisodeProblem& p, const EpiBuf& w, const QLay& y) {
+    const long R = p.S + p.Qn, S = p.S, N = p.N, H = p.h[1];
+    const int h0 = p.h[0], h1 = p.h[1];
+    tb.init();
+    tb.add(w.A0, R * h0, 0, 0, h0, p.S, p.S, h0, y.a[0], wg_ld(h0));                       // support rows of A0
+    tb.add(p.W[1], 0, 0, 0, h0, h1, h1, h0, y.W[1], wg_ld(h0));                            // meta-parameters of layer 1
+    tb.add(p.b[1], 0, 0, 0, h1, 1, 1, h1, y.bi[1], h1);
+    tb.add(p.head, N * (H + 1), 0, 0, H + 1, p.N, p.N, (int)H, y.Wh, wg_ld((int)H));      // the episode's head [Wh | bh]
+    tb.add(p.head + H, N * (H + 1), 0, 0, H + 1, p.N, p.N, 1, y.bh, 1);
+    tb.add(p.b[0], 0, 0, 0, h0, 1, 1, h0, y.b0, h0);
+    tb.add(w.G + S * S, R * S, (long)QR * S, 0, S, -1, QR, p.S, y.Gq, wg_ld(p.S));        // the tile's rows of G (its A0 rows: direct loads)
+    return stage_ok(tb);
+}
+
+bool stage_adapt(StageTab& tb, const EpisodeProblem& p, const EpiBuf& w, const ALay& y, int hpart) {
+    const long R = p.S + p.Qn, S = p.S, N = p.N;
+    const int H = p.h[p.L - 1];
+    tb.init();
+    tb.add(w.G, R * S, 0, 0, S, p.S, p.S, p.S, y.G, wg_ld(p.S));
+    for (int i = 1; i < p.L; ++i) {
+        // layer 1: this part's columns of every row (part stride hpart); deeper layers whole
+        const int kc = i == 1 ? hpart : p.h[i - 1];
+        tb.add(p.W[i], 0, 0, i == 1 ? hpart : 0, p.h[i - 1], p.h[i], p.h[i], kc, y.W[i], wg_ld(kc));
+        tb.add(p.b[i], 0, 0, 0, p.h[i], 1, 1, p.h[i], y.bi[i], p.h[i]);
+    }
+    tb.add(p.head, N * (H + 1), 0, 0, H + 1, p.N, p.N, H, y.Wh, wg_ld(H));
+    tb.add(p.head + H, N * (H + 1), 0, 0, H + 1, p.N, p.N, 1, y.bh, 1);
+    return stage_ok(tb);
+}
+
+bool stage_query(StageTab& tb, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const QLay& y) {
+    const long R = p.S + p.Qn, S = p.S, N = p.N, H = d.H;
+    const long slot = d.taped ? p.T : 0;
+    const int h0 = p.h[0];
+    tb.init();
+    tb.add(w.A0 + S * h0, R * h0, (long)QR * h0, 0, h0, -1, QR, h0, y.a[0], wg_ld(h0));
+    tb.add(w.D, S * h0, 0, 0, h0, p.S, p.S, h0, y.D, wg_ld(h0));
+    for (int i = 1; i < p.L; ++i) {
+        const long sz = (long)p.h[i] * p.h[i - 1];
+        tb.add(w.Wslot[i] + slot * sz, w.nslot * sz, 0, 0, p.h[i - 1], p.h[i], p.h[i], p.h[i - 1], y.W[i], wg_ld(p.h[i - 1]));
+    }
+    tb.add(w.G + S * S, R * S, (long)QR * S, 0, S, -1, QR, p.S, y.Gq, wg_ld(p.S));
+    tb.add(w.Whslot + slot * N * H, w.nslot * N * H, 0, 0, H, p.N, p.N, (int)H, y.Wh, wg_ld((int)H));
+    tb.add(p.b[0], 0, 0, 0, h0, 1, 1, h0, y.b0, h0);
+    tb.add(w.cs, h0, 0, 0, h0, 1, 1, h0, y.cs, h0);
+    for (int i = 1; i < p.L; ++i) tb.add(w.bcur[i], p.h[i], 0, 0, p.h[i], 1, 1, p.h[i], y.bi[i], p.h[i]);
+    tb.add(w.bh, N, 0, 0, N, 1, 1, p.N, y.bh, p.N);
+    return stage_ok(tb);
+}
+
+// adjoints after the query pass: sums over the tiles' partial slabs (+ G_ss)
+bool stage_reverse_init(StageTab& ti, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const RLay& y, int P) {
+    const long S = p.S, N = p.N, H = d.H, R = p.S + p.Qn, nt = w.ntile, h0 = p.h[0], h0c = h0 / P, h1 = p.h[1];
+    ti.init();
+    ti.add(w.pW[1], nt * h1 * h0, 0, h0c, h0, (int)h1, (int)h1, (int)h0c, y.Wb[1], wg_ld((int)h0c), (int)nt, h1 * h0);
+    ti.add(w.pD, nt * S * h0, 0, h0c, h0, p.S, p.S, (int)h0c, y.Db, wg_ld((int)h0c), (int)nt, S * h0);
+    ti.add(w.pb0, nt * h0, 0, h0c, h0, 1, 1, (int)h0c, y.b0b, (int)h0c, (int)nt, h0);
+    ti.add(w.pWh, nt * N * H, 0, 0, H, p.N, p.N, (int)H, y.Whb, wg_ld((int)H), (int)nt, N * H);
+    ti.add(w.pbh, nt * N, 0, 0, N, 1, 1, p.N, y.bhb, p.N, (int)nt, N);
+    for (int i = 1; i < p.L; ++i) {
+        const long hi = p.h[i], hp = p.h[i - 1];
+        ti.add(w.pb[i], nt * hi, 0, 0, hi, 1, 1, (int)hi, y.bb[i], (int)hi, (int)nt, hi);
+        if (i >= 2) ti.add(w.pW[i], nt * hi * hp, 0, 0, hp, (int)hi, (int)hi, (int)hp, y.Wb[i], wg_ld((int)hp), (int)nt, hi * hp);
+    }
+    ti.add(w.G, R * S, 0, 0, S, p.S, p.S, p.S, y.G, wg_ld(p.S));
+    return stage_ok(ti);
+}
+
+// the tape of step t (t rides in the "tile" slot of the table)
+bool stage_reverse_step(StageTab& ts, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const RLay& y, int P) {
+    const long S = p.S, N = p.N, H = d.H, h0 = p.h[0], h0c = h0 / P, h1 = p.h[1];
+    ts.init();
+    ts.add(w.ta[0], w.ntape * S * h0, S * h0, h0c, h0, p.S, p.S, (int)h0c, y.a[0], wg_ld((int)h0c));
+    ts.add(w.Wslot[1], w.nslot * h1 * h0, h1 * h0, h0c, h0, (int)h1, (int)h1, (int)h0c, y.W[1], wg_ld((int)h0c));
+    for (int i = 1; i < p.L; ++i) {
+        const long hi = p.h[i], hp = p.h[i - 1];
+        ts.add(w.ta[i], w.ntape * S * hi, S * hi, 0, hi, p.S, p.S, (int)hi, y.a[i], wg_ld((int)hi));
+        ts.add(w.tdz[i], w.ntape * S * hi, S * hi, 0, hi, p.S, p.S, (int)hi, y.dz[i], wg_ld((int)hi));
+        if (i >= 2) ts.add(w.Wslot[i], w.nslot * hi * hp, hi * hp, 0, hp, (int)hi, (int)hi, (int)hp, y.W[i], wg_ld((int)hp));
+    }
+    ts.add(w.Whslot, w.nslot * N * H, N * H, 0, H, p.N, p.N, (int)H, y.Wh, wg_ld((int)H));
+    ts.add(w.tp, w.ntape * S * N, S * N, 0, N, p.S, p.S, p.N, y.p, wg_ld(p.N));
+    ts.add(w.te, w.ntape * S * N, S * N, 0, N, p.S, p.S, p.N, y.e, wg_ld(p.N));
+    return stage_ok(ts);
+}
+
+// Decides every phase's form, each in its fall-back order: a form that fails its size cap or its table check (stage_*: false)
+// falls to the next.  Runs after carve: the fixed-shape reverse form depends on the alignment of carved arrays.
+void plan_episodes(EpiPlan& pl, const fumi_ws* ws, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w) {
+    const EpiKnobs& k = epi_knobs();
+    const int h0 = p.h[0];
+    pl.drop = d.drop_thr != 0;
+    // The backward X-panel pass in two launches (T >= 2): its query-row part beside the reverse sweep on the workspace's second
+    // stream (the sweep is a chain of T x ~30 us on P workgroups per episode -- 128 of the 256 CUs at the reference sizes --, the pass
+    // fills the others and is done before the sweep), its support-row part behind the sweep.  The adjoint array is then laid out
+    // split ([B,S,h0] | [B,Qn,h0]) so that each part reads one contiguous panel.  FUMI_EPI_OVERLAP=0: one launch behind the sweep (2: the two-launch form at any size, for tests).
+    // (measured: FuMI BERT T = 5, 32 episodes 0.436 -> 0.420 ms per step; a 4-episode MAML step, whose pass is 23 us, LOSES 18 us to
+    // the fork / join and the extra launch -- only meta-batches whose pass is long enough to be worth hiding: >= 2048 query rows.
+    // At T = 1 the sweep is one 42 us launch on half of the CUs and the query-row part takes the other half for about as long: the
+    // headline step 0.2200 -> 0.2153 ms without phase timing; not adopted -- the pass is the bench's roofline kernel, timed as ONE
+    // launch on the caller's stream, and +2 % does not pay for a second population of that kernel in every profile)
+    pl.two_part = k.overlap && p.need_grad && p.T >= 2 && ws->side && ws->evx[0] && ws->evx[1] && !ws->profiling && !p.after_reverse &&
+                  xpanel_bwd_two_part_ok(p.D, h0) && p.second_order && ((long)p.B * p.Qn >= 2048 || k.overlap == 2);      // (2: tests)
+    if (pl.two_part) xpanel_bwd_two_part_split(p.B, p.S, p.Qn, p.D, h0, &pl.nsq, &pl.kcq, &pl.nss, &pl.kcs);
+    // the reference shape of a training step: the query and reverse kernels compiled for it (REF_*; FUMI_EPI_FIXED=0: the
+    // run-time-shaped instances).  The layout is the one of S = REF_SP, N = REF_NP: every smaller S, N fits it (zero padding).
+    const bool fixed = k.fixed && !k.global && p.T == 1 && p.L == 2 && h0 == REF_H0 && p.h[1] == REF_H1 &&
+                       p.S <= REF_SP && p.N <= REF_NP && p.need_grad && p.second_order;
+
+    // ---- query: fused_fixed -> fused -> lds -> global.  Fused: one inner step on a two-layer network with at most 32 support
+    // rows -- every query tile runs the inner step itself (query_lds_kernel<true>), no adapt launch
+    bool fuse = k.fuse && !k.global && p.T == 1 && p.L == 2 && p.S <= QR && (h0 & 3) == 0 && p.head != nullptr;
+    bool fix_q = fixed && fuse && p.S <= REF_SQ;
+    if (fuse) {
+        if (fix_q) pl.ql = ref_qlay();             // (stays when only the alignment test fails: the run-time-shaped kernel runs on it)
+        else query_layout(pl.ql, p.L, p.h, p.S, p.N, true);
+        pl.stg.init();
+        fuse = pl.ql.total <= QLDS_CAP && stage_fused_query(pl.stg_sup, p, w, pl.ql) && h0 <= 256;
+        // (the fixed-shape kernel reads these jobs' base pointers itself: W_1, b_1, b_0 as float4)
+        fix_q = fix_q && a16(p.W[1]) && a16(p.b[1]) && a16(p.b[0]);
+    }
+    pl.adapt = AdaptForm::none; pl.AP = 1;
+    if (fuse) pl.query = fix_q ? QueryForm::fused_fixed : QueryForm::fused;
+    else {
+        query_layout(pl.ql, p.L, p.h, p.S, p.N);
+        pl.stg_sup.init();
+        const bool qlds = pl.ql.total <= QLDS_CAP && 7 + 2 * (p.L - 1) <= WG_MAXJOB && !k.global && stage_query(pl.stg, p, d, w, pl.ql);
+        pl.query = qlds ? QueryForm::lds : QueryForm::global;
+        // ---- adapt, when the query form is not fused: lds -> global
+        // column parts per episode (adapt_lds_kernel): the layer-0 columns can be split over AP workgroups that exchange the
+        // layer-1 partial sums once per inner step.  OFF by default: measured at the reference sizes (h0 = 256, AP = 4) the
+        // exchange costs what the smaller products save (phase trace: layer 1 + exchange 3.2 -> 6.0 us, the two backward
+        // products 10.3 -> 7.6 us; 0.3118 vs 0.3121 ms per step at T = 1, 0.515 vs 0.506 at T = 5): the inner loop is bound
+        // by per-phase latency, not by the CU's matrix rate.  FUMI_ADAPT_P=n enables it (wider first layers).
+        if (k.adapt_p > 1 && p.L >= 2 && w.acnt && p.B <= FUMI_ACNT) {
+            pl.AP = k.adapt_p > 8 ? 8 : k.adapt_p;
+            while (pl.AP > 1 && (h0 % (64 * pl.AP) != 0)) pl.AP >>= 1;         // every part: a multiple of 64 columns
+        }
+        int hs[MAXL];
+        for (int i = 0; i < MAXL; ++i) hs[i] = i < p.L ? p.h[i] : 0;
+        hs[0] = h0 / pl.AP;
+        adapt_layout(pl.al, p.L, hs, p.S, p.N);
+        const bool alds = pl.al.total <= ALDS_CAP && 4 + 2 * (p.L - 1) <= WG_MAXJOB && !k.global &&
+                          ((p.S + 15) / 16) * ((hs[0] + 63) / 64) <= 8 &&     // one layer-0 block per wave (A0s + b0 in registers)
+                          stage_adapt(pl.stg_adapt, p, w, pl.al, hs[0]);
+        pl.adapt = alds ? AdaptForm::lds : AdaptForm::global;
+    }
+
+    // ---- reverse: lds_fixed -> lds -> global.  P: the fewest column parts per episode whose layout fits
+    const bool split_ok = p.L >= 2 && p.L <= 4 && w.ntile <= 8 && !k.global;
+    pl.P = 0;
+    for (int cand = 1; split_ok && cand <= 8 && !pl.P && h0 % (4 * cand) == 0; cand *= 2) {
+        reverse_layout(pl.rl, p.L, p.h, p.S, p.N, cand);
+        if (pl.rl.total <= RLDS_CAP) pl.P = cand;
+    }
+    // the fixed-shape sweep where the run-time one splits the same way (the sum over the parts depends on P)
+    // (its staging is 16-byte loads at fixed offsets from these arrays)
+    const bool fix_r = fixed && pl.P == REF_P && a16(w.pW[1]) && a16(w.pD) && a16(w.pb0) && a16(w.pWh) && a16(w.pb[1]) &&
+                       a16(w.ta[0]) && a16(w.ta[1]) && a16(w.tdz[1]) && a16(w.Wslot[1]) && a16(w.Whslot);
+    if (fix_r) pl.rl = ref_rlay();
+    const bool rlds = pl.P > 0 && stage_reverse_init(pl.stg_init, p, d, w, pl.rl, pl.P) && stage_reverse_step(pl.stg_step, p, d, w, pl.rl, pl.P);
+    pl.reverse = !rlds ? ReverseForm::global : fix_r ? ReverseForm::lds_fixed : ReverseForm::lds;
+    pl.fixed_last = (pl.query == QueryForm::fused_fixed ? 1 : 0) | (pl.reverse == ReverseForm::lds_fixed ? 2 : 0);
+}
+
+// ---- the launches.  A template over the kernel: FUMI_SET_DYN_LDS keeps its "already set" state per expansion site, so every
+// kernel needs an instance of its own
+template <auto K, class... A>
+int launch_k(hipStream_t st, dim3 grid, int lds_floats, const A&... a) {
+    FUMI_SET_DYN_LDS(K, lds_floats * 4);
+    hipLaunchKernelGGL(K, grid, dim3(512), lds_floats * 4, st, a...);
+    LAUNCH_CHECK();
+    return FUMI_OK;
+}
+
+int launch_adapt(hipStream_t st, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const EpiPlan& pl) {
+    EpiParams prm;
+    for (int i = 0; i < MAXL; ++i) { prm.W[i] = i < p.L ? p.W[i] : nullptr; prm.b[i] = i < p.L ? p.b[i] : nullptr; }
+    if (pl.adapt == AdaptForm::global) return launch_k<adapt_kernel>(st, dim3(p.B), w.lds_adapt, d, w, prm, p.y_s, p.head, w.status);
+    const unsigned grid = pl.AP > 1 ? 8u * ((p.B + 7) / 8) * pl.AP : (unsigned)p.B;
+    return launch_k<adapt_lds_kernel>(st, dim3(grid), pl.al.total, pl.stg_adapt, d, w, pl.al, prm, p.y_s, w.status, pl.AP);
+}
+
+template <auto K>
+int launch_query_lds(hipStream_t st, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const EpiPlan& pl) {
+    return launch_k<K>(st, dim3(w.ntile, p.B), pl.ql.total, pl.stg, pl.stg_sup, d, w, pl.ql, p.y_q, p.logits_q, p.preds_q, p.preds_f,
+                       w.status, p.y_s);
+}
+int launch_query(hipStream_t st, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const EpiPlan& pl) {
+    switch (pl.query) {
+    case QueryForm::fused_fixed:
+        return pl.drop ? launch_query_lds<query_lds_kernel<true, true, true>>(st, p, d, w, pl)
+                       : launch_query_lds<query_lds_kernel<true, true, false>>(st, p, d, w, pl);
+    case QueryForm::fused: return launch_query_lds<query_lds_kernel<true>>(st, p, d, w, pl);
+    case QueryForm::lds: return launch_query_lds<query_lds_kernel<false>>(st, p, d, w, pl);
+    case QueryForm::global: break;
+    }
+    return launch_k<query_kernel>(st, dim3(w.ntile, p.B), w.lds_query, d, w, p.b[0], p.y_q, p.logits_q, p.preds_q, p.preds_f, w.status);
+}
+
+template <auto K>
+int launch_reverse_lds(hipStream_t st, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const EpiPlan& pl) {
+    return launch_k<K>(st, dim3(8 * ((p.B + 7) / 8) * pl.P), pl.rl.total, pl.stg_init, pl.stg_step, d, w, pl.rl, pl.P, p.loss_b,
+                       p.acc_b, p.head_bar);
+}
+int launch_reverse(hipStream_t st, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w, const EpiPlan& pl) {
+    switch (pl.reverse) {
+    case ReverseForm::lds_fixed:
+        return pl.drop ? launch_reverse_lds<reverse_lds_kernel<true, true>>(st, p, d, w, pl)
+                       : launch_reverse_lds<reverse_lds_kernel<true, false>>(st, p, d, w, pl);
+    case ReverseForm::lds: return launch_reverse_lds<reverse_lds_kernel<>>(st, p, d, w, pl);
+    case ReverseForm::global: break;
+    }
+    return launch_k<reverse_kernel>(st, dim3(p.B), w.lds_reverse, d, w, p.loss_b, p.acc_b, p.head_bar);
+}
 
 }  // namespace
 
@@ -1806,16 +2053,7 @@ size_t episode_workspace_bytes(const EpisodeProblem& p) {
     EpiBuf w;
     w.trace = nullptr;
     carve(c, p, w);
-    if (p.need_grad) {
-        int kc;
-        size_t ns = (size_t)xpanel_bwd_nsplit(p.B, p.S, p.Qn, p.D, p.h[0], &kc);
-        if (xpanel_bwd_two_part_ok(p.D, p.h[0])) {       // (the two-launch form has more, shorter slabs)
-            int nsq, kcq, nss, kcs;
-            xpanel_bwd_two_part_split(p.B, p.S, p.Qn, p.D, p.h[0], &nsq, &kcq, &nss, &kcs);
-            ns = std::max(ns, (size_t)(nsq + nss));
-        }
-        c.bytes += ws_align(ns * p.h[0] * (size_t)p.D * sizeof(float));
-    }
+    if (p.need_grad) c.bytes += ws_align(bwd_slab_count(p) * p.h[0] * (size_t)p.D * sizeof(float));
     return c.bytes;
 }
 
@@ -1840,246 +2078,50 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
         if (d.drop_thr == 0) d.drop_thr = 1;
         d.mscale = 1.f / (1.f - p.dropout_p);
     }
+    EpiPlan pl;                                  // (filled in place: its five staging tables are about a kilobyte each)
+    plan_episodes(pl, ws, p, d, w);
+    g_epi_fixed_last = pl.fixed_last;
     const int h0 = p.h[0];
-    int rc;
-    // The backward X-panel pass in two launches (T >= 2): its query-row part beside the reverse sweep on the workspace's second
-    // stream (the sweep is a chain of T x ~30 us on P workgroups per episode -- 128 of the 256 CUs at the reference sizes --, the pass
-    // fills the others and is done before the sweep), its support-row part behind the sweep.  The adjoint array is then laid out
-    // split ([B,S,h0] | [B,Qn,h0]) so that each part reads one contiguous panel.  FUMI_EPI_OVERLAP=0: one launch behind the sweep (2: the two-launch form at any size, for tests).
-    static const int ovl_env = getenv("FUMI_EPI_OVERLAP") ? atoi(getenv("FUMI_EPI_OVERLAP")) : 1;
-    // (measured: FuMI BERT T = 5, 32 episodes 0.436 -> 0.420 ms per step; a 4-episode MAML step, whose pass is 23 us, LOSES 18 us to
-    // the fork / join and the extra launch -- only meta-batches whose pass is long enough to be worth hiding: >= 2048 query rows.
-    // At T = 1 the sweep is one 42 us launch on half of the CUs and the query-row part takes the other half for about as long: the
-    // headline step 0.2200 -> 0.2153 ms without phase timing; not adopted -- the pass is the bench's roofline kernel, timed as ONE
-    // launch on the caller's stream, and +2 % does not pay for a second population of that kernel in every profile)
-    const bool two_part = ovl_env && p.need_grad && p.T >= 2 && ws->side && ws->evx[0] && ws->evx[1] && !ws->profiling && !p.after_reverse &&
-                          xpanel_bwd_two_part_ok(p.D, h0) && p.second_order && ((long)p.B * p.Qn >= 2048 || ovl_env == 2);      // (2: tests)
-    if (p.need_grad) {
-        w.ldsr = two_part ? p.S : p.S + p.Qn; w.ldq = two_part ? p.Qn : p.S + p.Qn;
-        w.A0bar_q = two_part ? w.A0bar + (size_t)p.B * p.S * h0 : w.A0bar + (size_t)p.S * h0;
+    const long slab = (long)h0 * p.D;
+    const XRows* rows = p.rows.table ? &p.rows : nullptr;
+    if (p.need_grad) {                           // two launches: the adjoint array split ([B,S,h0] | [B,Qn,h0]), each part one panel
+        w.ldsr = pl.two_part ? p.S : p.S + p.Qn; w.ldq = pl.two_part ? p.Qn : p.S + p.Qn;
+        w.A0bar_q = pl.two_part ? w.A0bar + (size_t)p.B * p.S * h0 : w.A0bar + (size_t)p.S * h0;
     } else { w.A0bar_q = nullptr; w.ldsr = w.ldq = 0; }
-    float* bwd_slabs = nullptr; int nsq = 0, kcq = 0, nss = 0, kcs = 0;
+    int rc;
 
     // ---- shared pass 1 over X: [A0 | G] = [Xs;Xq] [W0;Xs]^T for every episode, one launch (xpanel.hip)
     if (p.inputs_ready) HIP_TRY(hipEventRecord(p.inputs_ready, st));
     {
         ProfScope ps(ws, st, FUMI_PH_XPANEL_FWD);
         int rider_done = 0;
-        if ((rc = launch_xpanel_fwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, p.W[0], w.A0, w.G, p.rows.table ? &p.rows : nullptr,
-                                    p.fwd_rider, &rider_done, nullptr, nullptr, xpanel_planes(ws, p.B, p.S, p.D, h0), p.glove))) return rc;
+        if ((rc = launch_xpanel_fwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, p.W[0], w.A0, w.G, rows, p.fwd_rider, &rider_done,
+                                    nullptr, nullptr, xpanel_planes(ws, p.B, p.S, p.D, h0), p.glove))) return rc;
         if (p.fwd_rider && !rider_done && p.fwd_rider_fallback && (rc = p.fwd_rider_fallback(p.hook_ctx))) return rc;
     }
     if (p.after_xpanel_fwd && (rc = p.after_xpanel_fwd(p.hook_ctx))) return rc;
     // ---- per-episode phases
     if (p.head_ready) HIP_TRY(hipStreamWaitEvent(st, p.head_ready, 0));       // `head` was produced on another stream
-    EpiParams prm;
-    for (int i = 0; i < MAXL; ++i) { prm.W[i] = i < p.L ? p.W[i] : nullptr; prm.b[i] = i < p.L ? p.b[i] : nullptr; }
-    // one inner step on a two-layer network with at most 32 support rows: every query tile runs the inner step itself
-    // (query_lds_kernel<true>), no adapt launch
-    static const int fuse_env = getenv("FUMI_EPI_FUSE") ? atoi(getenv("FUMI_EPI_FUSE")) : 1;
-    QLay qlf; StageTab tbq, tbs;
-    bool fuse_q = fuse_env && !getenv("FUMI_EPI_GLOBAL") && p.T == 1 && p.L == 2 && p.S <= QR && (h0 & 3) == 0 && p.head != nullptr;
-    // the reference shape of a training step: the query and reverse kernels compiled for it (REF_*; FUMI_EPI_FIXED=0: the
-    // run-time-shaped instances).  The layout is the one of S = REF_SP, N = REF_NP: every smaller S, N fits it (zero padding).
-    static const int fixed_env = getenv("FUMI_EPI_FIXED") ? atoi(getenv("FUMI_EPI_FIXED")) : 1;
-    const bool fixed = fixed_env && !getenv("FUMI_EPI_GLOBAL") && p.T == 1 && p.L == 2 && p.h[0] == REF_H0 && p.h[1] == REF_H1 &&
-                       p.S <= REF_SP && p.N <= REF_NP && p.need_grad && p.second_order;
-    bool fixed_q = fixed && fuse_q && p.S <= REF_SQ;
-    g_epi_fixed_last = 0;
-    const bool drop = d.drop_thr != 0;
-    if (fuse_q) {
-        if (fixed_q) qlf = ref_qlay();
-        else query_layout(qlf, p.L, p.h, p.S, p.N, true);
-        fuse_q = qlf.total <= QLDS_CAP;
-    }
-    if (fuse_q) {
-        const long R = p.S + p.Qn, S = p.S, N = p.N, H = d.H;
-        const int h1 = p.h[1];
-        tbs.init(); tbq.init();
-        tbs.add(w.A0, R * h0, 0, 0, h0, p.S, p.S, h0, qlf.a[0], wg_ld(h0));                     // support rows of A0
-        tbs.add(p.W[1], 0, 0, 0, h0, h1, h1, h0, qlf.W[1], wg_ld(h0));                          // meta-parameters of layer 1
-        tbs.add(p.b[1], 0, 0, 0, h1, 1, 1, h1, qlf.bi[1], h1);
-        tbs.add(p.head, N * (H + 1), 0, 0, H + 1, p.N, p.N, (int)H, qlf.Wh, wg_ld((int)H));    // the episode's head [Wh | bh]
-        tbs.add(p.head + H, N * (H + 1), 0, 0, H + 1, p.N, p.N, 1, qlf.bh, 1);
-        tbs.add(p.b[0], 0, 0, 0, h0, 1, 1, h0, qlf.b0, h0);
-        tbs.add(w.G + S * S, R * S, (long)QR * S, 0, S, -1, QR, p.S, qlf.Gq, wg_ld(p.S));      // the tile's rows of G (its A0 rows: direct loads)
-        fuse_q = !tbs.bad && tbs.nunits <= 64 * 8 && h0 <= 256;
-        // (the fixed-shape kernel reads these jobs' base pointers itself: W_1, b_1, b_0 as float4)
-        auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-        fixed_q = fixed_q && a16(p.W[1]) && a16(p.b[1]) && a16(p.b[0]);
-    }
-    if (!fuse_q) {
+    if (pl.adapt != AdaptForm::none) {
         ProfScope ps(ws, st, FUMI_PH_ADAPT);
-        static const bool force_global_a = getenv("FUMI_EPI_GLOBAL") != nullptr;   // dev/test: take the generic kernels
-        // column parts per episode (adapt_lds_kernel): the layer-0 columns can be split over AP workgroups that exchange the
-        // layer-1 partial sums once per inner step.  OFF by default: measured at the reference sizes (h0 = 256, AP = 4) the
-        // exchange costs what the smaller products save (phase trace: layer 1 + exchange 3.2 -> 6.0 us, the two backward
-        // products 10.3 -> 7.6 us; 0.3118 vs 0.3121 ms per step at T = 1, 0.515 vs 0.506 at T = 5): the inner loop is bound
-        // by per-phase latency, not by the CU's matrix rate.  FUMI_ADAPT_P=n enables it (wider first layers).
-        static const int ap_env = getenv("FUMI_ADAPT_P") ? atoi(getenv("FUMI_ADAPT_P")) : 1;
-        int AP = 1;
-        if (ap_env > 1 && p.L >= 2 && w.acnt && p.B <= FUMI_ACNT) {
-            AP = ap_env > 8 ? 8 : ap_env;
-            while (AP > 1 && (h0 % (64 * AP) != 0)) AP >>= 1;            // every part: a multiple of 64 columns
-        }
-        int hs[MAXL];
-        for (int i = 0; i < MAXL; ++i) hs[i] = i < p.L ? p.h[i] : 0;
-        hs[0] = h0 / AP;
-        ALay al; adapt_layout(al, p.L, hs, p.S, p.N);
-        const int H = d.H;
-        bool lds_form = al.total <= ALDS_CAP && 4 + 2 * (p.L - 1) <= WG_MAXJOB && !force_global_a &&
-                        ((p.S + 15) / 16) * ((hs[0] + 63) / 64) <= 8;      // one layer-0 block per wave (A0s + b0 in registers)
-        StageTab tb; tb.init();
-        if (lds_form) {
-            const long R = p.S + p.Qn, S = p.S, N = p.N;
-            tb.add(w.G, R * S, 0, 0, S, p.S, p.S, p.S, al.G, wg_ld(p.S));
-            for (int i = 1; i < p.L; ++i) {
-                // layer 1: this part's columns of every row (part stride hs[0]); deeper layers whole
-                const int kc = i == 1 ? hs[0] : p.h[i - 1];
-                tb.add(p.W[i], 0, 0, i == 1 ? hs[0] : 0, p.h[i - 1], p.h[i], p.h[i], kc, al.W[i], wg_ld(kc));
-                tb.add(p.b[i], 0, 0, 0, p.h[i], 1, 1, p.h[i], al.bi[i], p.h[i]);
-            }
-            tb.add(p.head, N * (H + 1), 0, 0, H + 1, p.N, p.N, H, al.Wh, wg_ld(H));
-            tb.add(p.head + H, N * (H + 1), 0, 0, H + 1, p.N, p.N, 1, al.bh, 1);
-            lds_form = !tb.bad && tb.nunits <= 64 * 8;
-        }
-        if (lds_form) {
-            FUMI_SET_DYN_LDS(adapt_lds_kernel, al.total * 4);
-            const unsigned grid = AP > 1 ? 8u * ((p.B + 7) / 8) * AP : (unsigned)p.B;
-            hipLaunchKernelGGL(adapt_lds_kernel, dim3(grid), dim3(512), al.total * 4, st, tb, d, w, al, prm, p.y_s, ws->status, AP);
-        } else {
-            FUMI_SET_DYN_LDS(adapt_kernel, w.lds_adapt * 4);
-            hipLaunchKernelGGL(adapt_kernel, dim3(p.B), dim3(512), w.lds_adapt * 4, st, d, w, prm, p.y_s, p.head, ws->status);
-        }
-        LAUNCH_CHECK();
+        if ((rc = launch_adapt(st, p, d, w, pl))) return rc;
     }
-    if (fuse_q) {
+    {
         ProfScope ps(ws, st, FUMI_PH_QUERY);
-        auto launch = [&](auto tag) -> int {
-            constexpr auto kern = decltype(tag)::fn;
-            FUMI_SET_DYN_LDS(kern, qlf.total * 4);
-            hipLaunchKernelGGL(kern, dim3(w.ntile, p.B), dim3(512), qlf.total * 4, st, tbq, tbs, d, w, qlf, p.y_q,
-                               p.logits_q, p.preds_q, p.preds_f, ws->status, p.y_s);
-            LAUNCH_CHECK();
-            return FUMI_OK;
-        };
-        if (fixed_q) g_epi_fixed_last |= 1;
-        if (fixed_q) rc = drop ? launch(KernTag<query_lds_kernel<true, true, true>>{}) : launch(KernTag<query_lds_kernel<true, true, false>>{});
-        else rc = launch(KernTag<query_lds_kernel<true>>{});
-        if (rc) return rc;
-    } else {
-        ProfScope ps(ws, st, FUMI_PH_QUERY);
-        QLay ql; query_layout(ql, p.L, p.h, p.S, p.N);
-        static const bool force_global = getenv("FUMI_EPI_GLOBAL") != nullptr;     // dev/test: take the generic kernels
-        bool lds_form = ql.total <= QLDS_CAP && 7 + 2 * (p.L - 1) <= WG_MAXJOB && !force_global;
-        StageTab tb; tb.init();
-        if (lds_form) {
-            // staging plan: source = base + episode*sb + tile*st
-            const long R = p.S + p.Qn, S = p.S, N = p.N, H = d.H;
-            const long slot = d.taped ? p.T : 0;
-            tb.add(w.A0 + S * h0, R * h0, (long)QR * h0, 0, h0, -1, QR, h0, ql.a[0], wg_ld(h0));
-            tb.add(w.D, S * h0, 0, 0, h0, p.S, p.S, h0, ql.D, wg_ld(h0));
-            for (int i = 1; i < p.L; ++i) {
-                const long sz = (long)p.h[i] * p.h[i - 1];
-                tb.add(w.Wslot[i] + slot * sz, w.nslot * sz, 0, 0, p.h[i - 1], p.h[i], p.h[i], p.h[i - 1], ql.W[i], wg_ld(p.h[i - 1]));
-            }
-            tb.add(w.G + S * S, R * S, (long)QR * S, 0, S, -1, QR, p.S, ql.Gq, wg_ld(p.S));
-            tb.add(w.Whslot + slot * N * H, w.nslot * N * H, 0, 0, H, p.N, p.N, (int)H, ql.Wh, wg_ld((int)H));
-            tb.add(p.b[0], 0, 0, 0, h0, 1, 1, h0, ql.b0, h0);
-            tb.add(w.cs, h0, 0, 0, h0, 1, 1, h0, ql.cs, h0);
-            for (int i = 1; i < p.L; ++i) tb.add(w.bcur[i], p.h[i], 0, 0, p.h[i], 1, 1, p.h[i], ql.bi[i], p.h[i]);
-            tb.add(w.bh, N, 0, 0, N, 1, 1, p.N, ql.bh, p.N);
-            lds_form = !tb.bad && tb.nunits <= 64 * 8;      // wg_stage_rows: one unit per lane and wave
-        }
-        if (lds_form) {
-            StageTab none; none.init();
-            FUMI_SET_DYN_LDS(query_lds_kernel<false>, ql.total * 4);
-            hipLaunchKernelGGL(query_lds_kernel<false>, dim3(w.ntile, p.B), dim3(512), ql.total * 4, st, tb, none, d, w, ql, p.y_q,
-                               p.logits_q, p.preds_q, p.preds_f, ws->status, p.y_s);
-        } else {
-            FUMI_SET_DYN_LDS(query_kernel, w.lds_query * 4);
-            hipLaunchKernelGGL(query_kernel, dim3(w.ntile, p.B), dim3(512), w.lds_query * 4, st, d, w, p.b[0], p.y_q, p.logits_q,
-                               p.preds_q, p.preds_f, ws->status);
-        }
-        LAUNCH_CHECK();
+        if ((rc = launch_query(st, p, d, w, pl))) return rc;
     }
-    if (two_part) {
+    float* slabs = p.need_grad ? ws_f(ws, bwd_slab_count(p) * slab) : nullptr;     // of pass 2, either split
+    if (pl.two_part) {
         // query-row part of gW0 = Abar0^T X on the second stream, behind the query pass (whose adjoint rows it reads)
-        xpanel_bwd_two_part_split(p.B, p.S, p.Qn, p.D, h0, &nsq, &kcq, &nss, &kcs);
-        const long slab = (long)h0 * p.D;
-        bwd_slabs = ws_f(ws, (size_t)(nsq + nss) * slab);
         HIP_TRY(hipEventRecord(ws->evx[0], st));
         HIP_TRY(hipStreamWaitEvent(ws->side, ws->evx[0], 0));
-        if ((rc = launch_xpanel_bwd(ws->side, p.B, 0, p.Qn, p.D, h0, nullptr, p.x_q, w.A0bar_q, bwd_slabs, kcq, nsq,
-                                    p.rows.table ? &p.rows : nullptr, nullptr, nullptr))) return rc;
+        if ((rc = launch_xpanel_bwd(ws->side, p.B, 0, p.Qn, p.D, h0, nullptr, p.x_q, w.A0bar_q, slabs, pl.kcq, pl.nsq, rows,
+                                    nullptr, nullptr))) return rc;
         HIP_TRY(hipEventRecord(ws->evx[1], ws->side));
     }
     {
         ProfScope ps(ws, st, FUMI_PH_REVERSE);
-        static const bool force_global_r = getenv("FUMI_EPI_GLOBAL") != nullptr;   // dev/test: take the generic kernels
-        bool lds_form = p.L >= 2 && p.L <= 4 && w.ntile <= 8 && !force_global_r;
-        int P = 0; RLay rl; StageTab ti, tsx;
-        if (lds_form) {
-            for (int cand = 1; cand <= 8 && !P; cand *= 2) {
-                if (h0 % (4 * cand)) break;
-                reverse_layout(rl, p.L, p.h, p.S, p.N, cand);
-                if (rl.total <= RLDS_CAP) P = cand;
-            }
-            lds_form = P > 0;
-        }
-        // the fixed-shape sweep where the run-time one splits the same way (the sum over the parts depends on P)
-        // (its staging is 16-byte loads at fixed offsets from these arrays)
-        auto a16r = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-        const bool fixed_r = fixed && lds_form && P == REF_P && w.ntile <= 8 && a16r(w.pW[1]) && a16r(w.pD) && a16r(w.pb0) && a16r(w.pWh) &&
-                             a16r(w.pb[1]) && a16r(w.ta[0]) && a16r(w.ta[1]) && a16r(w.tdz[1]) && a16r(w.Wslot[1]) && a16r(w.Whslot);
-        if (fixed_r) rl = ref_rlay();
-        if (lds_form) {
-            const long S = p.S, N = p.N, H = d.H, R = p.S + p.Qn, nt = w.ntile, h0c = h0 / P, h1 = p.h[1];
-            ti.init(); tsx.init();
-            // adjoints after the query pass: sums over the tiles' partial slabs (+ G_ss)
-            ti.add(w.pW[1], nt * h1 * h0, 0, h0c, h0, (int)h1, (int)h1, (int)h0c, rl.Wb[1], wg_ld((int)h0c), (int)nt, h1 * h0);
-            ti.add(w.pD, nt * S * h0, 0, h0c, h0, p.S, p.S, (int)h0c, rl.Db, wg_ld((int)h0c), (int)nt, S * h0);
-            ti.add(w.pb0, nt * h0, 0, h0c, h0, 1, 1, (int)h0c, rl.b0b, (int)h0c, (int)nt, h0);
-            ti.add(w.pWh, nt * N * H, 0, 0, H, p.N, p.N, (int)H, rl.Whb, wg_ld((int)H), (int)nt, N * H);
-            ti.add(w.pbh, nt * N, 0, 0, N, 1, 1, p.N, rl.bhb, p.N, (int)nt, N);
-            for (int i = 1; i < p.L; ++i) {
-                const long hi = p.h[i], hp = p.h[i - 1];
-                ti.add(w.pb[i], nt * hi, 0, 0, hi, 1, 1, (int)hi, rl.bb[i], (int)hi, (int)nt, hi);
-                if (i >= 2) ti.add(w.pW[i], nt * hi * hp, 0, 0, hp, (int)hi, (int)hi, (int)hp, rl.Wb[i], wg_ld((int)hp), (int)nt, hi * hp);
-            }
-            ti.add(w.G, R * S, 0, 0, S, p.S, p.S, p.S, rl.G, wg_ld(p.S));
-            // the tape of step t (t rides in the "tile" slot of the plan)
-            tsx.add(w.ta[0], w.ntape * S * h0, S * h0, h0c, h0, p.S, p.S, (int)h0c, rl.a[0], wg_ld((int)h0c));
-            tsx.add(w.Wslot[1], w.nslot * h1 * h0, h1 * h0, h0c, h0, (int)h1, (int)h1, (int)h0c, rl.W[1], wg_ld((int)h0c));
-            for (int i = 1; i < p.L; ++i) {
-                const long hi = p.h[i], hp = p.h[i - 1];
-                tsx.add(w.ta[i], w.ntape * S * hi, S * hi, 0, hi, p.S, p.S, (int)hi, rl.a[i], wg_ld((int)hi));
-                tsx.add(w.tdz[i], w.ntape * S * hi, S * hi, 0, hi, p.S, p.S, (int)hi, rl.dz[i], wg_ld((int)hi));
-                if (i >= 2) tsx.add(w.Wslot[i], w.nslot * hi * hp, hi * hp, 0, hp, (int)hi, (int)hi, (int)hp, rl.W[i], wg_ld((int)hp));
-            }
-            tsx.add(w.Whslot, w.nslot * N * H, N * H, 0, H, p.N, p.N, (int)H, rl.Wh, wg_ld((int)H));
-            tsx.add(w.tp, w.ntape * S * N, S * N, 0, N, p.S, p.S, p.N, rl.p, wg_ld(p.N));
-            tsx.add(w.te, w.ntape * S * N, S * N, 0, N, p.S, p.S, p.N, rl.e, wg_ld(p.N));
-            lds_form = !ti.bad && !tsx.bad && ti.nunits <= 64 * 8 && tsx.nunits <= 64 * 8;
-        }
-        if (lds_form) {
-            auto launch = [&](auto tag) -> int {
-                constexpr auto kern = decltype(tag)::fn;
-                FUMI_SET_DYN_LDS(kern, rl.total * 4);
-                hipLaunchKernelGGL(kern, dim3(8 * ((p.B + 7) / 8) * P), dim3(512), rl.total * 4, st, ti, tsx, d, w, rl, P,
-                                   p.loss_b, p.acc_b, p.head_bar);
-                LAUNCH_CHECK();
-                return FUMI_OK;
-            };
-            if (fixed_r) g_epi_fixed_last |= 2;
-            if (fixed_r) rc = drop ? launch(KernTag<reverse_lds_kernel<true, true>>{}) : launch(KernTag<reverse_lds_kernel<true, false>>{});
-            else rc = launch(KernTag<reverse_lds_kernel<>>{});
-            if (rc) return rc;
-        } else {
-            FUMI_SET_DYN_LDS(reverse_kernel, w.lds_reverse * 4);
-            hipLaunchKernelGGL(reverse_kernel, dim3(p.B), dim3(512), w.lds_reverse * 4, st, d, w, p.loss_b, p.acc_b, p.head_bar);
-        }
-        LAUNCH_CHECK();
+        if ((rc = launch_reverse(st, p, d, w, pl))) return rc;
     }
     if (p.after_reverse) HIP_TRY(hipEventRecord(p.after_reverse, st));        // head_bar is complete
     // ---- sums over episodes in one launch: meta-gradients of the hidden layers, layer-0 bias, loss/accuracy totals
@@ -2104,20 +2146,18 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
     // ---- shared pass 2 over X: gW0 = Abar0^T [Xs;Xq], contraction over all B*R rows split into slabs (xpanel.hip)
     {
         ProfScope pg(ws, st, FUMI_PH_XPANEL_BWD);
-        int kc;
-        int ns = xpanel_bwd_nsplit(p.B, p.S, p.Qn, p.D, h0, &kc);
-        const long slab = (long)h0 * p.D;
-        float* slabs = two_part ? bwd_slabs : ws_f(ws, (size_t)ns * slab);
-        int rider_done = 0;
-        if (two_part) {
+        int kc, ns, rider_done = 0;
+        if (pl.two_part) {
             // support-row part behind the sweep (with the hypernetwork backward as its rider), then the second stream's part joins
-            if ((rc = launch_xpanel_bwd(st, p.B, p.S, 0, p.D, h0, p.x_s, nullptr, w.A0bar, bwd_slabs + (size_t)nsq * slab, kcs, nss,
-                                        p.rows.table ? &p.rows : nullptr, p.bwd_rider, &rider_done))) return rc;
+            if ((rc = launch_xpanel_bwd(st, p.B, p.S, 0, p.D, h0, p.x_s, nullptr, w.A0bar, slabs + (size_t)pl.nsq * slab, pl.kcs,
+                                        pl.nss, rows, p.bwd_rider, &rider_done))) return rc;
             HIP_TRY(hipStreamWaitEvent(st, ws->evx[1], 0));
-            ns = nsq + nss;
-        } else
-        if ((rc = launch_xpanel_bwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, w.A0bar, slabs, kc, ns, p.rows.table ? &p.rows : nullptr,
-                                    p.bwd_rider, &rider_done))) return rc;
+            ns = pl.nsq + pl.nss;
+        } else {
+            ns = xpanel_bwd_nsplit(p.B, p.S, p.Qn, p.D, h0, &kc);
+            if ((rc = launch_xpanel_bwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, w.A0bar, slabs, kc, ns, rows, p.bwd_rider,
+                                        &rider_done))) return rc;
+        }
         if (p.bwd_rider && !rider_done && p.bwd_rider_fallback && (rc = p.bwd_rider_fallback(p.hook_ctx2))) return rc;
         if (p.defer_reduce && p.defer_reduce->n < 24 && p.defer_reduce->scale == p.grad_scale) p.defer_reduce->add(slabs, ns, slab, slab, p.gW[0]);
         else if ((rc = launch_reduce_slabs(st, slabs, ns, slab, slab, p.grad_scale, p.gW[0]))) return rc;
