@@ -2,6 +2,7 @@
 #include "common.h"
 #include "hyper_fwd.h"
 #include "hyper_bwd.h"
+#include "meta_front.h"
 #include <stdio.h>
 #include <string.h>
 
@@ -55,6 +56,26 @@ hipStream_t ws_lane_stream(fumi_ws* ws, int i) {
         if (i == 1) ws->lane = s;
     }
     return s;
+}
+
+int ws_fork_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
+    if (lanes < 2) return FUMI_OK;
+    HIP_TRY(hipEventRecord(ws->ev[2], st));
+    for (int i = 1; i < lanes; ++i) HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
+    return FUMI_OK;
+}
+
+int ws_join_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
+    for (int i = 1; i < lanes; ++i) {
+        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
+        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
+    }
+    return FUMI_OK;
+}
+
+void ws_abandon_lanes(fumi_ws* ws) {
+    if (ws && ws->side) (void)hipStreamSynchronize(ws->side);
+    for (int i = 0; ws && i < 3; ++i) if (ws->lanes[i]) (void)hipStreamSynchronize(ws->lanes[i]);
 }
 
 extern "C" {
@@ -225,7 +246,7 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         p.h[i] = hid[i]; p.W[i] = theta[2 * i]; p.b[i] = theta[2 * i + 1];
         if (need_grad) { if (!g_theta[2 * i] || !g_theta[2 * i + 1]) return FUMI_EINVAL; p.gW[i] = g_theta[2 * i]; p.gb[i] = g_theta[2 * i + 1]; }
     }
-    for (int i = 0; i < 4; ++i) if (!phi[i] || (need_grad && !g_phi[i])) return FUMI_EINVAL;
+    if (!hyper_head_args_ok(phi, g_phi, need_grad)) return FUMI_EINVAL;
     const int H = hid[n_hidden - 1], R = B * N, H1 = H + 1;
     p.x_s = x_s; p.y_s = y_s; p.x_q = x_q; p.y_q = y_q;
     p.logits_q = logits_q; p.preds_q = preds_q; p.preds_f = preds_q_f32; p.loss_b = loss_b; p.acc_b = acc_b; p.stats = stats;
@@ -286,21 +307,15 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     const bool fork_bwd = ws->side && (overlap & 2) && need_grad;
     const bool fork = ws->side && (overlap & 1);       // forward fork
     hipStream_t sh = fork ? ws->side : st;             // stream of the hypernetwork forward
-    GemmArgs g;
+    const HyperHead hd = {R, Dt, Ht, H1, tanh_head, phi, c, u, ub, h, hbar, hpb, ctext};      // (own carving: ws_f above)
     auto hyper_forward = [&]() -> int {
         if (fork) HIP_TRY(hipStreamWaitEvent(sh, ws->ev[0], 0));     // class text rows are ready (recorded before xpanel_fwd)
         int r2;
         {
             ProfScope ps(ws, sh, FUMI_PH_HYPER_FWD);
             r2 = hyper_lds ? launch_hyper_fwd(sh, R, Dt, Ht, H1, tanh_head, ctext, phi[0], phi[1], phi[2], phi[3], u, h, hfp, ws->hcnt) : FUMI_ENOTSUP;
-            if (r2 == FUMI_ENOTSUP) {                                // shapes outside the LDS-resident kernels: plain GEMMs
-                g = gemm_args(R, Ht, Dt, ctext, Dt, phi[0], Dt, u, Ht);
-                g.bias = phi[1]; g.act = 1;
-                if ((r2 = launch_gemm(sh, g, 0, 0))) return r2;
-                g = gemm_args(R, H1, Ht, u, Ht, phi[2], Ht, h, H1);
-                g.bias = phi[3]; g.act = tanh_head ? 2 : 0;
-                if ((r2 = launch_gemm(sh, g, 0, 0))) return r2;
-            } else if (r2) return r2;
+            if (r2 == FUMI_ENOTSUP) r2 = hyper_head_fwd_gemm(sh, hd);   // shapes outside the LDS-resident kernels: plain GEMMs
+            if (r2) return r2;
         }
         if (fork) HIP_TRY(hipEventRecord(ws->ev[1], sh));
         return FUMI_OK;
@@ -357,27 +372,10 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
                                    g_phi[0], g_phi[1], g_phi[2], g_phi[3], &fin);
         if (rc2 != FUMI_ENOTSUP) return rc2;
     }
-    const float* hp = hbar;
-    if (tanh_head) { if ((rc = launch_tanh_bwd(sh, (long)R * H1, h, hbar, hpb))) return rc; hp = hpb; }
-    g = gemm_args(H1, Ht, R, hp, H1, u, Ht, g_phi[2], Ht);           // gA1 = hp^T u
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(sh, g, 1, 1))) return rc;
-    if ((rc = launch_colsum(sh, hp, R, H1, H1, grad_scale, g_phi[3]))) return rc;
-    g = gemm_args(R, Ht, H1, hp, H1, phi[2], Ht, ub, Ht);            // ubar = (hp A1) * relu'(u), mask in the epilogue
-    g.mask = u;
-    if ((rc = launch_gemm(sh, g, 0, 1))) return rc;
-    g = gemm_args(Ht, Dt, R, ub, Ht, ctext, Dt, g_phi[0], Dt);       // gA0 = ubar^T c
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(sh, g, 1, 1))) return rc;
-    if ((rc = launch_colsum(sh, ub, R, Ht, Ht, grad_scale, g_phi[1]))) return rc;
-    return FUMI_OK;
+    return hyper_head_bwd_gemm(sh, hd, grad_scale, g_phi, &text_grad);   // plain GEMMs (they consume text_grad themselves)
     }();
     if (rc) return rc;
-    if (text_grad) {                                                 // d(scale * sum_b loss_b) / d ctext = scale * ubar A0   [R,Dt]
-        g = gemm_args(R, Dt, Ht, ub, Ht, phi[0], Dt, text_grad, Dt);
-        g.alpha = grad_scale;
-        if ((rc = launch_gemm(sh, g, 0, 1))) return rc;
-    }
+    if (text_grad && (rc = hyper_head_text_grad_gemm(sh, hd, grad_scale, text_grad))) return rc;
     if (fork_bwd) {                                                  // join: the caller's stream owns every result again
         HIP_TRY(hipEventRecord(ws->ev[3], sh));
         HIP_TRY(hipStreamWaitEvent(st, ws->ev[3], 0));

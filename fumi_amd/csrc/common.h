@@ -45,6 +45,11 @@ struct fumi_ws {
 
 // stream of lane i (1..3) of a multi-lane step, created on first use together with its join event; nullptr when that fails
 hipStream_t ws_lane_stream(fumi_ws* ws, int i);
+// fork: lanes 1..lanes-1 start behind everything already on the caller's stream (ev[2]); join: the caller's stream waits for them
+int ws_fork_lanes(fumi_ws* ws, hipStream_t st, int lanes);
+int ws_join_lanes(fumi_ws* ws, hipStream_t st, int lanes);
+// after a failed call: launches may be left on ws->side and the lanes, and nothing else may touch the workspace before they are done
+void ws_abandon_lanes(fumi_ws* ws);
 
 // RAII phase timer: two hipEventRecords on the caller's stream when profiling is on, nothing otherwise
 struct ProfScope {
@@ -83,7 +88,7 @@ void fumi_set_hip_error(hipError_t e, const char* where);
 
 // make sure the slab holds `bytes`; grows (synchronising) when it does not
 int ws_reserve(fumi_ws* ws, size_t bytes);
-static inline size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
 // carve n floats (call only after ws_reserve of the total)
 static inline float* ws_f(fumi_ws* ws, size_t n) {
     float* p = (float*)(ws->base + ws->off);

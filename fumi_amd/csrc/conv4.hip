@@ -10,6 +10,7 @@
 // HBM is the tape: 288 GB hold every pre-activation, pooled activation and their gradients of every inner step (6.5 MB per
 // 84 x 84 image and step), nothing is recomputed except the arg-max of the pooling windows.
 #include "conv4.h"
+#include "meta_front.h"
 #include <string.h>
 #include <functional>
 
@@ -358,17 +359,7 @@ static ProbeTab g_probe;
 
 }  // namespace
 
-struct Conv4Problem {
-    int B, N, S, Qn, Cin, H, W, nblk, T;
-    float alpha, grad_scale;
-    int need_grad, second_order;
-    const float* x_s; const int64_t* y_s; const float* x_q; const int64_t* y_q;
-    const float* theta[3 * CV_MAXBLK];      // W [64][Cin|64][3][3], BN weight [64], BN bias [64] per block
-    const float* head;                      // [B][N][F+1]
-    float* logits_q; int64_t* preds_q; float* preds_f; float* loss_b; float* acc_b; float* stats;
-    float* g_theta[3 * CV_MAXBLK];
-    float* head_bar;                        // [B][N][F+1] d loss_b / d head_b (unscaled)
-};
+typedef EncProblem Conv4Problem;            // theta: W [64][Cin|64][3][3], BN weight [64], BN bias [64] per block
 
 int conv4_feature_dim(int nblk, int H, int W) {
     for (int l = 0; l < nblk; ++l) { H /= 2; W /= 2; }
@@ -455,10 +446,7 @@ int run_conv4_episodes(fumi_ws* ws, hipStream_t st, Conv4Problem p, const Conv4H
     ws->off += extra_bytes;                                           // (the caller's buffers: head, hypernetwork activations)
     const size_t lane0_off = ws->off;
     TRY(hooks.prepare(extra, &p.head, &p.head_bar));
-    if (lanes > 1) {
-        HIP_TRY(hipEventRecord(ws->ev[2], st));                       // the lanes start behind the head's producer on the caller's stream
-        for (int i = 1; i < lanes; ++i) HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
-    }
+    TRY(ws_fork_lanes(ws, st, lanes));                                // the lanes start behind the head's producer on the caller's stream
     ProbeTab& pt = g_probe;
     pt.valid = false;
     float* gsum_lane[MAXLANES] = {nullptr, nullptr, nullptr, nullptr};
@@ -544,16 +532,9 @@ int run_conv4_episodes(fumi_ws* ws, hipStream_t st, Conv4Problem p, const Conv4H
         const int b0 = i * Bc, bc = p.B - b0 < Bc ? p.B - b0 : Bc;
         if (bc > 0) TRY(chunk_body(i, b0, bc));
     }
-    for (int i = 1; i < lanes; ++i) {                                 // the caller's stream waits for the other lanes
-        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
-        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
-    }
+    TRY(ws_join_lanes(ws, st, lanes));                                // the caller's stream waits for the other lanes
     const Net& n = cx[0].n;
-    if (p.stats) {
-        ReduceSegs sg; sg.n = 0; sg.scale = p.grad_scale;
-        sg.add(p.loss_b, p.B, 1, 1, p.stats); sg.add(p.acc_b, p.B, 1, 1, p.stats + 1);
-        TRY(launch_reduce_multi(st, sg));
-    }
+    TRY(launch_episode_stats(st, p.B, p.loss_b, p.acc_b, p.grad_scale, p.stats));
     if (!grad) return FUMI_OK;
     // ---- meta-gradients: the lanes' sums added, back to the parameters' own layouts
     float* gsum = gsum_lane[0];
@@ -570,24 +551,6 @@ int run_conv4_episodes(fumi_ws* ws, hipStream_t st, Conv4Problem p, const Conv4H
 // ------------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------------
-static int fill_problem(Conv4Problem& p, int B, int N, int S, int Qn, int Cin, int H, int W, int nblk, int T, float alpha,
-                        int need_grad, int second_order, float grad_scale, const float* x_s, const int64_t* y_s,
-                        const float* x_q, const int64_t* y_q, const float* const* theta, float* logits_q, int64_t* preds_q,
-                        float* preds_f, float* loss_b, float* acc_b, float* stats, float* const* g_theta) {
-    memset(&p, 0, sizeof(p));
-    if (!x_s || !y_s || !x_q || !y_q || !theta || !logits_q || !preds_q || !loss_b || !acc_b) return FUMI_EINVAL;
-    if (nblk < 1 || nblk > CV_MAXBLK || (need_grad && !g_theta)) return FUMI_EINVAL;
-    p.B = B; p.N = N; p.S = S; p.Qn = Qn; p.Cin = Cin; p.H = H; p.W = W; p.nblk = nblk; p.T = T; p.alpha = alpha;
-    p.grad_scale = grad_scale; p.need_grad = need_grad ? 1 : 0; p.second_order = second_order ? 1 : 0;
-    p.x_s = x_s; p.y_s = y_s; p.x_q = x_q; p.y_q = y_q;
-    for (int i = 0; i < 3 * nblk; ++i) {
-        if (!theta[i] || (need_grad && !g_theta[i])) return FUMI_EINVAL;
-        p.theta[i] = theta[i]; p.g_theta[i] = need_grad ? g_theta[i] : nullptr;
-    }
-    p.logits_q = logits_q; p.preds_q = preds_q; p.preds_f = preds_f; p.loss_b = loss_b; p.acc_b = acc_b; p.stats = stats;
-    return FUMI_OK;
-}
-
 extern "C" {
 
 int fumi_hip_conv4_set_option(int key, int value) {
@@ -609,8 +572,8 @@ int fumi_hip_maml_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
     Conv4Problem p;
-    int rc = fill_problem(p, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, !first_order, grad_scale, x_s, y_s, x_q, y_q, params,
-                          logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_params);
+    int rc = enc_fill_problem(p, 3, CV_MAXBLK, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, !first_order, grad_scale, x_s, y_s,
+                              x_q, y_q, params, logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_params);
     if (rc) return rc;
     const float* Wf = params[3 * nblk]; const float* bf = params[3 * nblk + 1];
     if (!Wf || !bf || (need_grad && (!g_params[3 * nblk] || !g_params[3 * nblk + 1]))) return FUMI_EINVAL;
@@ -626,7 +589,7 @@ int fumi_hip_maml_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
         *head = h; *head_bar = hbar;
         return launch_broadcast_head(st, B, N, F, Wf, bf, h);            // every episode starts from lin_final (maml.py:24-31)
     };
-    if ((rc = run_conv4_episodes(ws, st, p, hk))) { for (int i = 0; i < 3; ++i) if (ws->lanes[i]) (void)hipStreamSynchronize(ws->lanes[i]); return rc; }
+    if ((rc = run_conv4_episodes(ws, st, p, hk))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
     return launch_split_head_grad(st, B, N, F, hbar, grad_scale, g_params[3 * nblk], g_params[3 * nblk + 1]);
 }
@@ -639,62 +602,31 @@ int fumi_hip_fumi_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
         float* const* g_theta, float* const* g_phi) {
-    if (!ws || !theta || !phi || (!cls_text && !text_s) || Dt < 1 || Ht < 1) return FUMI_EINVAL;
-    if (need_grad && !g_phi) return FUMI_EINVAL;
-    for (int i = 0; i < 4; ++i) if (!phi[i] || (need_grad && !g_phi[i])) return FUMI_EINVAL;
+    if (!ws || !theta || (!cls_text && !text_s) || Dt < 1 || Ht < 1 || !hyper_head_args_ok(phi, g_phi, need_grad)) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
     Conv4Problem p;
-    int rc = fill_problem(p, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, 1, grad_scale, x_s, y_s, x_q, y_q, theta,
-                          logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_theta);       // fumi.py:176: second order always
+    int rc = enc_fill_problem(p, 3, CV_MAXBLK, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, 1, grad_scale, x_s, y_s, x_q, y_q,
+                              theta, logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_theta);   // fumi.py:176: second order always
     if (rc) return rc;
     const int F = conv4_feature_dim(nblk, H, W);
     if (F < 64) return FUMI_EINVAL;
     const int R = B * N, H1 = F + 1;
-    // hypernetwork rows are (episode, class) pairs: Linear(Dt, Ht) . ReLU . Linear(Ht, F+1) [. Tanh]  (fumi.py:70-86,104-113)
-    float *c = nullptr, *u = nullptr, *ub = nullptr, *h = nullptr, *hbar = nullptr, *hpb = nullptr;
-    const float* ctext = cls_text;
+    HyperHead hd;                                                        // the hypernetwork behind the head (meta_front.h)
     Conv4Hooks hk;
-    hk.extra_bytes = ws_align((size_t)R * Dt * 4) + 2 * ws_align((size_t)R * Ht * 4) + 3 * ws_align((size_t)R * H1 * 4);
+    hk.extra_bytes = hyper_head_floats(R, Dt, Ht, H1) * sizeof(float);
     hk.prepare = [&](char* extra, const float** head, float** head_bar) -> int {
-        auto take = [&](size_t nfl) { float* q = (float*)extra; extra += ws_align(nfl * 4); return q; };
-        c = take((size_t)R * Dt); u = take((size_t)R * Ht); ub = take((size_t)R * Ht);
-        h = take((size_t)R * H1); hbar = take((size_t)R * H1); hpb = take((size_t)R * H1);
-        int r2;
-        if (!ctext) {                                                    // first support row of each class (fumi.py:207-210)
-            if ((r2 = launch_class_text_select(st, B, N, S, Dt, text_s, y_s, c, ws->status))) return r2;
-            ctext = c;
+        hd = hyper_head_carve((float*)extra, R, Dt, Ht, H1, tanh_head, phi, cls_text);
+        if (!hd.ctext) {                                                 // first support row of each class (fumi.py:207-210)
+            if (int r2 = launch_class_text_select(st, B, N, S, Dt, text_s, y_s, hd.c, ws->status)) return r2;
+            hd.ctext = hd.c;
         }
-        GemmArgs g = gemm_args(R, Ht, Dt, ctext, Dt, phi[0], Dt, u, Ht);
-        g.bias = phi[1]; g.act = 1;
-        if ((r2 = launch_gemm(st, g, 0, 0))) return r2;
-        g = gemm_args(R, H1, Ht, u, Ht, phi[2], Ht, h, H1);
-        g.bias = phi[3]; g.act = tanh_head ? 2 : 0;
-        if ((r2 = launch_gemm(st, g, 0, 0))) return r2;
-        *head = h; *head_bar = hbar;
-        return FUMI_OK;
+        *head = hd.h; *head_bar = hd.hbar;
+        return hyper_head_fwd_gemm(st, hd);
     };
-    if ((rc = run_conv4_episodes(ws, st, p, hk))) { for (int i = 0; i < 3; ++i) if (ws->lanes[i]) (void)hipStreamSynchronize(ws->lanes[i]); return rc; }
+    if ((rc = run_conv4_episodes(ws, st, p, hk))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
-    const float* hp = hbar;
-    if (tanh_head) { if ((rc = launch_tanh_bwd(st, (long)R * H1, h, hbar, hpb))) return rc; hp = hpb; }
-    GemmArgs g = gemm_args(H1, Ht, R, hp, H1, u, Ht, g_phi[2], Ht);    // gA1 = hp^T u
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(st, g, 1, 1))) return rc;
-    if ((rc = launch_colsum(st, hp, R, H1, H1, grad_scale, g_phi[3]))) return rc;
-    g = gemm_args(R, Ht, H1, hp, H1, phi[2], Ht, ub, Ht);              // ubar = (hp A1) * relu'(u)
-    g.mask = u;
-    if ((rc = launch_gemm(st, g, 0, 1))) return rc;
-    g = gemm_args(Ht, Dt, R, ub, Ht, ctext, Dt, g_phi[0], Dt);         // gA0 = ubar^T c
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(st, g, 1, 1))) return rc;
-    if (float* tg = ws->text_grad) {                                   // armed by fumi_hip_want_text_grad: scale * ubar A0  [R,Dt]
-        ws->text_grad = nullptr;
-        g = gemm_args(R, Dt, Ht, ub, Ht, phi[0], Dt, tg, Dt);
-        g.alpha = grad_scale;
-        if ((rc = launch_gemm(st, g, 0, 1))) return rc;
-    }
-    return launch_colsum(st, ub, R, Ht, Ht, grad_scale, g_phi[1]);
+    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, &ws->text_grad);   // (consumes a text gradient armed by fumi_hip_want_text_grad)
 }
 
 // Copies one intermediate of the LAST conv4 step of this process out of the workspace (tests compare every tensor of the
@@ -826,7 +758,6 @@ static int encode_lanes(fumi_ws* ws, int B) {
     for (int i = 1; i < lanes; ++i) if (!ws_lane_stream(ws, i)) return 1;
     return lanes;
 }
-static void encode_abandon(fumi_ws* ws) { for (int i = 0; i < 3; ++i) if (ws->lanes[i]) (void)hipStreamSynchronize(ws->lanes[i]); }
 
 // shared frame of the two encoder calls: `lanes` parts of the episodes, part i carved at i * region and run on its lane's stream by
 // body(ctx, bufs, b0, bc); fork after everything on the caller's stream, join before the caller's stream goes on
@@ -839,10 +770,7 @@ static int encode_on_lanes(fumi_ws* ws, hipStream_t st, int lanes, int B, int S,
     if (rc) return rc;
     const size_t region = ws_align(encode_bytes(c0.n, S, Qn, c0.sc) + 4096);
     if ((rc = ws_reserve(ws, lanes * region))) return rc;
-    if (lanes > 1) {
-        HIP_TRY(hipEventRecord(ws->ev[2], st));
-        for (int i = 1; i < lanes; ++i) HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
-    }
+    TRY(ws_fork_lanes(ws, st, lanes));
     for (int i = 0; i < lanes; ++i) {
         const int b0 = i * Bc, bc = B - b0 < Bc ? B - b0 : Bc;
         if (bc <= 0) continue;
@@ -855,11 +783,7 @@ static int encode_on_lanes(fumi_ws* ws, hipStream_t st, int lanes, int B, int S,
         if (view.off > (size_t)(i + 1) * region || view.off > ws->cap) return FUMI_ENOMEM;
         if ((rc = body(c, e, i, b0, bc))) return rc;
     }
-    for (int i = 1; i < lanes; ++i) {
-        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
-        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
-    }
-    return FUMI_OK;
+    return ws_join_lanes(ws, st, lanes);
 }
 
 int fumi_hip_conv4_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W, int nblk,
@@ -883,7 +807,7 @@ int fumi_hip_conv4_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int
         HIP_TRY(hipMemcpyAsync(feats_q + (size_t)b0 * Qn * n.F, e.pq.x[n.nblk - 1], (size_t)bc * Qn * n.F * 4, hipMemcpyDeviceToDevice, st));
         return FUMI_OK;
     });
-    if (rc) { encode_abandon(ws); return rc; }
+    if (rc) { ws_abandon_lanes(ws); return rc; }
     if (keep_tape) g_enc = EncodeToken{true, ws, ws->base, B, S, Qn, Cin, H, W, nblk, lanes};
     return FUMI_OK;
 }
@@ -919,7 +843,7 @@ int fumi_hip_conv4_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S,
         if (lane == 0) n0 = n;
         return FUMI_OK;
     });
-    if (rc) { encode_abandon(ws); return rc; }
+    if (rc) { ws_abandon_lanes(ws); return rc; }
     const Net& n = n0;
     float* gsum = gsum_lane[0];
     for (int i = 1; i < lanes; ++i) if (gsum_lane[i]) TRY(launch_axpy(st, n.PSZ, gsum, 1.f, gsum_lane[i], gsum));

@@ -13,6 +13,7 @@
 // meta-batch is processed in CHUNKS of episodes (episodes are independent given the meta-parameters; the meta-gradient is the sum
 // over chunks), the chunk size derived from the workspace budget.  Master weights and all parameter-space vectors are fp32.
 #include "rn12.h"
+#include "meta_front.h"
 #include "conv4.h"                     // head kernels, axpy / broadcast / batched reduction (conv_ew.hip)
 #include <string.h>
 #include <stdlib.h>
@@ -163,11 +164,7 @@ static hipStream_t rn_side_stream(fumi_ws* ws) {
     if (ws->profiling) return nullptr;              // phase timing (bench.py's roofline step): one stream, every phase on its own
     return on ? ws->side : nullptr;
 }
-// a failed call may leave weight-gradient launches on the second stream: nothing else may touch the workspace before they are done
-static void rn_abandon(fumi_ws* ws) {
-    if (ws && ws->side) (void)hipStreamSynchronize(ws->side);
-    for (int i = 0; ws && i < 3; ++i) if (ws->lanes[i]) (void)hipStreamSynchronize(ws->lanes[i]);
-}
+// (a failed call may leave weight-gradient launches on the second stream: ws_abandon_lanes waits for it too)
 // main waits for everything forked so far
 static int rn_join(RnCtx& c) {
     if (!c.forked) return FUMI_OK;
@@ -436,16 +433,8 @@ RnProbeTab g_rn_tab;
 
 }  // namespace
 
-struct Rn12Problem {
-    int B, N, S, Qn, Cimg, H, W, nblk, T; int channels[RN_MAXBLK];
-    float alpha, grad_scale;
-    int need_grad, second_order, chunk;
-    const float* x_s; const int64_t* y_s; const float* x_q; const int64_t* y_q;
-    const float* theta[12 * RN_MAXBLK];
-    const float* head; float* head_bar;              // [B][N][F+1]
-    float* logits_q; int64_t* preds_q; float* preds_f; float* loss_b; float* acc_b; float* stats;
-    float* g_theta[12 * RN_MAXBLK];
-};
+struct Rn12Problem : EncProblem { int channels[RN_MAXBLK]; int chunk; };
+static_assert(12 * RN_MAXBLK <= ENC_MAXTHETA, "theta table of the problem front");
 
 // bytes of the workspace a chunk of `Bc` episodes needs
 static size_t chunk_bytes(RnNet& n, int Bc, const Rn12Problem& p, RnScratch& sc) {
@@ -491,21 +480,6 @@ static int rn_fit_chunk(int Bc, size_t budget, const std::function<size_t(int)>&
     while (Bc > 1 && total(Bc) > budget) --Bc;
     return Bc;
 }
-// the lanes start behind everything already on the caller's stream ...
-static int rn_fork_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
-    if (lanes < 2) return FUMI_OK;
-    HIP_TRY(hipEventRecord(ws->ev[2], st));
-    for (int i = 1; i < lanes; ++i) HIP_TRY(hipStreamWaitEvent(ws->lanes[i - 1], ws->ev[2], 0));
-    return FUMI_OK;
-}
-// ... and the caller's stream waits for them
-static int rn_join_lanes(fumi_ws* ws, hipStream_t st, int lanes) {
-    for (int i = 1; i < lanes; ++i) {
-        HIP_TRY(hipEventRecord(ws->lane_ev[i - 1], ws->lanes[i - 1]));
-        HIP_TRY(hipStreamWaitEvent(st, ws->lane_ev[i - 1], 0));
-    }
-    return FUMI_OK;
-}
 // parameter slot of n.B episodes = theta (12 nblk tensors, torch layouts) broadcast to every episode
 static int slot_from_theta(hipStream_t st, const RnNet& n, const float* const* theta, float* params) {
     for (int l = 0; l < n.nblk; ++l)
@@ -537,7 +511,7 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
     RnCtx cx[MAXLANES];
     for (int i = 0; i < MAXLANES; ++i) { cx[i].ws = ws; cx[i].st = st; }
     RnCtx& c = cx[0];
-    int rc = net_init(c.n, p.B, p.nblk, p.Cimg, p.N, p.H, p.W, p.channels);
+    int rc = net_init(c.n, p.B, p.nblk, p.Cin, p.N, p.H, p.W, p.channels);
     if (rc) return rc;
     RnNet& n = c.n;
     if (p.T < 0 || p.S < 1 || p.Qn < 1) return FUMI_EINVAL;
@@ -558,7 +532,7 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
     // (one lane: its weight gradients fork onto ws->side; with two lanes a stream of weight gradients per lane added nothing --
     // 530.5 vs 524.2 ms per 8-episode step -- and they stay in line)
     if (lanes == 1) { c.side = rn_side_stream(ws); c.ev_fork = ws->ev[0]; c.ev_join = ws->ev[1]; }
-    TRY(rn_fork_lanes(ws, st, lanes));
+    TRY(ws_fork_lanes(ws, st, lanes));
     for (int i = 1; i < lanes; ++i) { cx[i].n = n; cx[i].st = ws->lanes[i - 1]; }
     const size_t F1 = (size_t)n.N * (n.F + 1);
     float* gacc_lane[MAXLANES] = {nullptr, nullptr, nullptr, nullptr};
@@ -608,11 +582,11 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
         auto P = [&](int s) { return params + (size_t)s * bc * n.PSZ; };
         auto Fr = [&](int s) { return frags + (size_t)s * bc * n.FSZ; };
         auto Hd = [&](int s) { return heads + (size_t)s * hsz; };
-        const float* x_s = p.x_s + (size_t)b0 * p.S * p.Cimg * p.H * p.W; const float* x_q = p.x_q + (size_t)b0 * p.Qn * p.Cimg * p.H * p.W;
+        const float* x_s = p.x_s + (size_t)b0 * p.S * p.Cin * p.H * p.W; const float* x_q = p.x_q + (size_t)b0 * p.Qn * p.Cin * p.H * p.W;
         const int64_t* y_s = p.y_s + (size_t)b0 * p.S; const int64_t* y_q = p.y_q + (size_t)b0 * p.Qn;
         // ---- images -> bf16 padded channels-last (once per chunk), slot 0 = the meta-parameters broadcast to every episode
-        TRY(launch_rn_img_prep(st, (long)bc * p.S, p.Cimg, n.g[0], x_s, img_s));
-        TRY(launch_rn_img_prep(st, (long)bc * p.Qn, p.Cimg, n.g[0], x_q, img_q));
+        TRY(launch_rn_img_prep(st, (long)bc * p.S, p.Cin, n.g[0], x_s, img_s));
+        TRY(launch_rn_img_prep(st, (long)bc * p.Qn, p.Cin, n.g[0], x_q, img_q));
         HIP_TRY(hipMemsetAsync(G, 0, (size_t)bc * n.PSZ * 4, st));          // (the slab's padding words stay 0 in every vector derived from G)
         HIP_TRY(hipMemsetAsync(P(0), 0, (size_t)bc * n.PSZ * 4, st));
         HIP_TRY(hipMemsetAsync(HV, 0, (size_t)bc * n.PSZ * 4, st));
@@ -673,14 +647,10 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
             first[lane] = false;
         }
     }
-    TRY(rn_join_lanes(ws, st, lanes));                                    // the caller's stream waits for the other lanes
+    TRY(ws_join_lanes(ws, st, lanes));                                    // the caller's stream waits for the other lanes
     float* gacc = gacc_lane[0];
     for (int i = 1; i < lanes; ++i) if (grad && gacc_lane[i]) TRY(launch_axpy(st, n.PSZ, gacc, 1.f, gacc_lane[i], gacc));
-    if (p.stats) {
-        ReduceSegs sg; sg.n = 0; sg.scale = p.grad_scale;
-        sg.add(p.loss_b, p.B, 1, 1, p.stats); sg.add(p.acc_b, p.B, 1, 1, p.stats + 1);
-        TRY(launch_reduce_multi(st, sg));
-    }
+    TRY(launch_episode_stats(st, p.B, p.loss_b, p.acc_b, p.grad_scale, p.stats));
     if (!grad) return FUMI_OK;
     return theta_grads_out(st, n, gacc, p.g_theta);
 }
@@ -688,23 +658,10 @@ int run_rn12_episodes(fumi_ws* ws, hipStream_t st, const Rn12Problem& p) {
 // ------------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------------
-static int fill_problem(Rn12Problem& p, int B, int N, int S, int Qn, int Cimg, int H, int W, int nblk, const int* channels, int T,
-                        float alpha, int need_grad, int second_order, float grad_scale, int chunk, const float* x_s, const int64_t* y_s,
-                        const float* x_q, const int64_t* y_q, const float* const* theta, float* logits_q, int64_t* preds_q,
-                        float* preds_f, float* loss_b, float* acc_b, float* stats, float* const* g_theta) {
-    memset(&p, 0, sizeof(p));
-    if (!x_s || !y_s || !x_q || !y_q || !theta || !logits_q || !preds_q || !loss_b || !acc_b || !channels) return FUMI_EINVAL;
-    if (nblk < 1 || nblk > RN_MAXBLK || (need_grad && !g_theta)) return FUMI_EINVAL;
-    p.B = B; p.N = N; p.S = S; p.Qn = Qn; p.Cimg = Cimg; p.H = H; p.W = W; p.nblk = nblk; p.T = T; p.alpha = alpha;
-    for (int l = 0; l < nblk; ++l) p.channels[l] = channels[l];
-    p.grad_scale = grad_scale; p.need_grad = need_grad ? 1 : 0; p.second_order = second_order ? 1 : 0; p.chunk = chunk;
-    p.x_s = x_s; p.y_s = y_s; p.x_q = x_q; p.y_q = y_q;
-    for (int i = 0; i < 12 * nblk; ++i) {
-        if (!theta[i] || (need_grad && !g_theta[i])) return FUMI_EINVAL;
-        p.theta[i] = theta[i]; p.g_theta[i] = need_grad ? g_theta[i] : nullptr;
-    }
-    p.logits_q = logits_q; p.preds_q = preds_q; p.preds_f = preds_f; p.loss_b = loss_b; p.acc_b = acc_b; p.stats = stats;
-    return FUMI_OK;
+// the ResNet-12 share of the problem front (after enc_fill_problem): channel counts and the caller's chunk
+static void fill_channels(Rn12Problem& p, const int* channels, int chunk) {
+    for (int l = 0; l < RN_MAXBLK; ++l) p.channels[l] = l < p.nblk ? channels[l] : 0;
+    p.chunk = chunk;
 }
 
 // small side allocation that outlives the chunk loop's workspace rewinds: the heads and their adjoints of the WHOLE meta-batch and
@@ -721,7 +678,6 @@ int side_reserve(fumi_ws* ws, size_t floats, float** out) {
     *out = ws->side_buf;
     return FUMI_OK;
 }
-size_t al64(size_t n) { return (n + 63) / 64 * 64; }
 }  // namespace
 
 // ---- first-order encoder pair (AM3's image encoder): encode with the tape kept, backward from the feature adjoints ---------------------
@@ -928,19 +884,20 @@ int fumi_hip_maml_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
     Rn12Problem p;
-    int rc = fill_problem(p, B, N, S, Qn, Cin, H, W, nblk, channels, T, alpha, need_grad, !first_order, grad_scale, chunk, x_s, y_s, x_q,
-                          y_q, params, logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_params);
+    int rc = enc_fill_problem(p, 12, RN_MAXBLK, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, !first_order, grad_scale, x_s, y_s,
+                              x_q, y_q, params, logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_params);
     if (rc) return rc;
+    fill_channels(p, channels, chunk);
     const float* Wf = params[12 * nblk]; const float* bf = params[12 * nblk + 1];
     if (!Wf || !bf || (need_grad && (!g_params[12 * nblk] || !g_params[12 * nblk + 1]))) return FUMI_EINVAL;
     const int F = channels[nblk - 1];
     const size_t hsz = (size_t)B * N * (F + 1);
     float* side;
-    if ((rc = side_reserve(ws, 2 * al64(hsz), &side))) return rc;
-    float* h = side; float* hbar = side + al64(hsz);
+    if ((rc = side_reserve(ws, 2 * head_al(hsz), &side))) return rc;
+    float* h = side; float* hbar = side + head_al(hsz);
     if ((rc = launch_broadcast_head(st, B, N, F, Wf, bf, h))) return rc;            // every episode starts from lin_final (maml.py:24-31)
     p.head = h; p.head_bar = hbar;
-    if ((rc = run_rn12_episodes(ws, st, p))) { rn_abandon(ws); return rc; }
+    if ((rc = run_rn12_episodes(ws, st, p))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
     return launch_split_head_grad(st, B, N, F, hbar, grad_scale, g_params[12 * nblk], g_params[12 * nblk + 1]);
 }
@@ -953,55 +910,29 @@ int fumi_hip_fumi_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
         float* const* g_theta, float* const* g_phi) {
-    if (!ws || !theta || !phi || !channels || (!cls_text && !text_s) || Dt < 1 || Ht < 1) return FUMI_EINVAL;
-    if (need_grad && !g_phi) return FUMI_EINVAL;
-    for (int i = 0; i < 4; ++i) if (!phi[i] || (need_grad && !g_phi[i])) return FUMI_EINVAL;
+    if (!ws || !theta || !channels || (!cls_text && !text_s) || Dt < 1 || Ht < 1 || !hyper_head_args_ok(phi, g_phi, need_grad))
+        return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
     Rn12Problem p;
-    int rc = fill_problem(p, B, N, S, Qn, Cin, H, W, nblk, channels, T, alpha, need_grad, 1, grad_scale, chunk, x_s, y_s, x_q, y_q, theta,
-                          logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_theta);          // fumi.py:176: second order always
+    int rc = enc_fill_problem(p, 12, RN_MAXBLK, B, N, S, Qn, Cin, H, W, nblk, T, alpha, need_grad, 1, grad_scale, x_s, y_s, x_q, y_q,
+                              theta, logits_q, preds_q, preds_q_f32, loss_b, acc_b, stats, g_theta);   // fumi.py:176: second order always
     if (rc) return rc;
+    fill_channels(p, channels, chunk);
     const int F = channels[nblk - 1];
     const int R = B * N, H1 = F + 1;
-    // hypernetwork rows are (episode, class) pairs: Linear(Dt, Ht) . ReLU . Linear(Ht, F+1) [. Tanh]  (fumi.py:70-86,104-113)
     float* side;
-    if ((rc = side_reserve(ws, al64((size_t)R * Dt) + 2 * al64((size_t)R * Ht) + 3 * al64((size_t)R * H1), &side))) return rc;
-    float* c = side; float* u = c + al64((size_t)R * Dt); float* ub = u + al64((size_t)R * Ht);
-    float* h = ub + al64((size_t)R * Ht); float* hbar = h + al64((size_t)R * H1); float* hpb = hbar + al64((size_t)R * H1);
-    const float* ctext = cls_text;
-    if (!ctext) {                                                        // first support row of each class (fumi.py:207-210)
-        if ((rc = launch_class_text_select(st, B, N, S, Dt, text_s, y_s, c, ws->status))) return rc;
-        ctext = c;
+    if ((rc = side_reserve(ws, hyper_head_floats(R, Dt, Ht, H1), &side))) return rc;
+    HyperHead hd = hyper_head_carve(side, R, Dt, Ht, H1, tanh_head, phi, cls_text);   // the hypernetwork behind the head (meta_front.h)
+    if (!hd.ctext) {                                                     // first support row of each class (fumi.py:207-210)
+        if ((rc = launch_class_text_select(st, B, N, S, Dt, text_s, y_s, hd.c, ws->status))) return rc;
+        hd.ctext = hd.c;
     }
-    GemmArgs g = gemm_args(R, Ht, Dt, ctext, Dt, phi[0], Dt, u, Ht);
-    g.bias = phi[1]; g.act = 1;
-    if ((rc = launch_gemm(st, g, 0, 0))) return rc;
-    g = gemm_args(R, H1, Ht, u, Ht, phi[2], Ht, h, H1);
-    g.bias = phi[3]; g.act = tanh_head ? 2 : 0;
-    if ((rc = launch_gemm(st, g, 0, 0))) return rc;
-    p.head = h; p.head_bar = hbar;
-    if ((rc = run_rn12_episodes(ws, st, p))) { rn_abandon(ws); return rc; }
+    if ((rc = hyper_head_fwd_gemm(st, hd))) return rc;
+    p.head = hd.h; p.head_bar = hd.hbar;
+    if ((rc = run_rn12_episodes(ws, st, p))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
-    const float* hp = hbar;
-    if (tanh_head) { if ((rc = launch_tanh_bwd(st, (long)R * H1, h, hbar, hpb))) return rc; hp = hpb; }
-    g = gemm_args(H1, Ht, R, hp, H1, u, Ht, g_phi[2], Ht);               // gA1 = hp^T u
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(st, g, 1, 1))) return rc;
-    if ((rc = launch_colsum(st, hp, R, H1, H1, grad_scale, g_phi[3]))) return rc;
-    g = gemm_args(R, Ht, H1, hp, H1, phi[2], Ht, ub, Ht);                // ubar = (hp A1) * relu'(u)
-    g.mask = u;
-    if ((rc = launch_gemm(st, g, 0, 1))) return rc;
-    g = gemm_args(Ht, Dt, R, ub, Ht, ctext, Dt, g_phi[0], Dt);           // gA0 = ubar^T c
-    g.alpha = grad_scale;
-    if ((rc = launch_gemm(st, g, 1, 1))) return rc;
-    if (float* tg = ws->text_grad) {                                     // armed by fumi_hip_want_text_grad: scale * ubar A0  [R,Dt]
-        ws->text_grad = nullptr;
-        g = gemm_args(R, Dt, Ht, ub, Ht, phi[0], Dt, tg, Dt);
-        g.alpha = grad_scale;
-        if ((rc = launch_gemm(st, g, 0, 1))) return rc;
-    }
-    return launch_colsum(st, ub, R, Ht, Ht, grad_scale, g_phi[1]);
+    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, &ws->text_grad);   // (consumes a text gradient armed by fumi_hip_want_text_grad)
 }
 
 // Forward only: feats [G*M, F] = ResNet12(x [G, M, Cin, H, W]) with the batch statistics of every group of M images taken separately.
@@ -1058,7 +989,7 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
     const size_t img = (size_t)Cin * H * W;
     const int F = c0.n.F;
     auto run = [&]() -> int {
-        TRY(rn_fork_lanes(ws, st, pl.lanes));
+        TRY(ws_fork_lanes(ws, st, pl.lanes));
         for (int i = 0; i < pl.lanes; ++i) {                               // theta's slab of each lane (n.B = Bc)
             TRY(slot_from_theta(cx[i].st, cx[i].n, theta, L[i].params));
             TRY(frags_of_slot(cx[i].st, cx[i].n, L[i].params, L[i].frags));
@@ -1075,9 +1006,9 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
             TRY(forward_pass(c, S, img_s, L[lane].params, L[lane].frags, ps, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
             TRY(forward_pass(c, Qn, img_q, L[lane].params, L[lane].frags, pq, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
         }
-        return rn_join_lanes(ws, st, pl.lanes);
+        return ws_join_lanes(ws, st, pl.lanes);
     };
-    if ((rc = run())) { rn_abandon(ws); return rc; }
+    if ((rc = run())) { ws_abandon_lanes(ws); return rc; }
     g_rn_enc_last = pl;
     if (keep_tape) {
         RnEncToken& t = g_rn_enc;
@@ -1120,7 +1051,7 @@ int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int
     const size_t img = (size_t)Cin * H * W;
     const int F = n0.F;
     auto run = [&]() -> int {
-        TRY(rn_fork_lanes(ws, st, pl.lanes));
+        TRY(ws_fork_lanes(ws, st, pl.lanes));
         for (int k = 0; k < pl.nchunks; ++k) {
             const int lane = k % pl.lanes, b0 = k * pl.Bc, bc = B - b0 < pl.Bc ? B - b0 : pl.Bc;
             RnCtx& c = cx[lane];
@@ -1144,12 +1075,12 @@ int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int
             }
             TRY(backward_pass(c, Qn, img_q, L[lane].frags, pq, nullptr, Gq + (size_t)b0 * n0.PSZ, nullptr));
         }
-        TRY(rn_join_lanes(ws, st, pl.lanes));
+        TRY(ws_join_lanes(ws, st, pl.lanes));
         // one sum over the 2 B slabs (support and query of every episode) in a fixed order, whatever the chunks and lanes were
         TRY(launch_reduce_batched(st, 1, 2 * B, n0.PSZ, Gs, scale, gsum, 0));
         return theta_grads_out(st, n0, gsum, g_theta);
     };
-    if ((rc = run())) { rn_abandon(ws); return rc; }
+    if ((rc = run())) { ws_abandon_lanes(ws); return rc; }
     return FUMI_OK;
 }
 

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the HIP stream; every tensor
 library as a raw device pointer.  There is NO CPU fallback: if the library is missing, or a tensor
 is not on a GPU, these functions raise.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -118,20 +119,25 @@ def lib():
         L.fumi_hip_get_profile.argtypes = [c_void_p, c_int, POINTER(ctypes.c_double), POINTER(c_int)]
         L.fumi_hip_phase_name.argtypes = [c_int]
         L.fumi_hip_phase_name.restype = c_char_p
-        PP = POINTER(c_void_p)
-        L.fumi_hip_fumi_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_int), c_int, c_int, c_int, c_float, c_int, c_int, c_float,
-                                                 c_float, ctypes.c_uint64]
-            + [c_void_p] * 6 + [PP, PP] + [c_void_p] * 6 + [PP, PP])
-        L.fumi_hip_fumi_step_indexed.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_int), c_int, c_int, c_int, c_float, c_int, c_int, c_float,
-                                                 c_float, ctypes.c_uint64]
-            + [c_void_p, c_int64] + [c_void_p] * 6 + [PP, PP] + [c_void_p] * 6 + [PP, PP])
-        L.fumi_hip_maml_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_int), c_int, c_float, c_int, c_int, c_float]
-            + [c_void_p] * 4 + [PP] + [c_void_p] * 6 + [PP])
-        L.fumi_hip_am3_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 10 + [c_float, c_float, ctypes.c_uint64] + [c_void_p] * 5 + [PP] + [c_void_p] * 4 + [PP, c_void_p])
+        PP, PI = POINTER(c_void_p), POINTER(c_int)
+        # the step entry points' argument lists, from the pieces include/fumi_hip.h writes them in (tests/test_abi.py holds every list
+        # to the header, argument by argument)
+        front = [c_void_p, c_void_p]                                   # ws, stream
+        mlp = [c_int] * 6 + [PI]                                       # B, N, S, Qn, D, n_hidden, hid
+        img = [c_int] * 8                                              # B, N, S, Qn, Cin, H, W, nblk
+        text_dims = [c_int, c_int]                                     # Dt, Ht
+        inner = [c_int, c_float, c_int, c_int, c_float]                # T, alpha, tanh_head | first_order, need_grad, grad_scale
+        drop = [c_float, ctypes.c_uint64]                              # dropout_p, seed
+        episodes = [c_void_p] * 4                                      # x_s | idx_s, y_s, x_q | idx_q, y_q
+        text_in = [c_void_p] * 2                                       # cls_text, text_s
+        outs = [c_void_p] * 6                                          # logits_q, preds_q, preds_q_f32, loss_b, acc_b + stats
+        fumi_io = episodes + text_in + [PP, PP] + outs + [PP, PP]      # ... theta, phi ... g_theta, g_phi
+        maml_io = episodes + [PP] + outs + [PP]                        # ... params ... g_params
+        L.fumi_hip_fumi_step.argtypes = front + mlp + text_dims + inner + drop + fumi_io
+        L.fumi_hip_fumi_step_indexed.argtypes = front + mlp + text_dims + inner + drop + [c_void_p, c_int64] + fumi_io    # table, n_rows
+        L.fumi_hip_maml_step.argtypes = front + mlp + inner + maml_io
+        L.fumi_hip_am3_step.argtypes = (front + [c_int] * 10 + [c_float] + drop        # B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad
+                                        + episodes + [c_void_p, PP] + [c_void_p] * 4 + [PP, c_void_p])   # text_s, w | 4 outputs | g_w, stats
         L.fumi_hip_am3_step_dx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p, c_void_p]
         L.fumi_hip_am3_step_tx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p]
         L.fumi_hip_am3_step_tx_dx.argtypes = L.fumi_hip_am3_step_tx.argtypes + [c_void_p, c_void_p]
@@ -177,21 +183,12 @@ def lib():
         L.fumi_hip_publish_scalars_deferred.argtypes = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_uint64]
         L.fumi_hip_publish_flush.argtypes = [c_void_p, c_void_p]
         L.fumi_hip_conv4_feature_dim.argtypes = [c_int] * 3
-        L.fumi_hip_fumi_conv4_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 10 + [c_int, c_float, c_int, c_int, c_float]
-            + [c_void_p] * 6 + [PP, PP] + [c_void_p] * 6 + [PP, PP])
-        L.fumi_hip_maml_conv4_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 8 + [c_int, c_float, c_int, c_int, c_float]
-            + [c_void_p] * 4 + [PP] + [c_void_p] * 6 + [PP])
+        L.fumi_hip_fumi_conv4_step.argtypes = front + img + text_dims + inner + fumi_io
+        L.fumi_hip_maml_conv4_step.argtypes = front + img + inner + maml_io
         L.fumi_hip_conv4_set_option.argtypes = [c_int, c_int]
-        PI = POINTER(c_int)
         L.fumi_hip_resnet12_set_budget.argtypes = [ctypes.c_double]
-        L.fumi_hip_fumi_resnet12_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 8 + [PI, c_int, c_int] + [c_int, c_float, c_int, c_int, c_float, c_int]
-            + [c_void_p] * 6 + [PP, PP] + [c_void_p] * 6 + [PP, PP])
-        L.fumi_hip_maml_resnet12_step.argtypes = (
-            [c_void_p, c_void_p] + [c_int] * 8 + [PI] + [c_int, c_float, c_int, c_int, c_float, c_int]
-            + [c_void_p] * 4 + [PP] + [c_void_p] * 6 + [PP])
+        L.fumi_hip_fumi_resnet12_step.argtypes = front + img + [PI] + text_dims + inner + [c_int] + fumi_io       # channels | chunk
+        L.fumi_hip_maml_resnet12_step.argtypes = front + img + [PI] + inner + [c_int] + maml_io
         L.fumi_hip_resnet12_features.argtypes = [c_void_p, c_void_p] + [c_int] * 6 + [PI, c_void_p, PP, c_void_p]
         L.fumi_hip_resnet12_encode.argtypes = ([c_void_p, c_void_p] + [c_int] * 7 + [PI, c_void_p, c_void_p, PP, c_void_p, c_void_p,
                                                                                   c_int])
@@ -458,6 +455,13 @@ def _paramset(key_lists, dims, build):
     return val
 
 
+def _step_outputs(dev, B, Qn, N):
+    """logits, preds, preds_f (the reference's float test_preds, same launch), loss_b, acc_b of a meta-step."""
+    return (torch.empty(B, Qn, N, device=dev, dtype=torch.float32), torch.empty(B, Qn, device=dev, dtype=torch.int64),
+            torch.empty(B, Qn, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32),
+            torch.empty(B, device=dev, dtype=torch.float32))
+
+
 def _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head,
                cls_text, text_s, need_grad, grad_scale, g_theta, g_phi, stats=None, dropout_p=0.0, seed=0):
     L = lib()
@@ -484,11 +488,7 @@ def _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, 
         _shape(cls_text, (B, N, Dt), "cls_text")
     else:
         _shape(text_s, (B, S, Dt), "text_s")
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    preds_f = torch.empty(B, Qn, device=dev, dtype=torch.float32)      # the reference's float test_preds, same launch
-    loss_b = torch.empty(B, device=dev, dtype=torch.float32)
-    acc_b = torch.empty(B, device=dev, dtype=torch.float32)
+    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
     if need_grad:
         if g_theta is None:
             g_theta = [torch.empty_like(t) for t in theta]
@@ -538,11 +538,7 @@ def maml_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, ne
     if need_grad and g_params is not None:
         for i, (g, t) in enumerate(zip(g_params, params)):
             _shape(g, t.shape, f"g_params[{i}]")
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    preds_f = torch.empty(B, Qn, device=dev, dtype=torch.float32)      # the reference's float test_preds, same launch
-    loss_b = torch.empty(B, device=dev, dtype=torch.float32)
-    acc_b = torch.empty(B, device=dev, dtype=torch.float32)
+    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
     if need_grad and g_params is None:
         g_params = [torch.empty_like(t) for t in params]
     if grad_scale is None:
@@ -1118,24 +1114,6 @@ def conv4_feature_dim(nblk, H, W):
     return int(lib().fumi_hip_conv4_feature_dim(int(nblk), int(H), int(W)))
 
 
-def _conv4_shapes(x_s, y_s, x_q, y_q, theta):
-    if x_s.dim() != 5 or x_q.dim() != 5:
-        raise FumiHipError("conv4: images must be [B, rows, Cin, H, W]")
-    B, S, Cin, H, W = x_s.shape
-    Qn = x_q.shape[1]
-    if len(theta) % 3 or not theta:
-        raise FumiHipError("conv4: theta must hold (conv weight, BN weight, BN bias) per block")
-    nblk = len(theta) // 3
-    _shape(x_q, (B, Qn, Cin, H, W), "x_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
-    for l in range(nblk):
-        _shape(theta[3 * l], (64, Cin if l == 0 else 64, 3, 3), f"theta[{3 * l}] (conv weight of block {l})")
-        _shape(theta[3 * l + 1], (64,), f"theta[{3 * l + 1}]"); _shape(theta[3 * l + 2], (64,), f"theta[{3 * l + 2}]")
-    F = conv4_feature_dim(nblk, H, W)
-    if F < 64:
-        raise FumiHipError(f"conv4: {H}x{W} images are too small for {nblk} blocks")
-    return B, S, Qn, Cin, H, W, nblk, F
-
-
 CONV4_MAX_TAPED_STEPS = 32
 
 
@@ -1147,75 +1125,38 @@ def _conv4_tape_limit(T, need_grad, second_order):
                            f"meta-gradient (first-order steps and evaluation take any number)")
 
 
-def _step_outputs(dev, B, Qn, N):
-    return (torch.empty(B, Qn, N, device=dev, dtype=torch.float32), torch.empty(B, Qn, device=dev, dtype=torch.int64),
-            torch.empty(B, Qn, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32),
-            torch.empty(B, device=dev, dtype=torch.float32))
+def _ci(v):
+    return (c_int * len(v))(*[int(x) for x in v])
 
 
-def fumi_conv4_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
-                    need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None):
-    """FuMI meta-step with the Conv4 encoder (fumi/models/fumi.py:146-192 with im_net = Conv4)."""
-    _conv4_tape_limit(T, need_grad, True)
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, F = _conv4_shapes(x_s, y_s, x_q, y_q, theta)
-    N = int(n_way)
-    Ht, Dt = int(phi[0].shape[0]), int(phi[0].shape[1])
-    _shape(phi[1], (Ht,), "phi[1]"); _shape(phi[2], (F + 1, Ht), "phi[2]"); _shape(phi[3], (F + 1,), "phi[3]")
-    if cls_text is not None:
-        _shape(cls_text, (B, N, Dt), "cls_text")
-    else:
-        _shape(text_s, (B, S, Dt), "text_s")
-    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
-    if need_grad:
-        g_theta = [torch.empty_like(t) for t in theta] if g_theta is None else g_theta
-        g_phi = [torch.empty_like(t) for t in phi] if g_phi is None else g_phi
-    rc = lib().fumi_hip_fumi_conv4_step(
-        ws.handle, _stream(dev), B, N, S, Qn, Cin, H, W, nblk, Dt, Ht, int(T), float(alpha), int(bool(tanh_head)),
-        int(bool(need_grad)), float(1.0 / B if grad_scale is None else grad_scale),
-        _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"),
-        _f32(cls_text, "cls_text") if cls_text is not None else None, _f32(text_s, "text_s") if text_s is not None else None,
-        _parr(theta, "theta"), _parr(phi, "phi"),
-        _f32(logits, "logits"), _i64(preds, "preds"), _f32(preds_f, "preds_f"), _f32(loss_b, "loss_b"), _f32(acc_b, "acc_b"),
-        _f32(stats, "stats") if stats is not None else None,
-        _parr(g_theta, "g_theta") if need_grad else None, _parr(g_phi, "g_phi") if need_grad else None)
-    _check(rc, "fumi_hip_fumi_conv4_step")
-    return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_theta=g_theta, g_phi=g_phi, stats=stats)
-
-
-def maml_conv4_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, need_grad=True, grad_scale=None,
-                    g_params=None, stats=None):
-    """MAML meta-step with the Conv4 encoder: params = theta (3 per block) + [lin_final W [N,F], b [N]]."""
-    _conv4_tape_limit(T, need_grad, not first_order)
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, F = _conv4_shapes(x_s, y_s, x_q, y_q, params[:-2])
-    N = int(params[-2].shape[0])
-    _shape(params[-2], (N, F), "lin_final.weight"); _shape(params[-1], (N,), "lin_final.bias")
-    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
-    if need_grad and g_params is None:
-        g_params = [torch.empty_like(t) for t in params]
-    rc = lib().fumi_hip_maml_conv4_step(
-        ws.handle, _stream(dev), B, N, S, Qn, Cin, H, W, nblk, int(T), float(alpha), int(bool(first_order)),
-        int(bool(need_grad)), float(1.0 / B if grad_scale is None else grad_scale),
-        _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"), _parr(params, "params"),
-        _f32(logits, "logits"), _i64(preds, "preds"), _f32(preds_f, "preds_f"), _f32(loss_b, "loss_b"), _f32(acc_b, "acc_b"),
-        _f32(stats, "stats") if stats is not None else None, _parr(g_params, "g_params") if need_grad else None)
-    _check(rc, "fumi_hip_maml_conv4_step")
-    return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_params=g_params, stats=stats)
-
-
-# ---- ResNet-12 (bf16) -----------------------------------------------------------------------------------------------
-def _resnet12_shapes(x_s, y_s, x_q, y_q, theta):
+def _image_dims(name, per_block, layout, x_s, y_s, x_q, y_q, theta):
     if x_s.dim() != 5 or x_q.dim() != 5:
-        raise FumiHipError("resnet12: images must be [B, rows, Cin, H, W]")
+        raise FumiHipError(f"{name}: images must be [B, rows, Cin, H, W]")
     B, S, Cin, H, W = x_s.shape
     Qn = x_q.shape[1]
-    if len(theta) % 12 or not theta:
-        raise FumiHipError("resnet12: theta must hold 12 tensors per block (W1,g1,b1, W2,g2,b2, W3,g3,b3, Ws,gs,bs)")
-    nblk = len(theta) // 12
+    if len(theta) % per_block or not theta:
+        raise FumiHipError(f"{name}: theta must hold {layout} per block")
     _shape(x_q, (B, Qn, Cin, H, W), "x_q")
-    if y_s is not None or y_q is not None:         # (the encoder pair has no labels)
+    if y_s is not None or y_q is not None:         # (the encoder pair and the feature call have no labels)
         _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
+    return B, S, Qn, Cin, H, W, len(theta) // per_block
+
+
+def _conv4_shapes(x_s, y_s, x_q, y_q, theta):
+    dims = _image_dims("conv4", 3, "(conv weight, BN weight, BN bias)", x_s, y_s, x_q, y_q, theta)
+    Cin, H, W, nblk = dims[3:]
+    for l in range(nblk):
+        _shape(theta[3 * l], (64, Cin if l == 0 else 64, 3, 3), f"theta[{3 * l}] (conv weight of block {l})")
+        _shape(theta[3 * l + 1], (64,), f"theta[{3 * l + 1}]"); _shape(theta[3 * l + 2], (64,), f"theta[{3 * l + 2}]")
+    F = conv4_feature_dim(nblk, H, W)
+    if F < 64:
+        raise FumiHipError(f"conv4: {H}x{W} images are too small for {nblk} blocks")
+    return dims, F, ()
+
+
+def _resnet12_shapes(x_s, y_s, x_q, y_q, theta):
+    dims = _image_dims("resnet12", 12, "12 tensors (W1,g1,b1, W2,g2,b2, W3,g3,b3, Ws,gs,bs)", x_s, y_s, x_q, y_q, theta)
+    Cin, H, W, nblk = dims[3:]
     channels, ci = [], Cin
     for l in range(nblk):
         c = int(theta[12 * l].shape[0])
@@ -1228,117 +1169,178 @@ def _resnet12_shapes(x_s, y_s, x_q, y_q, theta):
         channels.append(c); ci = c
     if min(H, W) >> nblk < 1:
         raise FumiHipError(f"resnet12: {H}x{W} images are too small for {nblk} blocks")
-    return B, S, Qn, Cin, H, W, nblk, channels
+    return dims, channels[-1], (_ci(channels),)
 
 
-def _ci(v):
-    return (c_int * len(v))(*[int(x) for x in v])
+# What differs between the two encoders' wrappers.  shapes(x_s, y_s, x_q, y_q, theta) checks every shape (the kernels index raw
+# pointers with the sizes they are told) and returns ((B, S, Qn, Cin, H, W, nblk), feature width F, the integer arguments the entry
+# points take after nblk).  Symbols: fumi_hip_{fumi,maml}_<name>_step, fumi_hip_<name>_{encode,encode_bwd,features}.
+_Encoder = collections.namedtuple("_Encoder", "name per_block shapes")
+_CONV4 = _Encoder("conv4", 3, _conv4_shapes)
+_RESNET12 = _Encoder("resnet12", 12, _resnet12_shapes)
 
 
-def resnet12_set_budget(gigabytes):
-    """Workspace budget (GB) from which the episode chunk of the ResNet-12 steps is derived (0: default 200)."""
-    _check(lib().fumi_hip_resnet12_set_budget(float(gigabytes)), "fumi_hip_resnet12_set_budget")
+def _inner_args(B, T, alpha, flag, need_grad, grad_scale, tail):
+    """T, alpha, tanh_head | first_order, need_grad, grad_scale [, chunk] as the step entry points take them."""
+    return (int(T), float(alpha), int(bool(flag)), int(bool(need_grad)), float(1.0 / B if grad_scale is None else grad_scale), *tail)
 
 
-def fumi_resnet12_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
-                       need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, chunk=0):
-    """FuMI meta-step with the bf16 ResNet-12 encoder (fumi/models/fumi.py:146-192 with im_net = ResNet-12)."""
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_shapes(x_s, y_s, x_q, y_q, theta)
-    N, F = int(n_way), channels[-1]
+def _enc_step(enc, kind, ws, N, x_s, y_s, x_q, y_q, dims, scalars, inputs, stats, grads):
+    """The call both step kinds share: image dims, the scalars after nblk, the episodes, inputs, the five outputs + stats, gradients."""
+    dev, (B, S, Qn) = _dev(x_s), dims[:3]
+    outs = _step_outputs(dev, B, Qn, N)
+    sym = f"fumi_hip_{kind}_{enc.name}_step"
+    rc = getattr(lib(), sym)(
+        ws.handle, _stream(dev), B, N, *dims[1:], *scalars,
+        _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"), *inputs,
+        _f32(outs[0], "logits"), _i64(outs[1], "preds"), _f32(outs[2], "preds_f"), _f32(outs[3], "loss_b"), _f32(outs[4], "acc_b"),
+        _f32(stats, "stats") if stats is not None else None, *grads)
+    _check(rc, sym)
+    return dict(logits=outs[0], preds=outs[1], preds_f=outs[2], loss_b=outs[3], acc_b=outs[4], stats=stats)
+
+
+def _enc_fumi_step(enc, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad, grad_scale,
+                   g_theta, g_phi, stats, tail=()):
+    dims, F, extra = enc.shapes(x_s, y_s, x_q, y_q, theta)
+    B, S, N = dims[0], dims[1], int(n_way)
     Ht, Dt = int(phi[0].shape[0]), int(phi[0].shape[1])
     _shape(phi[1], (Ht,), "phi[1]"); _shape(phi[2], (F + 1, Ht), "phi[2]"); _shape(phi[3], (F + 1,), "phi[3]")
     if cls_text is not None:
         _shape(cls_text, (B, N, Dt), "cls_text")
     else:
         _shape(text_s, (B, S, Dt), "text_s")
-    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
     if need_grad:
         g_theta = [torch.empty_like(t) for t in theta] if g_theta is None else g_theta
         g_phi = [torch.empty_like(t) for t in phi] if g_phi is None else g_phi
-    rc = lib().fumi_hip_fumi_resnet12_step(
-        ws.handle, _stream(dev), B, N, S, Qn, Cin, H, W, nblk, _ci(channels), Dt, Ht, int(T), float(alpha), int(bool(tanh_head)),
-        int(bool(need_grad)), float(1.0 / B if grad_scale is None else grad_scale), int(chunk),
-        _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"),
-        _f32(cls_text, "cls_text") if cls_text is not None else None, _f32(text_s, "text_s") if text_s is not None else None,
-        _parr(theta, "theta"), _parr(phi, "phi"),
-        _f32(logits, "logits"), _i64(preds, "preds"), _f32(preds_f, "preds_f"), _f32(loss_b, "loss_b"), _f32(acc_b, "acc_b"),
-        _f32(stats, "stats") if stats is not None else None,
-        _parr(g_theta, "g_theta") if need_grad else None, _parr(g_phi, "g_phi") if need_grad else None)
-    _check(rc, "fumi_hip_fumi_resnet12_step")
-    return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_theta=g_theta, g_phi=g_phi, stats=stats)
+    out = _enc_step(enc, "fumi", ws, N, x_s, y_s, x_q, y_q, dims,
+                    (*extra, Dt, Ht, *_inner_args(B, T, alpha, tanh_head, need_grad, grad_scale, tail)),
+                    (_f32(cls_text, "cls_text") if cls_text is not None else None,
+                     _f32(text_s, "text_s") if text_s is not None else None, _parr(theta, "theta"), _parr(phi, "phi")), stats,
+                    (_parr(g_theta, "g_theta") if need_grad else None, _parr(g_phi, "g_phi") if need_grad else None))
+    out.update(g_theta=g_theta, g_phi=g_phi)
+    return out
+
+
+def _enc_maml_step(enc, ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order, need_grad, grad_scale, g_params, stats, tail=()):
+    dims, F, extra = enc.shapes(x_s, y_s, x_q, y_q, params[:-2])
+    N = int(params[-2].shape[0])
+    _shape(params[-2], (N, F), "lin_final.weight"); _shape(params[-1], (N,), "lin_final.bias")
+    if need_grad and g_params is None:
+        g_params = [torch.empty_like(t) for t in params]
+    out = _enc_step(enc, "maml", ws, N, x_s, y_s, x_q, y_q, dims,
+                    (*extra, *_inner_args(dims[0], T, alpha, first_order, need_grad, grad_scale, tail)),
+                    (_parr(params, "params"),), stats, (_parr(g_params, "g_params") if need_grad else None,))
+    out.update(g_params=g_params)
+    return out
+
+
+def _enc_features(enc, ws, x, theta):
+    dev = _dev(x)
+    dims, F, extra = enc.shapes(x, None, x, None, theta)
+    G, M = dims[:2]
+    feats = torch.empty(G, M, F, device=dev, dtype=torch.float32)
+    sym = f"fumi_hip_{enc.name}_features"
+    _check(getattr(lib(), sym)(ws.handle, _stream(dev), G, M, *dims[3:], *extra, _f32(x, "x"), _parr(theta, "theta"),
+                               _f32(feats, "feats")), sym)
+    return feats
+
+
+def _enc_encode(enc, ws, x_s, x_q, theta, keep_tape):
+    dev = _dev(x_s)
+    dims, F, extra = enc.shapes(x_s, None, x_q, None, theta)
+    B, S, Qn = dims[:3]
+    fs = torch.empty(B, S, F, device=dev, dtype=torch.float32)
+    fq = torch.empty(B, Qn, F, device=dev, dtype=torch.float32)
+    sym = f"fumi_hip_{enc.name}_encode"
+    _check(getattr(lib(), sym)(ws.handle, _stream(dev), *dims, *extra, _f32(x_s, "x_s"), _f32(x_q, "x_q"), _parr(theta, "theta"),
+                               _f32(fs, "feats_s"), _f32(fq, "feats_q"), int(bool(keep_tape))), sym)
+    return fs, fq
+
+
+def _enc_encode_bwd(enc, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta):
+    dev = _dev(x_s)
+    dims, F, extra = enc.shapes(x_s, None, x_q, None, theta_like)
+    B, S, Qn = dims[:3]
+    _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q")
+    if g_theta is None:
+        g_theta = [torch.empty_like(t) for t in theta_like]
+    elif len(g_theta) != len(theta_like):
+        raise FumiHipError(f"{enc.name}_encode_bwd: g_theta must hold one tensor per theta tensor")
+    else:
+        for i, (g, t) in enumerate(zip(g_theta, theta_like)):
+            _shape(g, tuple(t.shape), f"g_theta[{i}]")
+    sym = f"fumi_hip_{enc.name}_encode_bwd"
+    _check(getattr(lib(), sym)(ws.handle, _stream(dev), *dims, *extra, _f32(x_s, "x_s"), _f32(x_q, "x_q"), _f32(dfeats_s, "dfeats_s"),
+                               _f32(dfeats_q, "dfeats_q"), float(scale), _parr(g_theta, "g_theta")), sym)
+    return g_theta
+
+
+def fumi_conv4_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
+                    need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None):
+    """FuMI meta-step with the Conv4 encoder (fumi/models/fumi.py:146-192 with im_net = Conv4)."""
+    _conv4_tape_limit(T, need_grad, True)
+    return _enc_fumi_step(_CONV4, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad,
+                          grad_scale, g_theta, g_phi, stats)
+
+
+def maml_conv4_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, need_grad=True, grad_scale=None,
+                    g_params=None, stats=None):
+    """MAML meta-step with the Conv4 encoder: params = theta (3 per block) + [lin_final W [N,F], b [N]]."""
+    _conv4_tape_limit(T, need_grad, not first_order)
+    return _enc_maml_step(_CONV4, ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order, need_grad, grad_scale, g_params, stats)
+
+
+def conv4_features(ws, x, theta):
+    """[G, M, F] = Conv4(x [G, M, Cin, H, W]) with the batch statistics of each group of M images (forward only)."""
+    return _enc_features(_CONV4, ws, x, theta)
+
+
+def conv4_encode(ws, x_s, x_q, theta, keep_tape=False):
+    """(feats_s [B,S,F], feats_q [B,Qn,F]) = Conv4 of every episode's support / query images (one batch-statistics group each).
+    keep_tape: the activations stay laid out in ``ws`` for ``conv4_encode_bwd`` -- no other call may use ``ws`` in between."""
+    return _enc_encode(_CONV4, ws, x_s, x_q, theta, keep_tape)
+
+
+def conv4_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_theta=None):
+    """Gradient of sum <dfeats, Conv4(x)> w.r.t. the encoder's parameters (summed over episodes, times ``scale``) from the tape the
+    last ``conv4_encode(..., keep_tape=True)`` left in ``ws``."""
+    return _enc_encode_bwd(_CONV4, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta)
+
+
+def fumi_resnet12_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
+                       need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, chunk=0):
+    """FuMI meta-step with the bf16 ResNet-12 encoder (fumi/models/fumi.py:146-192 with im_net = ResNet-12)."""
+    return _enc_fumi_step(_RESNET12, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad,
+                          grad_scale, g_theta, g_phi, stats, (int(chunk),))
 
 
 def maml_resnet12_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, need_grad=True, grad_scale=None,
                        g_params=None, stats=None, chunk=0):
     """MAML meta-step with the bf16 ResNet-12 encoder: params = theta (12 per block) + [lin_final W [N,F], b [N]]."""
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_shapes(x_s, y_s, x_q, y_q, params[:-2])
-    N, F = int(params[-2].shape[0]), channels[-1]
-    _shape(params[-2], (N, F), "lin_final.weight"); _shape(params[-1], (N,), "lin_final.bias")
-    logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
-    if need_grad:
-        g_params = [torch.empty_like(t) for t in params] if g_params is None else g_params
-    rc = lib().fumi_hip_maml_resnet12_step(
-        ws.handle, _stream(dev), B, N, S, Qn, Cin, H, W, nblk, _ci(channels), int(T), float(alpha), int(bool(first_order)),
-        int(bool(need_grad)), float(1.0 / B if grad_scale is None else grad_scale), int(chunk),
-        _f32(x_s, "x_s"), _i64(y_s, "y_s"), _f32(x_q, "x_q"), _i64(y_q, "y_q"), _parr(params, "params"),
-        _f32(logits, "logits"), _i64(preds, "preds"), _f32(preds_f, "preds_f"), _f32(loss_b, "loss_b"), _f32(acc_b, "acc_b"),
-        _f32(stats, "stats") if stats is not None else None, _parr(g_params, "g_params") if need_grad else None)
-    _check(rc, "fumi_hip_maml_resnet12_step")
-    return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_params=g_params, stats=stats)
+    return _enc_maml_step(_RESNET12, ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order, need_grad, grad_scale, g_params, stats,
+                          (int(chunk),))
 
 
 def resnet12_features(ws, x, theta):
     """feats [G, M, F] = ResNet12(x [G, M, Cin, H, W]); batch statistics per group of M images."""
-    dev = _dev(x)
-    G, M, Cin, H, W = x.shape
-    nblk = len(theta) // 12
-    channels = [int(theta[12 * l].shape[0]) for l in range(nblk)]
-    feats = torch.empty(G, M, channels[-1], device=dev, dtype=torch.float32)
-    _check(lib().fumi_hip_resnet12_features(ws.handle, _stream(dev), G, M, Cin, H, W, nblk, _ci(channels), _f32(x, "x"),
-                                            _parr(theta, "theta"), _f32(feats, "feats")), "fumi_hip_resnet12_features")
-    return feats
-
-
-def _resnet12_encode_shapes(what, x_s, x_q, theta):
-    if x_s.dim() != 5 or x_q.dim() != 5 or x_s.shape[0] != x_q.shape[0] or x_s.shape[2:] != x_q.shape[2:]:
-        raise FumiHipError(f"{what}: x_s [B,S,C,H,W] and x_q [B,Qn,C,H,W] expected")
-    return _resnet12_shapes(x_s, None, x_q, None, theta)
+    return _enc_features(_RESNET12, ws, x, theta)
 
 
 def resnet12_encode(ws, x_s, x_q, theta, keep_tape=False):
     """(feats_s [B,S,F], feats_q [B,Qn,F]) = ResNet-12 of every episode's support / query images (one batch-statistics group each).
     keep_tape: what the backward needs stays in ``ws`` for ``resnet12_encode_bwd`` -- no other call may use ``ws`` in between."""
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_encode_shapes("resnet12_encode", x_s, x_q, theta)
-    F = channels[-1]
-    fs = torch.empty(B, S, F, device=dev, dtype=torch.float32)
-    fq = torch.empty(B, Qn, F, device=dev, dtype=torch.float32)
-    _check(lib().fumi_hip_resnet12_encode(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _ci(channels), _f32(x_s, "x_s"),
-                                          _f32(x_q, "x_q"), _parr(theta, "theta"), _f32(fs, "feats_s"), _f32(fq, "feats_q"),
-                                          int(bool(keep_tape))), "fumi_hip_resnet12_encode")
-    return fs, fq
+    return _enc_encode(_RESNET12, ws, x_s, x_q, theta, keep_tape)
 
 
 def resnet12_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_theta=None):
     """Gradient of sum <dfeats, ResNet12(x)> w.r.t. the encoder's parameters (summed over episodes, times ``scale``) from what the
     last ``resnet12_encode(..., keep_tape=True)`` left in ``ws``."""
-    dev = _dev(x_s)
-    B, S, Qn, Cin, H, W, nblk, channels = _resnet12_encode_shapes("resnet12_encode_bwd", x_s, x_q, theta_like)
-    F = channels[-1]
-    _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q")
-    if g_theta is None:
-        g_theta = [torch.empty_like(t) for t in theta_like]
-    elif len(g_theta) != len(theta_like):
-        raise FumiHipError("resnet12_encode_bwd: g_theta must hold one tensor per theta tensor")
-    else:
-        for i, (g, t) in enumerate(zip(g_theta, theta_like)):
-            _shape(g, tuple(t.shape), f"g_theta[{i}]")
-    _check(lib().fumi_hip_resnet12_encode_bwd(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _ci(channels), _f32(x_s, "x_s"),
-                                              _f32(x_q, "x_q"), _f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), float(scale),
-                                              _parr(g_theta, "g_theta")), "fumi_hip_resnet12_encode_bwd")
-    return g_theta
+    return _enc_encode_bwd(_RESNET12, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta)
+
+
+def resnet12_set_budget(gigabytes):
+    """Workspace budget (GB) from which the episode chunk of the ResNet-12 steps is derived (0: default 200)."""
+    _check(lib().fumi_hip_resnet12_set_budget(float(gigabytes)), "fumi_hip_resnet12_set_budget")
 
 
 def resnet12_encode_plan():
@@ -1454,55 +1456,6 @@ def rn12_probe(ws, device, pass_, kind, block=0, idx=0):
 def conv4_set_option(key, value):
     """fumi_hip_conv4_set_option: key 0 = fused block 1 (default 1)."""
     _check(lib().fumi_hip_conv4_set_option(int(key), int(value)), "fumi_hip_conv4_set_option")
-
-
-def conv4_features(ws, x, theta):
-    """[G, M, F] = Conv4(x [G, M, Cin, H, W]) with the batch statistics of each group of M images (forward only)."""
-    dev = _dev(x)
-    if x.dim() != 5:
-        raise FumiHipError("conv4_features: x must be [groups, images, Cin, H, W]")
-    G, M, Cin, H, W = x.shape
-    nblk = len(theta) // 3
-    F = conv4_feature_dim(nblk, H, W)
-    out = torch.empty(G, M, F, device=dev, dtype=torch.float32)
-    _check(lib().fumi_hip_conv4_features(ws.handle, _stream(dev), G, M, Cin, H, W, nblk, _f32(x, "x"), _parr(theta, "theta"),
-                                         _f32(out, "feats")), "fumi_hip_conv4_features")
-    return out
-
-
-def conv4_encode(ws, x_s, x_q, theta, keep_tape=False):
-    """(feats_s [B,S,F], feats_q [B,Qn,F]) = Conv4 of every episode's support / query images (one batch-statistics group each).
-    keep_tape: the activations stay laid out in ``ws`` for ``conv4_encode_bwd`` -- no other call may use ``ws`` in between."""
-    dev = _dev(x_s)
-    if x_s.dim() != 5 or x_q.dim() != 5 or x_s.shape[0] != x_q.shape[0] or x_s.shape[2:] != x_q.shape[2:]:
-        raise FumiHipError("conv4_encode: x_s [B,S,C,H,W] and x_q [B,Qn,C,H,W] expected")
-    B, S, Cin, H, W = x_s.shape
-    Qn = x_q.shape[1]
-    nblk = len(theta) // 3
-    F = conv4_feature_dim(nblk, H, W)
-    fs = torch.empty(B, S, F, device=dev, dtype=torch.float32)
-    fq = torch.empty(B, Qn, F, device=dev, dtype=torch.float32)
-    _check(lib().fumi_hip_conv4_encode(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _f32(x_s, "x_s"), _f32(x_q, "x_q"),
-                                       _parr(theta, "theta"), _f32(fs, "feats_s"), _f32(fq, "feats_q"), int(bool(keep_tape))),
-           "fumi_hip_conv4_encode")
-    return fs, fq
-
-
-def conv4_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_theta=None):
-    """Gradient of sum <dfeats, Conv4(x)> w.r.t. the encoder's parameters (summed over episodes, times ``scale``) from the tape the
-    last ``conv4_encode(..., keep_tape=True)`` left in ``ws``."""
-    dev = _dev(x_s)
-    B, S, Cin, H, W = x_s.shape
-    Qn = x_q.shape[1]
-    nblk = len(theta_like) // 3
-    F = conv4_feature_dim(nblk, H, W)
-    _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q")
-    if g_theta is None:
-        g_theta = [torch.empty_like(t) for t in theta_like]
-    _check(lib().fumi_hip_conv4_encode_bwd(ws.handle, _stream(dev), B, S, Qn, Cin, H, W, nblk, _f32(x_s, "x_s"), _f32(x_q, "x_q"),
-                                           _f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), float(scale),
-                                           _parr(g_theta, "g_theta")), "fumi_hip_conv4_encode_bwd")
-    return g_theta
 
 
 def conv4_probe(ws, device, pass_, kind, block=0):

@@ -25,6 +25,55 @@ def test_library_exports_every_declared_symbol():
     assert sorted(hip.SYMBOLS) == declared, "fumi_amd/hip.py binds a different symbol set than the header declares"
 
 
+def _c_class(arg):
+    """Class of one declared argument: p pointer (anything with * and fumi_stream_t), i4 / i8 integers, f4 float, f8 double."""
+    words = arg.replace("*", " * ").split()
+    if "*" in words or "fumi_stream_t" in words:
+        return "p"
+    for word, cls in (("double", "f8"), ("float", "f4"), ("int64_t", "i8"), ("uint64_t", "i8"), ("size_t", "i8"), ("long", "i8"),
+                      ("int", "i4"), ("unsigned", "i4")):
+        if word in words:
+            return cls
+    raise AssertionError(f"argument {arg!r} of include/fumi_hip.h has a type this test does not know")
+
+
+def _ctypes_class(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes.Array)):
+        return "p"
+    if t in (ctypes.c_float, ctypes.c_double):
+        return "f%d" % ctypes.sizeof(t)
+    return "i%d" % ctypes.sizeof(t)
+
+
+def _prototypes():
+    src = open(os.path.join(ROOT, "include", "fumi_hip.h")).read()
+    src = re.sub(r"//.*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    out = {}
+    for name, args in re.findall(r"\b(fumi_hip_\w+)\s*\(([^)]*)\)\s*;", src):
+        out[name] = [_c_class(a) for a in args.split(",") if a.strip() not in ("", "void")]
+    return out
+
+
+def test_argtypes_agree_with_the_header_argument_by_argument():
+    """A miscounted argtypes list is silent stack corruption: every bound function takes what its prototype declares, in count and
+    in class (pointer, 4-byte integer, 8-byte integer, float, double)."""
+    from fumi_amd import hip
+    L = hip.lib()
+    protos = _prototypes()
+    assert sorted(protos) == _declared_symbols(), "a declaration of include/fumi_hip.h was not parsed as a prototype"
+    assert sum(1 for a in protos.values() if a) >= 89
+    for name, want in protos.items():
+        argtypes = getattr(L, name).argtypes
+        if not want:
+            assert not argtypes, f"{name} takes no arguments"
+            continue
+        assert argtypes is not None, f"{name}: fumi_amd/hip.py sets no argtypes"
+        got = [_ctypes_class(t) for t in argtypes]
+        assert len(got) == len(want), f"{name}: {len(got)} argtypes, the header declares {len(want)} arguments"
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g == w, f"{name}: argument {i} is bound as {g}, the header declares {w}"
+
+
 def test_strerror_and_version_without_gpu():
     from fumi_amd import hip
     L = hip.lib()

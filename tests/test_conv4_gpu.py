@@ -539,6 +539,26 @@ def test_am3_conv4_step_matches_autograd(lamda_fixed, Ht, dev):
         hip.conv4_encode_bwd(ws_enc, xs, xq, out["dx_s"], out["dx_q"], th_d)
 
 
+def test_conv4_encoder_pair_refuses_wrong_shapes_before_any_launch(dev):
+    """The kernels index raw pointers with the sizes they are told, so the wrappers check them first: a theta[0] of the wrong Cin in
+    conv4_encode and a g_theta entry of the wrong shape in conv4_encode_bwd raise, and the workspace status stays 0."""
+    from fumi_amd import hip
+    ws_enc = hip.Workspace.get(dev, "encoder")
+    g = torch.Generator().manual_seed(5)
+    xs, xq = torch.randn(1, 1, 3, 8, 8, generator=g).to(dev), torch.randn(1, 1, 3, 8, 8, generator=g).to(dev)
+    theta = [torch.randn(*s, generator=g).to(dev) for s in [(64, 3, 3, 3), (64,), (64,), (64, 64, 3, 3), (64,), (64,)]]
+    wrong_cin = [torch.zeros(64, 4, 3, 3, device=dev)] + theta[1:]
+    with pytest.raises(hip.FumiHipError, match="expected shape"):
+        hip.conv4_encode(ws_enc, xs, xq, wrong_cin, keep_tape=True)
+    assert ws_enc.read_status() == 0
+    df = torch.zeros(1, 1, 64 * 2 * 2, device=dev)
+    g_theta = [torch.empty_like(t) for t in theta]
+    g_theta[3] = torch.empty(64, 64, 3, 2, device=dev)
+    with pytest.raises(hip.FumiHipError, match="expected shape"):
+        hip.conv4_encode_bwd(ws_enc, xs, xq, df, df, theta, g_theta=g_theta)
+    assert ws_enc.read_status() == 0
+
+
 def test_cli_am3_conv4_end_to_end_on_gpu(dev, tmp_path, monkeypatch):
     """`python -m fumi_amd.main --model am3 --im_encoder conv4 --dataset synthetic` (BASELINE.json configs[3] as worded, shortened)."""
     from fumi_amd import main as cli
