@@ -530,6 +530,18 @@ int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
     return launch_reduce_slabs(st, slabs, ns, slab, slab, scale, gW0);
 }
 
+int fumi_hip_reduce_segments(fumi_ws_t* ws, fumi_stream_t stream, int n, const float* const* src, const int* nslab,
+        const long* stride, const long* count, float* const* dst, float scale) {
+    if (!ws || n < 0 || n > 24 || (n > 0 && (!src || !nslab || !stride || !count || !dst))) return FUMI_EINVAL;
+    ReduceSegs sg; sg.n = 0; sg.scale = scale;
+    for (int k = 0; k < n; ++k) {
+        if (!src[k] || !dst[k] || nslab[k] < 1 || count[k] < 0 || stride[k] < 0) return FUMI_EINVAL;
+        sg.add(src[k], nslab[k], stride[k], count[k], dst[k]);
+    }
+    HIP_TRY(hipSetDevice(ws->device));
+    return launch_reduce_multi((hipStream_t)stream, sg);
+}
+
 int fumi_hip_linear_fwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int N, int K,
         const float* x, const float* W, const float* b, int act, float* y) {
     if (!ws || !x || !W || !y || M < 1 || N < 1 || K < 1 || act < 0 || act > 2) return FUMI_EINVAL;

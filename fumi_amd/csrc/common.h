@@ -132,6 +132,10 @@ int launch_reduce_slabs(hipStream_t st, const float* slabs, int nslab, long stri
 struct ReduceSegs {
     const float* src[24]; float* dst[24]; long end[24]; long stride[24]; int nslab[24]; int vec[24];
     int n; float scale;
+    // Launch state, NOT part of the description: segment k owns the 256-thread workgroups [bend[k-1], bend[k]).  Valid only after
+    // blocks() has run on THIS object with its final segments; add / append / a copy made earlier leave it stale or unset, and the
+    // launchers (gemm.hip) call blocks() on the very struct they pass to the kernel.
+    int bend[24];
     // a segment whose rows and pointers are 16-byte aligned is processed four elements per thread (end[] counts threads)
     void add(const float* s, int ns, long st, long cnt, float* d) {
         const bool v4 = (cnt % 4 == 0) && (st % 4 == 0) && ((uintptr_t)s % 16 == 0) && ((uintptr_t)d % 16 == 0);
@@ -146,6 +150,18 @@ struct ReduceSegs {
             end[n] = (n ? end[n - 1] : 0) + (o.end[i] - (i ? o.end[i - 1] : 0)); ++n;
         }
         return true;
+    }
+    // The launch grid: every segment's thread count rounded up to whole 256-thread workgroups, so a workgroup lies in ONE segment
+    // and finds it with scalar compares (end[] keeps the true counts; the threads past a segment's end do nothing).  Entries past n
+    // are never reached by a workgroup id.  Returns the number of workgroups, -1 when it does not fit an int.
+    long blocks() {
+        long b = 0;
+        for (int k = 0; k < 24; ++k) {
+            if (k < n) b += (end[k] - (k ? end[k - 1] : 0) + 255) / 256;
+            if (b > 0x7fffffffL) return -1;
+            bend[k] = k < n ? (int)b : 0x7fffffff;
+        }
+        return b;
     }
 };
 int launch_reduce_multi(hipStream_t st, ReduceSegs& sg);

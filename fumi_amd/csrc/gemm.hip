@@ -186,111 +186,127 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     }
 }
 
-__global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int nslab, long stride, long n, float scale,
-                                    float* __restrict__ out) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < nslab; ++k) s += slabs[k * stride + i];
-        out[i] = scale * s;
+// ---- the slab sum shared by reduce_slabs_kernel, reduce_multi_kernel and reduce_multi_optim_kernel -----------------------------
+// scale * sum_t src[t*st] of one column (T = f32x4: four neighbouring columns), ns slabs.  TWO: even slabs in one chain and odd slabs
+// in the other, each in increasing slab index, then scale * (a0 + a1); otherwise ONE chain in increasing index.  The order of the
+// additions is the result (bit-reproducible), so only the LOADS are batched: all NB loads of a batch are issued before its first add
+// (one memory round trip per batch instead of one per two or four slabs), unconditionally, from slab indices clamped to ns - 1 --
+// a guarded load is a basic block of its own behind a vmcnt(0).  A clamped load's value is dropped by selecting the chain's OLD value,
+// not by adding a zero, so nothing about signed zeros or denormals has to hold.
+constexpr int RED_B4 = 16;        // float4 loads of one batch (64 VGPRs)
+constexpr int RED_B1 = 32;        // scalar loads of one batch
+template <typename T, int NB, bool TWO>
+__device__ __forceinline__ T slab_sum(const float* __restrict__ src, long st, int ns, float scale) {
+    T a0 = {}, a1 = {};
+    long o = 0;                                            // offset of slab min(t, ns - 1): advanced by adds, stops at the last slab
+    for (int t0 = 0; t0 < ns; t0 += NB) {
+        T v[NB];
+        const float* p[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) { p[j] = src + o; o += t0 + j + 1 < ns ? st : 0; }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) v[j] = *(const T*)p[j];
+        __builtin_amdgcn_sched_barrier(0);                 // (the scheduler otherwise deals the adds between the loads to save VGPRs)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const bool ok = t0 + j < ns;
+            if (TWO && (j & 1)) a1 = ok ? a1 + v[j] : a1;        // (NB is even: slab parity = j parity)
+            else a0 = ok ? a0 + v[j] : a0;
+        }
     }
+    return TWO ? scale * (a0 + a1) : scale * a0;
+}
+static_assert(RED_B4 % 2 == 0 && RED_B1 % 2 == 0, "slab parity must be the parity of the index in the batch");
+
+__global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ slabs, int nslab, long stride, long n, float scale,
+                                                           float* __restrict__ out) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        out[i] = slab_sum<float, RED_B1, false>(slabs + i, stride, nslab, scale);          // (ONE chain: part of its result)
+}
+
+// the segment of the calling workgroup and the thread's unit in it (ReduceSegs::blocks(): whole workgroups per segment).  The 24
+// workgroup bounds are read at compile-time indices -- one batch of scalar loads and 23 scalar compares, not a walk of dependent
+// loads -- and everything indexed by k afterwards is uniform over the workgroup.
+struct SegPos { int k; long u; bool live; };
+__device__ __forceinline__ SegPos seg_pos(const ReduceSegs& sg) {
+    const int b = blockIdx.x;
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < 23; ++j) k += b >= sg.bend[j] ? 1 : 0;
+    SegPos q;
+    q.k = k;
+    q.u = (long)(b - (k ? sg.bend[k - 1] : 0)) * 256 + threadIdx.x;
+    q.live = q.u < sg.end[k] - (k ? sg.end[k - 1] : 0);
+    return q;
 }
 
 // several slab reductions in ONE launch: segment k: dst[i] = scale * sum_t src[t*stride + i], i < n.  Even slabs and odd
 // slabs are summed in two chains (fixed order: bit-reproducible); aligned segments move 16 bytes per thread and slab.
-__global__ void reduce_multi_kernel(ReduceSegs sg) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= sg.end[sg.n - 1]) return;
-    int k = 0;
-    while (k + 1 < sg.n && i >= sg.end[k]) ++k;
-    const long u = i - (k ? sg.end[k - 1] : 0);
-    const long st = sg.stride[k];
-    const int ns = sg.nslab[k];
-    if (sg.vec[k]) {
-        const float* src = sg.src[k] + 4 * u;
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-        int t = 0;
-        for (; t + 3 < ns; t += 4) {                       // four independent 16-byte loads in flight
-            const f32x4 a = *(const f32x4*)(src + t * st), b = *(const f32x4*)(src + (t + 1) * st);
-            const f32x4 c = *(const f32x4*)(src + (t + 2) * st), d = *(const f32x4*)(src + (t + 3) * st);
-            s0 += a; s1 += b; s0 += c; s1 += d;
-        }
-        for (; t + 1 < ns; t += 2) { s0 += *(const f32x4*)(src + t * st); s1 += *(const f32x4*)(src + (t + 1) * st); }
-        if (t < ns) s0 += *(const f32x4*)(src + t * st);
-        *(f32x4*)(sg.dst[k] + 4 * u) = sg.scale * (s0 + s1);
-    } else {
-        const float* src = sg.src[k] + u;
-        float s0 = 0.f, s1 = 0.f;
-        int t = 0;
-        for (; t + 1 < ns; t += 2) { s0 += src[t * st]; s1 += src[(t + 1) * st]; }
-        if (t < ns) s0 += src[t * st];
-        sg.dst[k][u] = sg.scale * (s0 + s1);
-    }
+__global__ __launch_bounds__(256) void reduce_multi_kernel(ReduceSegs sg) {
+    const SegPos q = seg_pos(sg);
+    if (!q.live) return;
+    const int k = q.k;
+    const long u = q.u;
+    if (sg.vec[k]) *(f32x4*)(sg.dst[k] + 4 * u) = slab_sum<f32x4, RED_B4, true>(sg.src[k] + 4 * u, sg.stride[k], sg.nslab[k], sg.scale);
+    else sg.dst[k][u] = slab_sum<float, RED_B1, true>(sg.src[k] + u, sg.stride[k], sg.nslab[k], sg.scale);
 }
 
 // reduce_multi + the optimizer step + the publication of the statistics (launch_reduce_multi_final).  ad.p[k] != NULL: segment k's
 // outputs are the gradient of a parameter tensor: the parameter and the rule's state streams at the same offsets get the pending
-// rule's update (the expressions of optim_kernel, adam.hip, in the same order: bit-identical).  An output that lies in
+// rule's update (the expressions of optim_kernel, adam.hip, in the same order: bit-identical).  The parameter and the state depend
+// on nothing, so their loads are issued AHEAD of the slab loads and arrive under them.  An output that lies in
 // [pub_src, pub_src + pub_n) is also stored to the pinned host buffer; the lane whose store is the last one (a device counter)
 // stores the sequence word behind it.
 template <int NS> struct OptSegs { float* p[24]; float* s[NS][24]; OptCoef c; };
 template <> struct OptSegs<0> { float* p[24]; OptCoef c; };
 template <int RULE>
-__global__ void reduce_multi_optim_kernel(ReduceSegs sg, OptSegs<opt_nstate(RULE)> ad, const float* pub_src, int pub_n, float* pub_dst,
-                                          unsigned long long pub_seq, int* pub_cnt) {
+__global__ __launch_bounds__(256) void reduce_multi_optim_kernel(ReduceSegs sg, OptSegs<opt_nstate(RULE)> ad, const float* pub_src,
+                                                                 int pub_n, float* pub_dst, unsigned long long pub_seq, int* pub_cnt) {
     constexpr int NS = opt_nstate(RULE);
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= sg.end[sg.n - 1]) return;
-    int k = 0;
-    while (k + 1 < sg.n && i >= sg.end[k]) ++k;
-    const long u = i - (k ? sg.end[k - 1] : 0);
+    const SegPos q = seg_pos(sg);
+    if (!q.live) return;
+    const int k = q.k;
+    const long u = q.u;
     const long st = sg.stride[k];
     const int ns = sg.nslab[k];
     const bool rd0 = NS >= 1 && !(RULE == OPT_SGD_MOMENTUM && ad.c.first);  // (a momentum buffer's first step writes it only)
+    float* const P = ad.p[k];
     float* s0 = nullptr; float* s1 = nullptr;
     if constexpr (NS >= 1) s0 = ad.s[0][k];
     if constexpr (NS >= 2) s1 = ad.s[1][k];
     if (sg.vec[k]) {
-        const float* src = sg.src[k] + 4 * u;
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-        int t = 0;
-        for (; t + 3 < ns; t += 4) {
-            const f32x4 a = *(const f32x4*)(src + t * st), b = *(const f32x4*)(src + (t + 1) * st);
-            const f32x4 c = *(const f32x4*)(src + (t + 2) * st), d = *(const f32x4*)(src + (t + 3) * st);
-            a0 += a; a1 += b; a0 += c; a1 += d;
-        }
-        for (; t + 1 < ns; t += 2) { a0 += *(const f32x4*)(src + t * st); a1 += *(const f32x4*)(src + (t + 1) * st); }
-        if (t < ns) a0 += *(const f32x4*)(src + t * st);
-        const f32x4 g = sg.scale * (a0 + a1);
-        *(f32x4*)(sg.dst[k] + 4 * u) = g;
-        if (ad.p[k]) {
-            f32x4 pp = *(f32x4*)(ad.p[k] + 4 * u), aa = {0.f, 0.f, 0.f, 0.f}, bb = aa;
+        f32x4 pp = {0.f, 0.f, 0.f, 0.f}, aa = pp, bb = pp;
+        if (P) {                                           // (uniform over the workgroup: a scalar branch)
+            pp = *(f32x4*)(P + 4 * u);
             if (rd0) aa = *(f32x4*)(s0 + 4 * u);
             if constexpr (NS >= 2) bb = *(f32x4*)(s1 + 4 * u);
+        }
+        const f32x4 g = slab_sum<f32x4, RED_B4, true>(sg.src[k] + 4 * u, st, ns, sg.scale);
+        *(f32x4*)(sg.dst[k] + 4 * u) = g;
+        if (P) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pe = pp[e], ae = aa[e], be = bb[e];
                 opt_update1<RULE>(g[e], pe, ae, be, ad.c);
                 pp[e] = pe; aa[e] = ae; bb[e] = be;
             }
-            *(f32x4*)(ad.p[k] + 4 * u) = pp;
+            *(f32x4*)(P + 4 * u) = pp;
             if constexpr (NS >= 1) *(f32x4*)(s0 + 4 * u) = aa;
             if constexpr (NS >= 2) *(f32x4*)(s1 + 4 * u) = bb;
         }
     } else {
-        const float* src = sg.src[k] + u;
-        float a0 = 0.f, a1 = 0.f;
-        int t = 0;
-        for (; t + 1 < ns; t += 2) { a0 += src[t * st]; a1 += src[(t + 1) * st]; }
-        if (t < ns) a0 += src[t * st];
-        const float g = sg.scale * (a0 + a1);
-        float* d = sg.dst[k] + u;
-        *d = g;
-        if (ad.p[k]) {
-            float pe = ad.p[k][u], ae = 0.f, be = 0.f;
+        float pe = 0.f, ae = 0.f, be = 0.f;
+        if (P) {
+            pe = P[u];
             if (rd0) ae = s0[u];
             if constexpr (NS >= 2) be = s1[u];
+        }
+        const float g = slab_sum<float, RED_B1, true>(sg.src[k] + u, st, ns, sg.scale);
+        float* d = sg.dst[k] + u;
+        *d = g;
+        if (P) {
             opt_update1<RULE>(g, pe, ae, be, ad.c);
-            ad.p[k][u] = pe;
+            P[u] = pe;
             if constexpr (NS >= 1) s0[u] = ae;
             if constexpr (NS >= 2) s1[u] = be;
         }
@@ -306,7 +322,8 @@ __global__ void reduce_multi_optim_kernel(ReduceSegs sg, OptSegs<opt_nstate(RULE
 }
 
 // the folded launch for one rule: seg[k] = index of the pending step's tensor whose gradient segment k is, or -1
-template <int RULE> void launch_reduce_multi_optim(fumi_ws* ws, hipStream_t st, const ReduceSegs& sg, const AdamPending& ap, const int* seg) {
+template <int RULE> void launch_reduce_multi_optim(fumi_ws* ws, hipStream_t st, const ReduceSegs& sg, long nblk, const AdamPending& ap,
+                                                   const int* seg) {
     constexpr int NS = opt_nstate(RULE);
     OptSegs<NS> ad; memset(&ad, 0, sizeof(ad));
     for (int k = 0; k < sg.n; ++k) {
@@ -316,9 +333,8 @@ template <int RULE> void launch_reduce_multi_optim(fumi_ws* ws, hipStream_t st, 
         if constexpr (NS >= 2) ad.s[1][k] = ap.s[1][seg[k]];
     }
     ad.c = ap.c;
-    const long tot = sg.end[sg.n - 1];
-    hipLaunchKernelGGL(reduce_multi_optim_kernel<RULE>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sg, ad, ws->pub_src,
-                       ws->pub_n, ws->pub_dst, ws->pub_seq, ws->status + 48);
+    hipLaunchKernelGGL(reduce_multi_optim_kernel<RULE>, dim3((unsigned)nblk), dim3(256), 0, st, sg, ad, ws->pub_src, ws->pub_n,
+                       ws->pub_dst, ws->pub_seq, ws->status + 48);
 }
 
 __global__ void colsum_kernel(const float* __restrict__ X, int M, int N, long ld, float scale, float* __restrict__ out) {
@@ -396,9 +412,10 @@ int launch_reduce_slabs(hipStream_t st, const float* slabs, int nslab, long stri
 
 int launch_reduce_multi(hipStream_t st, ReduceSegs& sg) {
     if (sg.n < 1) return FUMI_OK;
-    const long tot = sg.end[sg.n - 1];
-    if (tot < 1) return FUMI_OK;
-    hipLaunchKernelGGL(reduce_multi_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sg);
+    const long nblk = sg.blocks();
+    if (nblk < 0) return FUMI_EINVAL;
+    if (nblk < 1) return FUMI_OK;
+    hipLaunchKernelGGL(reduce_multi_kernel, dim3((unsigned)nblk), dim3(256), 0, st, sg);
     LAUNCH_CHECK();
     return FUMI_OK;
 }
@@ -424,15 +441,16 @@ int launch_reduce_multi_final(fumi_ws* ws, hipStream_t st, ReduceSegs& sg) {
         if (ws->pub_dst && d >= ws->pub_src && d < ws->pub_src + ws->pub_n) { if (cnt == 1 && !sg.vec[k]) ++pub_found; else ok = false; }
     }
     ok = ok && matched == ap->n && (!ws->pub_dst || pub_found == ws->pub_n);
-    if (!ok) {                                             // separate launches, same results
+    const long nblk = ok ? sg.blocks() : 0;                // (the plain launch below lays out its own grid)
+    if (nblk < 1) {                                        // separate launches, same results
         int rc = launch_reduce_multi(st, sg);
         return rc ? rc : launch_adam_pending(ws, st);
     }
     switch (ap->rule) {
-        case OPT_ADAM: launch_reduce_multi_optim<OPT_ADAM>(ws, st, sg, *ap, seg); break;
-        case OPT_ADAMW: launch_reduce_multi_optim<OPT_ADAMW>(ws, st, sg, *ap, seg); break;
-        case OPT_SGD_MOMENTUM: launch_reduce_multi_optim<OPT_SGD_MOMENTUM>(ws, st, sg, *ap, seg); break;
-        case OPT_SGD: launch_reduce_multi_optim<OPT_SGD>(ws, st, sg, *ap, seg); break;
+        case OPT_ADAM: launch_reduce_multi_optim<OPT_ADAM>(ws, st, sg, nblk, *ap, seg); break;
+        case OPT_ADAMW: launch_reduce_multi_optim<OPT_ADAMW>(ws, st, sg, nblk, *ap, seg); break;
+        case OPT_SGD_MOMENTUM: launch_reduce_multi_optim<OPT_SGD_MOMENTUM>(ws, st, sg, nblk, *ap, seg); break;
+        case OPT_SGD: launch_reduce_multi_optim<OPT_SGD>(ws, st, sg, nblk, *ap, seg); break;
         default: return FUMI_EINVAL;
     }
     ap->on = 0;

@@ -38,11 +38,19 @@ __device__ __forceinline__ void glove_bag_row(const GloveArgs& ga, int r, float*
     const int64_t* t = tok + src_row * L;
     const int lw = (L + GW - 1) / GW;            // tokens per wave
     const int lbeg = wave * lw, lend = min(L, lbeg + lw);
-    for (int c = 0; c < nchunk; ++c) {
-        const int j = (c * 64 + lane) * W;
-        const int jc = j < E ? j : 0;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (mode == 1) acc = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    // CH chunks (c, .., c + CH - 1) in ONE pass over the wave's tokens: the CH * GU row gathers of a token batch are issued together.
+    // Every chunk still adds (maxes) its tokens in increasing order into its own accumulator, so the pooled bits do not depend on CH.
+    auto chunks = [&](auto ch, int c) {
+        constexpr int CH = decltype(ch)::value;
+        int jc[CH];
+        f32x4 acc[CH];
+#pragma unroll
+        for (int h = 0; h < CH; ++h) {
+            const int j = ((c + h) * 64 + lane) * W;
+            jc[h] = j < E ? j : 0;
+            acc[h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (mode == 1) acc[h] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        }
         int cnt = 0;
         for (int l0 = lbeg; l0 < lend; l0 += 64) {
             const int nl = min(64, lend - l0);
@@ -51,26 +59,38 @@ __device__ __forceinline__ void glove_bag_row(const GloveArgs& ga, int r, float*
             if (my < 0 || my >= V) { if (lane < nl) atomicOr(status, FUMI_ST_LABEL_RANGE); my = 0; }
             const int mylo = (int)my;
             for (int u0 = 0; u0 < nl; u0 += GU) {
-                f32x4 v[GU];
+                f32x4 v[CH][GU];
 #pragma unroll
                 for (int u = 0; u < GU; ++u) {
                     const int id = __shfl(mylo, min(u0 + u, nl - 1), 64);
-                    const float* row = table + (long)id * E + jc;
-                    if (VEC) v[u] = *(const f32x4*)row; else { v[u] = (f32x4){0.f, 0.f, 0.f, 0.f}; v[u][0] = row[0]; }
+#pragma unroll
+                    for (int h = 0; h < CH; ++h) {
+                        const float* row = table + (long)id * E + jc[h];
+                        if (VEC) v[h][u] = *(const f32x4*)row; else { v[h][u] = (f32x4){0.f, 0.f, 0.f, 0.f}; v[h][u][0] = row[0]; }
+                    }
                 }
 #pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    if (u0 + u < nl) {
-                        if (mode == 0) acc += v[u];
-                        else { acc[0] = fmaxf(acc[0], v[u][0]); acc[1] = fmaxf(acc[1], v[u][1]); acc[2] = fmaxf(acc[2], v[u][2]); acc[3] = fmaxf(acc[3], v[u][3]); }
+                for (int h = 0; h < CH; ++h) {
+#pragma unroll
+                    for (int u = 0; u < GU; ++u) {
+                        if (u0 + u < nl) {
+                            if (mode == 0) acc[h] += v[h][u];
+                            else { acc[h][0] = fmaxf(acc[h][0], v[h][u][0]); acc[h][1] = fmaxf(acc[h][1], v[h][u][1]); acc[h][2] = fmaxf(acc[h][2], v[h][u][2]); acc[h][3] = fmaxf(acc[h][3], v[h][u][3]); }
+                        }
                     }
                 }
             }
         }
-        float* pp = part + wave * Ep + (c * 64 + lane) * W;
-        if (VEC) *(f32x4*)pp = acc; else pp[0] = acc[0];
+#pragma unroll
+        for (int h = 0; h < CH; ++h) {
+            float* pp = part + wave * Ep + ((c + h) * 64 + lane) * W;
+            if (VEC) *(f32x4*)pp = acc[h]; else pp[0] = acc[h][0];
+        }
         if (lane == 0 && c == 0) cnts[wave] = (float)cnt;
-    }
+    };
+    int c = 0;
+    for (; c + 1 < nchunk; c += 2) chunks(WgInt<2>{}, c);                  // (E = 300: nchunk == 2, one pass, 32 gathers in flight)
+    if (c < nchunk) chunks(WgInt<1>{}, c);
     __syncthreads();
     float dn = 0.f;
 #pragma unroll

@@ -23,6 +23,7 @@ SYMBOLS = [
     "fumi_hip_set_profiling", "fumi_hip_set_profiling_every", "fumi_hip_get_profile", "fumi_hip_phase_name",
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
     "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
+    "fumi_hip_reduce_segments",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
     "fumi_hip_grad_norm", "fumi_hip_adam_step_clipped", "fumi_hip_adamw_step_clipped", "fumi_hip_sgd_step_clipped",
@@ -153,6 +154,8 @@ def lib():
         L.fumi_hip_xpanel_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5
         L.fumi_hip_xpanel_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [c_float, c_void_p]
         L.fumi_hip_xpanel_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_reduce_segments.argtypes = [c_void_p, c_void_p, c_int, PP, POINTER(c_int), POINTER(ctypes.c_long),
+                                               POINTER(ctypes.c_long), PP, c_float]
         L.fumi_hip_adam_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_step_deferred.argtypes = [c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
         L.fumi_hip_adam_flush.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
@@ -799,6 +802,28 @@ def xpanel_bwd(ws, x_s, x_q, Abar, scale=1.0, out=None):
     _check(lib().fumi_hip_xpanel_bwd(ws.handle, _stream(dev), B, S, Qn, D, h0, ps, pq,
                                      _f32(Abar, "Abar"), float(scale), _f32(gW0, "gW0")), "fumi_hip_xpanel_bwd")
     return gW0
+
+
+def reduce_segments(ws, segs, scale=1.0):
+    """The plain multi-segment slab reduction of a step's last launch, on its own (fumi_hip_reduce_segments).  ``segs``: up to 24
+    tuples (src, nslab, stride, count, dst) of flat float32 tensors: dst[i] = scale * (even slabs' sum + odd slabs' sum) of
+    src[t * stride + i], i < count.  A source or destination that starts off a 16-byte boundary (a view ``x[1:]``) takes the
+    one-float-per-thread path.  Writes ``dst`` in place."""
+    n = len(segs)
+    if n > 24:
+        raise FumiHipError(f"reduce_segments: {n} segments, at most 24")
+    if n == 0:
+        return
+    dev = _dev(segs[0][0])
+    src, dst = (c_void_p * n)(), (c_void_p * n)()
+    ns, st, cnt = (c_int * n)(), (ctypes.c_long * n)(), (ctypes.c_long * n)()
+    for k, (s, nslab, stride, count, d) in enumerate(segs):
+        src[k], dst[k] = _f32(s, "src").value, _f32(d, "dst").value
+        if nslab < 1 or count < 0 or stride < 0 or (nslab - 1) * stride + count > s.numel() or count > d.numel():
+            raise FumiHipError(f"reduce_segments: segment {k} reads or writes past its tensors")
+        ns[k], st[k], cnt[k] = nslab, stride, count
+    _check(lib().fumi_hip_reduce_segments(ws.handle, _stream(dev), n, src, ns, st, cnt, dst,
+                                          float(scale)), "fumi_hip_reduce_segments")
 
 
 XPANEL_PLAN_KEYS = ("fwd_kernel", "fwd_ring", "fwd_ksplit", "fwd_gram_blocks", "fwd_rode",

@@ -223,6 +223,11 @@ int fumi_hip_xpanel_fwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
         const float* x_s, const float* x_q, const float* W0, float* A0, float* G);
 int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
         const float* x_s, const float* x_q, const float* Abar, float scale, float* gW0);
+/* The plain multi-segment slab reduction of a step's last launch (csrc/gemm.hip: reduce_multi_kernel), exported for bit-exactness
+ * tests: n <= 24 segments, segment k: dst[k][i] = scale * (sum of the even slabs + sum of the odd slabs), slab t = src[k] + t *
+ * stride[k], i < count[k], nslab[k] >= 1, each chain in increasing slab index. */
+int fumi_hip_reduce_segments(fumi_ws_t* ws, fumi_stream_t stream, int n, const float* const* src, const int* nslab,
+        const long* stride, const long* count, float* const* dst, float scale);
 /* bwd also takes a one-sided panel: S == 0 (x_s may be NULL) or Qn == 0 (x_q may be NULL), not both.
  * Which kernel form the last fwd / bwd X-panel launch of this process took, up to 11 ints:
  *   [fwd kernel (1 generic guarded, 2 generic fast, 3 fp32 MFMA, 4 per-tile split, 5 pre-split), ring depth, ksplit, Gram column
