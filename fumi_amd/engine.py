@@ -140,6 +140,13 @@ class HipEngine:
         return hip.cls_head_step_soft(self._ws(feats), feats, y_a, W, b, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
                                       grad_scale=grad_scale, dfeats=dfeats, gW=gW, gb=gb)
 
+    def cos_proto_step(self, feats_s, y_s, feats_q, y_q, tau, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                       dfeats_q=None, dtau=None, n_way=None):
+        """Fused cosine nearest-centroid head with the temperature tau [1] on the device: mean cross-entropy of
+        tau * cos(query, class mean) over all query rows, its predictions and the gradients for both feature sets and tau."""
+        return hip.cos_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, tau, need_grad=need_grad, grad_scale=grad_scale,
+                                  want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau, n_way=n_way)
+
     def mix_images(self, x, partner, mode, lam=1.0, box=(0, 0, 0, 0)):
         """mixup (mode 0) / CutMix (mode 1) of a gathered image batch with its rows ``partner``."""
         return hip.mix_images(self._ws(x), x, partner, mode=mode, lam=lam, box=box)

@@ -42,6 +42,7 @@ SYMBOLS = [
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
+    "fumi_hip_cos_proto_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT = 1, 2, 4
@@ -232,6 +233,7 @@ def lib():
                                                   + [c_float] + [c_void_p] * 6)
         L.fumi_hip_mix_images.argtypes = ([c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_float] + [c_int] * 4
                                           + [c_void_p])
+        L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         _lib = L
     return _lib
 
@@ -1577,6 +1579,41 @@ def cls_head_step(ws, feats, y, W, b, *, need_grad=True, grad_scale=1.0, dfeats=
                                         float(grad_scale), _f32(loss, "loss"), _f32(correct, "correct"),
                                         _i64(preds, "preds") if want_preds else None, *grads), "fumi_hip_cls_head_step")
     return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+
+
+def cos_proto_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                   dfeats_q=None, dtau=None, n_way=None):
+    """The fused cosine nearest-centroid head (csrc/cosproto.hip): per episode the class means of feats_s [B,S,F] by y_s [B,S], logits
+    tau * cos(feats_q [B,Qn,F], mean), mean softmax cross-entropy against y_q [B,Qn] over all B * Qn rows.  ``tau`` is a GPU tensor [1]
+    (the kernels read it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers that know N pass it.
+    Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without
+    want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dtau [1] = gradients of grad_scale * loss (written into the
+    tensors given, else into new ones)."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError("cos_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(tau, (1,), "tau")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
+    if need_grad:
+        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
+        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
+        dtau = torch.empty(1, device=dev, dtype=torch.float32) if dtau is None else dtau
+        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dtau, (1,), "dtau")
+        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dtau, "dtau")]
+    else:
+        dfeats_s = dfeats_q = dtau = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_cos_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
+                                         _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(tau, "tau"), float(grad_scale),
+                                         _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
+                                         _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_cos_proto_step")
+    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau)
 
 
 def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,

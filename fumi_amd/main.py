@@ -18,7 +18,7 @@ import torch
 from . import dist as fdist
 from . import engine as _engine
 from . import hip
-from .models import am3, clip, fumi, maml, pretrain
+from .models import am3, clip, fumi, maml, metabaseline, pretrain
 from .utils import utils
 from .utils.wandb_compat import wandb
 
@@ -26,6 +26,9 @@ from .utils.wandb_compat import wandb
 def get_dataset(args):
     if args.model == "pretrain" and args.dataset not in ("synthetic-resident", "image-npy"):
         raise ValueError(f"--model pretrain trains on a GPU-resident uint8 pixel table: --dataset synthetic-resident or image-npy, "
+                         f"not {args.dataset} (embeddings and host loaders have no pixels for the backbone)")
+    if args.model == "metabaseline" and args.dataset not in ("synthetic-resident", "image-npy"):
+        raise ValueError(f"--model metabaseline trains on a GPU-resident uint8 pixel table: --dataset synthetic-resident or image-npy, "
                          f"not {args.dataset} (embeddings and host loaders have no pixels for the backbone)")
     if args.model == "clip" and args.dataset == "synthetic":        # the CLIP baseline consumes supervised mini-batches
         from .dataset.synthetic import get_synthetic_supervised
@@ -52,8 +55,8 @@ def get_dataset(args):
 _EMBEDDING_DIMS = {"resnet-152": ("Resnet-152", 2048), "resnet-34": ("Resnet-34", 512)}
 # names the test metrics are logged and printed under, in the order the test loops return them
 _TEST_METRICS = {"maml": ("loss", "acc"), "fumi": ("loss", "acc"), "am3": ("loss", "acc", "f1", "prec", "rec", "avg_lamda"),
-                 "pretrain": ("loss", "acc")}
-_FAMILIES = ("maml", "fumi", "clip", "pretrain")                                  # unknown names are AM3, like utils.init_model
+                 "pretrain": ("loss", "acc"), "metabaseline": ("loss", "acc")}
+_FAMILIES = ("maml", "fumi", "clip", "pretrain", "metabaseline")                                  # unknown names are AM3, like utils.init_model
 
 
 def _check_embedding_flags(args):
@@ -79,7 +82,7 @@ def _restore(args, model, optimizer):
 def main(args):
     check_supported(args)
     family = args.model if args.model in _FAMILIES else "am3"
-    mod = {"maml": maml, "fumi": fumi, "am3": am3, "clip": clip, "pretrain": pretrain}[family]
+    mod = {"maml": maml, "fumi": fumi, "am3": am3, "clip": clip, "pretrain": pretrain, "metabaseline": metabaseline}[family]
     results_path = f"{args.log_dir}/results"
     os.makedirs(results_path, exist_ok=True)
     os.environ["FUMI_LOG_DIR"] = args.log_dir        # where the local W&B stand-in keeps run directories
@@ -174,6 +177,17 @@ def check_supported(args):
             raise ValueError(f"--pretrain_batch {args.pretrain_batch} must be a multiple of 2 * --pretrain_bn_group "
                              f"{args.pretrain_bn_group}: the encoder normalises groups of that many images, half of them on "
                              f"each side of its call")
+    if family == "metabaseline":
+        if not raw:
+            raise ValueError("--model metabaseline trains an image backbone: it needs --im_encoder conv4 or resnet12")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("--model metabaseline runs on one rank: episode sharding and the gradient all-reduce of the "
+                                      "episodic step are not implemented (WORLD_SIZE > 1)")
+    metric, temp = getattr(args, "pretrain_metric", "euclidean"), getattr(args, "metric_temp", 10.0)
+    if family != "pretrain" and metric != "euclidean":
+        raise ValueError("--pretrain_metric chooses the few-shot validation metric of the supervised classifier: it needs --model pretrain")
+    if not temp > 0.0:
+        raise ValueError(f"--metric_temp {temp} must be positive")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):
@@ -186,8 +200,8 @@ def check_supported(args):
     if not 0.0 <= p_mix <= 1.0:
         raise ValueError(f"--mix_prob {p_mix} must lie in [0, 1]")
     if getattr(args, "encoder_checkpoint", None) and (family == "clip" or not raw):
-        raise ValueError("--encoder_checkpoint loads a Conv4 / ResNet-12 backbone: it needs --model fumi, maml or am3 with "
-                         "--im_encoder conv4 or resnet12")
+        raise ValueError("--encoder_checkpoint loads a Conv4 / ResNet-12 backbone: it needs --model fumi, maml, am3 or metabaseline "
+                         "with --im_encoder conv4 or resnet12")
     # (--fine_tune with --text_encoder RNN / RNNhid trains the bi-LSTM like the reference, fumi/models/fumi.py:65-67 / am3.py:74-76:
     # every meta-step hands back the adjoint of its text input, csrc/textenc.hip runs the LSTM's backward)
     if (family == "am3" and args.text_encoder == "rand" and args.dropout > 0 and not args.evaluate

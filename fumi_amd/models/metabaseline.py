@@ -1,0 +1,162 @@
+"""Meta-Baseline (``--model metabaseline``): the episodic stage that follows a classifier pre-training (Chen et
+al. 2021), and the image-only few-shot baseline on its own.
+
+The model is the backbone of ``Pretrain`` and AM3 under the same attribute name (``conv``, so ``state_dict`` keys ``conv.*`` and
+``--encoder_checkpoint`` / ``load_backbone_state`` work unchanged) and one scalar, the temperature ``temp``.  An episode is classified
+by the cosine between a query's features and the class means of the support features, scaled by ``temp``; the loss is the softmax
+cross-entropy over all query rows of the meta-batch.  A training step is three engine calls: ``encode`` (tape kept),
+``cos_proto_step`` (csrc/cosproto.hip: loss, predictions, the gradients for both feature sets and ``temp``) and ``encode_bwd``; the
+gradients land in one flat buffer and the fused optimizer step follows.  Validation and test run the head's forward form."""
+import os
+
+import torch
+import torch.nn as nn
+
+from .. import engine as _engine
+from .. import lazy
+from ..flatgrad import FlatGrads, ParamWatch
+from ..optim import clip_log
+from ..utils import utils as utils
+from ..utils.average_meter import AverageMeter
+from ..utils.wandb_compat import wandb
+
+
+class MetaBaseline(nn.Module):
+    def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0):
+        super().__init__()
+        if not float(init_temp) > 0.0:
+            raise ValueError(f"the temperature must be positive, got {init_temp}")
+        self.backbone = im_encoder
+        if im_encoder == "conv4":
+            from .conv4 import Conv4
+            self.conv = Conv4(image_channels, 64, 4, image_size)
+        elif im_encoder == "resnet12":
+            from .resnet12 import CHANNELS, ResNet12
+            self.conv = ResNet12(image_channels, CHANNELS, image_size)
+        else:
+            raise NameError(f"{im_encoder} not allowed as image encoder of --model metabaseline (conv4, resnet12)")
+        self.num_ways = num_ways               # N of the episodes (None: read from the support labels, which synchronises)
+        self.temp = nn.Parameter(torch.tensor([float(init_temp)]))
+        self._flat = None
+        self._pcache = None
+
+    def backbone_module(self):
+        return self.conv
+
+    def _step_params(self, need_grad):
+        """(detached temperature, detached backbone tensors, flat gradient buffer | None), the same objects from step to step; rebuilt
+        when a parameter object was replaced or moved (``_apply``)."""
+        c = self._pcache
+        if c is None or not c[0].valid():
+            th = self.conv.theta()
+            c = self._pcache = (ParamWatch(self, [self.temp] + th), self.temp.detach(), [p.detach() for p in th])
+            self._flat = None
+        fg = None
+        if need_grad:
+            fg = self._flat
+            if fg is None:
+                fg = self._flat = FlatGrads([self.temp] + self.conv.theta(), extra=2)
+        return c[1], c[2], fg
+
+    def _apply(self, fn, recurse=True):
+        self._pcache = None
+        return super()._apply(fn, recurse)
+
+    def _encoders(self, eng):
+        return ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
+                (eng.resnet12_encode, eng.resnet12_encode_bwd))
+
+    def _episode(self, batch, device):
+        (_, _, s_im), s_y = batch['train']
+        (_, _, q_im), q_y = batch['test']
+        to = lambda t: t.to(device).contiguous()
+        x_s, x_q, y_s, y_q = to(s_im).float(), to(q_im).float(), to(s_y), to(q_y)
+        N = int(self.num_ways) if self.num_ways else int(y_s.max().item()) + 1
+        return x_s, x_q, y_s, y_q, N
+
+    def train_step(self, batch, device, optimizer=None, scheduler=None):
+        """One episodic step on a meta-batch of the pixel samplers; returns the head's output dict.  The gradients are left attached
+        to the parameters; with an optimizer its fused step follows."""
+        eng = _engine.get_engine()
+        x_s, x_q, y_s, y_q, N = self._episode(batch, device)
+        temp, theta, fg = self._step_params(True)
+        encode, encode_bwd = self._encoders(eng)
+        f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
+        g_t, g_theta = fg.split(1)
+        out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
+        encode_bwd(x_s, x_q, out["dfeats_s"], out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
+        torch.cat((out["loss"], out["correct"] / y_q.numel()), out=fg.tail)
+        if optimizer is not None:
+            optimizer.zero_grad()
+        fg.attach()
+        if optimizer is not None:
+            getattr(optimizer, "step_fused", optimizer.step)()
+            if scheduler:
+                scheduler.step()
+        return out
+
+    def few_shot(self, batch, device):
+        """[loss, acc] of one episodic meta-batch from the head's forward form (a GPU tensor of two floats)."""
+        eng = _engine.get_engine()
+        x_s, x_q, y_s, y_q, N = self._episode(batch, device)
+        temp, theta, _ = self._step_params(False)
+        f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
+        out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
+        return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+
+    def evaluate(self, batch, optimizer, scheduler, device, task="train"):
+        """(loss, acc) of one episodic meta-batch: ``train`` runs a training step, ``val`` / ``test`` the forward form."""
+        device = torch.device(device) if not isinstance(device, torch.device) else device
+        if task == "train" and torch.is_grad_enabled():
+            if not self.training:
+                self.train()
+            self.train_step(batch, device, optimizer, scheduler)
+            return lazy.scalars(self._flat.tail, 2)
+        if self.training:
+            self.eval()
+        with torch.no_grad():
+            loss, acc = self.few_shot(batch, device).cpu().numpy()
+        return loss, acc
+
+
+def training_run(args, model, optimizer, train_loader, val_loader, max_test_batches):
+    """The structure of pretrain.training_run: validation at batch 0 and every --eval_freq, the usual checkpoint dictionary, patience,
+    reload of the best checkpoint (best validation loss) at the end."""
+    best_loss, best_acc = test_loop(args, model, val_loader, max_test_batches)
+    print(f"\ninitial loss: {best_loss}, acc: {best_acc}")
+    best_batch_idx = 0
+    opt, scheduler = optimizer if type(optimizer) == tuple else (optimizer, None)
+    try:
+        for batch_idx, batch in enumerate(train_loader):
+            tl, ta = model.evaluate(batch=batch, optimizer=opt, scheduler=scheduler, device=args.device, task="train")
+            wandb.log({"train/acc": ta, "train/loss": tl, "num_episodes": (batch_idx + 1) * args.batch_size}, step=batch_idx)
+            if batch_idx % args.eval_freq == 0:
+                val_loss, val_acc = test_loop(args, model, val_loader, max_test_batches)
+                is_best = val_loss < best_loss
+                if is_best:
+                    best_loss, best_batch_idx = val_loss, batch_idx
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, "temp": float(model.temp.detach()), **clip_log(opt)}, step=batch_idx)
+                utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
+                                       "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
+                print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"
+                      f"\nval/loss: {val_loss}, val/acc: {val_acc}")
+            if (batch_idx > args.epochs - 1) or (args.patience > 0 and batch_idx - best_batch_idx > args.patience):
+                break
+    except KeyboardInterrupt:
+        pass
+    best_file = os.path.join(wandb.run.dir, "best.pth.tar")
+    if os.path.exists(best_file):
+        model, _ = utils.load_checkpoint(model, opt, args.device, best_file)
+    return model
+
+
+def test_loop(args, model, test_dataloader, max_num_batches):
+    """(mean loss, mean acc) of the cosine nearest-centroid evaluation over max_num_batches + 1 episodic meta-batches."""
+    m_loss, m_acc = AverageMeter(), AverageMeter()
+    for batch_idx, batch in enumerate(test_dataloader):
+        loss, acc = model.evaluate(batch=batch, optimizer=None, scheduler=None, device=args.device, task="test")
+        m_loss.update(loss); m_acc.update(acc)
+        if batch_idx > max_num_batches - 1:
+            break
+    _engine.check_status(args.device)
+    return m_loss.avg, m_acc.avg

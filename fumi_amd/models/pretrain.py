@@ -28,8 +28,15 @@ from ..utils.wandb_compat import wandb
 
 
 class Pretrain(nn.Module):
-    def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0):
+    def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
+                 metric="euclidean", metric_temp=10.0):
         super().__init__()
+        if metric not in ("euclidean", "cosine"):
+            raise ValueError(f"the few-shot metric must be euclidean or cosine, got {metric}")
+        if not float(metric_temp) > 0.0:
+            raise ValueError(f"the temperature of the cosine metric must be positive, got {metric_temp}")
+        self.metric, self.metric_temp = metric, float(metric_temp)   # few-shot validation / test metric
+        self._tau = None
         if not 0.0 <= float(label_smoothing) < 1.0:
             raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
         self.label_smoothing = float(label_smoothing)     # eps of the training target; evaluation has none
@@ -112,7 +119,8 @@ class Pretrain(nn.Module):
 
     def few_shot(self, batch, device):
         """(loss, acc) of nearest-centroid classification on backbone features over one episodic meta-batch: class means of the support
-        features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min."""
+        features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min.
+        With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature."""
         eng = _engine.get_engine()
         (_, _, s_im), s_y = batch['train']
         (_, _, q_im), q_y = batch['test']
@@ -121,6 +129,11 @@ class Pretrain(nn.Module):
         _, theta, _ = self._step_params(False)
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
         N = int(self.num_ways) if self.num_ways else int(y_s.max().item()) + 1
+        if self.metric == "cosine":
+            if self._tau is None or self._tau.device != f_s.device:
+                self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
+            out = eng.cos_proto_step(f_s, y_s, f_q, y_q, self._tau, need_grad=False, n_way=N)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
         d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]
         loss = F.cross_entropy(-d2.reshape(-1, N), y_q.reshape(-1))

@@ -91,6 +91,10 @@ _ENGINE_FLAGS = [     # additive, not in the reference
     ("--pretrain_bn_group", dict(type=int, default=64, help="[--model pretrain] images per batch-statistics group of a training step")),
     ("--encoder_checkpoint", dict(type=str, default=None, help="[--model fumi / maml / am3 with --im_encoder conv4 / resnet12] a --model pretrain checkpoint whose backbone (conv.*) is loaded into the model's image encoder before training")),
 ]
+_METRIC_FLAGS = [           # the cosine nearest-centroid metric; a list of its own, between the two others
+    ("--metric_temp", dict(type=float, default=10.0, help="[--model metabaseline] initial temperature of the cosine classifier; [--model pretrain --pretrain_metric cosine] its fixed temperature (positive)")),
+    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, or their cosine at --metric_temp")),
+]
 _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain; a list of their own, after _ENGINE_FLAGS
     ("--label_smoothing", dict(type=float, default=0.0, help="[--model pretrain] label smoothing eps of the training loss, in [0, 1)")),
     ("--mixup_alpha", dict(type=float, default=0.0, help="[--model pretrain] mixup: lam ~ Beta(alpha, alpha) per training batch (0: off)")),
@@ -101,7 +105,7 @@ _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain (DESIGN.md sectio
 
 def parser():
     p = argparse.ArgumentParser(description="Multimodal image classification")
-    for flag, kw in _FLAGS + _ENGINE_FLAGS + _PRETRAIN_MIX_FLAGS:
+    for flag, kw in _FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -125,7 +129,12 @@ def init_model(args, dictionary, watch=True):
         from ..models import pretrain
         model = pretrain.Pretrain(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
                                   n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways,
-                                  label_smoothing=getattr(args, "label_smoothing", 0.0))
+                                  label_smoothing=getattr(args, "label_smoothing", 0.0),
+                                  metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0))
+    elif args.model == "metabaseline":
+        from ..models import metabaseline
+        model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
+                                          num_ways=args.num_ways, init_temp=getattr(args, "metric_temp", 10.0))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

@@ -481,6 +481,30 @@ int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int 
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
         const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* The cosine nearest-centroid head with a learned temperature (csrc/cosproto.hip): the few-shot metric of a
+ * pre-trained backbone and the episodic loss of the Meta-Baseline stage, fused.  Per episode b, with norm(x) = x / max(|x|_2, 1e-12)
+ * (F.normalize):
+ *     c_n = mean of the rows of feats_s[b] with y_s == n (count clamped to >= 1, as fumi_hip_proto_reduce),
+ *     z[q,n] = tau * <norm(feats_q[b,q]), norm(c_n)>,
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
+ * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).  tau [1] is read from DEVICE memory:
+ * it is a parameter the optimizer updates, no host synchronisation is needed.
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dtau [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training
+ * form) or all three NULL (forward form: loss, correct, preds and logits are bit-identical to the training form's).  dfeats_q goes
+ * through the row normalisation, dfeats_s through the prototype normalisation and the class mean (every support row of class n receives
+ * dc_n / count_n), dtau = sum dz[q,n] cos[q,n].  Where a norm is below the clamp the gradient is the plain d / 1e-12, as autograd gives
+ * it; the projection onto the tangent space applies only where the norm is at or above the clamp.
+ * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32, three launches (class means; 16-row query tiles; [16 classes x 128 features]
+ * blocks of the support gradient plus the final sums).  Every sum has a fixed order and there are no floating-point atomics: two calls
+ * on the same inputs give the same bits.
+ * A label outside [0,N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
+ * stays B * Qn); such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
+ * FUMI_ST_CLASS_MISSING and has a zero prototype.
+ * B >= 1, 1 <= S <= 1024, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
+ * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
+int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau);
 /* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
  * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
  *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
