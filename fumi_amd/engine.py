@@ -147,6 +147,14 @@ class HipEngine:
         return hip.cos_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, tau, need_grad=need_grad, grad_scale=grad_scale,
                                   want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau, n_way=n_way)
 
+    def ridge_head_step(self, feats_s, y_s, feats_q, y_q, params, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                        dfeats_q=None, dparams=None, n_way=None):
+        """Fused ridge-regression head with params [2] = (log lambda, logit scale) on the device: mean
+        cross-entropy of scale * query . W with W the closed-form ridge solution on the support rows, its predictions and the gradients
+        for both feature sets and params, through the solve."""
+        return hip.ridge_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, params, need_grad=need_grad, grad_scale=grad_scale,
+                                   want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams, n_way=n_way)
+
     def mix_images(self, x, partner, mode, lam=1.0, box=(0, 0, 0, 0)):
         """mixup (mode 0) / CutMix (mode 1) of a gathered image batch with its rows ``partner``."""
         return hip.mix_images(self._ws(x), x, partner, mode=mode, lam=lam, box=box)
@@ -158,7 +166,8 @@ class HipEngine:
         return hip.sgd_axpy(self._ws(p), p, step_size, g)
 
     def check(self, device):
-        """Synchronising validity check of the last calls (labels in range, every class has a support sample)."""
+        """Synchronising validity check of the last calls (labels in range, every class has a support sample, every pivot of the
+        ridge head positive)."""
         device = torch.device(device)
         if device.type == "cuda":
             hip.raise_on_status(hip.Workspace.get(device).read_status())

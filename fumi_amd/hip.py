@@ -42,10 +42,10 @@ SYMBOLS = [
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
-    "fumi_hip_cos_proto_step",
+    "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step",
 ]
 
-ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT = 1, 2, 4
+ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
 N_PHASES = 18
 
 _lib = None
@@ -234,6 +234,7 @@ def lib():
         L.fumi_hip_mix_images.argtypes = ([c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_float] + [c_int] * 4
                                           + [c_void_p])
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         _lib = L
     return _lib
 
@@ -405,6 +406,9 @@ def raise_on_status(status):
     if status & ST_SYNC_TIMEOUT:
         raise RuntimeError("a workgroup timed out waiting for the sibling workgroups of its episode "
                            "(FUMI_ST_SYNC_TIMEOUT): the results of that step are invalid")
+    if status & ST_NOT_POSDEF:
+        raise FloatingPointError("a pivot of the ridge head's Cholesky factorisation was not positive (FUMI_ST_NOT_POSDEF): "
+                                 "non-finite features or a ridge weight that underflowed")
     if status & ST_CLASS_MISSING:
         raise IndexError("a class has no support sample (the reference raises IndexError at fumi/models/fumi.py:209)")
     if status & ST_LABEL_RANGE:
@@ -1614,6 +1618,41 @@ def cos_proto_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_
                                          _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
                                          _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_cos_proto_step")
     return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau)
+
+
+def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                    dfeats_q=None, dparams=None, n_way=None):
+    """The fused ridge-regression head (csrc/ridgehead.hip): per episode A = (X X^T + exp(rho) I)^-1 onehot(y_s) on the support rows
+    X = feats_s [B,S,F], logits alpha * feats_q [B,Qn,F] X^T A, mean softmax cross-entropy against y_q [B,Qn] over all B * Qn rows.
+    ``params`` is a GPU tensor [2] = (rho, alpha) (the kernels read it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which
+    synchronises -- callers that know N pass it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn]
+    (first arg-max), logits [B,Qn,N] (None without want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dparams [2] =
+    gradients of grad_scale * loss through both solves (written into the tensors given, else into new ones)."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError("ridge_head_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(params, (2,), "params")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
+    if need_grad:
+        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
+        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
+        dparams = torch.empty(2, device=dev, dtype=torch.float32) if dparams is None else dparams
+        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dparams, (2,), "dparams")
+        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dparams, "dparams")]
+    else:
+        dfeats_s = dfeats_q = dparams = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_ridge_head_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
+                                          _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(params, "params"), float(grad_scale),
+                                          _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
+                                          _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_ridge_head_step")
+    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams)
 
 
 def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,

@@ -188,6 +188,16 @@ def check_supported(args):
         raise ValueError("--pretrain_metric chooses the few-shot validation metric of the supervised classifier: it needs --model pretrain")
     if not temp > 0.0:
         raise ValueError(f"--metric_temp {temp} must be positive")
+    head, r_lam, r_scale = (getattr(args, k, d) for k, d in (("fewshot_head", "cosine"), ("ridge_lambda", 50.0), ("ridge_scale", 1.0)))
+    if head == "ridge" and family != "metabaseline":
+        raise ValueError("--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: ridge needs --model metabaseline")
+    if not r_lam > 0.0:
+        raise ValueError(f"--ridge_lambda {r_lam} must be positive")
+    if not r_scale > 0.0:
+        raise ValueError(f"--ridge_scale {r_scale} must be positive")
+    if (head == "ridge" or metric == "ridge") and args.num_ways * args.num_shots > 128:
+        raise NotImplementedError(f"the ridge head factors the [S, S] Gram matrix of an episode's support set in LDS: S = --num_ways * "
+                                  f"--num_shots = {args.num_ways * args.num_shots} must not exceed 128")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):

@@ -6,7 +6,11 @@ The model is the backbone of ``Pretrain`` and AM3 under the same attribute name 
 by the cosine between a query's features and the class means of the support features, scaled by ``temp``; the loss is the softmax
 cross-entropy over all query rows of the meta-batch.  A training step is three engine calls: ``encode`` (tape kept),
 ``cos_proto_step`` (csrc/cosproto.hip: loss, predictions, the gradients for both feature sets and ``temp``) and ``encode_bwd``; the
-gradients land in one flat buffer and the fused optimizer step follows.  Validation and test run the head's forward form."""
+gradients land in one flat buffer and the fused optimizer step follows.  Validation and test run the head's forward form.
+
+``head="ridge"`` (``--fewshot_head ridge``) puts the closed-form ridge-regression base learner in the head's
+place: ``ridge_head_step`` (csrc/ridgehead.hip) and one parameter ``ridge = [log lambda, logit scale]`` instead of ``temp``."""
+import math
 import os
 
 import torch
@@ -22,10 +26,16 @@ from ..utils.wandb_compat import wandb
 
 
 class MetaBaseline(nn.Module):
-    def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0):
+    def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
+                 ridge_scale=1.0):
         super().__init__()
+        if head not in ("cosine", "ridge"):
+            raise ValueError(f"the few-shot head must be cosine or ridge, got {head}")
         if not float(init_temp) > 0.0:
             raise ValueError(f"the temperature must be positive, got {init_temp}")
+        if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
+            raise ValueError(f"the ridge weight and the logit scale must be positive, got {ridge_lambda}, {ridge_scale}")
+        self.head = head
         self.backbone = im_encoder
         if im_encoder == "conv4":
             from .conv4 import Conv4
@@ -36,26 +46,33 @@ class MetaBaseline(nn.Module):
         else:
             raise NameError(f"{im_encoder} not allowed as image encoder of --model metabaseline (conv4, resnet12)")
         self.num_ways = num_ways               # N of the episodes (None: read from the support labels, which synchronises)
-        self.temp = nn.Parameter(torch.tensor([float(init_temp)]))
+        if head == "ridge":
+            self.ridge = nn.Parameter(torch.tensor([math.log(float(ridge_lambda)), float(ridge_scale)]))
+        else:
+            self.temp = nn.Parameter(torch.tensor([float(init_temp)]))
         self._flat = None
         self._pcache = None
 
     def backbone_module(self):
         return self.conv
 
+    def head_param(self):
+        """The head's own parameter: ``temp`` [1] of the cosine head, ``ridge`` [2] of the ridge head."""
+        return self.ridge if self.head == "ridge" else self.temp
+
     def _step_params(self, need_grad):
-        """(detached temperature, detached backbone tensors, flat gradient buffer | None), the same objects from step to step; rebuilt
-        when a parameter object was replaced or moved (``_apply``)."""
+        """(detached temperature | ridge parameters, detached backbone tensors, flat gradient buffer | None), the same objects from step
+        to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
         c = self._pcache
         if c is None or not c[0].valid():
-            th = self.conv.theta()
-            c = self._pcache = (ParamWatch(self, [self.temp] + th), self.temp.detach(), [p.detach() for p in th])
+            th, hp = self.conv.theta(), self.head_param()
+            c = self._pcache = (ParamWatch(self, [hp] + th), hp.detach(), [p.detach() for p in th])
             self._flat = None
         fg = None
         if need_grad:
             fg = self._flat
             if fg is None:
-                fg = self._flat = FlatGrads([self.temp] + self.conv.theta(), extra=2)
+                fg = self._flat = FlatGrads([self.head_param()] + self.conv.theta(), extra=2)
         return c[1], c[2], fg
 
     def _apply(self, fn, recurse=True):
@@ -83,7 +100,10 @@ class MetaBaseline(nn.Module):
         encode, encode_bwd = self._encoders(eng)
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         g_t, g_theta = fg.split(1)
-        out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
+        if self.head == "ridge":
+            out = eng.ridge_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dparams=g_t[0], n_way=N)
+        else:
+            out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
         encode_bwd(x_s, x_q, out["dfeats_s"], out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
         torch.cat((out["loss"], out["correct"] / y_q.numel()), out=fg.tail)
         if optimizer is not None:
@@ -101,7 +121,8 @@ class MetaBaseline(nn.Module):
         x_s, x_q, y_s, y_q, N = self._episode(batch, device)
         temp, theta, _ = self._step_params(False)
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
-        out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
+        step = eng.ridge_head_step if self.head == "ridge" else eng.cos_proto_step
+        out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return torch.cat((out["loss"], out["correct"] / y_q.numel()))
 
     def evaluate(self, batch, optimizer, scheduler, device, task="train"):
@@ -117,6 +138,14 @@ class MetaBaseline(nn.Module):
         with torch.no_grad():
             loss, acc = self.few_shot(batch, device).cpu().numpy()
         return loss, acc
+
+
+def head_log(model):
+    """What a validation logs of the head's own parameter: ``temp``, or ``ridge_lambda`` and ``ridge_scale``."""
+    if model.head == "ridge":
+        rho, scale = model.ridge.detach().tolist()
+        return {"ridge_lambda": math.exp(rho), "ridge_scale": scale}
+    return {"temp": float(model.temp.detach())}
 
 
 def training_run(args, model, optimizer, train_loader, val_loader, max_test_batches):
@@ -135,7 +164,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 is_best = val_loss < best_loss
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
-                wandb.log({"val/acc": val_acc, "val/loss": val_loss, "temp": float(model.temp.detach()), **clip_log(opt)}, step=batch_idx)
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **head_log(model), **clip_log(opt)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"
@@ -151,7 +180,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
 
 
 def test_loop(args, model, test_dataloader, max_num_batches):
-    """(mean loss, mean acc) of the cosine nearest-centroid evaluation over max_num_batches + 1 episodic meta-batches."""
+    """(mean loss, mean acc) of the head's forward form over max_num_batches + 1 episodic meta-batches."""
     m_loss, m_acc = AverageMeter(), AverageMeter()
     for batch_idx, batch in enumerate(test_dataloader):
         loss, acc = model.evaluate(batch=batch, optimizer=None, scheduler=None, device=args.device, task="test")

@@ -12,6 +12,7 @@ side, so that the unchanged encode call normalises every R consecutive images by
 Validation and test are few-shot nearest-centroid classification on backbone features over the episodic batches the pixel samplers
 produce: the checkpoint with the best few-shot validation loss wins.  ``--encoder_checkpoint`` (fumi_amd/utils/utils.py) loads the
 ``conv.*`` tensors of such a checkpoint into ``--model fumi | maml | am3``."""
+import math
 import os
 
 import torch
@@ -29,10 +30,14 @@ from ..utils.wandb_compat import wandb
 
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
-                 metric="euclidean", metric_temp=10.0):
+                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0):
         super().__init__()
-        if metric not in ("euclidean", "cosine"):
-            raise ValueError(f"the few-shot metric must be euclidean or cosine, got {metric}")
+        if metric not in ("euclidean", "cosine", "ridge"):
+            raise ValueError(f"the few-shot metric must be euclidean, cosine or ridge, got {metric}")
+        if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
+            raise ValueError(f"the ridge weight and the logit scale of the ridge metric must be positive, got {ridge_lambda}, {ridge_scale}")
+        self.ridge_lambda, self.ridge_scale = float(ridge_lambda), float(ridge_scale)   # fixed values of the ridge metric (section 33)
+        self._ridge = None
         if not float(metric_temp) > 0.0:
             raise ValueError(f"the temperature of the cosine metric must be positive, got {metric_temp}")
         self.metric, self.metric_temp = metric, float(metric_temp)   # few-shot validation / test metric
@@ -120,7 +125,8 @@ class Pretrain(nn.Module):
     def few_shot(self, batch, device):
         """(loss, acc) of nearest-centroid classification on backbone features over one episodic meta-batch: class means of the support
         features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min.
-        With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature."""
+        With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature; with
+        ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale."""
         eng = _engine.get_engine()
         (_, _, s_im), s_y = batch['train']
         (_, _, q_im), q_y = batch['test']
@@ -133,6 +139,11 @@ class Pretrain(nn.Module):
             if self._tau is None or self._tau.device != f_s.device:
                 self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
             out = eng.cos_proto_step(f_s, y_s, f_q, y_q, self._tau, need_grad=False, n_way=N)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+        if self.metric == "ridge":
+            if self._ridge is None or self._ridge.device != f_s.device:
+                self._ridge = torch.tensor([math.log(self.ridge_lambda), self.ridge_scale], device=f_s.device, dtype=torch.float32)
+            out = eng.ridge_head_step(f_s, y_s, f_q, y_q, self._ridge, need_grad=False, n_way=N)
             return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
         d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]

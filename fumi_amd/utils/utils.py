@@ -93,7 +93,12 @@ _ENGINE_FLAGS = [     # additive, not in the reference
 ]
 _METRIC_FLAGS = [           # the cosine nearest-centroid metric; a list of its own, between the two others
     ("--metric_temp", dict(type=float, default=10.0, help="[--model metabaseline] initial temperature of the cosine classifier; [--model pretrain --pretrain_metric cosine] its fixed temperature (positive)")),
-    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, or their cosine at --metric_temp")),
+    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, or the ridge-regression head at --ridge_lambda / --ridge_scale")),
+]
+_RIDGE_FLAGS = [            # the ridge-regression head; a list of its own, between _FLAGS and _ENGINE_FLAGS
+    ("--fewshot_head", dict(type=str, choices=["cosine", "ridge"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, or closed-form ridge regression on the support features with a learned ridge weight and logit scale")),
+    ("--ridge_lambda", dict(type=float, default=50.0, help="[--fewshot_head ridge] initial ridge weight lambda (learned as its logarithm); [--pretrain_metric ridge] its fixed value (positive)")),
+    ("--ridge_scale", dict(type=float, default=1.0, help="[--fewshot_head ridge] initial logit scale (learned); [--pretrain_metric ridge] its fixed value (positive)")),
 ]
 _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain; a list of their own, after _ENGINE_FLAGS
     ("--label_smoothing", dict(type=float, default=0.0, help="[--model pretrain] label smoothing eps of the training loss, in [0, 1)")),
@@ -105,7 +110,7 @@ _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain (DESIGN.md sectio
 
 def parser():
     p = argparse.ArgumentParser(description="Multimodal image classification")
-    for flag, kw in _FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
+    for flag, kw in _FLAGS + _RIDGE_FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -130,11 +135,14 @@ def init_model(args, dictionary, watch=True):
         model = pretrain.Pretrain(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
                                   n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways,
                                   label_smoothing=getattr(args, "label_smoothing", 0.0),
-                                  metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0))
+                                  metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0),
+                                  ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0))
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
-                                          num_ways=args.num_ways, init_temp=getattr(args, "metric_temp", 10.0))
+                                          num_ways=args.num_ways, init_temp=getattr(args, "metric_temp", 10.0),
+                                          head=getattr(args, "fewshot_head", "cosine"), ridge_lambda=getattr(args, "ridge_lambda", 50.0),
+                                          ridge_scale=getattr(args, "ridge_scale", 1.0))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

@@ -49,6 +49,8 @@ typedef void* fumi_stream_t;          /* hipStream_t */
 #define FUMI_ST_CLASS_MISSING 2       /* a class without a support sample (fumi.py:209 would raise) */
 #define FUMI_ST_SYNC_TIMEOUT  4       /* a workgroup gave up waiting for the sibling workgroups of its episode (split inner loop /
                                        * split reverse sweep): the step's results are not to be trusted; the host raises RuntimeError */
+#define FUMI_ST_NOT_POSDEF    8       /* a pivot of the ridge head's Cholesky factorisation was not > 0 (a NaN counts) and was replaced
+                                       * by lambda: the episode's results are not to be trusted; the host raises FloatingPointError */
 
 #define FUMI_MAX_HIDDEN 8
 
@@ -505,6 +507,29 @@ int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int 
 int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau);
+/* The ridge-regression few-shot head with a backward (csrc/ridgehead.hip): the closed-form base learner of R2-D2
+ * and of MetaOptNet's ridge head, in the slot of fumi_hip_cos_proto_step.  params [2] = (rho, alpha) is read from DEVICE memory (both
+ * are parameters the optimizer updates); lam = exp(rho) is the ridge weight, alpha the logit scale.  Per episode b, with X = feats_s[b]
+ * [S,F], Y = onehot(y_s[b]) [S,N], Fq = feats_q[b] [Qn,F]:
+ *     M = X X^T + lam I,   A = M^-1 Y,   W = X^T A [F,N],   z = alpha Fq W,
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
+ * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dparams [2] = gradients of grad_scale * loss (written, not accumulated) -- all three given
+ * (training form) or all three NULL (forward form: loss, correct, preds and logits are bit-identical to the training form's):
+ *     dz = grad_scale / (B Qn) (softmax(z) - onehot(y_q)),   dfeats_q = alpha dz W^T,   dW = alpha Fq^T dz,   G = M^-1 (X dW),
+ *     dfeats_s = A (dW - X^T G)^T - G W^T,   dparams = (-lam sum G * A,  sum dz * (Fq W)).
+ * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32; M is factored once per episode (Cholesky in LDS) and the factor serves both
+ * solves.  Four launches in the forward form, six in the training form.  Every sum has a fixed order and there are no floating-point
+ * atomics: two calls on the same inputs give the same bits.
+ * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss, the count or any gradient (the divisor stays
+ * B * Qn).  A support label outside [0,N) sets the same bit and the row is left out exactly: its feature row counts as zero, its rows of
+ * Y, A and dfeats_s are zero.  A class without a support row sets FUMI_ST_CLASS_MISSING and has logits 0.  A pivot of the factorisation
+ * that is not > 0 (a NaN counts) sets FUMI_ST_NOT_POSDEF and is replaced by lam; the call returns and the other episodes are untouched.
+ * B >= 1, 1 <= S <= 128, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
+ * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
+int fumi_hip_ridge_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* params, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dparams);
 /* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
  * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
  *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
