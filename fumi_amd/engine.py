@@ -155,6 +155,14 @@ class HipEngine:
         return hip.ridge_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, params, need_grad=need_grad, grad_scale=grad_scale,
                                    want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams, n_way=n_way)
 
+    def logreg_head_step(self, feats_s, y_s, feats_q, y_q, steps=100, lr=1.0, momentum=0.9, C=1.0, normalize=True, want_logits=False,
+                         n_way=None):
+        """Fused logistic-regression head, forward only: ``steps`` steps of heavy-ball descent from zero on the
+        multinomial logistic regression of each episode's support rows, fitted in LDS; mean cross-entropy and predictions of the
+        query rows."""
+        return hip.logreg_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, steps=steps, lr=lr, momentum=momentum, C=C,
+                                    normalize=normalize, want_logits=want_logits, n_way=n_way)
+
     def mix_images(self, x, partner, mode, lam=1.0, box=(0, 0, 0, 0)):
         """mixup (mode 0) / CutMix (mode 1) of a gathered image batch with its rows ``partner``."""
         return hip.mix_images(self._ws(x), x, partner, mode=mode, lam=lam, box=box)

@@ -42,7 +42,7 @@ SYMBOLS = [
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
-    "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step",
+    "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step", "fumi_hip_logreg_head_step", "fumi_hip_logreg_set_form",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -235,6 +235,9 @@ def lib():
                                           + [c_void_p])
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_logreg_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4 + [c_int] + [c_float] * 3 + [c_int]
+                                                + [c_void_p] * 4)
+        L.fumi_hip_logreg_set_form.argtypes = [c_int]
         _lib = L
     return _lib
 
@@ -1653,6 +1656,37 @@ def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, g
                                           _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
                                           _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_ridge_head_step")
     return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams)
+
+
+def logreg_set_form(form):
+    """The form of the logistic-regression fit's K~ A product in the calls that follow: "valu", "mfma" or None (chosen per shape)."""
+    _check(lib().fumi_hip_logreg_set_form({None: -1, "valu": 0, "mfma": 1}[form]), "fumi_hip_logreg_set_form")
+
+
+def logreg_head_step(ws, feats_s, y_s, feats_q, y_q, *, steps=100, lr=1.0, momentum=0.9, C=1.0, normalize=True, want_logits=False,
+                     n_way=None):
+    """The fused logistic-regression head, forward only (csrc/logreghead.hip): per episode ``steps`` steps of heavy-ball descent (``lr``,
+    ``momentum``) from zero on the multinomial logistic regression of the support rows feats_s [B,S,F] (L2-normalised when
+    ``normalize``) with weight decay 1 / (C n), fitted in LDS in the dual; logits of feats_q [B,Qn,F] (normalised alike), mean softmax
+    cross-entropy against y_q [B,Qn] over all B * Qn rows.  ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers
+    that know N pass it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits
+    [B,Qn,N] (None without want_logits).  The fit is not differentiated: there are no gradients."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError("logreg_head_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
+    _check(lib().fumi_hip_logreg_head_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
+                                           _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), int(steps), float(lr), float(momentum), float(C),
+                                           1 if normalize else 0, _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
+                                           _f32(logits, "logits") if want_logits else None), "fumi_hip_logreg_head_step")
+    return dict(loss=loss, correct=correct, preds=preds, logits=logits)
 
 
 def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,

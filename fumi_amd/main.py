@@ -198,6 +198,24 @@ def check_supported(args):
     if (head == "ridge" or metric == "ridge") and args.num_ways * args.num_shots > 128:
         raise NotImplementedError(f"the ridge head factors the [S, S] Gram matrix of an episode's support set in LDS: S = --num_ways * "
                                   f"--num_shots = {args.num_ways * args.num_shots} must not exceed 128")
+    e_head = getattr(args, "eval_head", "train")
+    if e_head == "logreg" and family != "metabaseline":
+        raise ValueError("--eval_head chooses the validation / test classifier of the Meta-Baseline stage: logreg needs --model "
+                         "metabaseline (--model pretrain takes --pretrain_metric logreg)")
+    if e_head == "logreg" or metric == "logreg":   # (the --logreg_* values are asked of nothing that does not run the head)
+        lg = utils.logreg_config(args)          # (raises ValueError outside the kernel's limits)
+        S = args.num_ways * args.num_shots
+        if S > 128:
+            raise NotImplementedError(f"the logistic-regression head fits on the [S, S] Gram matrix of an episode's support set in LDS: "
+                                      f"S = --num_ways * --num_shots = {S} must not exceed 128")
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the logistic-regression head takes 2 to 64 classes, got --num_ways {args.num_ways}")
+        wd = 1.0 / (lg["C"] * max(S, 1))
+        if lg["normalize"] and lg["lr"] * (1.0 + wd) >= 2.0 * (1.0 + lg["momentum"]):
+            raise ValueError(f"--logreg_lr {lg['lr']} can diverge: on L2-normalised rows with a bias the curvature of the mean "
+                             f"cross-entropy is at most 1, so the objective's is at most 1 + wd with wd = 1 / (--logreg_C * S) = {wd:.4g}, "
+                             f"and the heavy-ball iteration is stable only for lr * (1 + wd) < 2 * (1 + --logreg_momentum) = "
+                             f"{2.0 * (1.0 + lg['momentum']):.4g}")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):

@@ -9,7 +9,11 @@ cross-entropy over all query rows of the meta-batch.  A training step is three e
 gradients land in one flat buffer and the fused optimizer step follows.  Validation and test run the head's forward form.
 
 ``head="ridge"`` (``--fewshot_head ridge``) puts the closed-form ridge-regression base learner in the head's
-place: ``ridge_head_step`` (csrc/ridgehead.hip) and one parameter ``ridge = [log lambda, logit scale]`` instead of ``temp``."""
+place: ``ridge_head_step`` (csrc/ridgehead.hip) and one parameter ``ridge = [log lambda, logit scale]`` instead of ``temp``.
+
+``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
+head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
+not a parameter: ``state_dict`` is the same either way."""
 import math
 import os
 
@@ -27,10 +31,14 @@ from ..utils.wandb_compat import wandb
 
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
-                 ridge_scale=1.0):
+                 ridge_scale=1.0, eval_head="train", logreg=None):
         super().__init__()
         if head not in ("cosine", "ridge"):
             raise ValueError(f"the few-shot head must be cosine or ridge, got {head}")
+        if eval_head not in ("train", "logreg"):
+            raise ValueError(f"the evaluation head must be train or logreg, got {eval_head}")
+        self.eval_head = eval_head             # validation / test classifier: the training head, or the logistic-regression head
+        self.logreg = utils.logreg_config(logreg)
         if not float(init_temp) > 0.0:
             raise ValueError(f"the temperature must be positive, got {init_temp}")
         if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
@@ -121,6 +129,9 @@ class MetaBaseline(nn.Module):
         x_s, x_q, y_s, y_q, N = self._episode(batch, device)
         temp, theta, _ = self._step_params(False)
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
+        if self.eval_head == "logreg":
+            out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         step = eng.ridge_head_step if self.head == "ridge" else eng.cos_proto_step
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return torch.cat((out["loss"], out["correct"] / y_q.numel()))

@@ -30,10 +30,11 @@ from ..utils.wandb_compat import wandb
 
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
-                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0):
+                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None):
         super().__init__()
-        if metric not in ("euclidean", "cosine", "ridge"):
-            raise ValueError(f"the few-shot metric must be euclidean, cosine or ridge, got {metric}")
+        if metric not in ("euclidean", "cosine", "ridge", "logreg"):
+            raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge or logreg, got {metric}")
+        self.logreg = utils.logreg_config(logreg)          # fixed hyper-parameters of the logistic-regression metric (section 34)
         if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
             raise ValueError(f"the ridge weight and the logit scale of the ridge metric must be positive, got {ridge_lambda}, {ridge_scale}")
         self.ridge_lambda, self.ridge_scale = float(ridge_lambda), float(ridge_scale)   # fixed values of the ridge metric (section 33)
@@ -126,7 +127,8 @@ class Pretrain(nn.Module):
         """(loss, acc) of nearest-centroid classification on backbone features over one episodic meta-batch: class means of the support
         features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min.
         With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature; with
-        ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale."""
+        ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale; with
+        ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters."""
         eng = _engine.get_engine()
         (_, _, s_im), s_y = batch['train']
         (_, _, q_im), q_y = batch['test']
@@ -144,6 +146,9 @@ class Pretrain(nn.Module):
             if self._ridge is None or self._ridge.device != f_s.device:
                 self._ridge = torch.tensor([math.log(self.ridge_lambda), self.ridge_scale], device=f_s.device, dtype=torch.float32)
             out = eng.ridge_head_step(f_s, y_s, f_q, y_q, self._ridge, need_grad=False, n_way=N)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+        if self.metric == "logreg":
+            out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
             return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
         d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]

@@ -93,12 +93,20 @@ _ENGINE_FLAGS = [     # additive, not in the reference
 ]
 _METRIC_FLAGS = [           # the cosine nearest-centroid metric; a list of its own, between the two others
     ("--metric_temp", dict(type=float, default=10.0, help="[--model metabaseline] initial temperature of the cosine classifier; [--model pretrain --pretrain_metric cosine] its fixed temperature (positive)")),
-    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, or the ridge-regression head at --ridge_lambda / --ridge_scale")),
+    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge", "logreg"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, the ridge-regression head at --ridge_lambda / --ridge_scale, or the logistic-regression head at --logreg_steps / --logreg_lr / --logreg_momentum / --logreg_C")),
 ]
 _RIDGE_FLAGS = [            # the ridge-regression head; a list of its own, between _FLAGS and _ENGINE_FLAGS
     ("--fewshot_head", dict(type=str, choices=["cosine", "ridge"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, or closed-form ridge regression on the support features with a learned ridge weight and logit scale")),
     ("--ridge_lambda", dict(type=float, default=50.0, help="[--fewshot_head ridge] initial ridge weight lambda (learned as its logarithm); [--pretrain_metric ridge] its fixed value (positive)")),
     ("--ridge_scale", dict(type=float, default=1.0, help="[--fewshot_head ridge] initial logit scale (learned); [--pretrain_metric ridge] its fixed value (positive)")),
+]
+_LOGREG_FLAGS = [           # the logistic-regression head; a list of its own, after _RIDGE_FLAGS
+    ("--logreg_steps", dict(type=int, default=100, help="[--pretrain_metric logreg / --eval_head logreg] heavy-ball steps of the per-episode fit (1 to 10000)")),
+    ("--logreg_lr", dict(type=float, default=1.0, help="[--pretrain_metric logreg / --eval_head logreg] step size of the fit (positive)")),
+    ("--logreg_momentum", dict(type=float, default=0.9, help="[--pretrain_metric logreg / --eval_head logreg] heavy-ball momentum of the fit, in [0, 1)")),
+    ("--logreg_C", dict(type=float, default=1.0, help="[--pretrain_metric logreg / --eval_head logreg] inverse regularisation strength, scikit-learn's LogisticRegression(C) (positive)")),
+    ("--logreg_raw", dict(action="store_true", help="[--pretrain_metric logreg / --eval_head logreg] fit on the raw features: skip the L2 normalisation of the support and query rows")),
+    ("--eval_head", dict(type=str, choices=["train", "logreg"], default="train", help="[--model metabaseline] the classifier of validation and test episodes: the head the model trains with, or a logistic regression fitted on each episode's backbone features")),
 ]
 _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain; a list of their own, after _ENGINE_FLAGS
     ("--label_smoothing", dict(type=float, default=0.0, help="[--model pretrain] label smoothing eps of the training loss, in [0, 1)")),
@@ -110,9 +118,26 @@ _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain (DESIGN.md sectio
 
 def parser():
     p = argparse.ArgumentParser(description="Multimodal image classification")
-    for flag, kw in _FLAGS + _RIDGE_FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
+    for flag, kw in _FLAGS + _RIDGE_FLAGS + _LOGREG_FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
         p.add_argument(flag, **kw)
     return p
+
+
+def logreg_config(cfg=None):
+    """The keyword arguments of ``logreg_head_step`` from a dict, an argparse namespace (--logreg_*) or None (the defaults), checked
+    against the kernel's limits."""
+    get = cfg.get if isinstance(cfg, dict) else (lambda k, dflt: getattr(cfg, "logreg_" + k, dflt))
+    c = dict(steps=int(get("steps", 100)), lr=float(get("lr", 1.0)), momentum=float(get("momentum", 0.9)), C=float(get("C", 1.0)))
+    c["normalize"] = bool(get("normalize", True)) if isinstance(cfg, dict) else not bool(get("raw", False))
+    if not 1 <= c["steps"] <= 10000:
+        raise ValueError(f"--logreg_steps {c['steps']} must lie in [1, 10000]")
+    if not c["lr"] > 0.0:
+        raise ValueError(f"--logreg_lr {c['lr']} must be positive")
+    if not 0.0 <= c["momentum"] < 1.0:
+        raise ValueError(f"--logreg_momentum {c['momentum']} must lie in [0, 1)")
+    if not c["C"] > 0.0:
+        raise ValueError(f"--logreg_C {c['C']} must be positive")
+    return c
 
 
 def init_model(args, dictionary, watch=True):
@@ -136,13 +161,15 @@ def init_model(args, dictionary, watch=True):
                                   n_classes=args.n_classes, bn_group=args.pretrain_bn_group, num_ways=args.num_ways,
                                   label_smoothing=getattr(args, "label_smoothing", 0.0),
                                   metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0),
-                                  ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0))
+                                  ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0),
+                                  logreg=logreg_config(args) if getattr(args, "pretrain_metric", "euclidean") == "logreg" else None)
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
                                           num_ways=args.num_ways, init_temp=getattr(args, "metric_temp", 10.0),
                                           head=getattr(args, "fewshot_head", "cosine"), ridge_lambda=getattr(args, "ridge_lambda", 50.0),
-                                          ridge_scale=getattr(args, "ridge_scale", 1.0))
+                                          ridge_scale=getattr(args, "ridge_scale", 1.0), eval_head=getattr(args, "eval_head", "train"),
+                                          logreg=logreg_config(args) if getattr(args, "eval_head", "train") == "logreg" else None)
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

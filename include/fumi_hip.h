@@ -530,6 +530,30 @@ int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, i
 int fumi_hip_ridge_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* params, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dparams);
+/* The logistic-regression few-shot head, forward only (csrc/logreghead.hip): the frozen-backbone protocol of Tian
+ * et al. 2020.  Per episode b, with X = feats_s[b] [S,F], x~_i = x_i / max(|x_i|, 1e-12) when `normalize` (the query rows alike), n the
+ * number of support rows with a label in [0,N) (at least 1), wd = 1 / (C n):
+ *     f(W, b) = (1/n) sum_i CE(W^T x~_i + b, y_i) + (wd/2) |W|^2      (scikit-learn's LogisticRegression(C) divided by n),
+ * `steps` steps of heavy-ball descent V <- momentum V + grad, (W, b) <- (W, b) - lr V from W = 0, b = 0, V = 0, iterated in the dual
+ * (W_t = X~^T A_t, on K~ = X~ X~^T in LDS; exactly the primal iteration), then z = Fq~ W + b.
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
+ * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).  There are no gradient outputs.
+ * fp32; four launches (fit, one workgroup per episode; W^T; 16-row query tiles; the final sums).  Every sum has a fixed order and there
+ * are no floating-point atomics: two calls on the same inputs give the same bits, with or without preds and logits.
+ * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss or the count (the divisor stays B * Qn).  A
+ * support label outside [0,N) sets the same bit and the row is left out exactly: its row and column of K~ and its rows of Y and R are
+ * zero and it does not count in n.  A class without a support row sets FUMI_ST_CLASS_MISSING and is fitted like any class.  The fit
+ * runs `steps` steps whatever the values are; non-finite features stay inside their episode.
+ * B >= 1, 1 <= S <= 128, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048, 1 <= steps <= 10000, lr > 0,
+ * 0 <= momentum < 1, C > 0: FUMI_ENOTSUP otherwise; FUMI_EINVAL for a NULL required pointer; both before any launch. */
+int fumi_hip_logreg_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, int steps, float lr, float momentum, float C,
+        int normalize, float* loss, float* correct, int64_t* preds, float* logits);
+/* The form of the fit's product K~ A [S,S] x [S,NP] in the calls that follow, process-wide: 0 the VALU loop, 1 the f32 MFMA
+ * (v_mfma_f32_16x16x4_f32), -1 (the default) the faster of the two as measured for the shape.  Both forms are held to the same
+ * float64 definition; each gives the same bits from call to call, the two need not agree in the last bits.  FUMI_EINVAL for any
+ * other value.  For tests and tools/bench_logreg_head.py. */
+int fumi_hip_logreg_set_form(int form);
 /* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
  * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
  *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
