@@ -147,6 +147,13 @@ class HipEngine:
         return hip.cos_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, tau, need_grad=need_grad, grad_scale=grad_scale,
                                   want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau, n_way=n_way)
 
+    def euclid_proto_step(self, feats_s, y_s, feats_q, y_q, alpha, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                          dfeats_q=None, dalpha=None, n_way=None):
+        """Fused prototypical-network head with the metric scale alpha [1] on the device: mean cross-entropy of
+        -alpha * |query - class mean|^2 over all query rows, its predictions and the gradients for both feature sets and alpha."""
+        return hip.euclid_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, alpha, need_grad=need_grad, grad_scale=grad_scale,
+                                     want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dalpha=dalpha, n_way=n_way)
+
     def ridge_head_step(self, feats_s, y_s, feats_q, y_q, params, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
                         dfeats_q=None, dparams=None, n_way=None):
         """Fused ridge-regression head with params [2] = (log lambda, logit scale) on the device: mean

@@ -43,6 +43,7 @@ SYMBOLS = [
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
     "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step", "fumi_hip_logreg_head_step", "fumi_hip_logreg_set_form",
+    "fumi_hip_euclid_proto_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -235,6 +236,7 @@ def lib():
                                           + [c_void_p])
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_euclid_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_logreg_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4 + [c_int] + [c_float] * 3 + [c_int]
                                                 + [c_void_p] * 4)
         L.fumi_hip_logreg_set_form.argtypes = [c_int]
@@ -1621,6 +1623,41 @@ def cos_proto_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_
                                          _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
                                          _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_cos_proto_step")
     return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau)
+
+
+def euclid_proto_step(ws, feats_s, y_s, feats_q, y_q, alpha, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                      dfeats_q=None, dalpha=None, n_way=None):
+    """The fused prototypical-network head (csrc/euclidproto.hip): per episode the class means of feats_s [B,S,F] by y_s [B,S], logits
+    -alpha * |feats_q [B,Qn,F] - mean|^2, mean softmax cross-entropy against y_q [B,Qn] over all B * Qn rows.  ``alpha`` is a GPU tensor
+    [1] (the kernels read it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers that know N pass
+    it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None
+    without want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dalpha [1] = gradients of grad_scale * loss (written
+    into the tensors given, else into new ones)."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError("euclid_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(alpha, (1,), "alpha")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
+    if need_grad:
+        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
+        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
+        dalpha = torch.empty(1, device=dev, dtype=torch.float32) if dalpha is None else dalpha
+        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dalpha, (1,), "dalpha")
+        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dalpha, "dalpha")]
+    else:
+        dfeats_s = dfeats_q = dalpha = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_euclid_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
+                                            _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(alpha, "alpha"), float(grad_scale),
+                                            _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
+                                            _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_euclid_proto_step")
+    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dalpha=dalpha)
 
 
 def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,

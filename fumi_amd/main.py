@@ -189,8 +189,8 @@ def check_supported(args):
     if not temp > 0.0:
         raise ValueError(f"--metric_temp {temp} must be positive")
     head, r_lam, r_scale = (getattr(args, k, d) for k, d in (("fewshot_head", "cosine"), ("ridge_lambda", 50.0), ("ridge_scale", 1.0)))
-    if head == "ridge" and family != "metabaseline":
-        raise ValueError("--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: ridge needs --model metabaseline")
+    if head in ("ridge", "proto") and family != "metabaseline":
+        raise ValueError(f"--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: {head} needs --model metabaseline")
     if not r_lam > 0.0:
         raise ValueError(f"--ridge_lambda {r_lam} must be positive")
     if not r_scale > 0.0:
@@ -198,6 +198,13 @@ def check_supported(args):
     if (head == "ridge" or metric == "ridge") and args.num_ways * args.num_shots > 128:
         raise NotImplementedError(f"the ridge head factors the [S, S] Gram matrix of an episode's support set in LDS: S = --num_ways * "
                                   f"--num_shots = {args.num_ways * args.num_shots} must not exceed 128")
+    p_scale, p_fixed = getattr(args, "proto_scale", 1.0), getattr(args, "proto_scale_fixed", False)
+    if not p_scale > 0.0:
+        raise ValueError(f"--proto_scale {p_scale} must be positive")
+    if p_fixed and head != "proto":
+        raise ValueError("--proto_scale_fixed fixes the scale of the prototypical head: it needs --fewshot_head proto")
+    if head == "proto" and not 2 <= args.num_ways <= 64:
+        raise NotImplementedError(f"the prototypical head takes 2 to 64 classes, got --num_ways {args.num_ways}")
     e_head = getattr(args, "eval_head", "train")
     if e_head == "logreg" and family != "metabaseline":
         raise ValueError("--eval_head chooses the validation / test classifier of the Meta-Baseline stage: logreg needs --model "

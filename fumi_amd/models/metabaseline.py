@@ -11,6 +11,11 @@ gradients land in one flat buffer and the fused optimizer step follows.  Validat
 ``head="ridge"`` (``--fewshot_head ridge``) puts the closed-form ridge-regression base learner in the head's
 place: ``ridge_head_step`` (csrc/ridgehead.hip) and one parameter ``ridge = [log lambda, logit scale]`` instead of ``temp``.
 
+``head="proto"`` (``--fewshot_head proto``) is Prototypical Networks: ``euclid_proto_step`` (csrc/euclidproto.hip),
+logits ``-proto_scale * |query - class mean|^2``.  ``proto_scale`` [1] is a parameter in ``temp``'s place (TADAM's metric scaling, the
+Euclidean variant of the Meta-Baseline stage) or, with ``proto_scale_fixed``, a persistent buffer that no optimizer sees: plain ProtoNet
+at the default 1.0.  ``state_dict`` holds it under the same name either way.
+
 ``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
 head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
 not a parameter: ``state_dict`` is the same either way."""
@@ -31,10 +36,10 @@ from ..utils.wandb_compat import wandb
 
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
-                 ridge_scale=1.0, eval_head="train", logreg=None):
+                 ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False):
         super().__init__()
-        if head not in ("cosine", "ridge"):
-            raise ValueError(f"the few-shot head must be cosine or ridge, got {head}")
+        if head not in ("cosine", "ridge", "proto"):
+            raise ValueError(f"the few-shot head must be cosine, ridge or proto, got {head}")
         if eval_head not in ("train", "logreg"):
             raise ValueError(f"the evaluation head must be train or logreg, got {eval_head}")
         self.eval_head = eval_head             # validation / test classifier: the training head, or the logistic-regression head
@@ -43,7 +48,12 @@ class MetaBaseline(nn.Module):
             raise ValueError(f"the temperature must be positive, got {init_temp}")
         if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
             raise ValueError(f"the ridge weight and the logit scale must be positive, got {ridge_lambda}, {ridge_scale}")
+        if not float(proto_scale) > 0.0:
+            raise ValueError(f"the scale of the prototypical head must be positive, got {proto_scale}")
+        if proto_scale_fixed and head != "proto":
+            raise ValueError(f"a fixed scale belongs to the prototypical head, got head {head}")
         self.head = head
+        self.proto_scale_fixed = bool(proto_scale_fixed)
         self.backbone = im_encoder
         if im_encoder == "conv4":
             from .conv4 import Conv4
@@ -56,31 +66,44 @@ class MetaBaseline(nn.Module):
         self.num_ways = num_ways               # N of the episodes (None: read from the support labels, which synchronises)
         if head == "ridge":
             self.ridge = nn.Parameter(torch.tensor([math.log(float(ridge_lambda)), float(ridge_scale)]))
+        elif head == "proto" and self.proto_scale_fixed:
+            self.register_buffer("proto_scale", torch.tensor([float(proto_scale)]))
+        elif head == "proto":
+            self.proto_scale = nn.Parameter(torch.tensor([float(proto_scale)]))
         else:
             self.temp = nn.Parameter(torch.tensor([float(init_temp)]))
         self._flat = None
         self._pcache = None
+        self._dscale = None
 
     def backbone_module(self):
         return self.conv
 
     def head_param(self):
-        """The head's own parameter: ``temp`` [1] of the cosine head, ``ridge`` [2] of the ridge head."""
+        """The head's own parameter: ``temp`` [1] of the cosine head, ``ridge`` [2] of the ridge head, ``proto_scale`` [1] of the
+        prototypical head -- None where that scale is fixed (a buffer: the head has no parameter then)."""
+        if self.head == "proto":
+            return None if self.proto_scale_fixed else self.proto_scale
         return self.ridge if self.head == "ridge" else self.temp
 
     def _step_params(self, need_grad):
-        """(detached temperature | ridge parameters, detached backbone tensors, flat gradient buffer | None), the same objects from step
-        to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
+        """(detached temperature | ridge parameters | scale, detached backbone tensors, flat gradient buffer | None), the same objects
+        from step to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
         c = self._pcache
-        if c is None or not c[0].valid():
+        if c is None or not c[0].valid() or (self.proto_scale_fixed and c[1] is not self._buffers["proto_scale"]):
             th, hp = self.conv.theta(), self.head_param()
-            c = self._pcache = (ParamWatch(self, [hp] + th), hp.detach(), [p.detach() for p in th])
+            own = [] if hp is None else [hp]
+            c = self._pcache = (ParamWatch(self, own + th), self._buffers["proto_scale"] if hp is None else hp.detach(),
+                                [p.detach() for p in th])
             self._flat = None
         fg = None
         if need_grad:
             fg = self._flat
             if fg is None:
-                fg = self._flat = FlatGrads([self.head_param()] + self.conv.theta(), extra=2)
+                hp = self.head_param()
+                fg = self._flat = FlatGrads(([] if hp is None else [hp]) + self.conv.theta(), extra=2)
+                # the fixed scale has no slot in the flat buffer: its gradient is written beside it and read by nobody
+                self._dscale = torch.empty(1, device=fg.flat.device, dtype=torch.float32) if hp is None else None
         return c[1], c[2], fg
 
     def _apply(self, fn, recurse=True):
@@ -107,8 +130,11 @@ class MetaBaseline(nn.Module):
         temp, theta, fg = self._step_params(True)
         encode, encode_bwd = self._encoders(eng)
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
-        g_t, g_theta = fg.split(1)
-        if self.head == "ridge":
+        g_t, g_theta = fg.split(0 if self.proto_scale_fixed else 1)
+        if self.head == "proto":
+            out = eng.euclid_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0,
+                                        dalpha=self._dscale if self.proto_scale_fixed else g_t[0], n_way=N)
+        elif self.head == "ridge":
             out = eng.ridge_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dparams=g_t[0], n_way=N)
         else:
             out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
@@ -132,7 +158,7 @@ class MetaBaseline(nn.Module):
         if self.eval_head == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
             return torch.cat((out["loss"], out["correct"] / y_q.numel()))
-        step = eng.ridge_head_step if self.head == "ridge" else eng.cos_proto_step
+        step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return torch.cat((out["loss"], out["correct"] / y_q.numel()))
 
@@ -152,7 +178,9 @@ class MetaBaseline(nn.Module):
 
 
 def head_log(model):
-    """What a validation logs of the head's own parameter: ``temp``, or ``ridge_lambda`` and ``ridge_scale``."""
+    """What a validation logs of the head's own parameter: ``temp``, ``ridge_lambda`` and ``ridge_scale``, or ``proto_scale``."""
+    if model.head == "proto":
+        return {"proto_scale": float(model.proto_scale.detach())}
     if model.head == "ridge":
         rho, scale = model.ridge.detach().tolist()
         return {"ridge_lambda": math.exp(rho), "ridge_scale": scale}

@@ -96,7 +96,7 @@ _METRIC_FLAGS = [           # the cosine nearest-centroid metric (DESIGN.md sect
     ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge", "logreg"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, the ridge-regression head at --ridge_lambda / --ridge_scale, or the logistic-regression head at --logreg_steps / --logreg_lr / --logreg_momentum / --logreg_C")),
 ]
 _RIDGE_FLAGS = [            # the ridge-regression head; a list of its own, between _FLAGS and _ENGINE_FLAGS
-    ("--fewshot_head", dict(type=str, choices=["cosine", "ridge"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, or closed-form ridge regression on the support features with a learned ridge weight and logit scale")),
+    ("--fewshot_head", dict(type=str, choices=["cosine", "ridge", "proto"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, closed-form ridge regression on the support features with a learned ridge weight and logit scale, or Prototypical Networks (squared Euclidean distance to the class means at --proto_scale)")),
     ("--ridge_lambda", dict(type=float, default=50.0, help="[--fewshot_head ridge] initial ridge weight lambda (learned as its logarithm); [--pretrain_metric ridge] its fixed value (positive)")),
     ("--ridge_scale", dict(type=float, default=1.0, help="[--fewshot_head ridge] initial logit scale (learned); [--pretrain_metric ridge] its fixed value (positive)")),
 ]
@@ -108,6 +108,10 @@ _LOGREG_FLAGS = [           # the logistic-regression head (DESIGN.md section 34
     ("--logreg_raw", dict(action="store_true", help="[--pretrain_metric logreg / --eval_head logreg] fit on the raw features: skip the L2 normalisation of the support and query rows")),
     ("--eval_head", dict(type=str, choices=["train", "logreg"], default="train", help="[--model metabaseline] the classifier of validation and test episodes: the head the model trains with, or a logistic regression fitted on each episode's backbone features")),
 ]
+_PROTO_FLAGS = [            # the prototypical-network head; a list of its own, directly after _LOGREG_FLAGS
+    ("--proto_scale", dict(type=float, default=1.0, help="[--fewshot_head proto] the scale alpha of the logits -alpha * |query - class mean|^2: its initial value (learned), or with --proto_scale_fixed its value (positive)")),
+    ("--proto_scale_fixed", dict(action="store_true", help="[--fewshot_head proto] keep --proto_scale fixed: plain Prototypical Networks at the default 1.0")),
+]
 _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain; a list of their own, after _ENGINE_FLAGS
     ("--label_smoothing", dict(type=float, default=0.0, help="[--model pretrain] label smoothing eps of the training loss, in [0, 1)")),
     ("--mixup_alpha", dict(type=float, default=0.0, help="[--model pretrain] mixup: lam ~ Beta(alpha, alpha) per training batch (0: off)")),
@@ -118,7 +122,7 @@ _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain (DESIGN.md sectio
 
 def parser():
     p = argparse.ArgumentParser(description="Multimodal image classification")
-    for flag, kw in _FLAGS + _RIDGE_FLAGS + _LOGREG_FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
+    for flag, kw in _FLAGS + _RIDGE_FLAGS + _LOGREG_FLAGS + _PROTO_FLAGS + _ENGINE_FLAGS + _METRIC_FLAGS + _PRETRAIN_MIX_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -169,7 +173,9 @@ def init_model(args, dictionary, watch=True):
                                           num_ways=args.num_ways, init_temp=getattr(args, "metric_temp", 10.0),
                                           head=getattr(args, "fewshot_head", "cosine"), ridge_lambda=getattr(args, "ridge_lambda", 50.0),
                                           ridge_scale=getattr(args, "ridge_scale", 1.0), eval_head=getattr(args, "eval_head", "train"),
-                                          logreg=logreg_config(args) if getattr(args, "eval_head", "train") == "logreg" else None)
+                                          logreg=logreg_config(args) if getattr(args, "eval_head", "train") == "logreg" else None,
+                                          proto_scale=getattr(args, "proto_scale", 1.0),
+                                          proto_scale_fixed=getattr(args, "proto_scale_fixed", False))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

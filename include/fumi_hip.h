@@ -507,6 +507,33 @@ int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int 
 int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau);
+/* The prototypical-network head with a metric scale (csrc/euclidproto.hip): Snell et al. 2017, and the Euclidean
+ * variant of the Meta-Baseline stage with TADAM's learned scale, in the slot of fumi_hip_cos_proto_step.  Per episode b:
+ *     c_n = mean of the rows of feats_s[b] with y_s == n (count clamped to >= 1, as fumi_hip_proto_reduce),
+ *     d2[q,n] = sum_f (feats_q[b,q,f] - c_n[f])^2,   z[q,n] = -alpha * d2[q,n],
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
+ * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).  alpha [1] is read from DEVICE
+ * memory: it may be a parameter the optimizer updates, no host synchronisation is needed.
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dalpha [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given
+ * (training form) or all three NULL (forward form: loss, correct, preds and logits are bit-identical to the training form's).  With
+ * dz = grad_scale / (B Qn) (softmax(z) - onehot(y_q)):
+ *     dfeats_q = 2 alpha dz C,   dc_n = 2 alpha ((dz^T F_q)_n - c_n sum_q dz[q,n]),   dalpha = -sum dz * d2,
+ * every support row of class n receives dc_n / count_n.  The term -2 alpha f_q sum_n dz[q,n] of dfeats_q is left out: the sum is zero
+ * in exact arithmetic.
+ * The [B,Qn,N,F] differences are never formed.  The distances come from one product per tile of 16 query rows, taken relative to the
+ * episode's mean prototype m = (1/N) sum_n c_n:  d2 = |f_q - m|^2 - 2 (f_q . c'_n - m . c'_n) + |c'_n|^2 with c'_n = c_n - m, so an
+ * offset common to all features of an episode (post-ReLU features have one) does not cost the distance its digits.
+ * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32, three launches (class means, centred; 16-row query tiles; [16 classes x 128
+ * features] blocks of the support gradient plus the final sums).  Every sum has a fixed order and there are no floating-point atomics:
+ * two calls on the same inputs give the same bits.
+ * A label outside [0,N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
+ * stays B * Qn); such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
+ * FUMI_ST_CLASS_MISSING and has a zero prototype: its logits are -alpha |f_q|^2.
+ * B >= 1, 1 <= S <= 1024, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
+ * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
+int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* alpha, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dalpha);
 /* The ridge-regression few-shot head with a backward (csrc/ridgehead.hip): the closed-form base learner of R2-D2
  * and of MetaOptNet's ridge head, in the slot of fumi_hip_cos_proto_step.  params [2] = (rho, alpha) is read from DEVICE memory (both
  * are parameters the optimizer updates); lam = exp(rho) is the ridge weight, alpha the logit scale.  Per episode b, with X = feats_s[b]
