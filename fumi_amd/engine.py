@@ -170,6 +170,13 @@ class HipEngine:
         return hip.logreg_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, steps=steps, lr=lr, momentum=momentum, C=C,
                                     normalize=normalize, want_logits=want_logits, n_way=n_way)
 
+    def trans_proto_step(self, feats_s, y_s, feats_q, y_q, scale, metric, steps, want_logits=False, n_way=None):
+        """Transductive prototype refinement, forward only: ``steps`` steps of soft k-means of the class
+        prototypes on each episode's query rows, then the mean cross-entropy and predictions of the cosine (``metric="cosine"``) or
+        squared-Euclidean (``"euclid"``) logits at ``scale`` [1] on the device."""
+        return hip.trans_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, scale, metric=metric, steps=steps,
+                                    want_logits=want_logits, n_way=n_way)
+
     def mix_images(self, x, partner, mode, lam=1.0, box=(0, 0, 0, 0)):
         """mixup (mode 0) / CutMix (mode 1) of a gathered image batch with its rows ``partner``."""
         return hip.mix_images(self._ws(x), x, partner, mode=mode, lam=lam, box=box)

@@ -43,7 +43,7 @@ SYMBOLS = [
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
     "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step", "fumi_hip_logreg_head_step", "fumi_hip_logreg_set_form",
-    "fumi_hip_euclid_proto_step",
+    "fumi_hip_euclid_proto_step", "fumi_hip_trans_proto_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -240,6 +240,7 @@ def lib():
         L.fumi_hip_logreg_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4 + [c_int] + [c_float] * 3 + [c_int]
                                                 + [c_void_p] * 4)
         L.fumi_hip_logreg_set_form.argtypes = [c_int]
+        L.fumi_hip_trans_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_int] * 2 + [c_void_p] * 4
         _lib = L
     return _lib
 
@@ -1723,6 +1724,37 @@ def logreg_head_step(ws, feats_s, y_s, feats_q, y_q, *, steps=100, lr=1.0, momen
                                            _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), int(steps), float(lr), float(momentum), float(C),
                                            1 if normalize else 0, _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
                                            _f32(logits, "logits") if want_logits else None), "fumi_hip_logreg_head_step")
+    return dict(loss=loss, correct=correct, preds=preds, logits=logits)
+
+
+TRANS_METRICS = {"cosine": 0, "euclid": 1}
+
+
+def trans_proto_step(ws, feats_s, y_s, feats_q, y_q, scale, *, metric, steps, want_logits=False, n_way=None):
+    """Transductive prototype refinement, forward only (csrc/transproto.hip): per episode ``steps`` steps of soft k-means on the query
+    rows feats_q [B,Qn,F] from the class means of feats_s [B,S,F] by y_s [B,S], c_n <- (s_n + sum_q w[q,n] f_q) / (k_n + sum_q w[q,n])
+    with w = softmax_n(z); z = scale * cos(query, c_n) for ``metric="cosine"``, -scale * |query - c_n|^2 for ``metric="euclid"``; mean
+    softmax cross-entropy of the refined logits against y_q [B,Qn] over all B * Qn rows.  ``scale`` is a GPU tensor [1] (the kernel
+    reads it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers that know N pass it.  ``steps=0``
+    is the forward form of ``cos_proto_step`` / ``euclid_proto_step``.  Returns a dict of GPU tensors: loss [1], correct [1] (count,
+    float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without want_logits).  There are no gradients."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError("trans_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    if metric not in TRANS_METRICS:
+        raise FumiHipError(f"trans_proto_step: metric must be cosine or euclid, got {metric}")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(scale, (1,), "scale")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
+    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
+    _check(lib().fumi_hip_trans_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
+                                           _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(scale, "scale"), TRANS_METRICS[metric],
+                                           int(steps), _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
+                                           _f32(logits, "logits") if want_logits else None), "fumi_hip_trans_proto_step")
     return dict(loss=loss, correct=correct, preds=preds, logits=logits)
 
 

@@ -223,6 +223,24 @@ def check_supported(args):
                              f"cross-entropy is at most 1, so the objective's is at most 1 + wd with wd = 1 / (--logreg_C * S) = {wd:.4g}, "
                              f"and the heavy-ball iteration is stable only for lr * (1 + wd) < 2 * (1 + --logreg_momentum) = "
                              f"{2.0 * (1.0 + lg['momentum']):.4g}")
+    t_steps = getattr(args, "transductive_steps", 0)
+    if not 0 <= t_steps <= 100:
+        raise ValueError(f"--transductive_steps {t_steps} must lie in [0, 100]")
+    if t_steps > 0:
+        if family not in ("metabaseline", "pretrain"):
+            raise ValueError("--transductive_steps refines the class prototypes of a nearest-centroid few-shot evaluation: it needs "
+                             "--model metabaseline or pretrain")
+        if head == "ridge" or e_head == "logreg" or metric in ("ridge", "logreg"):
+            raise ValueError("--transductive_steps refines class prototypes: it goes with the cosine and the Euclidean metric, not with "
+                             "--fewshot_head ridge, --eval_head logreg or --pretrain_metric ridge | logreg")
+        # the limits of fumi_hip_trans_proto_step (csrc/transproto.hip): w and the query rows of G of an episode are held in LDS
+        S, Qn = args.num_ways * args.num_shots, args.num_ways * args.num_shots_test
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the transductive head takes 2 to 64 classes, got --num_ways {args.num_ways}")
+        if S < 1 or Qn < 1 or S + Qn > 512 or Qn * args.num_ways > 8192:
+            raise NotImplementedError(f"the transductive head holds an episode's soft assignments in LDS: S + Qn = --num_ways * "
+                                      f"(--num_shots + --num_shots_test) = {S + Qn} must not exceed 512 and Qn * --num_ways = "
+                                      f"{Qn * args.num_ways} must not exceed 8192")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):

@@ -18,7 +18,11 @@ at the default 1.0.  ``state_dict`` holds it under the same name either way.
 
 ``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
 head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
-not a parameter: ``state_dict`` is the same either way."""
+not a parameter: ``state_dict`` is the same either way.
+
+``transductive_steps > 0`` (``--transductive_steps``) classifies validation and test episodes transductively:
+``trans_proto_step`` (csrc/transproto.hip) refines the class prototypes by that many soft k-means steps on the episode's queries, in the
+cosine metric at ``temp`` or the Euclidean one at ``proto_scale``.  Training and ``state_dict`` are the same either way."""
 import math
 import os
 
@@ -36,7 +40,7 @@ from ..utils.wandb_compat import wandb
 
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
-                 ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False):
+                 ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0):
         super().__init__()
         if head not in ("cosine", "ridge", "proto"):
             raise ValueError(f"the few-shot head must be cosine, ridge or proto, got {head}")
@@ -52,6 +56,12 @@ class MetaBaseline(nn.Module):
             raise ValueError(f"the scale of the prototypical head must be positive, got {proto_scale}")
         if proto_scale_fixed and head != "proto":
             raise ValueError(f"a fixed scale belongs to the prototypical head, got head {head}")
+        if not 0 <= int(transductive_steps) <= 100:
+            raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
+        if int(transductive_steps) > 0 and (head == "ridge" or eval_head == "logreg"):
+            raise ValueError("the transductive refinement moves class prototypes: it goes with the cosine and the prototypical head, "
+                             f"got head {head}, evaluation head {eval_head}")
+        self.transductive_steps = int(transductive_steps)   # soft k-means steps of validation / test episodes (0: inductive)
         self.head = head
         self.proto_scale_fixed = bool(proto_scale_fixed)
         self.backbone = im_encoder
@@ -158,6 +168,10 @@ class MetaBaseline(nn.Module):
         if self.eval_head == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
             return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+        if self.transductive_steps > 0:
+            out = eng.trans_proto_step(f_s, y_s, f_q, y_q, temp, metric="euclid" if self.head == "proto" else "cosine",
+                                       steps=self.transductive_steps, n_way=N)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return torch.cat((out["loss"], out["correct"] / y_q.numel()))
@@ -178,13 +192,15 @@ class MetaBaseline(nn.Module):
 
 
 def head_log(model):
-    """What a validation logs of the head's own parameter: ``temp``, ``ridge_lambda`` and ``ridge_scale``, or ``proto_scale``."""
+    """What a validation logs of the head's own parameter: ``temp``, ``ridge_lambda`` and ``ridge_scale``, or ``proto_scale``; with a
+    transductive evaluation also its number of steps."""
+    trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
     if model.head == "proto":
-        return {"proto_scale": float(model.proto_scale.detach())}
+        return {"proto_scale": float(model.proto_scale.detach()), **trans}
     if model.head == "ridge":
         rho, scale = model.ridge.detach().tolist()
         return {"ridge_lambda": math.exp(rho), "ridge_scale": scale}
-    return {"temp": float(model.temp.detach())}
+    return {"temp": float(model.temp.detach()), **trans}
 
 
 def training_run(args, model, optimizer, train_loader, val_loader, max_test_batches):

@@ -30,10 +30,16 @@ from ..utils.wandb_compat import wandb
 
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
-                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None):
+                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0):
         super().__init__()
         if metric not in ("euclidean", "cosine", "ridge", "logreg"):
             raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge or logreg, got {metric}")
+        if not 0 <= int(transductive_steps) <= 100:
+            raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
+        if int(transductive_steps) > 0 and metric in ("ridge", "logreg"):
+            raise ValueError(f"the transductive refinement moves class prototypes: it goes with the euclidean and the cosine metric, got {metric}")
+        self.transductive_steps = int(transductive_steps)   # soft k-means steps of the few-shot evaluation (section 36; 0: inductive)
+        self._one = None
         self.logreg = utils.logreg_config(logreg)          # fixed hyper-parameters of the logistic-regression metric (section 34)
         if not (float(ridge_lambda) > 0.0 and float(ridge_scale) > 0.0):
             raise ValueError(f"the ridge weight and the logit scale of the ridge metric must be positive, got {ridge_lambda}, {ridge_scale}")
@@ -128,7 +134,9 @@ class Pretrain(nn.Module):
         features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min.
         With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature; with
         ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale; with
-        ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters."""
+        ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters.
+        With ``transductive_steps > 0``: one call of the transductive head (trans_proto_step), cosine at the fixed temperature or
+        squared Euclidean at scale 1."""
         eng = _engine.get_engine()
         (_, _, s_im), s_y = batch['train']
         (_, _, q_im), q_y = batch['test']
@@ -137,6 +145,17 @@ class Pretrain(nn.Module):
         _, theta, _ = self._step_params(False)
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
         N = int(self.num_ways) if self.num_ways else int(y_s.max().item()) + 1
+        if self.transductive_steps > 0:
+            if self.metric == "cosine":
+                if self._tau is None or self._tau.device != f_s.device:
+                    self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
+                scale, trans_metric = self._tau, "cosine"
+            else:
+                if self._one is None or self._one.device != f_s.device:
+                    self._one = torch.ones(1, device=f_s.device, dtype=torch.float32)
+                scale, trans_metric = self._one, "euclid"
+            out = eng.trans_proto_step(f_s, y_s, f_q, y_q, scale, metric=trans_metric, steps=self.transductive_steps, n_way=N)
+            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
         if self.metric == "cosine":
             if self._tau is None or self._tau.device != f_s.device:
                 self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
@@ -193,7 +212,8 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 is_best = val_loss < best_loss
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
-                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **clip_log(opt)}, step=batch_idx)
+                trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **trans, **clip_log(opt)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"

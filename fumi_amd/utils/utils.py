@@ -99,6 +99,8 @@ _RIDGE_FLAGS = [            # the ridge-regression head; 
     ("--fewshot_head", dict(type=str, choices=["cosine", "ridge", "proto"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, closed-form ridge regression on the support features with a learned ridge weight and logit scale, or Prototypical Networks (squared Euclidean distance to the class means at --proto_scale)")),
     ("--ridge_lambda", dict(type=float, default=50.0, help="[--fewshot_head ridge] initial ridge weight lambda (learned as its logarithm); [--pretrain_metric ridge] its fixed value (positive)")),
     ("--ridge_scale", dict(type=float, default=1.0, help="[--fewshot_head ridge] initial logit scale (learned); [--pretrain_metric ridge] its fixed value (positive)")),
+    # (transductive inference, DESIGN.md section 36: appended here, the one list whose content no caller depends on)
+    ("--transductive_steps", dict(type=int, default=0, help="[--model metabaseline / pretrain] soft k-means refinement of the class prototypes on each validation / test episode's queries: the number of steps (0 to 100; 0: inductive, every query row is classified alone)")),
 ]
 _LOGREG_FLAGS = [           # the logistic-regression head; a list of its own, after _RIDGE_FLAGS
     ("--logreg_steps", dict(type=int, default=100, help="[--pretrain_metric logreg / --eval_head logreg] heavy-ball steps of the per-episode fit (1 to 10000)")),
@@ -166,7 +168,8 @@ def init_model(args, dictionary, watch=True):
                                   label_smoothing=getattr(args, "label_smoothing", 0.0),
                                   metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0),
                                   ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0),
-                                  logreg=logreg_config(args) if getattr(args, "pretrain_metric", "euclidean") == "logreg" else None)
+                                  logreg=logreg_config(args) if getattr(args, "pretrain_metric", "euclidean") == "logreg" else None,
+                                  transductive_steps=getattr(args, "transductive_steps", 0))
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
@@ -175,7 +178,8 @@ def init_model(args, dictionary, watch=True):
                                           ridge_scale=getattr(args, "ridge_scale", 1.0), eval_head=getattr(args, "eval_head", "train"),
                                           logreg=logreg_config(args) if getattr(args, "eval_head", "train") == "logreg" else None,
                                           proto_scale=getattr(args, "proto_scale", 1.0),
-                                          proto_scale_fixed=getattr(args, "proto_scale_fixed", False))
+                                          proto_scale_fixed=getattr(args, "proto_scale_fixed", False),
+                                          transductive_steps=getattr(args, "transductive_steps", 0))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

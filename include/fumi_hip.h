@@ -581,6 +581,25 @@ int fumi_hip_logreg_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S,
  * float64 definition; each gives the same bits from call to call, the two need not agree in the last bits.  FUMI_EINVAL for any
  * other value.  For tests and tools/bench_logreg_head.py. */
 int fumi_hip_logreg_set_form(int form);
+/* Transductive prototype refinement, forward only (csrc/transproto.hip): per episode, from the class sums s_n and
+ * counts k_n of feats_s [B,S,F] by y_s [B,S] and c^0_n = s_n / max(k_n, 1), `steps` steps of soft k-means on the query rows feats_q
+ * [B,Qn,F],
+ *     w = softmax_n(z(c^t)),   c^{t+1}_n = (s_n + sum_q w[q,n] f_q) / (k_n + sum_q w[q,n]),
+ * with z(c)[q,n] = scale[0] cos(f_q, c_n) (metric 0; both norms clamped at 1e-12) or -scale[0] |f_q - c_n|^2 (metric 1).  loss [1] is
+ * the mean softmax cross-entropy of z(c^steps) against y_q [B,Qn] over all B * Qn rows, correct [1] the number of rows whose first
+ * arg-max is the label, preds [B,Qn] that arg-max (optional), logits [B,Qn,N] z(c^steps) (optional).  steps = 0 is the forward form
+ * of fumi_hip_cos_proto_step / fumi_hip_euclid_proto_step.  scale is a device pointer.  The iteration runs in the dual on X_all S^T
+ * and X_all X_q^T (the f32 MFMA; metric 1 takes the rows relative to the mean step-0 prototype first), one workgroup per episode, two
+ * barriers per step.  Fixed-order sums, no floating-point atomics: equal inputs give equal bits.
+ * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss or the count (the divisor stays B * Qn) and
+ * still takes part in the refinement.  A support label outside [0,N) sets the same bit and the row is left out exactly.  A class
+ * without a support row sets FUMI_ST_CLASS_MISSING, starts from a zero prototype and is refined like any class.
+ * B >= 1, S >= 1, Qn >= 1, S + Qn <= 512, Qn * N <= 8192, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048,
+ * 0 <= steps <= 100: FUMI_ENOTSUP otherwise; FUMI_EINVAL for a NULL required pointer or a metric other than 0 or 1; both before any
+ * launch. */
+int fumi_hip_trans_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* scale, int metric, int steps,
+        float* loss, float* correct, int64_t* preds, float* logits);
 /* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
  * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
  *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
