@@ -140,6 +140,14 @@ class HipEngine:
         return hip.cls_head_step_soft(self._ws(feats), feats, y_a, W, b, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
                                       grad_scale=grad_scale, dfeats=dfeats, gW=gW, gb=gb)
 
+    def cls_head_step_distill(self, feats, y_a, W, b, feats_t, W_t, b_t, temp, alpha, ce_weight, y_b=None, lam=1.0, smoothing=0.0,
+                              need_grad=True, grad_scale=1.0, dfeats=None, gW=None, gb=None):
+        """The same head as the student of a frozen teacher: ce_weight * CE + alpha * T^2 KL(teacher || student)
+        at temperature ``temp``, with loss_ce, loss_kd and the count of rows that agree with the teacher."""
+        return hip.cls_head_step_distill(self._ws(feats), feats, y_a, W, b, feats_t, W_t, b_t, temp=temp, alpha=alpha,
+                                         ce_weight=ce_weight, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
+                                         grad_scale=grad_scale, dfeats=dfeats, gW=gW, gb=gb)
+
     def cos_proto_step(self, feats_s, y_s, feats_q, y_q, tau, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
                        dfeats_q=None, dtau=None, n_way=None):
         """Fused cosine nearest-centroid head with the temperature tau [1] on the device: mean cross-entropy of

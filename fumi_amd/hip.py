@@ -44,6 +44,7 @@ SYMBOLS = [
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
     "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step", "fumi_hip_logreg_head_step", "fumi_hip_logreg_set_form",
     "fumi_hip_euclid_proto_step", "fumi_hip_trans_proto_step",
+    "fumi_hip_cls_head_step_distill",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -232,6 +233,8 @@ def lib():
         L.fumi_hip_cls_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_float] + [c_void_p] * 6
         L.fumi_hip_cls_head_step_soft.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
                                                   + [c_float] + [c_void_p] * 6)
+        L.fumi_hip_cls_head_step_distill.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2
+                                                     + [c_void_p] * 5 + [c_float] * 4 + [c_void_p] * 8)
         L.fumi_hip_mix_images.argtypes = ([c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_float] + [c_int] * 4
                                           + [c_void_p])
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
@@ -1789,6 +1792,46 @@ def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0
                                              _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
            "fumi_hip_cls_head_step_soft")
     return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+
+
+def cls_head_step_distill(ws, feats, y_a, W, b, feats_t, W_t, b_t, *, temp, alpha, ce_weight, y_b=None, lam=1.0, smoothing=0.0,
+                          need_grad=True, grad_scale=1.0, dfeats=None, gW=None, gb=None, want_preds=True):
+    """``cls_head_step_soft`` as the student of a frozen teacher (fumi_hip_cls_head_step_distill): with
+    z_t = feats_t @ W_t.T + b_t and T = ``temp``, loss = ce_weight * loss_ce + alpha * loss_kd, loss_kd = T^2 KL(softmax(z_t / T) ||
+    softmax(z / T)) (batch mean).  The dict of ``cls_head_step_soft`` plus loss_ce [1], loss_kd [1] (views of loss_parts [2]) and
+    agree [1] (rows whose arg-max equals the teacher's, float)."""
+    dev = _dev(feats)
+    if feats.dim() != 2 or W.dim() != 2:
+        raise FumiHipError("cls_head_step_distill: feats [M,F] and W [C,F] expected")
+    M, F = (int(v) for v in feats.shape)
+    C = int(W.shape[0])
+    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y_a, (M,), "y_a")
+    _shape(feats_t, (M, F), "feats_t"); _shape(W_t, (C, F), "W_t"); _shape(b_t, (C,), "b_t")
+    if y_b is not None:
+        _shape(y_b, (M,), "y_b")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    loss_parts = torch.empty(2, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    agree = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
+    if need_grad:
+        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
+        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
+        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
+        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
+        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
+    else:
+        dfeats = gW = gb = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_cls_head_step_distill(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
+                                                _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
+                                                _f32(W, "W"), _f32(b, "b"), _f32(feats_t, "feats_t"), _f32(W_t, "W_t"),
+                                                _f32(b_t, "b_t"), float(temp), float(alpha), float(ce_weight), float(grad_scale),
+                                                _f32(loss, "loss"), _f32(loss_parts, "loss_parts"), _f32(correct, "correct"),
+                                                _f32(agree, "agree"), _i64(preds, "preds") if want_preds else None, *grads),
+           "fumi_hip_cls_head_step_distill")
+    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb, loss_parts=loss_parts, loss_ce=loss_parts[0:1],
+                loss_kd=loss_parts[1:2], agree=agree)
 
 
 MIX_MIXUP, MIX_CUTMIX = 0, 1

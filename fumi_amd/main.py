@@ -111,6 +111,8 @@ def main(args):
     print(model)
     if getattr(args, "encoder_checkpoint", None):                        # the backbone of a --model pretrain checkpoint
         model = utils.load_encoder_checkpoint(model, args.device, args.encoder_checkpoint)
+    if getattr(args, "distill_checkpoint", None):                        # the frozen teacher of a --model pretrain run
+        model = utils.load_distill_checkpoint(model, args, args.distill_checkpoint)
     optimizer = utils.init_optim(args, model)
     if args.checkpoint:
         model = _restore(args, model, optimizer)
@@ -252,6 +254,21 @@ def check_supported(args):
         raise ValueError(f"--mixup_alpha {a_mix} and --cutmix_alpha {a_cut} must not be negative (0 turns the mix off)")
     if not 0.0 <= p_mix <= 1.0:
         raise ValueError(f"--mix_prob {p_mix} must lie in [0, 1]")
+    d_ckpt, d_temp, d_alpha, d_ce = (getattr(args, k, d) for k, d in (("distill_checkpoint", None), ("distill_temp", 4.0),
+                                                                       ("distill_alpha", 0.5), ("distill_ce_weight", 0.5)))
+    d_moved = d_temp != 4.0 or d_alpha != 0.5 or d_ce != 0.5
+    if family != "pretrain" and (d_ckpt or d_moved):
+        raise ValueError("--distill_checkpoint, --distill_temp, --distill_alpha and --distill_ce_weight distil the supervised "
+                         "classifier from a teacher: they need --model pretrain")
+    if d_moved and not d_ckpt:
+        raise ValueError("--distill_temp, --distill_alpha and --distill_ce_weight weigh the distillation from a teacher: they need "
+                         "--distill_checkpoint")
+    if not d_temp > 0.0 or not d_temp < float("inf"):
+        raise ValueError(f"--distill_temp {d_temp} must be positive and finite")
+    if not 0.0 <= d_alpha < float("inf") or not 0.0 <= d_ce < float("inf"):
+        raise ValueError(f"--distill_alpha {d_alpha} and --distill_ce_weight {d_ce} must not be negative")
+    if d_ckpt and not os.path.isfile(d_ckpt):
+        raise ValueError(f"--distill_checkpoint {d_ckpt} does not exist")
     if getattr(args, "encoder_checkpoint", None) and (family == "clip" or not raw):
         raise ValueError("--encoder_checkpoint loads a Conv4 / ResNet-12 backbone: it needs --model fumi, maml, am3 or metabaseline "
                          "with --im_encoder conv4 or resnet12")

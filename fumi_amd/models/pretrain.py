@@ -11,7 +11,11 @@ side, so that the unchanged encode call normalises every R consecutive images by
 ``--pretrain_bn_group``); ``cls_head_step`` takes all M feature rows, ``encode_bwd`` the two halves of its ``dfeats``.
 Validation and test are few-shot nearest-centroid classification on backbone features over the episodic batches the pixel samplers
 produce: the checkpoint with the best few-shot validation loss wins.  ``--encoder_checkpoint`` (fumi_amd/utils/utils.py) loads the
-``conv.*`` tensors of such a checkpoint into ``--model fumi | maml | am3``."""
+``conv.*`` tensors of such a checkpoint into ``--model fumi | maml | am3``.
+
+Born-again distillation: ``Pretrain(distill=dict(temp=, alpha=, ce_weight=))`` with ``load_teacher(state_dict)``
+trains the classifier as the student of a frozen copy of an earlier generation.  Every step encodes the batch with the teacher first
+(no tape), then with the student (taped), and the distillation form of the head (``cls_head_step_distill``) takes both feature sets."""
 import math
 import os
 
@@ -30,8 +34,13 @@ from ..utils.wandb_compat import wandb
 
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
-                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0):
+                 metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0,
+                 distill=None):
         super().__init__()
+        self.distill = distill_config(distill)             # None, or the weights of the distillation loss (section 37)
+        self.last_out = None                               # the head's output dict of the last training step
+        object.__setattr__(self, "_teacher", None)         # (conv module, [W_t, b_t]) once loaded: frozen, outside parameters() / state_dict()
+        self._tcache = None
         if metric not in ("euclidean", "cosine", "ridge", "logreg"):
             raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge or logreg, got {metric}")
         if not 0 <= int(transductive_steps) <= 100:
@@ -65,6 +74,7 @@ class Pretrain(nn.Module):
         self.bn_group = int(bn_group)          # R: images per batch-statistics group of a training step
         self.num_ways = num_ways               # N of the validation / test episodes (None: read from the labels)
         self.classifier = nn.Linear(self.conv.feature_dim, self.n_classes)
+        self._image = (int(image_channels), int(image_size))
         self._flat = None
         self._pcache = None
 
@@ -88,7 +98,50 @@ class Pretrain(nn.Module):
 
     def _apply(self, fn, recurse=True):
         self._pcache = None
+        self._tcache = None
+        if self._teacher is not None:                      # the teacher moves with the model
+            conv_t, w_t = self._teacher
+            conv_t._apply(fn)
+            object.__setattr__(self, "_teacher", (conv_t, [fn(t) for t in w_t]))
         return super()._apply(fn, recurse)
+
+    def _new_backbone(self):
+        if self.backbone == "conv4":
+            from .conv4 import Conv4
+            return Conv4(self._image[0], 64, 4, self._image[1])
+        from .resnet12 import CHANNELS, ResNet12
+        return ResNet12(self._image[0], CHANNELS, self._image[1])
+
+    def load_teacher(self, state_dict):
+        """The frozen teacher of the distillation loss from a ``--model pretrain`` state_dict: a second backbone of this model's class
+        (``conv.*``) and its classifier (``classifier.weight``, ``classifier.bias``), on the device of the model.  A tensor that is
+        missing or of another shape is a ValueError naming it.  The teacher is no submodule: it appears in neither ``parameters()``,
+        ``state_dict()``, the flat gradient buffer nor the optimizer."""
+        if self.distill is None:
+            raise ValueError("load_teacher needs a model built with distill=dict(temp=, alpha=, ce_weight=)")
+        conv_t = self._new_backbone()
+        own = {"conv." + k: v for k, v in conv_t.state_dict().items()}
+        own["classifier.weight"], own["classifier.bias"] = self.classifier.weight, self.classifier.bias
+        for name, dst in own.items():
+            src = state_dict.get(name)
+            if src is None:
+                raise ValueError(f"the teacher's state_dict has no tensor {name}")
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"the teacher's tensor {name} is {tuple(src.shape)}, the student's is {tuple(dst.shape)}")
+        dev = self.classifier.weight.device
+        conv_t.load_state_dict({k[5:]: state_dict[k] for k in own if k.startswith("conv.")})
+        conv_t.to(dev).requires_grad_(False)
+        w_t = [state_dict[k].detach().to(device=dev, dtype=torch.float32).clone().contiguous() for k in ("classifier.weight", "classifier.bias")]
+        object.__setattr__(self, "_teacher", (conv_t, w_t))
+        self._tcache = None
+        return self
+
+    def _teacher_params(self):
+        """(detached teacher classifier [W_t, b_t], detached teacher backbone tensors), cached until the model moves."""
+        if self._tcache is None:
+            conv_t, w_t = self._teacher
+            self._tcache = (w_t, [p.detach() for p in conv_t.theta()])
+        return self._tcache
 
     def _encoders(self, eng):
         return ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
@@ -109,10 +162,25 @@ class Pretrain(nn.Module):
         encode, encode_bwd = self._encoders(eng)
         x = x.contiguous()
         x_s, x_q = x[:half].view(B, R, *x.shape[1:]), x[half:].view(B, R, *x.shape[1:])
+        feats_t = None
+        if self.distill is not None:
+            if self._teacher is None:
+                raise RuntimeError("Pretrain(distill=...) has no teacher: call load_teacher(state_dict) (--distill_checkpoint) before "
+                                   "the first training step")
+            # the teacher first: its untaped encode uses the encoder's workspace, which must stay untouched between the student's taped
+            # encode and its backward.  The same x as the student's (mixed images included), the same batch-statistics groups.
+            w_t, theta_t = self._teacher_params()
+            t_s, t_q = encode(x_s, x_q, theta_t, keep_tape=False)
+            feats_t = torch.cat((t_s.view(half, -1), t_q.view(half, -1)))
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         feats = torch.cat((f_s.view(half, -1), f_q.view(half, -1)))                 # [M, F], the images' order
         g_w, g_theta = fg.split(2)
-        if self.label_smoothing > 0 or y_b is not None:
+        if feats_t is not None:
+            out = eng.cls_head_step_distill(feats, y, w[0], w[1], feats_t, w_t[0], w_t[1], temp=self.distill["temp"],
+                                            alpha=self.distill["alpha"], ce_weight=self.distill["ce_weight"], y_b=y_b,
+                                            lam=float(lam), smoothing=self.label_smoothing, need_grad=True, grad_scale=1.0,
+                                            gW=g_w[0], gb=g_w[1])
+        elif self.label_smoothing > 0 or y_b is not None:
             out = eng.cls_head_step_soft(feats, y, w[0], w[1], y_b=y_b, lam=float(lam), smoothing=self.label_smoothing, need_grad=True,
                                          grad_scale=1.0, gW=g_w[0], gb=g_w[1])
         else:
@@ -127,6 +195,7 @@ class Pretrain(nn.Module):
             getattr(optimizer, "step_fused", optimizer.step)()
             if scheduler:
                 scheduler.step()
+        self.last_out = out
         return out
 
     def few_shot(self, batch, device):
@@ -196,6 +265,27 @@ class Pretrain(nn.Module):
         return loss, acc
 
 
+def distill_config(cfg):
+    """None, or dict(temp, alpha, ce_weight) of the distillation loss as floats, checked: temp positive, the weights not negative."""
+    if cfg is None:
+        return None
+    c = dict(temp=float(cfg.get("temp", 4.0)), alpha=float(cfg.get("alpha", 0.5)), ce_weight=float(cfg.get("ce_weight", 0.5)))
+    if not (math.isfinite(c["temp"]) and c["temp"] > 0.0):
+        raise ValueError(f"the distillation temperature must be positive, got {c['temp']}")
+    if not (math.isfinite(c["alpha"]) and c["alpha"] >= 0.0 and math.isfinite(c["ce_weight"]) and c["ce_weight"] >= 0.0):
+        raise ValueError(f"the distillation weights must not be negative, got alpha {c['alpha']}, ce_weight {c['ce_weight']}")
+    return c
+
+
+def distill_log(model):
+    """train/loss_ce, train/loss_kd and train/teacher_agree (a fraction of the batch) of the last distillation step, else nothing."""
+    out = getattr(model, "last_out", None)
+    if not out or "loss_kd" not in out:
+        return {}
+    return {"train/loss_ce": float(out["loss_ce"]), "train/loss_kd": float(out["loss_kd"]),
+            "train/teacher_agree": float(out["agree"]) / max(int(out["preds"].numel()), 1)}
+
+
 def training_run(args, model, optimizer, train_loader, val_loader, max_test_batches):
     """The structure of am3.training_run: validation at batch 0 and every --eval_freq, the usual checkpoint dictionary, patience,
     reload of the best checkpoint (best few-shot validation loss) at the end."""
@@ -213,7 +303,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
                 trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
-                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **trans, **clip_log(opt)}, step=batch_idx)
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **trans, **clip_log(opt), **distill_log(model)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"

@@ -15,7 +15,7 @@ import torch
 from .wandb_compat import wandb
 
 # (flag, kwargs) in the reference's order; defaults/types/help are the contract
-_FLAGS = [
+_REFERENCE_FLAGS = [
     ("--wandb_entity", dict(type=str, default="multimodal-image-cls", help="W&B entity")),
     ("--wandb_project", dict(type=str, default="fumi", help="W&B project")),
     ("--dataset", dict(type=str, default="inat-anim", help="Dataset to use (inat-anim, supervised-inat-anim, synthetic, synthetic-resident, image-npy)")),
@@ -72,6 +72,13 @@ _FLAGS = [
     ("--disable_cuda", dict(action="store_true", help="don't use GPU")),
     ("--wandb_offline", dict(action="store_true", help="don't save to wandb")),
 ]
+_DISTILL_FLAGS = [          # born-again distillation of --model pretrain: the tail of _FLAGS, the one open slot
+    ("--distill_checkpoint", dict(type=str, default=None, help="[--model pretrain] a --model pretrain checkpoint of the same backbone: the frozen teacher the classifier is distilled from (a born-again chain is repeated runs, each naming the previous run's best.pth.tar)")),
+    ("--distill_temp", dict(type=float, default=4.0, help="[--distill_checkpoint] temperature T of the distillation term T^2 KL(softmax(z_teacher / T) || softmax(z / T)) (positive)")),
+    ("--distill_alpha", dict(type=float, default=0.5, help="[--distill_checkpoint] weight of the distillation term (not negative)")),
+    ("--distill_ce_weight", dict(type=float, default=0.5, help="[--distill_checkpoint] weight of the cross-entropy term (not negative)")),
+]
+_FLAGS = _REFERENCE_FLAGS + _DISTILL_FLAGS
 _ENGINE_FLAGS = [     # additive, not in the reference
     ("--synthetic_classes", dict(type=int, default=64, help="[synthetic dataset] number of classes per split")),
     ("--synthetic_vocab", dict(type=int, default=2000, help="[synthetic dataset] vocabulary size for token text")),
@@ -169,7 +176,10 @@ def init_model(args, dictionary, watch=True):
                                   metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0),
                                   ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0),
                                   logreg=logreg_config(args) if getattr(args, "pretrain_metric", "euclidean") == "logreg" else None,
-                                  transductive_steps=getattr(args, "transductive_steps", 0))
+                                  transductive_steps=getattr(args, "transductive_steps", 0),
+                                  distill=(dict(temp=getattr(args, "distill_temp", 4.0), alpha=getattr(args, "distill_alpha", 0.5),
+                                                ce_weight=getattr(args, "distill_ce_weight", 0.5))
+                                           if getattr(args, "distill_checkpoint", None) else None))
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
@@ -279,6 +289,20 @@ def load_encoder_checkpoint(model, device, checkpoint_file):
     checkpoint = torch.load(checkpoint_file, map_location=device, weights_only=False)
     names = load_backbone_state(model, checkpoint["state_dict"])
     print(f"Loaded the backbone ({len(names)} tensors) of {checkpoint_file}, pre-trained to batch {checkpoint.get('batch_idx')}")
+    return model
+
+
+def load_distill_checkpoint(model, args, checkpoint_file):
+    """--distill_checkpoint: the ``--model pretrain`` checkpoint file becomes the frozen teacher of ``model`` (``Pretrain.load_teacher``).
+    A teacher saved with another --im_encoder, --image_size or --image_channels is refused by name."""
+    checkpoint = torch.load(checkpoint_file, map_location=args.device, weights_only=False)
+    saved = checkpoint.get("args") or {}
+    for key in ("im_encoder", "image_size", "image_channels"):
+        if key in saved and saved[key] != getattr(args, key):
+            raise ValueError(f"--distill_checkpoint: the teacher was trained with --{key} {saved[key]}, this run has --{key} "
+                             f"{getattr(args, key)}")
+    model.load_teacher(checkpoint["state_dict"])
+    print(f"Loaded the teacher of {checkpoint_file}, pre-trained to batch {checkpoint.get('batch_idx')}")
     return model
 
 

@@ -483,6 +483,26 @@ int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int 
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
         const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* The same head as the student of a frozen teacher: knowledge distillation beside the soft target of the entry
+ * above.  feats_t [M,F], W_t [C,F], b_t [C] are the teacher's features and classifier; with T = kd_temp, z_t = feats_t W_t^T + b_t,
+ * p = softmax(z_t / T), q = softmax(z / T) and t the soft target,
+ *     loss_ce = mean_m (lse(z_m) - sum_c t z),   loss_kd = T^2 mean_m KL(p || q),
+ *     loss = ce_weight * loss_ce + kd_alpha * loss_kd,
+ *     dlogits = grad_scale / M * (ce_weight (softmax(z) - t) + kd_alpha T (q - p));
+ * KL is formed as sum_c p (z_t / T) - lse(z_t / T) - sum_c p (z / T) + lse(z / T), no logarithm of a probability is taken.  dfeats, gW,
+ * gb follow from dlogits as above (the teacher receives no gradient), correct and preds are those of the soft entry,
+ * loss_parts [2] = (loss_ce, loss_kd), agree [1] = number of rows whose first arg-max of z equals the first arg-max of z_t (float).
+ * The same two launches, LDS image, shapes, fixed summation orders and forward form: the teacher's logits of a 16-row tile are formed in
+ * the LDS image first, p goes to the workspace ([M,C] floats, the teacher's only trace in memory), then the student's logits overwrite
+ * the image.  With kd_alpha = 0, ce_weight = 1 loss, correct, preds, dfeats, gW and gb are bit-identical to fumi_hip_cls_head_step_soft.
+ * A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to either loss, correct, agree or the gradients.
+ * FUMI_EINVAL before any launch: a NULL teacher pointer, loss_parts or agree; kd_temp, kd_alpha or ce_weight not finite; kd_temp <= 0;
+ * a negative kd_alpha or ce_weight; the refusals of the soft entry. */
+int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
+        const float* W, const float* b, const float* feats_t, const float* W_t, const float* b_t,
+        float kd_temp, float kd_alpha, float ce_weight, float grad_scale,
+        float* loss, float* loss_parts, float* correct, float* agree, int64_t* preds, float* dfeats, float* gW, float* gb);
 /* The cosine nearest-centroid head with a learned temperature (csrc/cosproto.hip): the few-shot metric of a
  * pre-trained backbone and the episodic loss of the Meta-Baseline stage, fused.  Per episode b, with norm(x) = x / max(|x|_2, 1e-12)
  * (F.normalize):
