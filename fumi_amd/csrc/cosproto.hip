@@ -16,28 +16,16 @@
 //       scattered to the support rows of class n as dc_n / count_n; one further workgroup adds part[0..ntile): loss, correct, dtau.
 //   The forward form (no gradient pointers) is launch 1, launch 2 without its backward half and the last workgroup of launch 3: the
 //   same instructions produce loss, correct, preds and logits in both forms.
-// Every sum has a fixed order (MFMA chains over k, butterflies, index-ordered loops): equal inputs give equal bits.  No floating-point
-// atomics; the only atomic is the OR into the status word.  tau is read from device memory by the kernels.
-// A label outside [0, N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
-// stays B * Qn), such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
-// FUMI_ST_CLASS_MISSING and has a zero prototype.
-#include "common.h"
+// Fixed summation orders, the first arg-max, the label-range and missing-class rules and the absence of floating-point atomics are
+// those of fewshot_head.h.  A support row left out gets a zero gradient, a class without a support row a zero prototype.  tau is
+// read from device memory by the kernels.
+#include "fewshot_head.h"
 
 namespace {
 
-constexpr int CP_TM = 16;          // query rows per workgroup of launch 2, classes per workgroup of launch 3
-constexpr int CP_NB = 128;         // output columns of one wg_mm call
-constexpr int CP_MM = 16384;       // floats of LDS the products stage their operands in
-constexpr int CP_PF = 256;         // features per workgroup of launch 1: one column per thread
-constexpr int CP_LDC = CP_NB + 4;  // row stride of launch 3's dc image
 constexpr float CP_EPS = 1e-12f;   // F.normalize's clamp
 
-struct CosProto {
-    int B, S, Qn, N, F, ldz, tpe, ntile, nfb1, train;   // tpe: row tiles per episode, nfb1: feature blocks of launch 1
-    float gs;                                           // grad_scale / (B Qn)
-};
-
-__global__ __launch_bounds__(256) void cos_proto_means_kernel(CosProto d, const float* __restrict__ xs, const int64_t* __restrict__ ys,
+__global__ __launch_bounds__(256) void cos_proto_means_kernel(HeadDims d, const float* __restrict__ xs, const int64_t* __restrict__ ys,
                                                               float* __restrict__ protos, float* __restrict__ psq,
                                                               float* __restrict__ cntf, int* status) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -45,46 +33,20 @@ __global__ __launch_bounds__(256) void cos_proto_means_kernel(CosProto d, const 
     const int S = d.S, N = d.N, F = d.F;
     const int b = blockIdx.x / d.nfb1, fb = blockIdx.x - b * d.nfb1;
     float* acc = sm;                             // [N, 256] class sums, then means
-    int* lab = (int*)(acc + N * CP_PF);          // [S] labels, -1 where out of range
+    int* lab = (int*)(acc + N * FH_PF);          // [S] labels, -1 where out of range
     int* cnt = lab + S;                          // [N]
-    const int64_t* y = ys + (long)b * S;
-    bool bad = false;
-    for (int i = tid; i < S; i += 256) {
-        const long t = y[i];
-        const bool ok = t >= 0 && t < N;
-        lab[i] = ok ? (int)t : -1;
-        bad |= !ok;
-    }
+    const bool bad = fh_stage_labels(ys + (long)b * S, S, N, lab);
     if (bad && fb == 0) atomicOr(status, FUMI_ST_LABEL_RANGE);
-    for (int i = tid; i < N * CP_PF; i += 256) acc[i] = 0.f;
+    for (int i = tid; i < N * FH_PF; i += 256) acc[i] = 0.f;
     __syncthreads();
-    if (tid < N) {
-        int c = 0;
-        for (int i = 0; i < S; ++i) c += lab[i] == tid ? 1 : 0;
-        cnt[tid] = c > 0 ? c : 1;
-        if (fb == 0) {
-            cntf[(long)b * N + tid] = (float)(c > 0 ? c : 1);
-            if (c == 0) atomicOr(status, FUMI_ST_CLASS_MISSING);
-        }
-    }
-    const int f = fb * CP_PF + tid;
-    if (f < F) {
-        const float* x = xs + (long)b * S * F + f;
-        int i = 0;
-        for (; i + 4 <= S; i += 4) {             // four loads in flight, added in index order
-            float v[4]; int l[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { v[u] = x[(long)(i + u) * F]; l[u] = lab[i + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (l[u] >= 0) acc[l[u] * CP_PF + tid] += v[u];
-        }
-        for (; i < S; ++i) { const int l = lab[i]; if (l >= 0) acc[l * CP_PF + tid] += x[(long)i * F]; }
-    }
+    fh_proto_counts(lab, S, N, cnt, cntf, b, fb == 0, status);
+    const int f = fb * FH_PF + tid;
+    if (f < F) fh_class_sums(acc, lab, xs + (long)b * S * F + f, S, F);
     __syncthreads();
     if (f < F) {
         for (int n = 0; n < N; ++n) {
-            const float m = acc[n * CP_PF + tid] / (float)cnt[n];
-            acc[n * CP_PF + tid] = m;
+            const float m = acc[n * FH_PF + tid] / (float)cnt[n];
+            acc[n * FH_PF + tid] = m;
             protos[((long)b * N + n) * F + f] = m;
         }
     }
@@ -94,14 +56,14 @@ __global__ __launch_bounds__(256) void cos_proto_means_kernel(CosProto d, const 
         for (int n = wave; n < N; n += 4) {
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const float v = acc[n * CP_PF + lane + 64 * j]; s += v * v; }
+            for (int j = 0; j < 4; ++j) { const float v = acc[n * FH_PF + lane + 64 * j]; s += v * v; }
             for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
             if (lane == 0) psq[((long)b * d.nfb1 + fb) * N + n] = s;
         }
     }
 }
 
-__global__ __launch_bounds__(256) void cos_proto_rows_kernel(CosProto d, const float* __restrict__ fq, const int64_t* __restrict__ yq,
+__global__ __launch_bounds__(256) void cos_proto_rows_kernel(HeadDims d, const float* __restrict__ fq, const int64_t* __restrict__ yq,
                                                              const float* __restrict__ protos, const float* __restrict__ psq,
                                                              const float* __restrict__ tau_p, int64_t* __restrict__ preds,
                                                              float* __restrict__ logits, float* __restrict__ part,
@@ -110,10 +72,10 @@ __global__ __launch_bounds__(256) void cos_proto_rows_kernel(CosProto d, const f
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int Qn = d.Qn, N = d.N, F = d.F, ldz = d.ldz;
-    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * CP_TM, rows = min(CP_TM, Qn - q0);
+    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * FH_TM, rows = min(FH_TM, Qn - q0);
     const long r0 = (long)b * Qn + q0;           // the tile's first row among all B * Qn
     float* Z = sm;                               // [16, ldz] cos, then dcos rp
-    float* rq = Z + CP_TM * ldz;                 // [16] 1 / max(|f_q|, eps)
+    float* rq = Z + FH_TM * ldz;                 // [16] 1 / max(|f_q|, eps)
     float* se = rq + 16;                         // [16] |f_q| >= eps, then rq sum_n dcos cos where it is
     float* rl = se + 16;                         // [16] row losses, [16] row hits, [16] row dtau
     float* rp = rl + 48;                         // [64] 1 / max(|c_n|, eps)
@@ -143,7 +105,7 @@ __global__ __launch_bounds__(256) void cos_proto_rows_kernel(CosProto d, const f
         rp[tid] = 1.f / fmaxf(sqrtf(s), CP_EPS);
     }
     __syncthreads();
-    wg_mm(mm, CP_MM, rows, N, F, ft, F, 1, pc, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc * rq[m] * rp[n]; });
+    wg_mm(mm, FH_MM, rows, N, F, ft, F, 1, pc, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc * rq[m] * rp[n]; });
     __syncthreads();
 
     {
@@ -153,6 +115,9 @@ __global__ __launch_bounds__(256) void cos_proto_rows_kernel(CosProto d, const f
             float cs[4], z[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; cs[j] = n < N ? c[n] : 0.f; z[j] = tau * cs[j]; }
+            // The row's softmax cross-entropy, the same block in the four rows kernels.  It stays a copy: through helper functions (a
+            // softmax helper alone included) the compiler allocates this kernel's registers differently and the training heads measured
+            // 0.2 - 0.7 % slower.  A change to the arg-max, the label rule or the NLL is made in all four.
             float mx = -INFINITY; int arg = N;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; if (n < N && z[j] > mx) { mx = z[j]; arg = n; } }
@@ -196,22 +161,18 @@ __global__ __launch_bounds__(256) void cos_proto_rows_kernel(CosProto d, const f
         if (l == 0) { rl[row] = loss; rl[16 + row] = hit; rl[32 + row] = dt; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int r = 0; r < CP_TM; ++r) { a += rl[r]; h += rl[16 + r]; t += rl[32 + r]; }
-        part[blockIdx.x] = a; part[d.ntile + blockIdx.x] = h; part[2 * d.ntile + blockIdx.x] = t;
-    }
+    fh_tile_part<3>(rl, part, d.ntile);
     if (!d.train) return;
     // dfeats_tile [rows, F] = rq ((dcos rp) [rows, N] C [N, F] - f_tile se)
-    for (int f0 = 0; f0 < F; f0 += CP_NB) {
-        const int nb = min(CP_NB, F - f0);
-        wg_mm2(mm, CP_MM, rows, nb, N, Z, ldz, 1, pc + f0, F, 1,
+    for (int f0 = 0; f0 < F; f0 += FH_NB) {
+        const int nb = min(FH_NB, F - f0);
+        wg_mm2(mm, FH_MM, rows, nb, N, Z, ldz, 1, pc + f0, F, 1,
                [&](int m, int n) { return ft[(long)m * F + f0 + n]; },
                [&](int m, int n, float acc, float x) { dfq[(r0 + m) * F + f0 + n] = rq[m] * (acc - x * se[m]); });
     }
 }
 
-__global__ __launch_bounds__(256) void cos_proto_sgrad_kernel(CosProto d, int nfb, int ncb, const float* __restrict__ fq,
+__global__ __launch_bounds__(256) void cos_proto_sgrad_kernel(HeadDims d, int nfb, int ncb, const float* __restrict__ fq,
                                                               const int64_t* __restrict__ ys, const float* __restrict__ protos,
                                                               const float* __restrict__ psq, const float* __restrict__ cntf,
                                                               const float* __restrict__ Wd, const float* __restrict__ U,
@@ -221,25 +182,19 @@ __global__ __launch_bounds__(256) void cos_proto_sgrad_kernel(CosProto d, int nf
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int S = d.S, Qn = d.Qn, N = d.N, F = d.F;
-    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles: 256 strided sums, then those in index order
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int i = tid; i < d.ntile; i += 256) { a += part[i]; h += part[d.ntile + i]; t += part[2 * d.ntile + i]; }
-        sm[tid] = a; sm[256 + tid] = h; sm[512 + tid] = t;
-        __syncthreads();
-        if (tid == 0) {
-            a = 0.f; h = 0.f; t = 0.f;
-            for (int i = 0; i < 256; ++i) { a += sm[i]; h += sm[256 + i]; t += sm[512 + i]; }
-            loss[0] = a / (float)((long)d.B * Qn); correct[0] = h;
-            if (dtau) dtau[0] = t;
-        }
+    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles
+        fh_sum_parts<3>(part, d.ntile, sm, [&](const float (&t)[3]) {
+            loss[0] = t[0] / (float)((long)d.B * Qn); correct[0] = t[1];
+            if (dtau) dtau[0] = t[2];
+        });
         return;
     }
     const int per = ncb * nfb;
     const int b = blockIdx.x / per, r = blockIdx.x - b * per, cb = r / nfb, fb = r - cb * nfb;
-    const int c0 = cb * CP_TM, f0 = fb * CP_NB;
-    const int nc = min(CP_TM, N - c0), nf = min(CP_NB, F - f0);
-    float* dc = sm + CP_MM;                      // [16, CP_LDC]
-    float* ts = dc + CP_TM * CP_LDC;             // [16, 16] strided column sums of dcos cos
+    const int c0 = cb * FH_TM, f0 = fb * FH_NB;
+    const int nc = min(FH_TM, N - c0), nf = min(FH_NB, F - f0);
+    float* dc = sm + FH_MM;                      // [16, FH_LDC]
+    float* ts = dc + FH_TM * FH_LDC;             // [16, 16] strided column sums of dcos cos
     float* rps = ts + 256;                       // [16] 1 / max(|c_n|, eps)
     float* tc = rps + 16;                        // [16] rp_n sum_q dcos cos where |c_n| >= eps, else 0
     {   // sum_q dcos[q, n] cos[q, n]: 16 strided partial sums per class, added in index order
@@ -258,25 +213,11 @@ __global__ __launch_bounds__(256) void cos_proto_sgrad_kernel(CosProto d, int nf
     }
     __syncthreads();
     // dc[m, n] = rp_m (sum_k (dcos rq)[k, c0 + m] f_q[k, f0 + n] - c[c0 + m, f0 + n] tc_m)
-    wg_mm2(sm, CP_MM, nc, nf, Qn, Wd + (long)b * Qn * N + c0, 1, N, fq + (long)b * Qn * F + f0, F, 1,
+    wg_mm2(sm, FH_MM, nc, nf, Qn, Wd + (long)b * Qn * N + c0, 1, N, fq + (long)b * Qn * F + f0, F, 1,
            [&](int m, int n) { return protos[((long)b * N + c0 + m) * F + f0 + n]; },
-           [&](int m, int n, float acc, float c) { dc[m * CP_LDC + n] = rps[m] * (acc - c * tc[m]); });
+           [&](int m, int n, float acc, float c) { dc[m * FH_LDC + n] = rps[m] * (acc - c * tc[m]); });
     __syncthreads();
-    {   // every support row of class n receives dc_n / count_n; the first class block zeroes the rows whose label is out of range
-        const int n = tid & (CP_NB - 1);
-        if (n < nf) {
-            for (int i = tid >> 7; i < S; i += 2) {
-                const long t = ys[(long)b * S + i];
-                float* o = dfs + ((long)b * S + i) * F + f0 + n;
-                if (t >= 0 && t < N) {
-                    const int m = (int)t - c0;
-                    if (m >= 0 && m < nc) *o = dc[m * CP_LDC + n] / cntf[(long)b * N + t];
-                } else if (cb == 0) {
-                    *o = 0.f;
-                }
-            }
-        }
-    }
+    fh_scatter_class_grad(dc, ys, cntf, dfs, b, S, N, F, c0, nc, f0, nf, cb == 0);
 }
 
 }  // namespace
@@ -284,19 +225,12 @@ __global__ __launch_bounds__(256) void cos_proto_sgrad_kernel(CosProto d, int nf
 extern "C" int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau) {
-    if (!ws) return FUMI_EINVAL;
-    if (B < 1 || S < 1 || S > 1024 || Qn < 1 || N < 2 || N > 64 || F % 32 != 0 || F < 32 || F > 2048 || (long)B * Qn > 65536)
-        return FUMI_ENOTSUP;
-    if (!feats_s || !y_s || !feats_q || !y_q || !tau || !loss || !correct) return FUMI_EINVAL;
-    const int ngrad = (dfeats_s ? 1 : 0) + (dfeats_q ? 1 : 0) + (dtau ? 1 : 0);
-    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
+    if (int rc = head_args_check(ws, B, S, Qn, N, F, S <= 1024, {feats_s, y_s, feats_q, y_q, tau, loss, correct})) return rc;
+    const int train = head_grad_form(dfeats_s, dfeats_q, dtau);
+    if (train < 0) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
-    const int train = ngrad == 3;
-    CosProto d;
-    d.B = B; d.S = S; d.Qn = Qn; d.N = N; d.F = F; d.ldz = ((N + 15) & ~15) + 4; d.tpe = (Qn + CP_TM - 1) / CP_TM; d.ntile = B * d.tpe;
-    d.nfb1 = (F + CP_PF - 1) / CP_PF; d.train = train;
-    d.gs = grad_scale / (float)((long)B * Qn);
+    const HeadDims d = head_dims_fill(B, S, Qn, N, F, train, grad_scale);
     const size_t n_pro = (size_t)B * N * F, n_psq = (size_t)B * d.nfb1 * N, n_cnt = (size_t)B * N, n_part = (size_t)3 * d.ntile,
                  n_dz = (size_t)B * Qn * N;
     int rc = ws_reserve(ws, ws_align(n_pro * 4) + ws_align(n_psq * 4) + ws_align(n_cnt * 4) + ws_align(n_part * 4)
@@ -304,9 +238,9 @@ extern "C" int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int 
     if (rc) return rc;
     float* protos = ws_f(ws, n_pro); float* psq = ws_f(ws, n_psq); float* cntf = ws_f(ws, n_cnt); float* part = ws_f(ws, n_part);
     float* Wd = train ? ws_f(ws, n_dz) : nullptr; float* U = train ? ws_f(ws, n_dz) : nullptr;
-    const size_t lds1 = ((size_t)N * CP_PF + S + N) * 4;
-    const size_t lds2 = ((size_t)CP_TM * d.ldz + 144 + CP_MM) * 4;
-    const size_t lds3 = train ? ((size_t)CP_MM + CP_TM * CP_LDC + 256 + 32) * 4 : (size_t)768 * 4;   // the forward form's one workgroup only adds the tile sums
+    const size_t lds1 = ((size_t)N * FH_PF + S + N) * 4;
+    const size_t lds2 = ((size_t)FH_TM * d.ldz + 144 + FH_MM) * 4;
+    const size_t lds3 = train ? ((size_t)FH_MM + FH_TM * FH_LDC + 256 + 32) * 4 : (size_t)768 * 4;   // the forward form's one workgroup only adds the tile sums
     FUMI_SET_DYN_LDS(cos_proto_means_kernel, lds1);
     hipLaunchKernelGGL(cos_proto_means_kernel, dim3(B * d.nfb1), dim3(256), lds1, st, d, feats_s, y_s, protos, psq, cntf, ws->status);
     LAUNCH_CHECK();
@@ -314,7 +248,7 @@ extern "C" int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int 
     hipLaunchKernelGGL(cos_proto_rows_kernel, dim3(d.ntile), dim3(256), lds2, st, d, feats_q, y_q, protos, psq, tau, preds, logits, part,
                        Wd, U, dfeats_q, ws->status);
     LAUNCH_CHECK();
-    const int nfb = (F + CP_NB - 1) / CP_NB, ncb = (N + CP_TM - 1) / CP_TM;
+    const int nfb = (F + FH_NB - 1) / FH_NB, ncb = (N + FH_TM - 1) / FH_TM;
     FUMI_SET_DYN_LDS(cos_proto_sgrad_kernel, lds3);
     hipLaunchKernelGGL(cos_proto_sgrad_kernel, dim3((train ? B * ncb * nfb : 0) + 1), dim3(256), lds3, st, d, nfb, ncb, feats_q, y_s,
                        protos, psq, cntf, Wd, U, part, loss, correct, dtau, dfeats_s);

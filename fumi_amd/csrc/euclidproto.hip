@@ -22,27 +22,14 @@
 //       scattered to the support rows of class n as dc_n / count_n; one further workgroup adds part[0..ntile): loss, correct, dalpha.
 //   The forward form (no gradient pointers) is launch 1, launch 2 without its backward half and the last workgroup of launch 3: the
 //   same instructions produce loss, correct, preds and logits in both forms.
-// Every sum has a fixed order (MFMA chains over k, butterflies, index-ordered loops): equal inputs give equal bits.  No floating-point
-// atomics; the only atomic is the OR into the status word.  alpha is read from device memory by the kernels.
-// A label outside [0, N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
-// stays B * Qn), such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
-// FUMI_ST_CLASS_MISSING and has a zero prototype (it counts as such in m).
-#include "common.h"
+// Fixed summation orders, the first arg-max, the label-range and missing-class rules and the absence of floating-point atomics are
+// those of fewshot_head.h.  A support row left out gets a zero gradient, a class without a support row a zero prototype (it counts
+// as such in m).  alpha is read from device memory by the kernels.
+#include "fewshot_head.h"
 
 namespace {
 
-constexpr int EP_TM = 16;          // query rows per workgroup of launch 2, classes per workgroup of launch 3
-constexpr int EP_NB = 128;         // output columns of one wg_mm call
-constexpr int EP_MM = 16384;       // floats of LDS the products stage their operands in
-constexpr int EP_PF = 256;         // features per workgroup of launch 1: one column per thread
-constexpr int EP_LDC = EP_NB + 4;  // row stride of launch 3's dc image
-
-struct EuclidProto {
-    int B, S, Qn, N, F, ldz, tpe, ntile, nfb1, train;   // tpe: row tiles per episode, nfb1: feature blocks of launch 1
-    float gs;                                           // grad_scale / (B Qn)
-};
-
-__global__ __launch_bounds__(256) void euclid_proto_means_kernel(EuclidProto d, const float* __restrict__ xs,
+__global__ __launch_bounds__(256) void euclid_proto_means_kernel(HeadDims d, const float* __restrict__ xs,
                                                                  const int64_t* __restrict__ ys, float* __restrict__ protos,
                                                                  float* __restrict__ mvec, float* __restrict__ psq,
                                                                  float* __restrict__ cntf, int* status) {
@@ -51,54 +38,28 @@ __global__ __launch_bounds__(256) void euclid_proto_means_kernel(EuclidProto d, 
     const int S = d.S, N = d.N, F = d.F;
     const int b = blockIdx.x / d.nfb1, fb = blockIdx.x - b * d.nfb1;
     float* acc = sm;                             // [N, 256] class sums, then means, then c'
-    float* mcol = acc + N * EP_PF;               // [256] the mean prototype of each column
-    int* lab = (int*)(mcol + EP_PF);             // [S] labels, -1 where out of range
+    float* mcol = acc + N * FH_PF;               // [256] the mean prototype of each column
+    int* lab = (int*)(mcol + FH_PF);             // [S] labels, -1 where out of range
     int* cnt = lab + S;                          // [N]
-    const int64_t* y = ys + (long)b * S;
-    bool bad = false;
-    for (int i = tid; i < S; i += 256) {
-        const long t = y[i];
-        const bool ok = t >= 0 && t < N;
-        lab[i] = ok ? (int)t : -1;
-        bad |= !ok;
-    }
+    const bool bad = fh_stage_labels(ys + (long)b * S, S, N, lab);
     if (bad && fb == 0) atomicOr(status, FUMI_ST_LABEL_RANGE);
-    for (int i = tid; i < N * EP_PF; i += 256) acc[i] = 0.f;
+    for (int i = tid; i < N * FH_PF; i += 256) acc[i] = 0.f;
     __syncthreads();
-    if (tid < N) {
-        int c = 0;
-        for (int i = 0; i < S; ++i) c += lab[i] == tid ? 1 : 0;
-        cnt[tid] = c > 0 ? c : 1;
-        if (fb == 0) {
-            cntf[(long)b * N + tid] = (float)(c > 0 ? c : 1);
-            if (c == 0) atomicOr(status, FUMI_ST_CLASS_MISSING);
-        }
-    }
-    const int f = fb * EP_PF + tid;
-    if (f < F) {
-        const float* x = xs + (long)b * S * F + f;
-        int i = 0;
-        for (; i + 4 <= S; i += 4) {             // four loads in flight, added in index order
-            float v[4]; int l[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { v[u] = x[(long)(i + u) * F]; l[u] = lab[i + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (l[u] >= 0) acc[l[u] * EP_PF + tid] += v[u];
-        }
-        for (; i < S; ++i) { const int l = lab[i]; if (l >= 0) acc[l * EP_PF + tid] += x[(long)i * F]; }
-    }
+    fh_proto_counts(lab, S, N, cnt, cntf, b, fb == 0, status);
+    const int f = fb * FH_PF + tid;
+    if (f < F) fh_class_sums(acc, lab, xs + (long)b * S * F + f, S, F);
     __syncthreads();
     float m = 0.f;
     if (f < F) {
         for (int n = 0; n < N; ++n) {            // the means, and their mean over the classes in index order
-            const float c = acc[n * EP_PF + tid] / (float)cnt[n];
-            acc[n * EP_PF + tid] = c;
+            const float c = acc[n * FH_PF + tid] / (float)cnt[n];
+            acc[n * FH_PF + tid] = c;
             m += c;
         }
         m /= (float)N;
         for (int n = 0; n < N; ++n) {
-            const float c = acc[n * EP_PF + tid] - m;
-            acc[n * EP_PF + tid] = c;
+            const float c = acc[n * FH_PF + tid] - m;
+            acc[n * FH_PF + tid] = c;
             protos[((long)b * N + n) * F + f] = c;
         }
         mvec[(long)b * F + f] = m;
@@ -110,7 +71,7 @@ __global__ __launch_bounds__(256) void euclid_proto_means_kernel(EuclidProto d, 
         for (int n = wave; n < N; n += 4) {
             float s = 0.f, t = 0.f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const float v = acc[n * EP_PF + lane + 64 * j]; s += v * v; t += v * mcol[lane + 64 * j]; }
+            for (int j = 0; j < 4; ++j) { const float v = acc[n * FH_PF + lane + 64 * j]; s += v * v; t += v * mcol[lane + 64 * j]; }
             for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); t += __shfl_xor(t, o, 64); }
             if (lane == 0) {
                 psq[(((long)b * d.nfb1 + fb) * 2) * N + n] = s;
@@ -120,7 +81,7 @@ __global__ __launch_bounds__(256) void euclid_proto_means_kernel(EuclidProto d, 
     }
 }
 
-__global__ __launch_bounds__(256) void euclid_proto_rows_kernel(EuclidProto d, const float* __restrict__ fq,
+__global__ __launch_bounds__(256) void euclid_proto_rows_kernel(HeadDims d, const float* __restrict__ fq,
                                                                 const int64_t* __restrict__ yq, const float* __restrict__ protos,
                                                                 const float* __restrict__ mvec, const float* __restrict__ psq,
                                                                 const float* __restrict__ alpha_p, int64_t* __restrict__ preds,
@@ -129,10 +90,10 @@ __global__ __launch_bounds__(256) void euclid_proto_rows_kernel(EuclidProto d, c
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int Qn = d.Qn, N = d.N, F = d.F, ldz = d.ldz;
-    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * EP_TM, rows = min(EP_TM, Qn - q0);
+    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * FH_TM, rows = min(FH_TM, Qn - q0);
     const long r0 = (long)b * Qn + q0;           // the tile's first row among all B * Qn
     float* Z = sm;                               // [16, ldz] d2, then dz
-    float* qs = Z + EP_TM * ldz;                 // [16] |f_q - m|^2
+    float* qs = Z + FH_TM * ldz;                 // [16] |f_q - m|^2
     float* rl = qs + 16;                         // [16] row losses, [16] row hits, [16] row dalpha
     float* cn = rl + 48;                         // [64] |c'_n|^2
     float* mc = cn + 64;                         // [64] m . c'_n
@@ -170,7 +131,7 @@ __global__ __launch_bounds__(256) void euclid_proto_rows_kernel(EuclidProto d, c
         cn[tid] = s; mc[tid] = t;
     }
     __syncthreads();
-    wg_mm(mm, EP_MM, rows, N, F, ft, F, 1, pc, 1, F,
+    wg_mm(mm, FH_MM, rows, N, F, ft, F, 1, pc, 1, F,
           [&](int m, int n, float acc) { Z[m * ldz + n] = (qs[m] + cn[n]) - 2.f * (acc - mc[n]); });
     __syncthreads();
 
@@ -181,6 +142,9 @@ __global__ __launch_bounds__(256) void euclid_proto_rows_kernel(EuclidProto d, c
             float ds[4], z[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; ds[j] = n < N ? c[n] : 0.f; z[j] = -alpha * ds[j]; }
+            // The row's softmax cross-entropy, the same block in the four rows kernels.  It stays a copy: through helper functions (a
+            // softmax helper alone included) the compiler allocates this kernel's registers differently and the training heads measured
+            // 0.2 - 0.7 % slower.  A change to the arg-max, the label rule or the NLL is made in all four.
             float mx = -INFINITY; int arg = N;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; if (n < N && z[j] > mx) { mx = z[j]; arg = n; } }
@@ -225,22 +189,18 @@ __global__ __launch_bounds__(256) void euclid_proto_rows_kernel(EuclidProto d, c
         if (l == 0) { rl[row] = loss; rl[16 + row] = hit; rl[32 + row] = da; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int r = 0; r < EP_TM; ++r) { a += rl[r]; h += rl[16 + r]; t += rl[32 + r]; }
-        part[blockIdx.x] = a; part[d.ntile + blockIdx.x] = h; part[2 * d.ntile + blockIdx.x] = t;
-    }
+    fh_tile_part<3>(rl, part, d.ntile);
     if (!d.train) return;
     // dfeats_tile [rows, F] = 2 alpha dz [rows, N] C' [N, F]
     const float a2 = 2.f * alpha;
-    for (int f0 = 0; f0 < F; f0 += EP_NB) {
-        const int nb = min(EP_NB, F - f0);
-        wg_mm(mm, EP_MM, rows, nb, N, Z, ldz, 1, pc + f0, F, 1,
+    for (int f0 = 0; f0 < F; f0 += FH_NB) {
+        const int nb = min(FH_NB, F - f0);
+        wg_mm(mm, FH_MM, rows, nb, N, Z, ldz, 1, pc + f0, F, 1,
               [&](int m, int n, float acc) { dfq[(r0 + m) * F + f0 + n] = a2 * acc; });
     }
 }
 
-__global__ __launch_bounds__(256) void euclid_proto_sgrad_kernel(EuclidProto d, int nfb, int ncb, const float* __restrict__ fq,
+__global__ __launch_bounds__(256) void euclid_proto_sgrad_kernel(HeadDims d, int nfb, int ncb, const float* __restrict__ fq,
                                                                  const int64_t* __restrict__ ys, const float* __restrict__ protos,
                                                                  const float* __restrict__ mvec, const float* __restrict__ cntf,
                                                                  const float* __restrict__ Wd, const float* __restrict__ alpha_p,
@@ -250,25 +210,19 @@ __global__ __launch_bounds__(256) void euclid_proto_sgrad_kernel(EuclidProto d, 
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int S = d.S, Qn = d.Qn, N = d.N, F = d.F;
-    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles: 256 strided sums, then those in index order
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int i = tid; i < d.ntile; i += 256) { a += part[i]; h += part[d.ntile + i]; t += part[2 * d.ntile + i]; }
-        sm[tid] = a; sm[256 + tid] = h; sm[512 + tid] = t;
-        __syncthreads();
-        if (tid == 0) {
-            a = 0.f; h = 0.f; t = 0.f;
-            for (int i = 0; i < 256; ++i) { a += sm[i]; h += sm[256 + i]; t += sm[512 + i]; }
-            loss[0] = a / (float)((long)d.B * Qn); correct[0] = h;
-            if (dalpha) dalpha[0] = t;
-        }
+    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles
+        fh_sum_parts<3>(part, d.ntile, sm, [&](const float (&t)[3]) {
+            loss[0] = t[0] / (float)((long)d.B * Qn); correct[0] = t[1];
+            if (dalpha) dalpha[0] = t[2];
+        });
         return;
     }
     const int per = ncb * nfb;
     const int b = blockIdx.x / per, r = blockIdx.x - b * per, cb = r / nfb, fb = r - cb * nfb;
-    const int c0 = cb * EP_TM, f0 = fb * EP_NB;
-    const int nc = min(EP_TM, N - c0), nf = min(EP_NB, F - f0);
-    float* dc = sm + EP_MM;                      // [16, EP_LDC]
-    float* ts = dc + EP_TM * EP_LDC;             // [16, 16] strided column sums of dz
+    const int c0 = cb * FH_TM, f0 = fb * FH_NB;
+    const int nc = min(FH_TM, N - c0), nf = min(FH_NB, F - f0);
+    float* dc = sm + FH_MM;                      // [16, FH_LDC]
+    float* ts = dc + FH_TM * FH_LDC;             // [16, 16] strided column sums of dz
     float* tc = ts + 256;                        // [16] sum_q dz[q, n]
     const float a2 = 2.f * alpha_p[0];
     {   // sum_q dz[q, n]: 16 strided partial sums per class, added in index order
@@ -285,25 +239,11 @@ __global__ __launch_bounds__(256) void euclid_proto_sgrad_kernel(EuclidProto d, 
     }
     __syncthreads();
     // dc[m, n] = 2 alpha (sum_k dz[k, c0 + m] f_q[k, f0 + n] - (c'[c0 + m, f0 + n] + m[f0 + n]) tc_m)
-    wg_mm2(sm, EP_MM, nc, nf, Qn, Wd + (long)b * Qn * N + c0, 1, N, fq + (long)b * Qn * F + f0, F, 1,
+    wg_mm2(sm, FH_MM, nc, nf, Qn, Wd + (long)b * Qn * N + c0, 1, N, fq + (long)b * Qn * F + f0, F, 1,
            [&](int m, int n) { return f32pair{protos[((long)b * N + c0 + m) * F + f0 + n], mvec[(long)b * F + f0 + n]}; },
-           [&](int m, int n, float acc, f32pair c) { dc[m * EP_LDC + n] = a2 * (acc - (c.x + c.y) * tc[m]); });
+           [&](int m, int n, float acc, f32pair c) { dc[m * FH_LDC + n] = a2 * (acc - (c.x + c.y) * tc[m]); });
     __syncthreads();
-    {   // every support row of class n receives dc_n / count_n; the first class block zeroes the rows whose label is out of range
-        const int n = tid & (EP_NB - 1);
-        if (n < nf) {
-            for (int i = tid >> 7; i < S; i += 2) {
-                const long t = ys[(long)b * S + i];
-                float* o = dfs + ((long)b * S + i) * F + f0 + n;
-                if (t >= 0 && t < N) {
-                    const int m = (int)t - c0;
-                    if (m >= 0 && m < nc) *o = dc[m * EP_LDC + n] / cntf[(long)b * N + t];
-                } else if (cb == 0) {
-                    *o = 0.f;
-                }
-            }
-        }
-    }
+    fh_scatter_class_grad(dc, ys, cntf, dfs, b, S, N, F, c0, nc, f0, nf, cb == 0);
 }
 
 }  // namespace
@@ -311,19 +251,12 @@ __global__ __launch_bounds__(256) void euclid_proto_sgrad_kernel(EuclidProto d, 
 extern "C" int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* alpha, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dalpha) {
-    if (!ws) return FUMI_EINVAL;
-    if (B < 1 || S < 1 || S > 1024 || Qn < 1 || N < 2 || N > 64 || F % 32 != 0 || F < 32 || F > 2048 || (long)B * Qn > 65536)
-        return FUMI_ENOTSUP;
-    if (!feats_s || !y_s || !feats_q || !y_q || !alpha || !loss || !correct) return FUMI_EINVAL;
-    const int ngrad = (dfeats_s ? 1 : 0) + (dfeats_q ? 1 : 0) + (dalpha ? 1 : 0);
-    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
+    if (int rc = head_args_check(ws, B, S, Qn, N, F, S <= 1024, {feats_s, y_s, feats_q, y_q, alpha, loss, correct})) return rc;
+    const int train = head_grad_form(dfeats_s, dfeats_q, dalpha);
+    if (train < 0) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
-    const int train = ngrad == 3;
-    EuclidProto d;
-    d.B = B; d.S = S; d.Qn = Qn; d.N = N; d.F = F; d.ldz = ((N + 15) & ~15) + 4; d.tpe = (Qn + EP_TM - 1) / EP_TM; d.ntile = B * d.tpe;
-    d.nfb1 = (F + EP_PF - 1) / EP_PF; d.train = train;
-    d.gs = grad_scale / (float)((long)B * Qn);
+    const HeadDims d = head_dims_fill(B, S, Qn, N, F, train, grad_scale);
     const size_t n_pro = (size_t)B * N * F, n_m = (size_t)B * F, n_psq = (size_t)B * d.nfb1 * 2 * N, n_cnt = (size_t)B * N,
                  n_part = (size_t)3 * d.ntile, n_dz = (size_t)B * Qn * N;
     int rc = ws_reserve(ws, ws_align(n_pro * 4) + ws_align(n_m * 4) + ws_align(n_psq * 4) + ws_align(n_cnt * 4) + ws_align(n_part * 4)
@@ -332,9 +265,9 @@ extern "C" int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, i
     float* protos = ws_f(ws, n_pro); float* mvec = ws_f(ws, n_m); float* psq = ws_f(ws, n_psq); float* cntf = ws_f(ws, n_cnt);
     float* part = ws_f(ws, n_part);
     float* Wd = train ? ws_f(ws, n_dz) : nullptr;
-    const size_t lds1 = ((size_t)N * EP_PF + EP_PF + S + N) * 4;
-    const size_t lds2 = ((size_t)EP_TM * d.ldz + 192 + EP_MM) * 4;
-    const size_t lds3 = train ? ((size_t)EP_MM + EP_TM * EP_LDC + 256 + 16) * 4 : (size_t)768 * 4;   // the forward form's one workgroup only adds the tile sums
+    const size_t lds1 = ((size_t)N * FH_PF + FH_PF + S + N) * 4;
+    const size_t lds2 = ((size_t)FH_TM * d.ldz + 192 + FH_MM) * 4;
+    const size_t lds3 = train ? ((size_t)FH_MM + FH_TM * FH_LDC + 256 + 16) * 4 : (size_t)768 * 4;   // the forward form's one workgroup only adds the tile sums
     FUMI_SET_DYN_LDS(euclid_proto_means_kernel, lds1);
     hipLaunchKernelGGL(euclid_proto_means_kernel, dim3(B * d.nfb1), dim3(256), lds1, st, d, feats_s, y_s, protos, mvec, psq, cntf,
                        ws->status);
@@ -343,7 +276,7 @@ extern "C" int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, i
     hipLaunchKernelGGL(euclid_proto_rows_kernel, dim3(d.ntile), dim3(256), lds2, st, d, feats_q, y_q, protos, mvec, psq, alpha, preds,
                        logits, part, Wd, dfeats_q, ws->status);
     LAUNCH_CHECK();
-    const int nfb = (F + EP_NB - 1) / EP_NB, ncb = (N + EP_TM - 1) / EP_TM;
+    const int nfb = (F + FH_NB - 1) / FH_NB, ncb = (N + FH_TM - 1) / FH_TM;
     FUMI_SET_DYN_LDS(euclid_proto_sgrad_kernel, lds3);
     hipLaunchKernelGGL(euclid_proto_sgrad_kernel, dim3((train ? B * ncb * nfb : 0) + 1), dim3(256), lds3, st, d, nfb, ncb, feats_q, y_s,
                        protos, mvec, cntf, Wd, alpha, part, loss, correct, dalpha, dfeats_s);

@@ -29,18 +29,14 @@
 //   launch 3, one workgroup per (episode, tile of 16 query rows): the tile's inverse row norms, u = f_tile W on the f32 MFMA into LDS,
 //       z = u / |f| + b; per row first arg-max, log-sum-exp, NLL; the tile's loss and correct sums go to part[tile].
 //   launch 4, one workgroup: the tile partials added in index order into loss and correct.
-// Every sum has a fixed order (MFMA chains over k, butterflies, index-ordered loops): equal inputs give equal bits.  No floating-point
-// atomics; the only atomic is the OR into the status word.  The fit runs a fixed number of steps whatever the values are.
-// A query label outside [0, N) sets FUMI_ST_LABEL_RANGE and the row adds nothing; a support label outside [0, N) sets the same bit and
-// the row is left out (zero row and column of K~, zero rows of Y and R, not counted in n); a class without a support row sets
-// FUMI_ST_CLASS_MISSING and is fitted like any class.
-#include "common.h"
+// Fixed summation orders, the first arg-max, the label-range and missing-class rules and the absence of floating-point atomics are
+// those of fewshot_head.h.  The fit runs a fixed number of steps whatever the values are.  A support row left out is a zero row and
+// column of K~ and zero rows of Y and R, and is not counted in n; a class without a support row is fitted like any class.
+// After the Gram product the fit keeps A (and A' or VA) in the FH_MM floats of the products' staging area.
+#include "fewshot_head.h"
 
 namespace {
 
-constexpr int LR_TM = 16;          // query rows per workgroup of launch 3
-constexpr int LR_NB = 128;         // features per workgroup of launch 2
-constexpr int LR_MM = 16384;       // floats of LDS the products stage their operands in; the fit keeps A (and A' or VA) there afterwards
 constexpr size_t LR_LDS_MAX = 160 * 1024;
 // the form of K~ A the host picks when none is forced (measured, profiles/logreg_head/): the MFMA from S * NP elements of Z on
 #define LOGREG_AUTO_MFMA(S, NP) ((S) * (NP) >= 1024)
@@ -57,13 +53,14 @@ __global__ __launch_bounds__(256) void logreg_fit_kernel(Logreg d, const float* 
     const int S = d.S, N = d.N, F = d.F, ldl = d.ldl, NP = d.NP, SN = S * NP;
     const int b = blockIdx.x;
     float* mm = sm;                              // wg_mm's staging area, then A [S, NP] twice (or A and VA)
-    float* Km = mm + LR_MM;                      // [S, ldl]
+    float* Km = mm + FH_MM;                      // [S, ldl]
     float* A0 = mm;
     float* A1 = mm + SN;                         // the second copy of A when double-buffered
     float* VA = d.db ? Km + S * ldl : mm + SN;   // [S, NP]
     float* inv = Km + S * ldl + (d.db ? SN : 0); // [S] 1 / |x_i|, 0 for a row left out
     int* lab = (int*)(inv + S);                  // [S] labels, -1 where out of range
     float* red = (float*)(lab + S);              // [2][4][64] per-wave column sums of R, two slots
+    // (the label block of fewshot_head.h, kept inline: through the helpers this kernel's long loops below measured 0.5 - 1 % slower)
     bool bad = false;
     for (int i = tid; i < S; i += 256) {
         const long t = ys[(long)b * S + i];
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(256) void logreg_fit_kernel(Logreg d, const float* 
     for (int i = 0; i < S; ++i) cnt += lab[i] >= 0 ? 1 : 0;
     const float nf = (float)max(cnt, 1), invn = 1.f / nf, wd = 1.f / (d.C * nf), eta = d.lr, beta = d.beta;
     const float* X = xs + (long)b * S * F;
-    wg_mm(mm, LR_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) { Km[m * ldl + n] = acc; });
+    wg_mm(mm, FH_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) { Km[m * ldl + n] = acc; });
     __syncthreads();
     for (int i = tid; i < S; i += 256)
         inv[i] = lab[i] < 0 ? 0.f : (d.normalize ? 1.f / fmaxf(sqrtf(Km[i * ldl + i]), 1e-12f) : 1.f);
@@ -159,6 +156,7 @@ __global__ __launch_bounds__(256) void logreg_fit_mfma_kernel(Logreg d, const fl
     float* inv = mm + d.body;                    // [S] 1 / |x_i|, 0 for a row left out
     int* lab = (int*)(inv + S);                  // [S] labels, -1 where out of range
     float* red = (float*)(lab + S);              // [2][4][64] per-wave column sums of R, two slots
+    // (the label block of fewshot_head.h, kept inline: through the helpers this kernel's long loops below measured 0.5 - 1 % slower)
     bool bad = false;
     for (int i = tid; i < S; i += 256) {
         const long t = ys[(long)b * S + i];
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(256) void logreg_fit_mfma_kernel(Logreg d, const fl
     for (int i = 0; i < S; ++i) cnt += lab[i] >= 0 ? 1 : 0;
     const float nf = (float)max(cnt, 1), invn = 1.f / nf, wd = 1.f / (d.C * nf), eta = d.lr, beta = d.beta;
     const float* X = xs + (long)b * S * F;
-    wg_mm(mm, LR_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) { Km[m * ldk + n] = acc; });
+    wg_mm(mm, FH_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) { Km[m * ldk + n] = acc; });
     __syncthreads();
     for (int i = tid; i < S; i += 256)
         inv[i] = lab[i] < 0 ? 0.f : (d.normalize ? 1.f / fmaxf(sqrtf(Km[i * ldk + i]), 1e-12f) : 1.f);
@@ -285,9 +283,9 @@ __global__ __launch_bounds__(256) void logreg_w_kernel(Logreg d, const float* __
                                                        float* __restrict__ Wt) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int S = d.S, N = d.N, F = d.F;
-    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * LR_NB, nf = min(LR_NB, F - f0);
+    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * FH_NB, nf = min(FH_NB, F - f0);
     // W^T[m, f0 + n] = sum_k A'[k, m] X[k, f0 + n]
-    wg_mm(sm, LR_MM, N, nf, S, Aw + (long)b * S * N, 1, N, xs + (long)b * S * F + f0, F, 1,
+    wg_mm(sm, FH_MM, N, nf, S, Aw + (long)b * S * N, 1, N, xs + (long)b * S * F + f0, F, 1,
           [&](int m, int n, float acc) { Wt[((long)b * N + m) * F + f0 + n] = acc; });
 }
 
@@ -298,10 +296,10 @@ __global__ __launch_bounds__(256) void logreg_rows_kernel(Logreg d, const float*
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int Qn = d.Qn, N = d.N, F = d.F, ldz = d.ldz;
-    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * LR_TM, rows = min(LR_TM, Qn - q0);
+    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * FH_TM, rows = min(FH_TM, Qn - q0);
     const long r0 = (long)b * Qn + q0;           // the tile's first row among all B * Qn
     float* Z = sm;                               // [16, ldz] u, then z
-    float* rl = Z + LR_TM * ldz;                 // [16] row losses, [16] row hits
+    float* rl = Z + FH_TM * ldz;                 // [16] row losses, [16] row hits
     float* iq = rl + 32;                         // [16] 1 / |f_row|
     float* mm = iq + 16;
     const float* ft = fq + r0 * F;
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(256) void logreg_rows_kernel(Logreg d, const float*
         for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if (l == 0) iq[row] = d.normalize ? 1.f / fmaxf(sqrtf(s), 1e-12f) : 1.f;
     }
-    wg_mm(mm, LR_MM, rows, N, F, ft, F, 1, wt, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc; });
+    wg_mm(mm, FH_MM, rows, N, F, ft, F, 1, wt, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc; });
     __syncthreads();
     for (int t = tid; t < rows * N; t += 256) { const int m = t / N, n = t - m * N; Z[m * ldz + n] = Z[m * ldz + n] * iq[m] + bb[n]; }
     __syncthreads();
@@ -330,6 +328,9 @@ __global__ __launch_bounds__(256) void logreg_rows_kernel(Logreg d, const float*
             float z[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; z[j] = n < N ? c[n] : 0.f; }
+            // The row's softmax cross-entropy, the same block in the four rows kernels.  It stays a copy: through helper functions (a
+            // softmax helper alone included) the compiler allocates this kernel's registers differently and the training heads measured
+            // 0.2 - 0.7 % slower.  A change to the arg-max, the label rule or the NLL is made in all four.
             float mx = -INFINITY; int arg = N;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; if (n < N && z[j] > mx) { mx = z[j]; arg = n; } }
@@ -356,26 +357,15 @@ __global__ __launch_bounds__(256) void logreg_rows_kernel(Logreg d, const float*
         if (l == 0) { rl[row] = loss; rl[16 + row] = hit; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, h = 0.f;
-        for (int r = 0; r < LR_TM; ++r) { a += rl[r]; h += rl[16 + r]; }
-        part[blockIdx.x] = a; part[d.ntile + blockIdx.x] = h;
-    }
+    fh_tile_part<2>(rl, part, d.ntile);
 }
 
 __global__ __launch_bounds__(256) void logreg_sum_kernel(Logreg d, const float* __restrict__ part, float* __restrict__ loss,
                                                          float* __restrict__ correct) {
     __shared__ float sm[512];
-    const int tid = threadIdx.x;                 // the sums over the row tiles: 256 strided sums, then those in index order
-    float a = 0.f, h = 0.f;
-    for (int i = tid; i < d.ntile; i += 256) { a += part[i]; h += part[d.ntile + i]; }
-    sm[tid] = a; sm[256 + tid] = h;
-    __syncthreads();
-    if (tid == 0) {
-        a = 0.f; h = 0.f;
-        for (int i = 0; i < 256; ++i) { a += sm[i]; h += sm[256 + i]; }
-        loss[0] = a / (float)((long)d.B * d.Qn); correct[0] = h;
-    }
+    fh_sum_parts<2>(part, d.ntile, sm, [&](const float (&t)[2]) {      // the sums over the row tiles
+        loss[0] = t[0] / (float)((long)d.B * d.Qn); correct[0] = t[1];
+    });
 }
 
 int g_logreg_form = -1;           // -1: chosen per shape, 0: VALU loop, 1: f32 MFMA
@@ -391,17 +381,14 @@ extern "C" int fumi_hip_logreg_set_form(int form) {
 extern "C" int fumi_hip_logreg_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, int steps, float lr, float momentum, float C,
         int normalize, float* loss, float* correct, int64_t* preds, float* logits) {
-    if (!ws) return FUMI_EINVAL;
-    if (B < 1 || S < 1 || S > 128 || Qn < 1 || N < 2 || N > 64 || F % 32 != 0 || F < 32 || F > 2048 || (long)B * Qn > 65536)
-        return FUMI_ENOTSUP;
-    if (steps < 1 || steps > 10000 || !(lr > 0.f) || !(momentum >= 0.f && momentum < 1.f) || !(C > 0.f)) return FUMI_ENOTSUP;
-    if (!feats_s || !y_s || !feats_q || !y_q || !loss || !correct) return FUMI_EINVAL;
+    const bool own = S <= 128 && steps >= 1 && steps <= 10000 && lr > 0.f && momentum >= 0.f && momentum < 1.f && C > 0.f;
+    if (int rc = head_args_check(ws, B, S, Qn, N, F, own, {feats_s, y_s, feats_q, y_q, loss, correct})) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
     Logreg d;
-    d.B = B; d.S = S; d.Qn = Qn; d.N = N; d.F = F; d.ldz = ((N + 15) & ~15) + 4; d.tpe = (Qn + LR_TM - 1) / LR_TM; d.ntile = B * d.tpe;
+    head_rows_fill(d, B, S, Qn, N, F);
     d.ldl = S | 1; d.lg = 1; while ((1 << d.lg) < N) ++d.lg;
-    d.NP = 1 << d.lg; d.nfb = (F + LR_NB - 1) / LR_NB;
+    d.NP = 1 << d.lg; d.nfb = (F + FH_NB - 1) / FH_NB;
     d.steps = steps; d.normalize = normalize ? 1 : 0; d.lr = lr; d.beta = momentum; d.C = C;
     const size_t fit_small = ((size_t)2 * S + 512) * 4;   // 1 / |x|, labels, two slots of per-wave column sums
     const bool mfma = g_logreg_form == 1 || (g_logreg_form < 0 && LOGREG_AUTO_MFMA(S, d.NP));
@@ -409,17 +396,17 @@ extern "C" int fumi_hip_logreg_head_step(fumi_ws_t* ws, fumi_stream_t stream, in
     d.Sp = (S + 15) & ~15; d.lda = (d.NP < 16 ? 16 : d.NP) + 4; d.body = 0;
     if (mfma) {                                 // K~ [Sp, Sp + 4] | max(staging, A, VA [, A]) | small
         const size_t SA = (size_t)d.Sp * d.lda, km = (size_t)d.Sp * (d.Sp + 4);
-        auto body = [&](size_t nbuf) { return nbuf * SA > (size_t)LR_MM ? nbuf * SA : (size_t)LR_MM; };
+        auto body = [&](size_t nbuf) { return nbuf * SA > (size_t)FH_MM ? nbuf * SA : (size_t)FH_MM; };
         d.db = (km + body(3)) * 4 + fit_small <= LR_LDS_MAX ? 1 : 0;
         d.body = (int)body(d.db ? 3 : 2);
         lds1 = (km + d.body) * 4 + fit_small;
     } else {                                    // staging / A twice (S NP <= 8192 floats each) | K~ [S, S | 1] | [VA] | small
-        const size_t lds_db = ((size_t)LR_MM + S * d.ldl + S * d.NP) * 4 + fit_small;
+        const size_t lds_db = ((size_t)FH_MM + S * d.ldl + S * d.NP) * 4 + fit_small;
         d.db = lds_db <= LR_LDS_MAX ? 1 : 0;
-        lds1 = d.db ? lds_db : ((size_t)LR_MM + S * d.ldl) * 4 + fit_small;
+        lds1 = d.db ? lds_db : ((size_t)FH_MM + S * d.ldl) * 4 + fit_small;
     }
-    const size_t lds2 = (size_t)LR_MM * 4;
-    const size_t lds3 = ((size_t)LR_TM * d.ldz + 48 + LR_MM) * 4;
+    const size_t lds2 = (size_t)FH_MM * 4;
+    const size_t lds3 = ((size_t)FH_TM * d.ldz + 48 + FH_MM) * 4;
     const size_t n_A = (size_t)B * S * N, n_b = (size_t)B * N, n_W = (size_t)B * N * F, n_part = (size_t)2 * d.ntile;
     int rc = ws_reserve(ws, ws_align(n_A * 4) + ws_align(n_b * 4) + ws_align(n_W * 4) + ws_align(n_part * 4));
     if (rc) return rc;

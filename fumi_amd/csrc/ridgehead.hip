@@ -20,21 +20,14 @@
 //       tile and episode partials in index order into loss, correct and dparams.
 //   The forward form (no gradient pointers) is launches 1 to 3 without the backward half of launch 3, and the last workgroup of
 //   launch 6: the same instructions produce loss, correct, preds and logits in both forms.
-// Every sum has a fixed order (MFMA chains over k, butterflies, index-ordered loops): equal inputs give equal bits.  No floating-point
-// atomics; the only atomic is the OR into the status word.  rho and alpha are read from device memory by the kernels.
-// A query label outside [0, N) sets FUMI_ST_LABEL_RANGE and the row adds nothing; a support label outside [0, N) sets the same bit and
-// the row is left out; a class without a support row sets FUMI_ST_CLASS_MISSING and has logits 0; a pivot that is not > 0 (a NaN
-// counts) sets FUMI_ST_NOT_POSDEF and is replaced by lam.
-#include "common.h"
+// Fixed summation orders, the first arg-max, the label-range and missing-class rules and the absence of floating-point atomics are
+// those of fewshot_head.h.  A class without a support row has logits 0; a pivot that is not > 0 (a NaN counts) sets
+// FUMI_ST_NOT_POSDEF and is replaced by lam.  rho and alpha are read from device memory by the kernels.
+#include "fewshot_head.h"
 
 namespace {
 
-constexpr int RH_TM = 16;          // query rows per workgroup of launch 3
-constexpr int RH_NB = 128;         // features per workgroup of launches 2, 4 and 6; output columns of one wg_mm call of launch 3
-constexpr int RH_MM = 16384;       // floats of LDS the products stage their operands in
-constexpr int RH_LDC = RH_NB + 4;  // row stride of the [N, 128] images of launches 4 and 6
-
-struct Ridge {
+struct Ridge {                     // (HeadDims' fields without nfb1, filled by head_rows_fill)
     int B, S, Qn, N, F, ldz, tpe, ntile, ldl, NP, lg, nfb, train;   // ldl: odd row stride of L; NP = 1 << lg: N rounded up to a power of two
     float gs;                                                       // grad_scale / (B Qn)
 };
@@ -69,10 +62,11 @@ __global__ __launch_bounds__(256) void ridge_factor_kernel(Ridge d, const float*
     const int S = d.S, N = d.N, F = d.F, ldl = d.ldl, NP = d.NP;
     const int b = blockIdx.x;
     float* mm = sm;                              // wg_mm's staging area, then Y / A [S, NP]
-    float* Lm = mm + RH_MM;                      // [S, ldl]
+    float* Lm = mm + FH_MM;                      // [S, ldl]
     float* dinv = Lm + S * ldl;                  // [S]
     int* lab = (int*)(dinv + S);                 // [S] labels, -1 where out of range
     const float lam = expf(params[0]);
+    // (the label block of fewshot_head.h, kept inline: through the helpers this kernel's long loops below measured 0.5 - 1 % slower)
     bool bad = false;
     for (int i = tid; i < S; i += 256) {
         const long t = ys[(long)b * S + i];
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(256) void ridge_factor_kernel(Ridge d, const float*
         if (c == 0) atomicOr(status, FUMI_ST_CLASS_MISSING);
     }
     const float* X = xs + (long)b * S * F;
-    wg_mm(mm, RH_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) {
+    wg_mm(mm, FH_MM, S, S, F, X, F, 1, X, 1, F, [&](int m, int n, float acc) {
         const float v = (lab[m] >= 0 && lab[n] >= 0) ? acc : 0.f;
         Lm[m * ldl + n] = m == n ? v + lam : v;
     });
@@ -121,9 +115,9 @@ __global__ __launch_bounds__(256) void ridge_w_kernel(Ridge d, const float* __re
                                                       float* __restrict__ Wt) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int S = d.S, N = d.N, F = d.F;
-    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * RH_NB, nf = min(RH_NB, F - f0);
+    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * FH_NB, nf = min(FH_NB, F - f0);
     // W^T[m, f0 + n] = sum_k A[k, m] X[k, f0 + n]
-    wg_mm(sm, RH_MM, N, nf, S, Aw + (long)b * S * N, 1, N, xs + (long)b * S * F + f0, F, 1,
+    wg_mm(sm, FH_MM, N, nf, S, Aw + (long)b * S * N, 1, N, xs + (long)b * S * F + f0, F, 1,
           [&](int m, int n, float acc) { Wt[((long)b * N + m) * F + f0 + n] = acc; });
 }
 
@@ -135,17 +129,17 @@ __global__ __launch_bounds__(256) void ridge_rows_kernel(Ridge d, const float* _
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int Qn = d.Qn, N = d.N, F = d.F, ldz = d.ldz;
-    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * RH_TM, rows = min(RH_TM, Qn - q0);
+    const int b = blockIdx.x / d.tpe, q0 = (blockIdx.x - b * d.tpe) * FH_TM, rows = min(FH_TM, Qn - q0);
     const long r0 = (long)b * Qn + q0;           // the tile's first row among all B * Qn
     float* Z = sm;                               // [16, ldz] u, then alpha dz
-    float* rl = Z + RH_TM * ldz;                 // [16] row losses, [16] row hits, [16] row dalpha
+    float* rl = Z + FH_TM * ldz;                 // [16] row losses, [16] row hits, [16] row dalpha
     float* mm = rl + 48;
     const float* ft = fq + r0 * F;
     const float* wt = Wt + (long)b * N * F;
     const float alpha = params[1];
     const int row = tid >> 4, l = tid & 15;      // 16 lanes per row
 
-    wg_mm(mm, RH_MM, rows, N, F, ft, F, 1, wt, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc; });
+    wg_mm(mm, FH_MM, rows, N, F, ft, F, 1, wt, 1, F, [&](int m, int n, float acc) { Z[m * ldz + n] = acc; });
     __syncthreads();
 
     {
@@ -155,6 +149,9 @@ __global__ __launch_bounds__(256) void ridge_rows_kernel(Ridge d, const float* _
             float us[4], z[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; us[j] = n < N ? c[n] : 0.f; z[j] = alpha * us[j]; }
+            // The row's softmax cross-entropy, the same block in the four rows kernels.  It stays a copy: through helper functions (a
+            // softmax helper alone included) the compiler allocates this kernel's registers differently and the training heads measured
+            // 0.2 - 0.7 % slower.  A change to the arg-max, the label rule or the NLL is made in all four.
             float mx = -INFINITY; int arg = N;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int n = l + 16 * j; if (n < N && z[j] > mx) { mx = z[j]; arg = n; } }
@@ -195,16 +192,12 @@ __global__ __launch_bounds__(256) void ridge_rows_kernel(Ridge d, const float* _
         if (l == 0) { rl[row] = loss; rl[16 + row] = hit; rl[32 + row] = da; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int r = 0; r < RH_TM; ++r) { a += rl[r]; h += rl[16 + r]; t += rl[32 + r]; }
-        part[blockIdx.x] = a; part[d.ntile + blockIdx.x] = h; part[2 * d.ntile + blockIdx.x] = t;
-    }
+    fh_tile_part<3>(rl, part, d.ntile);
     if (!d.train) return;
     // dfeats_tile [rows, F] = (alpha dz) [rows, N] W^T [N, F]
-    for (int f0 = 0; f0 < F; f0 += RH_NB) {
-        const int nb = min(RH_NB, F - f0);
-        wg_mm(mm, RH_MM, rows, nb, N, Z, ldz, 1, wt + f0, F, 1,
+    for (int f0 = 0; f0 < F; f0 += FH_NB) {
+        const int nb = min(FH_NB, F - f0);
+        wg_mm(mm, FH_MM, rows, nb, N, Z, ldz, 1, wt + f0, F, 1,
               [&](int m, int n, float acc) { dfq[(r0 + m) * F + f0 + n] = acc; });
     }
 }
@@ -214,19 +207,19 @@ __global__ __launch_bounds__(256) void ridge_dw_kernel(Ridge d, const float* __r
                                                        float* __restrict__ dWt, float* __restrict__ P) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int S = d.S, Qn = d.Qn, N = d.N, F = d.F;
-    const int b = blockIdx.x / d.nfb, fb = blockIdx.x - b * d.nfb, f0 = fb * RH_NB, nf = min(RH_NB, F - f0);
-    float* dWl = sm + RH_MM;                     // [N, RH_LDC] this block of dW^T
+    const int b = blockIdx.x / d.nfb, fb = blockIdx.x - b * d.nfb, f0 = fb * FH_NB, nf = min(FH_NB, F - f0);
+    float* dWl = sm + FH_MM;                     // [N, FH_LDC] this block of dW^T
     const float alpha = params[1];
     // dW^T[m, f0 + n] = alpha sum_q dz[q, m] Fq[q, f0 + n]
-    wg_mm(sm, RH_MM, N, nf, Qn, dzw + (long)b * Qn * N, 1, N, fq + (long)b * Qn * F + f0, F, 1, [&](int m, int n, float acc) {
+    wg_mm(sm, FH_MM, N, nf, Qn, dzw + (long)b * Qn * N, 1, N, fq + (long)b * Qn * F + f0, F, 1, [&](int m, int n, float acc) {
         const float v = alpha * acc;
-        dWl[m * RH_LDC + n] = v;
+        dWl[m * FH_LDC + n] = v;
         dWt[((long)b * N + m) * F + f0 + n] = v;
     });
     __syncthreads();
     // this block's share of (X dW)[m, n] = sum_k X[m, f0 + k] dW^T[n, f0 + k]
     float* p = P + ((long)b * d.nfb + fb) * S * N;
-    wg_mm(sm, RH_MM, S, N, nf, xs + (long)b * S * F + f0, F, 1, dWl, 1, RH_LDC, [&](int m, int n, float acc) { p[m * N + n] = acc; });
+    wg_mm(sm, FH_MM, S, N, nf, xs + (long)b * S * F + f0, F, 1, dWl, 1, FH_LDC, [&](int m, int n, float acc) { p[m * N + n] = acc; });
 }
 
 __global__ __launch_bounds__(256) void ridge_g_kernel(Ridge d, const int64_t* __restrict__ ys, const float* __restrict__ params,
@@ -274,37 +267,31 @@ __global__ __launch_bounds__(256) void ridge_dx_kernel(Ridge d, const float* __r
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int S = d.S, N = d.N, F = d.F;
-    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles: 256 strided sums, then those in index order
-        float a = 0.f, h = 0.f, t = 0.f;
-        for (int i = tid; i < d.ntile; i += 256) { a += part[i]; h += part[d.ntile + i]; t += part[2 * d.ntile + i]; }
-        sm[tid] = a; sm[256 + tid] = h; sm[512 + tid] = t;
-        __syncthreads();
-        if (tid == 0) {
-            a = 0.f; h = 0.f; t = 0.f;
-            for (int i = 0; i < 256; ++i) { a += sm[i]; h += sm[256 + i]; t += sm[512 + i]; }
-            loss[0] = a / (float)((long)d.B * d.Qn); correct[0] = h;
+    if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles, and the episodes' drho in index order
+        fh_sum_parts<3>(part, d.ntile, sm, [&](const float (&t)[3]) {
+            loss[0] = t[0] / (float)((long)d.B * d.Qn); correct[0] = t[1];
             if (dparams) {
                 float r = 0.f;
                 for (int i = 0; i < d.B; ++i) r += partd[i];
-                dparams[0] = r; dparams[1] = t;
+                dparams[0] = r; dparams[1] = t[2];
             }
-        }
+        });
         return;
     }
-    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * RH_NB, nf = min(RH_NB, F - f0);
-    float* Dl = sm + RH_MM;                      // [N, RH_LDC] dW^T - G^T X of this feature block
+    const int b = blockIdx.x / d.nfb, f0 = (blockIdx.x - b * d.nfb) * FH_NB, nf = min(FH_NB, F - f0);
+    float* Dl = sm + FH_MM;                      // [N, FH_LDC] dW^T - G^T X of this feature block
     const float* X = xs + (long)b * S * F + f0;
     const float* A = Aw + (long)b * S * N;
     const float* G = Gw + (long)b * S * N;
     float* o = dfs + (long)b * S * F + f0;
-    wg_mm2(sm, RH_MM, N, nf, S, G, 1, N, X, F, 1,
+    wg_mm2(sm, FH_MM, N, nf, S, G, 1, N, X, F, 1,
            [&](int m, int n) { return dWt[((long)b * N + m) * F + f0 + n]; },
-           [&](int m, int n, float acc, float w) { Dl[m * RH_LDC + n] = w - acc; });
+           [&](int m, int n, float acc, float w) { Dl[m * FH_LDC + n] = w - acc; });
     __syncthreads();
     // dX = A D - G W^T: the second product first, the first one added to what it left
-    wg_mm(sm, RH_MM, S, nf, N, G, N, 1, Wt + (long)b * N * F + f0, F, 1, [&](int m, int n, float acc) { o[(long)m * F + n] = -acc; });
+    wg_mm(sm, FH_MM, S, nf, N, G, N, 1, Wt + (long)b * N * F + f0, F, 1, [&](int m, int n, float acc) { o[(long)m * F + n] = -acc; });
     __syncthreads();
-    wg_mm2(sm, RH_MM, S, nf, N, A, N, 1, Dl, RH_LDC, 1,
+    wg_mm2(sm, FH_MM, S, nf, N, A, N, 1, Dl, FH_LDC, 1,
            [&](int m, int n) { return o[(long)m * F + n]; },
            [&](int m, int n, float acc, float x) { o[(long)m * F + n] = x + acc; });
 }
@@ -314,20 +301,16 @@ __global__ __launch_bounds__(256) void ridge_dx_kernel(Ridge d, const float* __r
 extern "C" int fumi_hip_ridge_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* params, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dparams) {
-    if (!ws) return FUMI_EINVAL;
-    if (B < 1 || S < 1 || S > 128 || Qn < 1 || N < 2 || N > 64 || F % 32 != 0 || F < 32 || F > 2048 || (long)B * Qn > 65536)
-        return FUMI_ENOTSUP;
-    if (!feats_s || !y_s || !feats_q || !y_q || !params || !loss || !correct) return FUMI_EINVAL;
-    const int ngrad = (dfeats_s ? 1 : 0) + (dfeats_q ? 1 : 0) + (dparams ? 1 : 0);
-    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
+    if (int rc = head_args_check(ws, B, S, Qn, N, F, S <= 128, {feats_s, y_s, feats_q, y_q, params, loss, correct})) return rc;
+    const int train = head_grad_form(dfeats_s, dfeats_q, dparams);
+    if (train < 0) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
-    const int train = ngrad == 3;
     Ridge d;
-    d.B = B; d.S = S; d.Qn = Qn; d.N = N; d.F = F; d.ldz = ((N + 15) & ~15) + 4; d.tpe = (Qn + RH_TM - 1) / RH_TM; d.ntile = B * d.tpe;
+    head_rows_fill(d, B, S, Qn, N, F);
     d.ldl = S | 1; d.lg = 1; while ((1 << d.lg) < N) ++d.lg;
-    d.NP = 1 << d.lg; d.nfb = (F + RH_NB - 1) / RH_NB; d.train = train;
-    d.gs = grad_scale / (float)((long)B * Qn);
+    d.NP = 1 << d.lg; d.nfb = (F + FH_NB - 1) / FH_NB; d.train = train;
+    d.gs = head_grad_scale(grad_scale, B, Qn);
     const size_t n_L = (size_t)B * S * d.ldl, n_di = (size_t)B * S, n_A = (size_t)B * S * N, n_W = (size_t)B * N * F,
                  n_part = (size_t)3 * d.ntile, n_dz = (size_t)B * Qn * N, n_P = (size_t)B * d.nfb * S * N;
     int rc = ws_reserve(ws, ws_align(n_L * 4) + ws_align(n_di * 4) + ws_align(n_A * 4) + ws_align(n_W * 4) + ws_align(n_part * 4)
@@ -339,10 +322,10 @@ extern "C" int fumi_hip_ridge_head_step(fumi_ws_t* ws, fumi_stream_t stream, int
     float* dzw = train ? ws_f(ws, n_dz) : nullptr; float* dWt = train ? ws_f(ws, n_W) : nullptr;
     float* P = train ? ws_f(ws, n_P) : nullptr; float* Gw = train ? ws_f(ws, n_A) : nullptr;
     float* partd = train ? ws_f(ws, (size_t)B) : nullptr;
-    const size_t lds1 = ((size_t)RH_MM + S * d.ldl + 2 * S) * 4;
-    const size_t lds2 = (size_t)RH_MM * 4;
-    const size_t lds3 = ((size_t)RH_TM * d.ldz + 48 + RH_MM) * 4;
-    const size_t lds4 = ((size_t)RH_MM + 64 * RH_LDC) * 4;
+    const size_t lds1 = ((size_t)FH_MM + S * d.ldl + 2 * S) * 4;
+    const size_t lds2 = (size_t)FH_MM * 4;
+    const size_t lds3 = ((size_t)FH_TM * d.ldz + 48 + FH_MM) * 4;
+    const size_t lds4 = ((size_t)FH_MM + 64 * FH_LDC) * 4;
     const size_t lds5 = ((size_t)S * d.ldl + S + S * d.NP + 256) * 4;
     const size_t lds6 = train ? lds4 : (size_t)768 * 4;   // the forward form's one workgroup only adds the tile sums
     FUMI_SET_DYN_LDS(ridge_factor_kernel, lds1);

@@ -30,16 +30,13 @@
 //       wave's column sums of the new w) | barrier.  After the last step phase b writes logits, predictions and the row losses, and
 //       the episode's loss / correct sums go to part[b] in a fixed order.
 //   launch 4, one workgroup: the episode partials added in index order into loss and correct.
-// Every sum has a fixed order (MFMA chains over k, butterflies, index-ordered loops): equal inputs give equal bits.  No floating-point
-// atomics; the only atomic is the OR into the status word.  scale is read from device memory by the kernel.
-// A query label outside [0, N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss or the count (the divisor stays B * Qn) but
-// takes part in the refinement, which reads no query label.  A support label outside [0, N) sets the same bit and the row is left out
-// exactly.  A class without a support row sets FUMI_ST_CLASS_MISSING.
-#include "common.h"
+// Fixed summation orders, the first arg-max, the label-range and missing-class rules and the absence of floating-point atomics are
+// those of fewshot_head.h.  A query row whose label is out of range still takes part in the refinement, which reads no query label.
+// scale is read from device memory by the kernel.
+#include "fewshot_head.h"
 
 namespace {
 
-constexpr int TP_PF = 256;         // features per workgroup of launch 1: one column per thread
 constexpr int TP_T = 64;           // rows and columns of a tile of launch 2
 constexpr int TP_KC = 32;          // features per staged chunk of launch 2
 constexpr int TP_LDI = TP_KC + 4;  // row stride of its LDS images (= 4 mod 32: conflict-free ds_read_b128)
@@ -57,51 +54,32 @@ __global__ __launch_bounds__(256) void trans_proto_means_kernel(TransProto d, co
     const int S = d.S, N = d.N, F = d.F;
     const int b = blockIdx.x / d.nfb1, fb = blockIdx.x - b * d.nfb1;
     float* acc = sm;                             // [N, 256] class sums
-    float* mcol = acc + N * TP_PF;               // [256] m[f]^2 of each column
-    int* lab = (int*)(mcol + TP_PF);             // [S] labels, -1 where out of range
+    float* mcol = acc + N * FH_PF;               // [256] m[f]^2 of each column
+    int* lab = (int*)(mcol + FH_PF);             // [S] labels, -1 where out of range
     int* cnt = lab + S;                          // [N]
-    const int64_t* y = ys + (long)b * S;
-    bool bad = false;
-    for (int i = tid; i < S; i += 256) {
-        const long t = y[i];
-        const bool ok = t >= 0 && t < N;
-        lab[i] = ok ? (int)t : -1;
-        bad |= !ok;
-    }
+    const bool bad = fh_stage_labels(ys + (long)b * S, S, N, lab);
     if (bad && fb == 0) atomicOr(status, FUMI_ST_LABEL_RANGE);
-    for (int i = tid; i < N * TP_PF; i += 256) acc[i] = 0.f;
+    for (int i = tid; i < N * FH_PF; i += 256) acc[i] = 0.f;
     __syncthreads();
-    if (tid < N) {
-        int c = 0;
-        for (int i = 0; i < S; ++i) c += lab[i] == tid ? 1 : 0;
+    if (tid < N) {                               // the raw counts: k_n = 0 is a case of its own here
+        const int c = fh_class_count(lab, S, tid);
         cnt[tid] = c;
         if (c == 0 && fb == 0) atomicOr(status, FUMI_ST_CLASS_MISSING);
     }
-    const int f = fb * TP_PF + tid;
-    if (f < F) {
-        const float* x = xs + (long)b * S * F + f;
-        int i = 0;
-        for (; i + 4 <= S; i += 4) {             // four loads in flight, added in index order
-            float v[4]; int l[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { v[u] = x[(long)(i + u) * F]; l[u] = lab[i + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (l[u] >= 0) acc[l[u] * TP_PF + tid] += v[u];
-        }
-        for (; i < S; ++i) { const int l = lab[i]; if (l >= 0) acc[l * TP_PF + tid] += x[(long)i * F]; }
-    }
+    const int f = fb * FH_PF + tid;
+    if (f < F) fh_class_sums(acc, lab, xs + (long)b * S * F + f, S, F);
     __syncthreads();
     float m = 0.f;
     if (f < F) {
         if (d.metric) {                          // the mean of the step-0 prototypes, classes in index order
-            for (int n = 0; n < N; ++n) m += acc[n * TP_PF + tid] / (float)max(cnt[n], 1);
+            for (int n = 0; n < N; ++n) m += acc[n * FH_PF + tid] / (float)max(cnt[n], 1);
             m /= (float)N;
             for (int n = 0; n < N; ++n) {
                 const float k = (float)max(cnt[n], 1);
-                U[((long)b * N + n) * F + f] = (acc[n * TP_PF + tid] / k - m) * k;
+                U[((long)b * N + n) * F + f] = (acc[n * FH_PF + tid] / k - m) * k;
             }
         } else {
-            for (int n = 0; n < N; ++n) U[((long)b * N + n) * F + f] = acc[n * TP_PF + tid];
+            for (int n = 0; n < N; ++n) U[((long)b * N + n) * F + f] = acc[n * FH_PF + tid];
         }
         mvec[(long)b * F + f] = m;
     }
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(256) void trans_proto_loop_kernel(TransProto d, con
     int* kcnt = lab + Sp;                        // [64] class counts
     const float* P0b = P0 + (long)b * MP * ldp;
     const float* KQb = KQ + (long)b * MP * Qp;
-    for (int i = tid; i < Sp; i += 256) {
+    for (int i = tid; i < Sp; i += 256) {        // (not fh_stage_labels: padded to Sp, and launch 1 has reported the status)
         long t = -1;
         if (i < S) t = ys[(long)b * S + i];
         lab[i] = (t >= 0 && t < N) ? (int)t : -1;
@@ -330,6 +308,8 @@ __global__ __launch_bounds__(256) void trans_proto_loop_kernel(TransProto d, con
                 const float* g = G + qi * ldw + r;
                 const float f2 = fq2[qi];
                 const float fi = d.metric ? 0.f : scale / fmaxf(sqrtf(f2), 1e-12f);
+                // (fh_row_softmax's block over CT columns, kept inline with the arg-max fused into the loop that forms z: through the
+                // helper the compiler reorders this step loop and the head measured 0.2 - 0.4 % slower)
                 float z[CT];
                 float mx = -INFINITY; int arg = N;
 #pragma unroll
@@ -404,16 +384,9 @@ __global__ __launch_bounds__(256) void trans_proto_loop_kernel(TransProto d, con
 __global__ __launch_bounds__(256) void trans_proto_sum_kernel(TransProto d, const float* __restrict__ part, float* __restrict__ loss,
                                                               float* __restrict__ correct) {
     __shared__ float sm[512];
-    const int tid = threadIdx.x;                 // the sums over the episodes: 256 strided sums, then those in index order
-    float a = 0.f, h = 0.f;
-    for (int i = tid; i < d.B; i += 256) { a += part[i]; h += part[d.B + i]; }
-    sm[tid] = a; sm[256 + tid] = h;
-    __syncthreads();
-    if (tid == 0) {
-        a = 0.f; h = 0.f;
-        for (int i = 0; i < 256; ++i) { a += sm[i]; h += sm[256 + i]; }
-        loss[0] = a / (float)((long)d.B * d.Qn); correct[0] = h;
-    }
+    fh_sum_parts<2>(part, d.B, sm, [&](const float (&t)[2]) {          // the sums over the episodes
+        loss[0] = t[0] / (float)((long)d.B * d.Qn); correct[0] = t[1];
+    });
 }
 
 }  // namespace
@@ -421,18 +394,15 @@ __global__ __launch_bounds__(256) void trans_proto_sum_kernel(TransProto d, cons
 extern "C" int fumi_hip_trans_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* scale, int metric, int steps,
         float* loss, float* correct, int64_t* preds, float* logits) {
-    if (!ws) return FUMI_EINVAL;
-    if (B < 1 || S < 1 || Qn < 1 || S + Qn > 512 || N < 2 || N > 64 || (long)Qn * N > 8192 || (long)B * Qn > 65536 || F % 32 != 0 ||
-        F < 32 || F > 2048 || steps < 0 || steps > 100)
-        return FUMI_ENOTSUP;
-    if (!feats_s || !y_s || !feats_q || !y_q || !scale || !loss || !correct) return FUMI_EINVAL;
+    const bool own = S + Qn <= 512 && (long)Qn * N <= 8192 && steps >= 0 && steps <= 100;
+    if (int rc = head_args_check(ws, B, S, Qn, N, F, own, {feats_s, y_s, feats_q, y_q, scale, loss, correct})) return rc;
     if (metric != 0 && metric != 1) return FUMI_EINVAL;
     TransProto d;
     d.B = B; d.S = S; d.Qn = Qn; d.N = N; d.F = F; d.Sp = (S + 15) & ~15; d.Qp = (Qn + 15) & ~15; d.MP = d.Sp + d.Qp;
-    d.CT = (N + 15) >> 4; d.ldw = 16 * d.CT + 4; d.steps = steps; d.metric = metric; d.nfb1 = (F + TP_PF - 1) / TP_PF;
+    d.CT = (N + 15) >> 4; d.ldw = 16 * d.CT + 4; d.steps = steps; d.metric = metric; d.nfb1 = (F + FH_PF - 1) / FH_PF;
     d.rtm = (d.MP + TP_T - 1) / TP_T; d.ctq = (d.Qp + TP_T - 1) / TP_T;
     d.vec = ((((uintptr_t)feats_s) | ((uintptr_t)feats_q)) & 15) == 0 ? 1 : 0;
-    const size_t lds1 = ((size_t)N * TP_PF + TP_PF + S + N) * 4;
+    const size_t lds1 = ((size_t)N * FH_PF + FH_PF + S + N) * 4;
     const size_t lds3 = ((size_t)2 * d.Qp * d.ldw + 3 * d.Qp + 256 + 512 + d.Sp + 64) * 4;
     if (lds3 > TP_LDS_MAX) return FUMI_ENOTSUP;  // (not reached inside the limits above: at most 152256 bytes, at Qn = 481, N = 17)
     hipStream_t st = (hipStream_t)stream;

@@ -1594,6 +1594,50 @@ def cls_head_step(ws, feats, y, W, b, *, need_grad=True, grad_scale=1.0, dfeats=
     return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
 
 
+def _episode_head_io(name, feats_s, y_s, feats_q, y_q, n_way, want_logits, param=None, metric=None):
+    """What the episode heads share before their call: the checks of feats_s [B,S,F], y_s [B,S], feats_q [B,Qn,F], y_q [B,Qn], the
+    ``n_way`` default and the outputs.  ``param`` = (tensor, shape, name) is the head's device parameter, checked with the shapes;
+    ``metric`` the transductive head's, checked after the dimensions.  Returns (dev, (B, S, Qn, N, F), dict(loss, correct, preds,
+    logits))."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3 or feats_q.dim() != 3:
+        raise FumiHipError(f"{name}: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
+    if metric is not None and metric not in TRANS_METRICS:
+        raise FumiHipError(f"{name}: metric must be cosine or euclid, got {metric}")
+    B, S, F = (int(v) for v in feats_s.shape)
+    Qn = int(feats_q.shape[1])
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
+    if param is not None:
+        _shape(*param)
+    out = dict(loss=torch.empty(1, device=dev, dtype=torch.float32), correct=torch.empty(1, device=dev, dtype=torch.float32),
+               preds=torch.empty(B, Qn, device=dev, dtype=torch.int64),
+               logits=torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None)
+    return dev, (B, S, Qn, N, F), out
+
+
+def _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out):
+    """The leading (dims, features, labels) and the trailing (loss, correct, preds, logits) ctypes arguments of an episode head's
+    entry, with their dtype checks; called after the gradients' shapes are checked, as the order of errors always was."""
+    lead = (*dims, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"), _f32(feats_q, "feats_q"), _i64(y_q, "y_q"))
+    tail = (_f32(out["loss"], "loss"), _f32(out["correct"], "correct"), _i64(out["preds"], "preds"),
+            _f32(out["logits"], "logits") if out["logits"] is not None else None)
+    return lead, tail
+
+
+def _head_grads(dev, need_grad, out, **given):
+    """The three gradients of a head, name=(shape, tensor given or None): into ``out`` the tensors given, else new ones, None without
+    need_grad; returns their ctypes arguments."""
+    args = []
+    for name, (shape, t) in given.items():
+        if need_grad:
+            t = torch.empty(*shape, device=dev, dtype=torch.float32) if t is None else t
+            _shape(t, shape, name)
+        out[name] = t if need_grad else None
+        args.append(_f32(t, name) if need_grad else None)
+    return args
+
+
 def cos_proto_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
                    dfeats_q=None, dtau=None, n_way=None):
     """The fused cosine nearest-centroid head (csrc/cosproto.hip): per episode the class means of feats_s [B,S,F] by y_s [B,S], logits
@@ -1602,31 +1646,14 @@ def cos_proto_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_
     Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without
     want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dtau [1] = gradients of grad_scale * loss (written into the
     tensors given, else into new ones)."""
-    dev = _dev(feats_s)
-    if feats_s.dim() != 3 or feats_q.dim() != 3:
-        raise FumiHipError("cos_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
-    B, S, F = (int(v) for v in feats_s.shape)
-    Qn = int(feats_q.shape[1])
-    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
-    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(tau, (1,), "tau")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
-    if need_grad:
-        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
-        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
-        dtau = torch.empty(1, device=dev, dtype=torch.float32) if dtau is None else dtau
-        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dtau, (1,), "dtau")
-        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dtau, "dtau")]
-    else:
-        dfeats_s = dfeats_q = dtau = None
-        grads = [None, None, None]
-    _check(lib().fumi_hip_cos_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
-                                         _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(tau, "tau"), float(grad_scale),
-                                         _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
-                                         _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_cos_proto_step")
-    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau)
+    dev, dims, out = _episode_head_io("cos_proto_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                                              param=(tau, (1,), "tau"))
+    B, S, Qn, N, F = dims
+    grads = _head_grads(dev, need_grad, out, dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q), dtau=((1,), dtau))
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_cos_proto_step(ws.handle, _stream(dev), *lead, _f32(tau, "tau"), float(grad_scale), *tail, *grads),
+           "fumi_hip_cos_proto_step")
+    return out
 
 
 def euclid_proto_step(ws, feats_s, y_s, feats_q, y_q, alpha, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
@@ -1637,31 +1664,14 @@ def euclid_proto_step(ws, feats_s, y_s, feats_q, y_q, alpha, *, need_grad=True, 
     it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None
     without want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dalpha [1] = gradients of grad_scale * loss (written
     into the tensors given, else into new ones)."""
-    dev = _dev(feats_s)
-    if feats_s.dim() != 3 or feats_q.dim() != 3:
-        raise FumiHipError("euclid_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
-    B, S, F = (int(v) for v in feats_s.shape)
-    Qn = int(feats_q.shape[1])
-    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
-    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(alpha, (1,), "alpha")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
-    if need_grad:
-        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
-        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
-        dalpha = torch.empty(1, device=dev, dtype=torch.float32) if dalpha is None else dalpha
-        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dalpha, (1,), "dalpha")
-        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dalpha, "dalpha")]
-    else:
-        dfeats_s = dfeats_q = dalpha = None
-        grads = [None, None, None]
-    _check(lib().fumi_hip_euclid_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
-                                            _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(alpha, "alpha"), float(grad_scale),
-                                            _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
-                                            _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_euclid_proto_step")
-    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dalpha=dalpha)
+    dev, dims, out = _episode_head_io("euclid_proto_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                                              param=(alpha, (1,), "alpha"))
+    B, S, Qn, N, F = dims
+    grads = _head_grads(dev, need_grad, out, dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q), dalpha=((1,), dalpha))
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_euclid_proto_step(ws.handle, _stream(dev), *lead, _f32(alpha, "alpha"), float(grad_scale), *tail, *grads),
+           "fumi_hip_euclid_proto_step")
+    return out
 
 
 def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
@@ -1672,31 +1682,14 @@ def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, g
     synchronises -- callers that know N pass it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn]
     (first arg-max), logits [B,Qn,N] (None without want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dparams [2] =
     gradients of grad_scale * loss through both solves (written into the tensors given, else into new ones)."""
-    dev = _dev(feats_s)
-    if feats_s.dim() != 3 or feats_q.dim() != 3:
-        raise FumiHipError("ridge_head_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
-    B, S, F = (int(v) for v in feats_s.shape)
-    Qn = int(feats_q.shape[1])
-    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
-    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(params, (2,), "params")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
-    if need_grad:
-        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32) if dfeats_s is None else dfeats_s
-        dfeats_q = torch.empty(B, Qn, F, device=dev, dtype=torch.float32) if dfeats_q is None else dfeats_q
-        dparams = torch.empty(2, device=dev, dtype=torch.float32) if dparams is None else dparams
-        _shape(dfeats_s, (B, S, F), "dfeats_s"); _shape(dfeats_q, (B, Qn, F), "dfeats_q"); _shape(dparams, (2,), "dparams")
-        grads = [_f32(dfeats_s, "dfeats_s"), _f32(dfeats_q, "dfeats_q"), _f32(dparams, "dparams")]
-    else:
-        dfeats_s = dfeats_q = dparams = None
-        grads = [None, None, None]
-    _check(lib().fumi_hip_ridge_head_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
-                                          _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(params, "params"), float(grad_scale),
-                                          _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
-                                          _f32(logits, "logits") if want_logits else None, *grads), "fumi_hip_ridge_head_step")
-    return dict(loss=loss, correct=correct, preds=preds, logits=logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams)
+    dev, dims, out = _episode_head_io("ridge_head_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                                              param=(params, (2,), "params"))
+    B, S, Qn, N, F = dims
+    grads = _head_grads(dev, need_grad, out, dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q), dparams=((2,), dparams))
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_ridge_head_step(ws.handle, _stream(dev), *lead, _f32(params, "params"), float(grad_scale), *tail, *grads),
+           "fumi_hip_ridge_head_step")
+    return out
 
 
 def logreg_set_form(form):
@@ -1712,22 +1705,11 @@ def logreg_head_step(ws, feats_s, y_s, feats_q, y_q, *, steps=100, lr=1.0, momen
     cross-entropy against y_q [B,Qn] over all B * Qn rows.  ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers
     that know N pass it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits
     [B,Qn,N] (None without want_logits).  The fit is not differentiated: there are no gradients."""
-    dev = _dev(feats_s)
-    if feats_s.dim() != 3 or feats_q.dim() != 3:
-        raise FumiHipError("logreg_head_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
-    B, S, F = (int(v) for v in feats_s.shape)
-    Qn = int(feats_q.shape[1])
-    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
-    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
-    _check(lib().fumi_hip_logreg_head_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
-                                           _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), int(steps), float(lr), float(momentum), float(C),
-                                           1 if normalize else 0, _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
-                                           _f32(logits, "logits") if want_logits else None), "fumi_hip_logreg_head_step")
-    return dict(loss=loss, correct=correct, preds=preds, logits=logits)
+    dev, dims, out = _episode_head_io("logreg_head_step", feats_s, y_s, feats_q, y_q, n_way, want_logits)
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_logreg_head_step(ws.handle, _stream(dev), *lead, int(steps), float(lr), float(momentum), float(C),
+                                           1 if normalize else 0, *tail), "fumi_hip_logreg_head_step")
+    return out
 
 
 TRANS_METRICS = {"cosine": 0, "euclid": 1}
@@ -1741,24 +1723,12 @@ def trans_proto_step(ws, feats_s, y_s, feats_q, y_q, scale, *, metric, steps, wa
     reads it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers that know N pass it.  ``steps=0``
     is the forward form of ``cos_proto_step`` / ``euclid_proto_step``.  Returns a dict of GPU tensors: loss [1], correct [1] (count,
     float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without want_logits).  There are no gradients."""
-    dev = _dev(feats_s)
-    if feats_s.dim() != 3 or feats_q.dim() != 3:
-        raise FumiHipError("trans_proto_step: feats_s [B,S,F] and feats_q [B,Qn,F] expected")
-    if metric not in TRANS_METRICS:
-        raise FumiHipError(f"trans_proto_step: metric must be cosine or euclid, got {metric}")
-    B, S, F = (int(v) for v in feats_s.shape)
-    Qn = int(feats_q.shape[1])
-    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
-    _shape(feats_q, (B, Qn, F), "feats_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(scale, (1,), "scale")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
-    logits = torch.empty(B, Qn, N, device=dev, dtype=torch.float32) if want_logits else None
-    _check(lib().fumi_hip_trans_proto_step(ws.handle, _stream(dev), B, S, Qn, N, F, _f32(feats_s, "feats_s"), _i64(y_s, "y_s"),
-                                           _f32(feats_q, "feats_q"), _i64(y_q, "y_q"), _f32(scale, "scale"), TRANS_METRICS[metric],
-                                           int(steps), _f32(loss, "loss"), _f32(correct, "correct"), _i64(preds, "preds"),
-                                           _f32(logits, "logits") if want_logits else None), "fumi_hip_trans_proto_step")
-    return dict(loss=loss, correct=correct, preds=preds, logits=logits)
+    dev, dims, out = _episode_head_io("trans_proto_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                               param=(scale, (1,), "scale"), metric=metric)
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_trans_proto_step(ws.handle, _stream(dev), *lead, _f32(scale, "scale"), TRANS_METRICS[metric], int(steps),
+                                           *tail), "fumi_hip_trans_proto_step")
+    return out
 
 
 def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,

@@ -145,3 +145,8 @@ class RNN(_BiLstmEncoder):
 class RnnHid(_BiLstmEncoder):
     """common.py:110-161: the LSTM's final CELL states c_n of each direction."""
     use_cell = True
+
+
+def _loss_acc(out, y_q, into=None):
+    """[loss, acc] of an episode head's result dict as one GPU tensor of two floats (written into ``into`` when given)."""
+    return torch.cat((out["loss"], out["correct"] / y_q.numel()), out=into)

@@ -36,6 +36,7 @@ from ..optim import clip_log
 from ..utils import utils as utils
 from ..utils.average_meter import AverageMeter
 from ..utils.wandb_compat import wandb
+from .common import _loss_acc
 
 
 class MetaBaseline(nn.Module):
@@ -149,7 +150,7 @@ class MetaBaseline(nn.Module):
         else:
             out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
         encode_bwd(x_s, x_q, out["dfeats_s"], out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
-        torch.cat((out["loss"], out["correct"] / y_q.numel()), out=fg.tail)
+        _loss_acc(out, y_q, into=fg.tail)
         if optimizer is not None:
             optimizer.zero_grad()
         fg.attach()
@@ -167,14 +168,14 @@ class MetaBaseline(nn.Module):
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
         if self.eval_head == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         if self.transductive_steps > 0:
             out = eng.trans_proto_step(f_s, y_s, f_q, y_q, temp, metric="euclid" if self.head == "proto" else "cosine",
                                        steps=self.transductive_steps, n_way=N)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
-        return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+        return _loss_acc(out, y_q)
 
     def evaluate(self, batch, optimizer, scheduler, device, task="train"):
         """(loss, acc) of one episodic meta-batch: ``train`` runs a training step, ``val`` / ``test`` the forward form."""

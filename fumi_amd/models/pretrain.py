@@ -30,6 +30,7 @@ from ..optim import clip_log
 from ..utils import utils as utils
 from ..utils.average_meter import AverageMeter
 from ..utils.wandb_compat import wandb
+from .common import _loss_acc
 
 
 class Pretrain(nn.Module):
@@ -224,20 +225,20 @@ class Pretrain(nn.Module):
                     self._one = torch.ones(1, device=f_s.device, dtype=torch.float32)
                 scale, trans_metric = self._one, "euclid"
             out = eng.trans_proto_step(f_s, y_s, f_q, y_q, scale, metric=trans_metric, steps=self.transductive_steps, n_way=N)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         if self.metric == "cosine":
             if self._tau is None or self._tau.device != f_s.device:
                 self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
             out = eng.cos_proto_step(f_s, y_s, f_q, y_q, self._tau, need_grad=False, n_way=N)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         if self.metric == "ridge":
             if self._ridge is None or self._ridge.device != f_s.device:
                 self._ridge = torch.tensor([math.log(self.ridge_lambda), self.ridge_scale], device=f_s.device, dtype=torch.float32)
             out = eng.ridge_head_step(f_s, y_s, f_q, y_q, self._ridge, need_grad=False, n_way=N)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         if self.metric == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
-            return torch.cat((out["loss"], out["correct"] / y_q.numel()))
+            return _loss_acc(out, y_q)
         protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
         d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]
         loss = F.cross_entropy(-d2.reshape(-1, N), y_q.reshape(-1))

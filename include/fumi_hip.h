@@ -503,6 +503,12 @@ int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, i
         const float* W, const float* b, const float* feats_t, const float* W_t, const float* b_t,
         float kd_temp, float kd_alpha, float ce_weight, float grad_scale,
         float* loss, float* loss_parts, float* correct, float* agree, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* ---- The episode heads (fumi_hip_cos_proto_step ... fumi_hip_trans_proto_step; shared code in csrc/fewshot_head.h) ----
+ * LABELS, for all five: a label outside [0,N) sets FUMI_ST_LABEL_RANGE.  Such a query row adds nothing to the loss, the count or any
+ * gradient while the divisor stays B * Qn; such a support row is left out exactly (of every mean, count, sum and fit) and gets a zero
+ * gradient.  A class without a support row sets FUMI_ST_CLASS_MISSING.  Each entry says below only what is its own.
+ * ORDER, for all five: every sum has a fixed order and there are no floating-point atomics, so two calls on the same inputs give the
+ * same bits; preds is the first arg-max, as torch.max gives it. */
 /* The cosine nearest-centroid head with a learned temperature (csrc/cosproto.hip): the few-shot metric of a
  * pre-trained backbone and the episodic loss of the Meta-Baseline stage, fused.  Per episode b, with norm(x) = x / max(|x|_2, 1e-12)
  * (F.normalize):
@@ -517,11 +523,8 @@ int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, i
  * dc_n / count_n), dtau = sum dz[q,n] cos[q,n].  Where a norm is below the clamp the gradient is the plain d / 1e-12, as autograd gives
  * it; the projection onto the tangent space applies only where the norm is at or above the clamp.
  * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32, three launches (class means; 16-row query tiles; [16 classes x 128 features]
- * blocks of the support gradient plus the final sums).  Every sum has a fixed order and there are no floating-point atomics: two calls
- * on the same inputs give the same bits.
- * A label outside [0,N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
- * stays B * Qn); such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
- * FUMI_ST_CLASS_MISSING and has a zero prototype.
+ * blocks of the support gradient plus the final sums).  ORDER as above.
+ * LABELS as above; a class without a support row has a zero prototype.
  * B >= 1, 1 <= S <= 1024, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
  * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
 int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
@@ -544,11 +547,8 @@ int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, i
  * episode's mean prototype m = (1/N) sum_n c_n:  d2 = |f_q - m|^2 - 2 (f_q . c'_n - m . c'_n) + |c'_n|^2 with c'_n = c_n - m, so an
  * offset common to all features of an episode (post-ReLU features have one) does not cost the distance its digits.
  * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32, three launches (class means, centred; 16-row query tiles; [16 classes x 128
- * features] blocks of the support gradient plus the final sums).  Every sum has a fixed order and there are no floating-point atomics:
- * two calls on the same inputs give the same bits.
- * A label outside [0,N) sets FUMI_ST_LABEL_RANGE: such a query row adds nothing to the loss, the count or any gradient (the divisor
- * stays B * Qn); such a support row is left out of the means and gets a zero gradient.  A class without a support row sets
- * FUMI_ST_CLASS_MISSING and has a zero prototype: its logits are -alpha |f_q|^2.
+ * features] blocks of the support gradient plus the final sums).  ORDER as above.
+ * LABELS as above; a class without a support row has a zero prototype: its logits are -alpha |f_q|^2.
  * B >= 1, 1 <= S <= 1024, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
  * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
 int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
@@ -566,11 +566,9 @@ int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S
  *     dz = grad_scale / (B Qn) (softmax(z) - onehot(y_q)),   dfeats_q = alpha dz W^T,   dW = alpha Fq^T dz,   G = M^-1 (X dW),
  *     dfeats_s = A (dW - X^T G)^T - G W^T,   dparams = (-lam sum G * A,  sum dz * (Fq W)).
  * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32; M is factored once per episode (Cholesky in LDS) and the factor serves both
- * solves.  Four launches in the forward form, six in the training form.  Every sum has a fixed order and there are no floating-point
- * atomics: two calls on the same inputs give the same bits.
- * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss, the count or any gradient (the divisor stays
- * B * Qn).  A support label outside [0,N) sets the same bit and the row is left out exactly: its feature row counts as zero, its rows of
- * Y, A and dfeats_s are zero.  A class without a support row sets FUMI_ST_CLASS_MISSING and has logits 0.  A pivot of the factorisation
+ * solves.  Four launches in the forward form, six in the training form.  ORDER as above.
+ * LABELS as above; a support row left out counts as a zero feature row, its rows of Y, A and dfeats_s are zero; a class without a
+ * support row has logits 0.  A pivot of the factorisation
  * that is not > 0 (a NaN counts) sets FUMI_ST_NOT_POSDEF and is replaced by lam; the call returns and the other episodes are untouched.
  * B >= 1, 1 <= S <= 128, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
  * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
@@ -585,11 +583,10 @@ int fumi_hip_ridge_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
  * (W_t = X~^T A_t, on K~ = X~ X~^T in LDS; exactly the primal iteration), then z = Fq~ W + b.
  * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
  * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).  There are no gradient outputs.
- * fp32; four launches (fit, one workgroup per episode; W^T; 16-row query tiles; the final sums).  Every sum has a fixed order and there
- * are no floating-point atomics: two calls on the same inputs give the same bits, with or without preds and logits.
- * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss or the count (the divisor stays B * Qn).  A
- * support label outside [0,N) sets the same bit and the row is left out exactly: its row and column of K~ and its rows of Y and R are
- * zero and it does not count in n.  A class without a support row sets FUMI_ST_CLASS_MISSING and is fitted like any class.  The fit
+ * fp32; four launches (fit, one workgroup per episode; W^T; 16-row query tiles; the final sums).  ORDER as above, with or
+ * without preds and logits.
+ * LABELS as above; a support row left out has a zero row and column of K~ and zero rows of Y and R and does not count in n; a class
+ * without a support row is fitted like any class.  The fit
  * runs `steps` steps whatever the values are; non-finite features stay inside their episode.
  * B >= 1, 1 <= S <= 128, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048, 1 <= steps <= 10000, lr > 0,
  * 0 <= momentum < 1, C > 0: FUMI_ENOTSUP otherwise; FUMI_EINVAL for a NULL required pointer; both before any launch. */
@@ -610,10 +607,9 @@ int fumi_hip_logreg_set_form(int form);
  * arg-max is the label, preds [B,Qn] that arg-max (optional), logits [B,Qn,N] z(c^steps) (optional).  steps = 0 is the forward form
  * of fumi_hip_cos_proto_step / fumi_hip_euclid_proto_step.  scale is a device pointer.  The iteration runs in the dual on X_all S^T
  * and X_all X_q^T (the f32 MFMA; metric 1 takes the rows relative to the mean step-0 prototype first), one workgroup per episode, two
- * barriers per step.  Fixed-order sums, no floating-point atomics: equal inputs give equal bits.
- * A query label outside [0,N) sets FUMI_ST_LABEL_RANGE: the row adds nothing to the loss or the count (the divisor stays B * Qn) and
- * still takes part in the refinement.  A support label outside [0,N) sets the same bit and the row is left out exactly.  A class
- * without a support row sets FUMI_ST_CLASS_MISSING, starts from a zero prototype and is refined like any class.
+ * barriers per step.  ORDER as above.
+ * LABELS as above; a query row whose label is out of range still takes part in the refinement; a class without a support row starts
+ * from a zero prototype and is refined like any class.
  * B >= 1, S >= 1, Qn >= 1, S + Qn <= 512, Qn * N <= 8192, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048,
  * 0 <= steps <= 100: FUMI_ENOTSUP otherwise; FUMI_EINVAL for a NULL required pointer or a metric other than 0 or 1; both before any
  * launch. */
