@@ -170,6 +170,16 @@ class HipEngine:
         return hip.ridge_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, params, need_grad=need_grad, grad_scale=grad_scale,
                                    want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dparams=dparams, n_way=n_way)
 
+    def svm_head_step(self, feats_s, y_s, feats_q, y_q, scale, C=0.1, eps=1.0, steps=120, bwd_steps=40, need_grad=True, grad_scale=1.0,
+                      want_logits=False, dfeats_s=None, dfeats_q=None, dscale=None, n_way=None):
+        """Fused MetaOptNet-SVM head with the logit scale [1] on the device: mean cross-entropy of scale *
+        query . W with W the multi-class SVM fitted on the support rows by ``steps`` steps of FISTA on its dual, its predictions and the
+        implicit gradients for both feature sets and the scale (``bwd_steps`` steps of conjugate gradients); ``stats`` [B,2] holds the
+        fit's KKT residual and the conjugate gradients' relative residual per episode."""
+        return hip.svm_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, scale, C=C, eps=eps, steps=steps, bwd_steps=bwd_steps,
+                                 need_grad=need_grad, grad_scale=grad_scale, want_logits=want_logits, dfeats_s=dfeats_s,
+                                 dfeats_q=dfeats_q, dscale=dscale, n_way=n_way)
+
     def logreg_head_step(self, feats_s, y_s, feats_q, y_q, steps=100, lr=1.0, momentum=0.9, C=1.0, normalize=True, want_logits=False,
                          n_way=None):
         """Fused logistic-regression head, forward only: ``steps`` steps of heavy-ball descent from zero on the

@@ -45,6 +45,7 @@ SYMBOLS = [
     "fumi_hip_cos_proto_step", "fumi_hip_ridge_head_step", "fumi_hip_logreg_head_step", "fumi_hip_logreg_set_form",
     "fumi_hip_euclid_proto_step", "fumi_hip_trans_proto_step",
     "fumi_hip_cls_head_step_distill",
+    "fumi_hip_svm_head_step", "fumi_hip_svm_set_form", "fumi_hip_svm_get_fit",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -244,6 +245,10 @@ def lib():
                                                 + [c_void_p] * 4)
         L.fumi_hip_logreg_set_form.argtypes = [c_int]
         L.fumi_hip_trans_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_int] * 2 + [c_void_p] * 4
+        L.fumi_hip_svm_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] * 2 + [c_int] * 2 + [c_float]
+                                             + [c_void_p] * 8)
+        L.fumi_hip_svm_set_form.argtypes = [c_int]
+        L.fumi_hip_svm_get_fit.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2
         _lib = L
     return _lib
 
@@ -1710,6 +1715,43 @@ def logreg_head_step(ws, feats_s, y_s, feats_q, y_q, *, steps=100, lr=1.0, momen
     _check(lib().fumi_hip_logreg_head_step(ws.handle, _stream(dev), *lead, int(steps), float(lr), float(momentum), float(C),
                                            1 if normalize else 0, *tail), "fumi_hip_logreg_head_step")
     return out
+
+
+def svm_set_form(form):
+    """The form of the SVM head's K' alpha products in the calls that follow: "valu", "mfma" or None (chosen per shape)."""
+    _check(lib().fumi_hip_svm_set_form({None: -1, "valu": 0, "mfma": 1}[form]), "fumi_hip_svm_set_form")
+
+
+def svm_head_step(ws, feats_s, y_s, feats_q, y_q, scale, *, C=0.1, eps=1.0, steps=120, bwd_steps=40, need_grad=True, grad_scale=1.0,
+                  want_logits=False, dfeats_s=None, dfeats_q=None, dscale=None, n_way=None):
+    """The fused MetaOptNet-SVM head (csrc/svmhead.hip): per episode the Crammer-Singer dual on K' = X X^T + eps I of the support rows
+    X = feats_s [B,S,F] (alpha <= C onehot(y_s), rows summing to zero) fitted by ``steps`` steps of FISTA in LDS, logits
+    scale * feats_q [B,Qn,F] X^T alpha, mean softmax cross-entropy against y_q [B,Qn] over all B * Qn rows.  ``scale`` is a GPU tensor
+    [1] (the kernels read it on the device); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises -- callers that know N pass
+    it.  Returns a dict of GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None
+    without want_logits), stats [B,2] (the fit's KKT residual and the relative residual of the backward's conjugate gradients, 0
+    without need_grad) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F], dscale [1] = the implicit gradients of grad_scale *
+    loss at the fitted point, ``bwd_steps`` steps of conjugate gradients (written into the tensors given, else into new ones)."""
+    dev, dims, out = _episode_head_io("svm_head_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                                              param=(scale, (1,), "scale"))
+    B, S, Qn, N, F = dims
+    grads = _head_grads(dev, need_grad, out, dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q), dscale=((1,), dscale))
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    out["stats"] = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    _check(lib().fumi_hip_svm_head_step(ws.handle, _stream(dev), *lead, _f32(scale, "scale"), float(C), float(eps), int(steps),
+                                        int(bwd_steps), float(grad_scale), *tail, *grads, _f32(out["stats"], "stats")),
+           "fumi_hip_svm_head_step")
+    return out
+
+
+def svm_get_fit(ws, B, S, N):
+    """(alpha [B,S,N] float32, bound mask [B,S,N] bool) of the ``svm_head_step`` call that was the last call on ``ws``.  For tests."""
+    dev = ws.device
+    alpha = torch.empty(B, S, N, device=dev, dtype=torch.float32)
+    mask = torch.empty(B, S, N, device=dev, dtype=torch.int32)
+    _check(lib().fumi_hip_svm_get_fit(ws.handle, _stream(dev), int(B), int(S), int(N), ctypes.c_void_p(alpha.data_ptr()),
+                                      ctypes.c_void_p(mask.data_ptr())), "fumi_hip_svm_get_fit")
+    return alpha, mask != 0
 
 
 TRANS_METRICS = {"cosine": 0, "euclid": 1}

@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.cli_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -191,7 +191,7 @@ def check_supported(args):
     if not temp > 0.0:
         raise ValueError(f"--metric_temp {temp} must be positive")
     head, r_lam, r_scale = (getattr(args, k, d) for k, d in (("fewshot_head", "cosine"), ("ridge_lambda", 50.0), ("ridge_scale", 1.0)))
-    if head in ("ridge", "proto") and family != "metabaseline":
+    if head in ("ridge", "proto", "svm") and family != "metabaseline":
         raise ValueError(f"--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: {head} needs --model metabaseline")
     if not r_lam > 0.0:
         raise ValueError(f"--ridge_lambda {r_lam} must be positive")
@@ -225,6 +225,21 @@ def check_supported(args):
                              f"cross-entropy is at most 1, so the objective's is at most 1 + wd with wd = 1 / (--logreg_C * S) = {wd:.4g}, "
                              f"and the heavy-ball iteration is stable only for lr * (1 + wd) < 2 * (1 + --logreg_momentum) = "
                              f"{2.0 * (1.0 + lg['momentum']):.4g}")
+    sv = utils.svm_config(args)                 # (raises ValueError for a non-positive --svm_C / --svm_eps / --svm_scale, a step count outside the kernel's limits)
+    if head != "svm" and metric != "svm":
+        moved = utils.svm_flags_moved(args)
+        if moved:
+            raise ValueError(f"{', '.join(moved)} set the MetaOptNet-SVM head: they need --fewshot_head svm or --pretrain_metric svm")
+    else:
+        if head != "svm" and sv["bwd_steps"] != 40:
+            raise ValueError("--svm_bwd_steps counts the conjugate-gradient steps of the SVM head's backward: it needs --fewshot_head svm "
+                             "(--pretrain_metric svm runs the forward form only)")
+        S = args.num_ways * args.num_shots
+        if S > 128:
+            raise NotImplementedError(f"the SVM head fits on the [S, S] Gram matrix of an episode's support set in LDS: S = --num_ways * "
+                                      f"--num_shots = {S} must not exceed 128")
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the SVM head takes 2 to 64 classes, got --num_ways {args.num_ways}")
     t_steps = getattr(args, "transductive_steps", 0)
     if not 0 <= t_steps <= 100:
         raise ValueError(f"--transductive_steps {t_steps} must lie in [0, 100]")
@@ -232,9 +247,9 @@ def check_supported(args):
         if family not in ("metabaseline", "pretrain"):
             raise ValueError("--transductive_steps refines the class prototypes of a nearest-centroid few-shot evaluation: it needs "
                              "--model metabaseline or pretrain")
-        if head == "ridge" or e_head == "logreg" or metric in ("ridge", "logreg"):
+        if head in ("ridge", "svm") or e_head == "logreg" or metric in ("ridge", "logreg", "svm"):
             raise ValueError("--transductive_steps refines class prototypes: it goes with the cosine and the Euclidean metric, not with "
-                             "--fewshot_head ridge, --eval_head logreg or --pretrain_metric ridge | logreg")
+                             "--fewshot_head ridge | svm, --eval_head logreg or --pretrain_metric ridge | logreg | svm")
         # the limits of fumi_hip_trans_proto_step (csrc/transproto.hip): w and the query rows of G of an episode are held in LDS
         S, Qn = args.num_ways * args.num_shots, args.num_ways * args.num_shots_test
         if not 2 <= args.num_ways <= 64:

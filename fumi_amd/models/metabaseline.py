@@ -16,6 +16,12 @@ logits ``-proto_scale * |query - class mean|^2``.  ``proto_scale`` [1] is a para
 Euclidean variant of the Meta-Baseline stage) or, with ``proto_scale_fixed``, a persistent buffer that no optimizer sees: plain ProtoNet
 at the default 1.0.  ``state_dict`` holds it under the same name either way.
 
+``head="svm"`` (``--fewshot_head svm``) is MetaOptNet's multi-class SVM base learner: ``svm_head_step``
+(csrc/svmhead.hip) fits the Crammer-Singer dual of each episode by FISTA and differentiates it implicitly at the fitted point.  One
+parameter ``svm = [logit scale]`` in ``temp``'s place; ``C``, ``eps`` and the two step counts are fixed and always given (``svm`` dict,
+as ``utils.svm_config`` returns it: the head has no silent defaults).  The largest KKT
+residual and conjugate-gradient residual of the last training step are kept on the device (``svm_stats``) and logged at each validation.
+
 ``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
 head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
 not a parameter: ``state_dict`` is the same either way.
@@ -41,10 +47,16 @@ from .common import _loss_acc
 
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
-                 ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0):
+                 ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0,
+                 svm=None):
         super().__init__()
-        if head not in ("cosine", "ridge", "proto"):
-            raise ValueError(f"the few-shot head must be cosine, ridge or proto, got {head}")
+        if head not in ("cosine", "ridge", "proto", "svm"):
+            raise ValueError(f"the few-shot head must be cosine, ridge, proto or svm, got {head}")
+        if head == "svm" and svm is None:
+            raise ValueError("the SVM head takes its hyper-parameters explicitly: svm=dict(C, eps, scale, steps, bwd_steps) "
+                             "(utils.svm_config fills in the defaults of the flags)")
+        self.svm_cfg = utils.svm_config(svm)   # C, eps, scale (initial) and the step counts of the SVM head (section 39)
+        self.svm_stats = None                  # [2] on the device: max KKT residual, max CG residual of the last training step
         if eval_head not in ("train", "logreg"):
             raise ValueError(f"the evaluation head must be train or logreg, got {eval_head}")
         self.eval_head = eval_head             # validation / test classifier: the training head, or the logistic-regression head
@@ -59,7 +71,7 @@ class MetaBaseline(nn.Module):
             raise ValueError(f"a fixed scale belongs to the prototypical head, got head {head}")
         if not 0 <= int(transductive_steps) <= 100:
             raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
-        if int(transductive_steps) > 0 and (head == "ridge" or eval_head == "logreg"):
+        if int(transductive_steps) > 0 and (head in ("ridge", "svm") or eval_head == "logreg"):
             raise ValueError("the transductive refinement moves class prototypes: it goes with the cosine and the prototypical head, "
                              f"got head {head}, evaluation head {eval_head}")
         self.transductive_steps = int(transductive_steps)   # soft k-means steps of validation / test episodes (0: inductive)
@@ -77,6 +89,8 @@ class MetaBaseline(nn.Module):
         self.num_ways = num_ways               # N of the episodes (None: read from the support labels, which synchronises)
         if head == "ridge":
             self.ridge = nn.Parameter(torch.tensor([math.log(float(ridge_lambda)), float(ridge_scale)]))
+        elif head == "svm":
+            self.svm = nn.Parameter(torch.tensor([self.svm_cfg["scale"]]))
         elif head == "proto" and self.proto_scale_fixed:
             self.register_buffer("proto_scale", torch.tensor([float(proto_scale)]))
         elif head == "proto":
@@ -91,10 +105,12 @@ class MetaBaseline(nn.Module):
         return self.conv
 
     def head_param(self):
-        """The head's own parameter: ``temp`` [1] of the cosine head, ``ridge`` [2] of the ridge head, ``proto_scale`` [1] of the
-        prototypical head -- None where that scale is fixed (a buffer: the head has no parameter then)."""
+        """The head's own parameter: ``temp`` [1] of the cosine head, ``ridge`` [2] of the ridge head, ``svm`` [1] of the SVM head,
+        ``proto_scale`` [1] of the prototypical head -- None where that scale is fixed (a buffer: the head has no parameter then)."""
         if self.head == "proto":
             return None if self.proto_scale_fixed else self.proto_scale
+        if self.head == "svm":
+            return self.svm
         return self.ridge if self.head == "ridge" else self.temp
 
     def _step_params(self, need_grad):
@@ -120,6 +136,9 @@ class MetaBaseline(nn.Module):
     def _apply(self, fn, recurse=True):
         self._pcache = None
         return super()._apply(fn, recurse)
+
+    def _svm_kw(self):
+        return {k: self.svm_cfg[k] for k in ("C", "eps", "steps", "bwd_steps")}
 
     def _encoders(self, eng):
         return ((eng.conv4_encode, eng.conv4_encode_bwd) if self.backbone == "conv4" else
@@ -147,6 +166,9 @@ class MetaBaseline(nn.Module):
                                         dalpha=self._dscale if self.proto_scale_fixed else g_t[0], n_way=N)
         elif self.head == "ridge":
             out = eng.ridge_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dparams=g_t[0], n_way=N)
+        elif self.head == "svm":
+            out = eng.svm_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dscale=g_t[0], n_way=N, **self._svm_kw())
+            self.svm_stats = out["stats"].amax(dim=0)
         else:
             out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
         encode_bwd(x_s, x_q, out["dfeats_s"], out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
@@ -173,6 +195,9 @@ class MetaBaseline(nn.Module):
             out = eng.trans_proto_step(f_s, y_s, f_q, y_q, temp, metric="euclid" if self.head == "proto" else "cosine",
                                        steps=self.transductive_steps, n_way=N)
             return _loss_acc(out, y_q)
+        if self.head == "svm":
+            out = eng.svm_head_step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N, **self._svm_kw())
+            return _loss_acc(out, y_q)
         step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return _loss_acc(out, y_q)
@@ -193,11 +218,19 @@ class MetaBaseline(nn.Module):
 
 
 def head_log(model):
-    """What a validation logs of the head's own parameter: ``temp``, ``ridge_lambda`` and ``ridge_scale``, or ``proto_scale``; with a
-    transductive evaluation also its number of steps."""
+    """What a validation logs of the head's own parameter: ``temp``, ``ridge_lambda`` and ``ridge_scale``, ``proto_scale`` or
+    ``svm_scale``; with a transductive evaluation also its number of steps; for the SVM head also ``train/svm_kkt`` and
+    ``train/svm_cg_res``, the largest KKT residual of the fit and the largest relative residual of the backward's conjugate gradients
+    over the meta-batch of the last training step (the implicit gradient is only as good as the fit)."""
     trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
     if model.head == "proto":
         return {"proto_scale": float(model.proto_scale.detach()), **trans}
+    if model.head == "svm":
+        log = {"svm_scale": float(model.svm.detach())}
+        if model.svm_stats is not None:
+            kkt, cg = model.svm_stats.tolist()
+            log.update({"train/svm_kkt": kkt, "train/svm_cg_res": cg})
+        return log
     if model.head == "ridge":
         rho, scale = model.ridge.detach().tolist()
         return {"ridge_lambda": math.exp(rho), "ridge_scale": scale}

@@ -36,17 +36,19 @@ from .common import _loss_acc
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
                  metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0,
-                 distill=None):
+                 distill=None, svm=None):
         super().__init__()
+        self.svm_cfg = utils.svm_config(svm)               # fixed hyper-parameters of the SVM metric (section 39)
+        self._svm = None
         self.distill = distill_config(distill)             # None, or the weights of the distillation loss (section 37)
         self.last_out = None                               # the head's output dict of the last training step
         object.__setattr__(self, "_teacher", None)         # (conv module, [W_t, b_t]) once loaded: frozen, outside parameters() / state_dict()
         self._tcache = None
-        if metric not in ("euclidean", "cosine", "ridge", "logreg"):
-            raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge or logreg, got {metric}")
+        if metric not in ("euclidean", "cosine", "ridge", "logreg", "svm"):
+            raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge, logreg or svm, got {metric}")
         if not 0 <= int(transductive_steps) <= 100:
             raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
-        if int(transductive_steps) > 0 and metric in ("ridge", "logreg"):
+        if int(transductive_steps) > 0 and metric in ("ridge", "logreg", "svm"):
             raise ValueError(f"the transductive refinement moves class prototypes: it goes with the euclidean and the cosine metric, got {metric}")
         self.transductive_steps = int(transductive_steps)   # soft k-means steps of the few-shot evaluation (section 36; 0: inductive)
         self._one = None
@@ -204,7 +206,8 @@ class Pretrain(nn.Module):
         features (proto_reduce), squared Euclidean distances, softmax cross-entropy on their negatives (prototypical_loss), arg-min.
         With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature; with
         ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale; with
-        ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters.
+        ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters; with
+        ``metric == "svm"``: one forward call of the MetaOptNet-SVM head (svm_head_step) at the fixed C, eps, scale and step count.
         With ``transductive_steps > 0``: one call of the transductive head (trans_proto_step), cosine at the fixed temperature or
         squared Euclidean at scale 1."""
         eng = _engine.get_engine()
@@ -238,6 +241,12 @@ class Pretrain(nn.Module):
             return _loss_acc(out, y_q)
         if self.metric == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
+            return _loss_acc(out, y_q)
+        if self.metric == "svm":
+            if self._svm is None or self._svm.device != f_s.device:
+                self._svm = torch.tensor([self.svm_cfg["scale"]], device=f_s.device, dtype=torch.float32)
+            c = self.svm_cfg
+            out = eng.svm_head_step(f_s, y_s, f_q, y_q, self._svm, C=c["C"], eps=c["eps"], steps=c["steps"], need_grad=False, n_way=N)
             return _loss_acc(out, y_q)
         protos = eng.proto_reduce(f_s, y_s, N)                                       # [B, N, F]
         d2 = ((f_q[:, :, None, :] - protos[:, None, :, :]) ** 2).sum(-1)              # [B, Qn, N]

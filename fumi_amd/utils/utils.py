@@ -79,6 +79,13 @@ _DISTILL_FLAGS = [          # born-again distillation of --model pretrain (DESIG
     ("--distill_ce_weight", dict(type=float, default=0.5, help="[--distill_checkpoint] weight of the cross-entropy term (not negative)")),
 ]
 _FLAGS = _REFERENCE_FLAGS + _DISTILL_FLAGS
+_SVM_FLAGS = [              # the MetaOptNet-SVM head; a list of its own that cli_parser() appends to parser()'s
+    ("--svm_C", dict(type=float, default=0.1, help="[--fewshot_head svm / --pretrain_metric svm] the regularisation parameter C of the multi-class SVM: alpha_ik <= C onehot(y)_ik (positive)")),
+    ("--svm_eps", dict(type=float, default=1.0, help="[--fewshot_head svm / --pretrain_metric svm] the weight eps of the identity added to the support Gram matrix (positive)")),
+    ("--svm_scale", dict(type=float, default=1.0, help="[--fewshot_head svm] initial logit scale (learned); [--pretrain_metric svm] its fixed value (positive)")),
+    ("--svm_steps", dict(type=int, default=120, help="[--fewshot_head svm / --pretrain_metric svm] FISTA steps of the per-episode fit (1 to 10000)")),
+    ("--svm_bwd_steps", dict(type=int, default=40, help="[--fewshot_head svm] conjugate-gradient steps of the implicit backward (1 to 1000)")),
+]
 _ENGINE_FLAGS = [     # additive, not in the reference
     ("--synthetic_classes", dict(type=int, default=64, help="[synthetic dataset] number of classes per split")),
     ("--synthetic_vocab", dict(type=int, default=2000, help="[synthetic dataset] vocabulary size for token text")),
@@ -100,10 +107,10 @@ _ENGINE_FLAGS = [     # additive, not in the reference
 ]
 _METRIC_FLAGS = [           # the cosine nearest-centroid metric; a list of its own, between the two others
     ("--metric_temp", dict(type=float, default=10.0, help="[--model metabaseline] initial temperature of the cosine classifier; [--model pretrain --pretrain_metric cosine] its fixed temperature (positive)")),
-    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge", "logreg"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, the ridge-regression head at --ridge_lambda / --ridge_scale, or the logistic-regression head at --logreg_steps / --logreg_lr / --logreg_momentum / --logreg_C")),
+    ("--pretrain_metric", dict(type=str, choices=["euclidean", "cosine", "ridge", "logreg", "svm"], default="euclidean", help="[--model pretrain] few-shot validation / test metric: squared Euclidean distance to the class means, their cosine at --metric_temp, the ridge-regression head at --ridge_lambda / --ridge_scale, the logistic-regression head at --logreg_steps / --logreg_lr / --logreg_momentum / --logreg_C, or the SVM head at --svm_C / --svm_eps / --svm_scale / --svm_steps")),
 ]
 _RIDGE_FLAGS = [            # the ridge-regression head; a list of its own, between _FLAGS and _ENGINE_FLAGS
-    ("--fewshot_head", dict(type=str, choices=["cosine", "ridge", "proto"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, closed-form ridge regression on the support features with a learned ridge weight and logit scale, or Prototypical Networks (squared Euclidean distance to the class means at --proto_scale)")),
+    ("--fewshot_head", dict(type=str, choices=["cosine", "ridge", "proto"], default="cosine", help="[--model metabaseline] the episodic classifier: cosine nearest-centroid with a learned temperature, closed-form ridge regression on the support features with a learned ridge weight and logit scale, or Prototypical Networks (squared Euclidean distance to the class means at --proto_scale); the command line (cli_parser) also takes svm: MetaOptNet's multi-class SVM on the support features with a learned logit scale and an implicit gradient (--svm_*)")),
     ("--ridge_lambda", dict(type=float, default=50.0, help="[--fewshot_head ridge] initial ridge weight lambda (learned as its logarithm); [--pretrain_metric ridge] its fixed value (positive)")),
     ("--ridge_scale", dict(type=float, default=1.0, help="[--fewshot_head ridge] initial logit scale (learned); [--pretrain_metric ridge] its fixed value (positive)")),
     # (transductive inference, DESIGN.md section 36: appended here, the one list whose content no caller depends on)
@@ -136,6 +143,19 @@ def parser():
     return p
 
 
+def cli_parser():
+    """What the command line takes (``main.parse_args``): ``parser()``, the choice ``svm`` of --fewshot_head, and after every flag of
+    ``parser()`` the --svm_* flags.  ``parser()`` itself keeps the flag sequence and the choices the earlier heads were written
+    against."""
+    p = parser()
+    for act in p._actions:
+        if act.dest == "fewshot_head":
+            act.choices = list(act.choices) + ["svm"]
+    for flag, kw in _SVM_FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
 def logreg_config(cfg=None):
     """The keyword arguments of ``logreg_head_step`` from a dict, an argparse namespace (--logreg_*) or None (the defaults), checked
     against the kernel's limits."""
@@ -151,6 +171,29 @@ def logreg_config(cfg=None):
     if not c["C"] > 0.0:
         raise ValueError(f"--logreg_C {c['C']} must be positive")
     return c
+
+
+_SVM_DEFAULTS = dict(C=0.1, eps=1.0, scale=1.0, steps=120, bwd_steps=40)
+
+
+def svm_config(cfg=None):
+    """C, eps, scale and the two step counts of the SVM head from a dict, an argparse namespace (--svm_*) or None (the defaults),
+    checked against the kernel's limits."""
+    get = cfg.get if isinstance(cfg, dict) else (lambda k, dflt: getattr(cfg, "svm_" + k, dflt))
+    c = {k: type(v)(get(k, v)) for k, v in _SVM_DEFAULTS.items()}
+    for k in ("C", "eps", "scale"):
+        if not c[k] > 0.0:
+            raise ValueError(f"--svm_{k} {c[k]} must be positive")
+    if not 1 <= c["steps"] <= 10000:
+        raise ValueError(f"--svm_steps {c['steps']} must lie in [1, 10000]")
+    if not 1 <= c["bwd_steps"] <= 1000:
+        raise ValueError(f"--svm_bwd_steps {c['bwd_steps']} must lie in [1, 1000]")
+    return c
+
+
+def svm_flags_moved(args):
+    """The --svm_* flags that differ from their defaults (they belong to --fewshot_head svm / --pretrain_metric svm)."""
+    return ["--svm_" + k for k, v in _SVM_DEFAULTS.items() if getattr(args, "svm_" + k, v) != v]
 
 
 def init_model(args, dictionary, watch=True):
@@ -176,6 +219,7 @@ def init_model(args, dictionary, watch=True):
                                   metric=getattr(args, "pretrain_metric", "euclidean"), metric_temp=getattr(args, "metric_temp", 10.0),
                                   ridge_lambda=getattr(args, "ridge_lambda", 50.0), ridge_scale=getattr(args, "ridge_scale", 1.0),
                                   logreg=logreg_config(args) if getattr(args, "pretrain_metric", "euclidean") == "logreg" else None,
+                                  svm=svm_config(args) if getattr(args, "pretrain_metric", "euclidean") == "svm" else None,
                                   transductive_steps=getattr(args, "transductive_steps", 0),
                                   distill=(dict(temp=getattr(args, "distill_temp", 4.0), alpha=getattr(args, "distill_alpha", 0.5),
                                                 ce_weight=getattr(args, "distill_ce_weight", 0.5))
@@ -189,7 +233,8 @@ def init_model(args, dictionary, watch=True):
                                           logreg=logreg_config(args) if getattr(args, "eval_head", "train") == "logreg" else None,
                                           proto_scale=getattr(args, "proto_scale", 1.0),
                                           proto_scale_fixed=getattr(args, "proto_scale_fixed", False),
-                                          transductive_steps=getattr(args, "transductive_steps", 0))
+                                          transductive_steps=getattr(args, "transductive_steps", 0),
+                                          svm=svm_config(args) if getattr(args, "fewshot_head", "cosine") == "svm" else None)
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

@@ -598,6 +598,44 @@ int fumi_hip_logreg_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S,
  * float64 definition; each gives the same bits from call to call, the two need not agree in the last bits.  FUMI_EINVAL for any
  * other value.  For tests and tools/bench_logreg_head.py. */
 int fumi_hip_logreg_set_form(int form);
+/* The MetaOptNet-SVM few-shot head with an implicit backward (csrc/svmhead.hip): the multi-class SVM base
+ * learner of Lee et al. 2019, in the slot of fumi_hip_ridge_head_step.  scale [1] is read from DEVICE memory (a parameter the
+ * optimizer updates); C and eps are fixed.  Per episode b, with X = feats_s[b] [S,F], Y = onehot(y_s[b]) [S,N], Fq = feats_q[b]
+ * [Qn,F], K' = X X^T + eps I:
+ *     alpha = argmin 1/2 tr(alpha^T K' alpha) - <alpha, Y>   subject to   alpha_ik <= C Y_ik,   sum_k alpha_ik = 0 for every i,
+ *     W = X^T alpha [F,N],   z = scale Fq W,
+ * fitted by `steps` steps of FISTA from zero at the step 1 / max_i sum_j |K'_ij| with the momentum sequence
+ * t' = (1 + sqrt(1 + 4 t^2)) / 2; the projection on the constraints is exact (from the breakpoints of each row, no tolerance).
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, preds [B,Qn] = first arg-max of z (may be
+ * NULL), correct [1] = number of rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dscale [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given
+ * (training form) or all three NULL (forward form: loss, correct, preds and logits are bit-identical to the training form's).  The
+ * gradient is the implicit one at the fitted point, not an unrolled one: with `bound` the entries the last projection clamped
+ * (v_k - tau >= C Y_ik in the kernel's arithmetic), P the map that zeroes the bound entries and takes from every row the mean of its
+ * free entries (a row with fewer than two free entries becomes zero), dz = grad_scale / (B Qn) (softmax(z) - onehot(y_q)):
+ *     dW = scale Fq^T dz,   p: P K' P p = P (X dW)   (`bwd_steps` steps of conjugate gradients from zero, ended early when r.r <= 1e-12 r0.r0),
+ *     dfeats_s = alpha (dW - X^T p)^T - p W^T,   dfeats_q = scale dz W^T,   dscale = sum dz * (Fq W).
+ * stats [B,2] (may be NULL) = per episode the KKT residual max |alpha - proj(alpha - (K' alpha - Y))| of the fit and the relative
+ * residual sqrt(r.r / r0.r0) the conjugate gradients ended at (0 in the forward form): the gradient is only as good as the fit.
+ * fp32; K' alpha on v_mfma_f32_16x16x4_f32 or in a VALU loop (fumi_hip_svm_set_form), K' and the iterates in LDS, one workgroup per
+ * episode for the fit and for the conjugate gradients.  Four launches in the forward form, six in the training form.  ORDER as above.
+ * LABELS as above; a support row left out counts as a zero feature row, has alpha_i = 0 and a zero row of dfeats_s; a class without
+ * a support row is fitted like any class.  The fit runs `steps` steps whatever the values are.
+ * B >= 1, 1 <= S <= 128, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 4 == 0, 4 <= F <= 2048, 1 <= steps <= 10000,
+ * 1 <= bwd_steps <= 1000, C > 0, eps > 0, no NULL required pointer, all or none of the three gradient pointers: FUMI_EINVAL
+ * otherwise, before any launch. */
+int fumi_hip_svm_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* scale, float C, float eps,
+        int steps, int bwd_steps, float grad_scale, float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s,
+        float* dfeats_q, float* dscale, float* stats);
+/* The form of the products K' Zt and K' d [S,S] x [S,N] of the fit and of the conjugate gradients in the calls that follow,
+ * process-wide: 0 the VALU loop, 1 the f32 MFMA, -1 (the default) the faster of the two as measured for the shape.  Both forms are
+ * held to the same float64 definition; each gives the same bits from call to call, the two need not agree in the last bits.
+ * FUMI_EINVAL for any other value.  For tests and tools/bench_svm_head.py. */
+int fumi_hip_svm_set_form(int form);
+/* alpha [B,S,N] (float) and the bound mask [B,S,N] (int32, 1 = bound) of the fumi_hip_svm_head_step call that was the last call on
+ * this workspace, copied from the workspace on `stream` into device memory.  B, S, N are that call's.  For tests. */
+int fumi_hip_svm_get_fit(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int N, float* alpha, int32_t* mask);
 /* Transductive prototype refinement, forward only (csrc/transproto.hip): per episode, from the class sums s_n and
  * counts k_n of feats_s [B,S,F] by y_s [B,S] and c^0_n = s_n / max(k_n, 1), `steps` steps of soft k-means on the query rows feats_q
  * [B,Qn,F],
