@@ -519,11 +519,10 @@ static int am3_step_impl(int text_form, float* tx_out, fumi_ws_t* ws, fumi_strea
         float dropout_p, uint64_t seed,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
-        float* stats, float* dx_s, float* dx_q) {
+        float* stats, float* dx_s, float* dx_q, float* g_text) {
     const bool tf = text_form != 0;
     if (!ws || !x_s || !y_s || !x_q || !y_q || !w || !loss || !preds_q || !lamda_s || !correct) return FUMI_EINVAL;
     if (tf ? (text_form == 2) != (text_s == nullptr) || (!text_s && !tx_out) : !text_s) return FUMI_EINVAL;
-    if (tf && ws->text_grad) { ws->text_grad = nullptr; return FUMI_EINVAL; }       // no text adjoint exists in this form: disarm, refuse
     if (tf) Dt = P;
     if (B < 1 || N < 1 || S < 1 || Qn < 1 || D < 1 || Dt < 1 || Ht < 1 || P < 1 || lamda_fixed < -1 || lamda_fixed > 1) return FUMI_EINVAL;
     for (int i = 0; i < 10; ++i) {
@@ -774,9 +773,8 @@ static int am3_step_impl(int text_form, float* tx_out, fumi_ws_t* ws, fumi_strea
             cj.add(t1b, (int)Rs, Ht, Ht, g_w[3]);
         }
         if ((rc = wgrad(Ht, Dt, t1b, Ht, text_s, Dt, g_w[2]))) return rc;                  // gG0 = t1bar^T text (800 x 768: 128-row slabs)
-        if (float* tg = ws->text_grad) {                  // armed by fumi_hip_want_text_grad: d loss / d text_s = t1bar G0  [B*S,Dt]
-            ws->text_grad = nullptr;                      // (t1bar carries grad_scale and the dropout scale already)
-            g = gemm_args((int)Rs, Dt, Ht, t1b, Ht, G0, Dt, tg, Dt);
+        if (g_text) {                                     // d loss / d text_s = t1bar G0  [B*S,Dt]
+            g = gemm_args((int)Rs, Dt, Ht, t1b, Ht, G0, Dt, g_text, Dt);      // (t1bar carries grad_scale and the dropout scale already)
             if ((rc = launch_gemm(st, g, 0, 1))) return rc;
         }
     }
@@ -804,9 +802,9 @@ extern "C" int fumi_hip_am3_step(fumi_ws_t* ws, fumi_stream_t stream,
         float dropout_p, uint64_t seed,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
-        float* stats) {
+        float* stats, float* g_text) {
     return am3_step_impl(0, nullptr, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
-                         text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr);
+                         text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr, g_text);
 }
 
 extern "C" int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
@@ -814,10 +812,10 @@ extern "C" int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
         float dropout_p, uint64_t seed,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
-        float* stats, float* dx_s, float* dx_q) {
+        float* stats, float* dx_s, float* dx_q, float* g_text) {
     if (need_grad && (!dx_s || !dx_q)) return FUMI_EINVAL;
     return am3_step_impl(0, nullptr, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed, x_s, y_s, x_q, y_q,
-                         text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q);
+                         text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q, g_text);
 }
 
 // The text-rows forms (text_encoder = 'rand'): text_s [B*S,P] or NULL (drawn into tx_out); Dt is not used.
@@ -828,7 +826,7 @@ extern "C" int fumi_hip_am3_step_tx(fumi_ws_t* ws, fumi_stream_t stream,
         const float* const* w, float* loss, int64_t* preds_q, float* lamda_s, float* correct, float* const* g_w,
         float* stats, float* tx_out) {
     return am3_step_impl(text_s ? 1 : 2, tx_out, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed,
-                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr);
+                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, nullptr, nullptr, nullptr);
 }
 
 extern "C" int fumi_hip_am3_step_tx_dx(fumi_ws_t* ws, fumi_stream_t stream,
@@ -839,7 +837,7 @@ extern "C" int fumi_hip_am3_step_tx_dx(fumi_ws_t* ws, fumi_stream_t stream,
         float* stats, float* tx_out, float* dx_s, float* dx_q) {
     if (need_grad && (!dx_s || !dx_q)) return FUMI_EINVAL;
     return am3_step_impl(text_s ? 1 : 2, tx_out, ws, stream, B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad, grad_scale, dropout_p, seed,
-                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q);
+                         x_s, y_s, x_q, y_q, text_s, w, loss, preds_q, lamda_s, correct, g_w, stats, dx_s, dx_q, nullptr);
 }
 
 extern "C" int fumi_hip_am3_step_plan(int* plan, int n) {

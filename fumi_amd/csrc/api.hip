@@ -103,7 +103,7 @@ int fumi_hip_workspace_create(int device, size_t bytes_hint, fumi_ws_t** out) {
     if (device < 0 || device >= ndev) return FUMI_EINVAL;
     HIP_TRY(hipSetDevice(device));
     fumi_ws* ws = new fumi_ws();
-    ws->device = device; ws->base = nullptr; ws->cap = 0; ws->off = 0; ws->status = nullptr; ws->status_host = nullptr; ws->hcnt = nullptr; ws->acnt = nullptr; ws->w0p = nullptr; ws->w0p_cap = 0; ws->side_buf = nullptr; ws->side_cap = 0; ws->clip_parts = nullptr; ws->pub_src = nullptr; ws->pub_dst = nullptr; ws->pub_n = 0; ws->pub_seq = 0; ws->adam = nullptr; ws->glove = nullptr; ws->text_grad = nullptr;
+    ws->device = device; ws->base = nullptr; ws->cap = 0; ws->off = 0; ws->status = nullptr; ws->status_host = nullptr; ws->hcnt = nullptr; ws->acnt = nullptr; ws->w0p = nullptr; ws->w0p_cap = 0; ws->side_buf = nullptr; ws->side_cap = 0; ws->clip_parts = nullptr; ws->pub_src = nullptr; ws->pub_dst = nullptr; ws->pub_n = 0; ws->pub_seq = 0; ws->adam = nullptr; ws->glove = nullptr;
     ws->profiling = 0; ws->prof_every = 1; memset(ws->prof_seen, 0, sizeof(ws->prof_seen)); ws->recs = new std::vector<ProfRec>(); ws->pool = new std::vector<hipEvent_t>();
     ws->side = nullptr; ws->lane = nullptr;
     for (int i = 0; i < 3; ++i) { ws->lanes[i] = nullptr; ws->lane_ev[i] = nullptr; }
@@ -225,7 +225,7 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi, const XRows* rows) {
+        float* const* g_theta, float* const* g_phi, float* g_cls_text, const XRows* rows) {
     if (!ws || !hid || !theta || !phi || !y_s || !y_q || !logits_q || !preds_q || !loss_b || !acc_b) return FUMI_EINVAL;
     if (rows ? (!rows->table || !rows->idx_s || !rows->idx_q || rows->n_rows < 1) : (!x_s || !x_q)) return FUMI_EINVAL;
     if (!cls_text && !text_s) return FUMI_EINVAL;
@@ -347,9 +347,9 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     HyperBwdArgs brider;
     struct BwdCtx { hipStream_t st; const HyperBwdArgs* a; } bctx{st, &brider};
     bool fused_bwd = false;
-    // an armed text gradient (fumi_hip_want_text_grad) needs ubar [R,Ht] in memory: every form of the backward leaves it in ub
-    float* text_grad = need_grad ? ws->text_grad : nullptr;
-    if (need_grad) ws->text_grad = nullptr;
+    // the text gradient (g_cls_text) needs ubar [R,Ht] in memory: every form of the backward leaves it in ub
+    float* text_grad = need_grad ? g_cls_text : nullptr;
+    bool text_gemm_here = text_grad != nullptr;                 // false where the plain-GEMM backward issues the GEMM itself
     if (need_grad && !fork_bwd && hbf &&
         hyper_bwd_fused_args(R, Dt, Ht, H1, tanh_head, 1.f, ctext, u, h, hbar, phi[2], hbf, g_phi[0], g_phi[1], g_phi[2], g_phi[3],
                              &fin, &brider, text_grad ? ub : nullptr)) {
@@ -372,10 +372,11 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
                                    g_phi[0], g_phi[1], g_phi[2], g_phi[3], &fin);
         if (rc2 != FUMI_ENOTSUP) return rc2;
     }
-    return hyper_head_bwd_gemm(sh, hd, grad_scale, g_phi, &text_grad);   // plain GEMMs (they consume text_grad themselves)
+    text_gemm_here = false;
+    return hyper_head_bwd_gemm(sh, hd, grad_scale, g_phi, text_grad);    // plain GEMMs (the text-gradient GEMM among them)
     }();
     if (rc) return rc;
-    if (text_grad && (rc = hyper_head_text_grad_gemm(sh, hd, grad_scale, text_grad))) return rc;
+    if (text_gemm_here && (rc = hyper_head_text_grad_gemm(sh, hd, grad_scale, text_grad))) return rc;
     if (fork_bwd) {                                                  // join: the caller's stream owns every result again
         HIP_TRY(hipEventRecord(ws->ev[3], sh));
         HIP_TRY(hipStreamWaitEvent(st, ws->ev[3], 0));
@@ -387,12 +388,6 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     return FUMI_OK;
 }
 
-int fumi_hip_want_text_grad(fumi_ws_t* ws, float* g_cls_text) {
-    if (!ws) return FUMI_EINVAL;
-    ws->text_grad = g_cls_text;
-    return FUMI_OK;
-}
-
 int fumi_hip_fumi_step(fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int Dt, int Ht,
         int T, float alpha, int tanh_head, int need_grad, float grad_scale, float dropout_p, uint64_t seed,
@@ -400,10 +395,10 @@ int fumi_hip_fumi_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi) {
+        float* const* g_theta, float* const* g_phi, float* g_cls_text) {
     return fumi_step_impl(ws, stream, B, N, S, Qn, D, n_hidden, hid, Dt, Ht, T, alpha, tanh_head, need_grad, grad_scale, dropout_p,
                           seed, x_s, y_s, x_q, y_q, cls_text, text_s, theta, phi, logits_q, preds_q, preds_q_f32, loss_b, acc_b,
-                          stats, g_theta, g_phi, nullptr);
+                          stats, g_theta, g_phi, g_cls_text, nullptr);
 }
 
 int fumi_hip_fumi_step_indexed(fumi_ws_t* ws, fumi_stream_t stream,
@@ -413,11 +408,11 @@ int fumi_hip_fumi_step_indexed(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi) {
+        float* const* g_theta, float* const* g_phi, float* g_cls_text) {
     XRows rows{table, idx_s, idx_q, (long)n_rows};
     return fumi_step_impl(ws, stream, B, N, S, Qn, D, n_hidden, hid, Dt, Ht, T, alpha, tanh_head, need_grad, grad_scale, dropout_p,
                           seed, nullptr, y_s, nullptr, y_q, cls_text, text_s, theta, phi, logits_q, preds_q, preds_q_f32, loss_b,
-                          acc_b, stats, g_theta, g_phi, &rows);
+                          acc_b, stats, g_theta, g_phi, g_cls_text, &rows);
 }
 
 // ------------------------------------------------------------------------------------------------------------

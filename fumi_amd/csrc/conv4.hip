@@ -601,7 +601,7 @@ int fumi_hip_fumi_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi) {
+        float* const* g_theta, float* const* g_phi, float* g_cls_text) {
     if (!ws || !theta || (!cls_text && !text_s) || Dt < 1 || Ht < 1 || !hyper_head_args_ok(phi, g_phi, need_grad)) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
@@ -626,7 +626,7 @@ int fumi_hip_fumi_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
     };
     if ((rc = run_conv4_episodes(ws, st, p, hk))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
-    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, &ws->text_grad);   // (consumes a text gradient armed by fumi_hip_want_text_grad)
+    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, g_cls_text);
 }
 
 // Copies one intermediate of the LAST conv4 step of this process out of the workspace (tests compare every tensor of the

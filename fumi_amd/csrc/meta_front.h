@@ -47,10 +47,9 @@ static inline int hyper_head_text_grad_gemm(hipStream_t st, const HyperHead& hd,
     return launch_gemm(st, g, 0, 1);
 }
 // From hd.hbar = d loss_b / d h (unscaled), in ONE launch order at every site:
-//     tanh' -> gA1 -> colsum g_b1 -> ubar (ReLU mask in the epilogue) -> gA0 -> text gradient (when armed) -> colsum g_b0.
-// *text_grad (may be NULL, or point at NULL) is an armed text-gradient buffer (fumi_hip_want_text_grad): it is consumed -- set to
-// NULL -- once gA0 has been launched, right before its own GEMM, so an error before that point leaves it armed.
-static inline int hyper_head_bwd_gemm(hipStream_t st, const HyperHead& hd, float grad_scale, float* const* g_phi, float** text_grad) {
+//     tanh' -> gA1 -> colsum g_b1 -> ubar (ReLU mask in the epilogue) -> gA0 -> text gradient (when wanted) -> colsum g_b0.
+// text_grad (may be NULL) is the step's g_cls_text buffer [R,Dt].
+static inline int hyper_head_bwd_gemm(hipStream_t st, const HyperHead& hd, float grad_scale, float* const* g_phi, float* text_grad) {
     const float* hp = hd.hbar;
     int rc;
     if (hd.tanh_head) { if ((rc = launch_tanh_bwd(st, (long)hd.R * hd.H1, hd.h, hd.hbar, hd.hpb))) return rc; hp = hd.hpb; }
@@ -64,11 +63,7 @@ static inline int hyper_head_bwd_gemm(hipStream_t st, const HyperHead& hd, float
     g = gemm_args(hd.Ht, hd.Dt, hd.R, hd.ub, hd.Ht, hd.ctext, hd.Dt, g_phi[0], hd.Dt);        // gA0 = ubar^T c
     g.alpha = grad_scale;
     if ((rc = launch_gemm(st, g, 1, 1))) return rc;
-    if (text_grad && *text_grad) {
-        float* tg = *text_grad;
-        *text_grad = nullptr;
-        if ((rc = hyper_head_text_grad_gemm(st, hd, grad_scale, tg))) return rc;
-    }
+    if (text_grad && (rc = hyper_head_text_grad_gemm(st, hd, grad_scale, text_grad))) return rc;
     return launch_colsum(st, hd.ub, hd.R, hd.Ht, hd.Ht, grad_scale, g_phi[1]);
 }
 

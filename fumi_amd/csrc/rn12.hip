@@ -909,7 +909,7 @@ int fumi_hip_fumi_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi) {
+        float* const* g_theta, float* const* g_phi, float* g_cls_text) {
     if (!ws || !theta || !channels || (!cls_text && !text_s) || Dt < 1 || Ht < 1 || !hyper_head_args_ok(phi, g_phi, need_grad))
         return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -932,7 +932,7 @@ int fumi_hip_fumi_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
     p.head = hd.h; p.head_bar = hd.hbar;
     if ((rc = run_rn12_episodes(ws, st, p))) { ws_abandon_lanes(ws); return rc; }
     if (!need_grad) return FUMI_OK;
-    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, &ws->text_grad);   // (consumes a text gradient armed by fumi_hip_want_text_grad)
+    return hyper_head_bwd_gemm(st, hd, grad_scale, g_phi, g_cls_text);
 }
 
 // Forward only: feats [G*M, F] = ResNet12(x [G, M, Cin, H, W]) with the batch statistics of every group of M images taken separately.

@@ -18,16 +18,17 @@ class HipEngine:
         return hip.Workspace.get(t.device if isinstance(t, torch.Tensor) and t.is_cuda else hip._dev(t))
 
     def fumi_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                  g_theta=None, g_phi=None, cls_text=None, stats=None, dropout_p=0.0, seed=0):
+                  g_theta=None, g_phi=None, cls_text=None, stats=None, dropout_p=0.0, seed=0, g_cls_text=None):
         """text_s [B,S,Dt] (class rows selected on the device) or cls_text [B,N,Dt] (already selected).
-        stats [2] (optional) receives grad_scale * (sum loss_b, sum acc_b)."""
+        stats [2] (optional) receives grad_scale * (sum loss_b, sum acc_b); g_cls_text [B,N,Dt] (optional, need_grad) receives
+        d loss / d class text rows."""
         if cls_text is not None:
             return hip.fumi_step(self._ws(x_s), x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text=cls_text,
                                  need_grad=need_grad, grad_scale=grad_scale, g_theta=g_theta, g_phi=g_phi, stats=stats,
-                                 dropout_p=dropout_p, seed=seed)
+                                 dropout_p=dropout_p, seed=seed, g_cls_text=g_cls_text)
         return hip.fumi_step_select(self._ws(x_s), n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head,
                                     need_grad=need_grad, grad_scale=grad_scale, g_theta=g_theta, g_phi=g_phi, stats=stats,
-                                    dropout_p=dropout_p, seed=seed)
+                                    dropout_p=dropout_p, seed=seed, g_cls_text=g_cls_text)
 
     def glove_bag_select(self, tokens_s, y_s, n_way, table, pad_id, mode, defer=False):
         """defer: the bag rides in the first launch of the ``fumi_step`` that must follow with the result as ``cls_text``"""
@@ -39,9 +40,11 @@ class HipEngine:
                              grad_scale=grad_scale, g_params=g_params, stats=stats)
 
     def am3_step(self, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed, need_grad, grad_scale, g_w=None,
-                 dropout_p=0.0, seed=0, stats=None, want_dx=False):
+                 dropout_p=0.0, seed=0, stats=None, want_dx=False, g_text=None):
+        """g_text [B,S,Dt] (optional, need_grad) receives d loss / d text_s."""
         return hip.am3_step(self._ws(x_s), x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed, need_grad=need_grad,
-                            grad_scale=grad_scale, g_w=g_w, dropout_p=dropout_p, seed=seed, stats=stats, want_dx=want_dx)
+                            grad_scale=grad_scale, g_w=g_w, dropout_p=dropout_p, seed=seed, stats=stats, want_dx=want_dx,
+                            g_text=g_text)
 
     def am3_step_tx(self, x_s, y_s, x_q, y_q, text_rows, w, n_way, lamda_fixed, need_grad, grad_scale, g_w=None,
                     dropout_p=0.0, seed=0, stats=None, want_dx=False):
@@ -66,11 +69,11 @@ class HipEngine:
                                        scale=scale, g_theta=g_theta)
 
     def fumi_conv4_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                        g_theta=None, g_phi=None, cls_text=None, stats=None):
+                        g_theta=None, g_phi=None, cls_text=None, stats=None, g_cls_text=None):
         """FuMI with the Conv4 encoder at the im_net seam: x_s [B,S,C,H,W], x_q [B,Qn,C,H,W]."""
         return hip.fumi_conv4_step(self._ws(x_s), n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text=cls_text,
                                    text_s=text_s, need_grad=need_grad, grad_scale=grad_scale, g_theta=g_theta, g_phi=g_phi,
-                                   stats=stats)
+                                   stats=stats, g_cls_text=g_cls_text)
 
     def maml_conv4_step(self, x_s, y_s, x_q, y_q, params, T, alpha, first_order, need_grad, grad_scale, g_params=None,
                         stats=None):
@@ -78,11 +81,11 @@ class HipEngine:
                                    grad_scale=grad_scale, g_params=g_params, stats=stats)
 
     def fumi_resnet12_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                           g_theta=None, g_phi=None, cls_text=None, stats=None):
+                           g_theta=None, g_phi=None, cls_text=None, stats=None, g_cls_text=None):
         """FuMI with the bf16 ResNet-12 encoder at the im_net seam (BASELINE.json configs[4])."""
         return hip.fumi_resnet12_step(self._ws(x_s), n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text=cls_text,
                                       text_s=text_s, need_grad=need_grad, grad_scale=grad_scale, g_theta=g_theta, g_phi=g_phi,
-                                      stats=stats)
+                                      stats=stats, g_cls_text=g_cls_text)
 
     def maml_resnet12_step(self, x_s, y_s, x_q, y_q, params, T, alpha, first_order, need_grad, grad_scale, g_params=None,
                            stats=None):
@@ -115,10 +118,6 @@ class HipEngine:
             out = hip.class_text_select(self._ws(rows_s), rows_s.contiguous().view(torch.float32), y_s, n_way)
             return out.view(torch.int64)
         return hip.class_text_select(self._ws(rows_s), rows_s.contiguous(), y_s, n_way)
-
-    def want_text_grad(self, device, g_cls_text):
-        """The next fumi_step(need_grad=True) on `device` also writes d loss / d class text rows into g_cls_text [B,N,Dt]."""
-        hip.want_text_grad(hip.Workspace.get(torch.device(device)), g_cls_text)
 
     def am3_metrics(self, n_way, stats):
         return hip.am3_metrics(self._ws(stats), n_way, stats)

@@ -38,7 +38,6 @@ SYMBOLS = [
     "fumi_hip_rn12_conv_plan", "fumi_hip_rn12_conv_query", "fumi_hip_rn12_wgrad_query", "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
     "fumi_hip_conv3x3_fwd", "fumi_hip_conv3x3_bwd_data", "fumi_hip_conv3x3_bwd_weight",
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
-    "fumi_hip_want_text_grad",
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
     "fumi_hip_cls_head_step",
     "fumi_hip_cls_head_step_soft", "fumi_hip_mix_images",
@@ -136,16 +135,18 @@ def lib():
         episodes = [c_void_p] * 4                                      # x_s | idx_s, y_s, x_q | idx_q, y_q
         text_in = [c_void_p] * 2                                       # cls_text, text_s
         outs = [c_void_p] * 6                                          # logits_q, preds_q, preds_q_f32, loss_b, acc_b + stats
-        fumi_io = episodes + text_in + [PP, PP] + outs + [PP, PP]      # ... theta, phi ... g_theta, g_phi
+        fumi_io = episodes + text_in + [PP, PP] + outs + [PP, PP, c_void_p]   # ... theta, phi ... g_theta, g_phi, g_cls_text
         maml_io = episodes + [PP] + outs + [PP]                        # ... params ... g_params
         L.fumi_hip_fumi_step.argtypes = front + mlp + text_dims + inner + drop + fumi_io
         L.fumi_hip_fumi_step_indexed.argtypes = front + mlp + text_dims + inner + drop + [c_void_p, c_int64] + fumi_io    # table, n_rows
         L.fumi_hip_maml_step.argtypes = front + mlp + inner + maml_io
-        L.fumi_hip_am3_step.argtypes = (front + [c_int] * 10 + [c_float] + drop        # B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad
-                                        + episodes + [c_void_p, PP] + [c_void_p] * 4 + [PP, c_void_p])   # text_s, w | 4 outputs | g_w, stats
-        L.fumi_hip_am3_step_dx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p, c_void_p]
-        L.fumi_hip_am3_step_tx.argtypes = L.fumi_hip_am3_step.argtypes + [c_void_p]
-        L.fumi_hip_am3_step_tx_dx.argtypes = L.fumi_hip_am3_step_tx.argtypes + [c_void_p, c_void_p]
+        am3_io = (front + [c_int] * 10 + [c_float] + drop                              # B, N, S, Qn, D, Dt, Ht, P, lamda_fixed, need_grad
+                  + episodes + [c_void_p, PP] + [c_void_p] * 4 + [PP, c_void_p])       # text_s, w | 4 outputs | g_w, stats
+        dx = [c_void_p, c_void_p]                                      # dx_s, dx_q
+        L.fumi_hip_am3_step.argtypes = am3_io + [c_void_p]             # g_text
+        L.fumi_hip_am3_step_dx.argtypes = am3_io + dx + [c_void_p]
+        L.fumi_hip_am3_step_tx.argtypes = am3_io + [c_void_p]          # tx_out
+        L.fumi_hip_am3_step_tx_dx.argtypes = am3_io + [c_void_p] + dx
         L.fumi_hip_am3_metrics.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
         L.fumi_hip_glove_bag.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int,
                                          c_int, c_void_p]
@@ -229,7 +230,6 @@ def lib():
         L.fumi_hip_lstm_bidir_train.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int64, PP, c_int,
                                                 c_void_p, c_void_p]
         L.fumi_hip_lstm_bidir_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_int64, PP, c_int, c_void_p, c_void_p, PP]
-        L.fumi_hip_want_text_grad.argtypes = [c_void_p, c_void_p]
         L.fumi_hip_proto_reduce.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3
         L.fumi_hip_cls_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_float] + [c_void_p] * 6
         L.fumi_hip_cls_head_step_soft.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
@@ -291,6 +291,18 @@ def _shape(t, shape, name):
     got = tuple(t.shape)
     if got != tuple(shape):
         raise FumiHipError(f"{name}: expected shape {tuple(shape)}, got {got}")
+
+
+def _text_grad(g, dev, B, rows, Dt, name):
+    """The optional text-gradient buffer of a step (include/fumi_hip.h, "The text gradient"): float32 [B, rows, Dt] or
+    [B * rows, Dt] on the step's device.  None -> NULL."""
+    if g is None:
+        return None
+    if tuple(g.shape) not in ((B, rows, Dt), (B * rows, Dt)):
+        raise FumiHipError(f"{name}: expected shape {(B, rows, Dt)} or {(B * rows, Dt)}, got {tuple(g.shape)}")
+    if g.device != dev:
+        raise FumiHipError(f"{name}: on {g.device}, the step runs on {dev}")
+    return _f32(g, name)
 
 
 def _mlp_shapes(params, D, name, n_layers):
@@ -431,8 +443,9 @@ def raise_on_status(status):
 
 # ----------------------------------------------------------------------------------------------------------------
 def fumi_step(ws, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
-              need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, dropout_p=0.0, seed=0):
-    """One FuMI meta-step over B episodes (fumi/models/fumi.py:146-192).  Returns a dict of GPU tensors."""
+              need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, dropout_p=0.0, seed=0, g_cls_text=None):
+    """One FuMI meta-step over B episodes (fumi/models/fumi.py:146-192).  Returns a dict of GPU tensors.  ``g_cls_text``: optional
+    fp32 [B, N, Dt] buffer that a step with ``need_grad`` fills with the adjoint of the class text rows."""
     dev = _dev(x_s)
     B, S, D = x_s.shape
     Qn = x_q.shape[1]
@@ -443,11 +456,12 @@ def fumi_step(ws, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_te
     if N is None:
         raise FumiHipError("fumi_step: pass n_way through cls_text=[B,N,Dt] or use fumi_step_select")
     return _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head,
-                      cls_text, text_s, need_grad, grad_scale, g_theta, g_phi, stats, dropout_p, seed)
+                      cls_text, text_s, need_grad, grad_scale, g_theta, g_phi, stats, dropout_p, seed, g_cls_text)
 
 
 def fumi_step_select(ws, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, *,
-                     need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, dropout_p=0.0, seed=0):
+                     need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, dropout_p=0.0, seed=0,
+                     g_cls_text=None):
     """Same, selecting the per-class text rows from text_s [B,S,Dt] on the device (fumi.py:207-210)."""
     dev = _dev(x_s)
     B, S, D = x_s.shape
@@ -456,7 +470,7 @@ def fumi_step_select(ws, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha
     hid = [int(theta[2 * i].shape[0]) for i in range(n_hidden)]
     Ht, Dt = int(phi[0].shape[0]), int(phi[0].shape[1])
     return _fumi_step(ws, dev, B, n_way, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head,
-                      None, text_s, need_grad, grad_scale, g_theta, g_phi, stats, dropout_p, seed)
+                      None, text_s, need_grad, grad_scale, g_theta, g_phi, stats, dropout_p, seed, g_cls_text)
 
 
 # Parameter / gradient LISTS that a model hands over unchanged step after step (the same list objects: fumi_amd/models cache
@@ -486,7 +500,7 @@ def _step_outputs(dev, B, Qn, N):
 
 
 def _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head,
-               cls_text, text_s, need_grad, grad_scale, g_theta, g_phi, stats=None, dropout_p=0.0, seed=0):
+               cls_text, text_s, need_grad, grad_scale, g_theta, g_phi, stats=None, dropout_p=0.0, seed=0, g_cls_text=None):
     L = lib()
 
     def check_params():
@@ -511,6 +525,7 @@ def _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, 
         _shape(cls_text, (B, N, Dt), "cls_text")
     else:
         _shape(text_s, (B, S, Dt), "text_s")
+    g_ct = _text_grad(g_cls_text, dev, B, N, Dt, "g_cls_text")
     logits, preds, preds_f, loss_b, acc_b = _step_outputs(dev, B, Qn, N)
     if need_grad:
         if g_theta is None:
@@ -538,7 +553,8 @@ def _fumi_step(ws, dev, B, N, S, Qn, D, hid, Dt, Ht, x_s, y_s, x_q, y_q, theta, 
         c_void_p(acc_b.data_ptr()),
         _f32(stats, "stats") if stats is not None else None,
         (arrs[2] if arrs[2] is not None else _parr(g_theta, "g_theta")) if need_grad else None,
-        (arrs[3] if arrs[3] is not None else _parr(g_phi, "g_phi")) if need_grad else None)
+        (arrs[3] if arrs[3] is not None else _parr(g_phi, "g_phi")) if need_grad else None,
+        g_ct)
     _check(rc, "fumi_hip_fumi_step")
     return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_theta=g_theta, g_phi=g_phi, stats=stats)
 
@@ -582,10 +598,11 @@ AM3_KEYS = ["Wi", "bi", "G0", "g0", "G1", "g1", "H0", "h0", "H1", "h1"]
 
 
 def am3_step(ws, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed=None, *, need_grad=True, grad_scale=None, g_w=None,
-             dropout_p=0.0, seed=0, stats=None, want_dx=False):
+             dropout_p=0.0, seed=0, stats=None, want_dx=False, g_text=None):
     """One AM3 step (fumi/models/am3.py:160-200).  w: list of the 10 tensors in AM3_KEYS order.  ``stats``: optional fp32
     [3 + n_way**2] device tensor receiving [loss, correct count, grad_scale * sum of the episodes' mean lamda, confusion
-    counts] (the input of ``am3_metrics``)."""
+    counts] (the input of ``am3_metrics``).  ``g_text``: optional fp32 [B, S, Dt] buffer that a step with ``need_grad`` fills with
+    the adjoint of ``text_s``."""
     dev = _dev(x_s)
     L = lib()
     B, S, D = x_s.shape
@@ -604,6 +621,7 @@ def am3_step(ws, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed=None, *, need
 
     arrs = _paramset((w, g_w), (D,), check_params) if (need_grad and g_w is not None) else check_params()
     _shape(x_q, (B, Qn, D), "x_q"); _shape(y_s, (B, S), "y_s"); _shape(y_q, (B, Qn), "y_q"); _shape(text_s, (B, S, Dt), "text_s")
+    g_t = _text_grad(g_text, dev, B, S, Dt, "g_text")
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     correct = torch.empty(1, device=dev, dtype=torch.float32)
     preds = torch.empty(B, Qn, device=dev, dtype=torch.int64)
@@ -622,9 +640,9 @@ def am3_step(ws, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed=None, *, need
     dx_s = dx_q = None
     if want_dx and need_grad:               # adjoints of the image rows (an encoder in front of the step continues from them)
         dx_s, dx_q = torch.empty_like(x_s), torch.empty_like(x_q)
-        _check(L.fumi_hip_am3_step_dx(*args, _f32(dx_s, "dx_s"), _f32(dx_q, "dx_q")), "fumi_hip_am3_step_dx")
+        _check(L.fumi_hip_am3_step_dx(*args, _f32(dx_s, "dx_s"), _f32(dx_q, "dx_q"), g_t), "fumi_hip_am3_step_dx")
     else:
-        _check(L.fumi_hip_am3_step(*args), "fumi_hip_am3_step")
+        _check(L.fumi_hip_am3_step(*args, g_t), "fumi_hip_am3_step")
     return dict(loss=loss, preds=preds, lamda_s=lam, correct=correct, grads=g_w, stats=stats, dx_s=dx_s, dx_q=dx_q)
 
 
@@ -648,11 +666,14 @@ def _parr_opt(tensors, name):
 
 
 def am3_step_tx(ws, x_s, y_s, x_q, y_q, text_rows, w, n_way, lamda_fixed=None, *, need_grad=True, grad_scale=None, g_w=None,
-                dropout_p=0.0, seed=0, stats=None, want_dx=False):
+                dropout_p=0.0, seed=0, stats=None, want_dx=False, g_text=None):
     """The text-rows form of the AM3 step (fumi/models/am3.py:118-126 then :160-200, ``text_encoder='rand'``): the text prototypes are
     rows of the prototype space, g is not applied and dropout acts in h only.  ``text_rows``: fp32 [B, S, P], or ``None`` -- then the
     step draws them uniformly on [-1, 1) from ``seed`` on the device.  ``w`` / ``g_w`` keep the AM3_KEYS layout; entries 2..5 (g) may
-    be ``None`` and are never read or written.  Returns what ``am3_step`` returns plus ``"tx"``, the rows the step used."""
+    be ``None`` and are never read or written.  Returns what ``am3_step`` returns plus ``"tx"``, the rows the step used.  No text
+    adjoint exists in this form: a ``g_text`` other than ``None`` is refused before anything is launched."""
+    if g_text is not None:
+        raise FumiHipError("am3_step_tx: invalid argument: the text-rows form has no text adjoint, g_text must be None")
     dev = _dev(x_s)
     L = lib()
     B, S, D = x_s.shape
@@ -761,7 +782,7 @@ def glove_bag_select(ws, tokens_s, y_s, n_way, table, pad_id, mode="mean", defer
                                                       int(pad_id), _f32(table, "table"), V, E, 0 if mode == "mean" else 1,
                                                       _f32(out, "out"))
         _check(rc, "fumi_hip_glove_bag_select_deferred")
-        ws._glove_keep = (tokens_s, y_s, table)       # (the request holds raw pointers until the step has launched it)
+        ws._glove_keep = (tokens_s, y_s, table, out)  # (the request holds raw pointers until the step has launched it)
         return out
     rc = lib().fumi_hip_glove_bag_select(ws.handle, _stream(dev), _i64(tokens_s, "tokens"), _i64(y_s, "y_s"), B, n_way, S,
                                          Lseq, int(pad_id), _f32(table, "table"), V, E, 0 if mode == "mean" else 1,
@@ -1245,7 +1266,7 @@ def _enc_step(enc, kind, ws, N, x_s, y_s, x_q, y_q, dims, scalars, inputs, stats
 
 
 def _enc_fumi_step(enc, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad, grad_scale,
-                   g_theta, g_phi, stats, tail=()):
+                   g_theta, g_phi, stats, g_cls_text, tail=()):
     dims, F, extra = enc.shapes(x_s, y_s, x_q, y_q, theta)
     B, S, N = dims[0], dims[1], int(n_way)
     Ht, Dt = int(phi[0].shape[0]), int(phi[0].shape[1])
@@ -1254,6 +1275,7 @@ def _enc_fumi_step(enc, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tan
         _shape(cls_text, (B, N, Dt), "cls_text")
     else:
         _shape(text_s, (B, S, Dt), "text_s")
+    g_ct = _text_grad(g_cls_text, _dev(x_s), B, N, Dt, "g_cls_text")
     if need_grad:
         g_theta = [torch.empty_like(t) for t in theta] if g_theta is None else g_theta
         g_phi = [torch.empty_like(t) for t in phi] if g_phi is None else g_phi
@@ -1261,7 +1283,7 @@ def _enc_fumi_step(enc, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tan
                     (*extra, Dt, Ht, *_inner_args(B, T, alpha, tanh_head, need_grad, grad_scale, tail)),
                     (_f32(cls_text, "cls_text") if cls_text is not None else None,
                      _f32(text_s, "text_s") if text_s is not None else None, _parr(theta, "theta"), _parr(phi, "phi")), stats,
-                    (_parr(g_theta, "g_theta") if need_grad else None, _parr(g_phi, "g_phi") if need_grad else None))
+                    (_parr(g_theta, "g_theta") if need_grad else None, _parr(g_phi, "g_phi") if need_grad else None, g_ct))
     out.update(g_theta=g_theta, g_phi=g_phi)
     return out
 
@@ -1321,11 +1343,11 @@ def _enc_encode_bwd(enc, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_
 
 
 def fumi_conv4_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
-                    need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None):
-    """FuMI meta-step with the Conv4 encoder (fumi/models/fumi.py:146-192 with im_net = Conv4)."""
+                    need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, g_cls_text=None):
+    """FuMI meta-step with the Conv4 encoder (fumi/models/fumi.py:146-192 with im_net = Conv4).  ``g_cls_text`` as in ``fumi_step``."""
     _conv4_tape_limit(T, need_grad, True)
     return _enc_fumi_step(_CONV4, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad,
-                          grad_scale, g_theta, g_phi, stats)
+                          grad_scale, g_theta, g_phi, stats, g_cls_text)
 
 
 def maml_conv4_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, need_grad=True, grad_scale=None,
@@ -1353,10 +1375,11 @@ def conv4_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0, g_
 
 
 def fumi_resnet12_step(ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, *, cls_text=None, text_s=None,
-                       need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, chunk=0):
-    """FuMI meta-step with the bf16 ResNet-12 encoder (fumi/models/fumi.py:146-192 with im_net = ResNet-12)."""
+                       need_grad=True, grad_scale=None, g_theta=None, g_phi=None, stats=None, chunk=0, g_cls_text=None):
+    """FuMI meta-step with the bf16 ResNet-12 encoder (fumi/models/fumi.py:146-192 with im_net = ResNet-12).  ``g_cls_text`` as in
+    ``fumi_step``."""
     return _enc_fumi_step(_RESNET12, ws, n_way, x_s, y_s, x_q, y_q, theta, phi, T, alpha, tanh_head, cls_text, text_s, need_grad,
-                          grad_scale, g_theta, g_phi, stats, (int(chunk),))
+                          grad_scale, g_theta, g_phi, stats, g_cls_text, (int(chunk),))
 
 
 def maml_resnet12_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, need_grad=True, grad_scale=None,
@@ -1944,9 +1967,3 @@ def lstm_bidir_bwd(ws, tokens, table, lstm_w, pad_id, use_cell, tape, d_out):
                                          int(bool(use_cell)), _f32(tape, "tape"), _f32(d_out, "d_out"), _parr(g_w, "g_w")),
            "fumi_hip_lstm_bidir_bwd")
     return g_w
-
-
-def want_text_grad(ws, g_cls_text):
-    """Arm the next fumi_step(need_grad=True) on ws to write d loss / d class text rows into g_cls_text [B*N, Dt] (None disarms)."""
-    _check(lib().fumi_hip_want_text_grad(ws.handle, None if g_cls_text is None else _f32(g_cls_text, "g_cls_text")),
-           "fumi_hip_want_text_grad")

@@ -226,13 +226,13 @@ class AM3(nn.Module):
             w_det = w_det[:2] + self._rand_g(x_s.device) + w_det[6:]
             if need_grad:
                 g_w = list(g_w[:2]) + self._rand_g_scratch + list(g_w[6:])
-        if lstm_ft:
+        if lstm_ft:                          # (never with rand_native: am3_step_tx has no text adjoint and takes no g_text)
             g_text = torch.empty_like(text)
-            eng.want_text_grad(x_s.device, g_text)
         out = (eng.am3_step_tx if rand_native else eng.am3_step)(
             x_s, y_s, x_q, y_q, text, w_det, num_ways,
             self.lamda_fixed, need_grad=need_grad, grad_scale=1.0 / B,
             g_w=g_w, dropout_p=drop_p, seed=drop_seed,
+            **({"g_text": g_text} if lstm_ft else {}),
             **({"stats": tail} if on_device else {}),
             **({"want_dx": True} if (self.conv is not None and need_grad) else {}))
         if self.conv is not None and need_grad:     # ... and backwards from the adjoints of the features (already scaled by 1/B)

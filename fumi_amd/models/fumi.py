@@ -244,7 +244,6 @@ class FUMI(nn.Module):
             tok_cls = eng.class_rows_select(to(s_text), y_s, self.n_way)
             cls_text, lstm_tape = self.text_encoder.forward_train(tok_cls)
             g_cls_text = torch.empty_like(cls_text)
-            eng.want_text_grad(x_s.device, g_cls_text)
         else:
             text_s = self._encode_text(to(s_text), dev)
 
@@ -261,14 +260,16 @@ class FUMI(nn.Module):
                 and not lazy.USE_EVENT and optimizer.defer_step(x_s.device))
         if fold:
             loss, acc = lazy.scalars(tail, 2, defer=True)
+        text_grad = {"g_cls_text": g_cls_text} if lstm_ft else {}
         if self.im_encoder in ("conv4", "resnet12"):
             step = eng.fumi_conv4_step if self.im_encoder == "conv4" else eng.fumi_resnet12_step
             out = step(self.n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, args.step_size, self.norm_hypernet,
-                       need_grad=train, grad_scale=1.0 / B, g_theta=g_th, g_phi=g_ph, cls_text=cls_text, stats=tail)
+                       need_grad=train, grad_scale=1.0 / B, g_theta=g_th, g_phi=g_ph, cls_text=cls_text, stats=tail, **text_grad)
         else:
             out = eng.fumi_step(self.n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, args.step_size, self.norm_hypernet,
                                 need_grad=train, grad_scale=1.0 / B,
-                                g_theta=g_th, g_phi=g_ph, cls_text=cls_text, stats=tail, dropout_p=drop_p, seed=drop_seed)
+                                g_theta=g_th, g_phi=g_ph, cls_text=cls_text, stats=tail, dropout_p=drop_p, seed=drop_seed,
+                                **text_grad)
         fdist.all_reduce_sum_(fg.flat if train else tail)
         if lstm_ft:                              # the encoder's .grad (this rank's episodes, then summed like every other gradient)
             for g in self.text_encoder.backward(tok_cls, lstm_tape, g_cls_text):

@@ -113,7 +113,8 @@ const char*  fumi_hip_phase_name(int phase);
  *           what the reference's float `test_preds` tensor holds, fumi.py:180-183), loss_b [B] (query CE), acc_b [B];
  *           stats [2] (optional, may be NULL) = grad_scale * (sum_b loss_b, sum_b acc_b): with grad_scale = 1/B the
  *           meta-batch mean loss / accuracy that fumi.py:187-188 computes, ready for the same all-reduce as the gradients;
- *           g_theta/g_phi (same shapes as theta/phi) only when need_grad != 0.
+ *           g_theta/g_phi (same shapes as theta/phi) only when need_grad != 0;
+ *           g_cls_text [B*N,Dt] or NULL: the text gradient (contract: "The text gradient" below, before fumi_hip_fumi_step_indexed).
  * second-order outer gradient always (fumi.py:176 hard-codes first_order=False).
  * dropout_p > 0 applies the reference's train-mode Dropout after every ReLU of im_net (fumi.py:93-99) with a fresh mask per
  * forward call (each inner step and the query pass), drawn from a counter-based hash of (seed, episode, call, layer,
@@ -125,7 +126,7 @@ int fumi_hip_fumi_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi);
+        float* const* g_theta, float* const* g_phi, float* g_cls_text);
 
 /* ---- MAML meta-step (replaces fumi/models/maml.py:156-191) ---------------------------------------------------
  * params: 2*n_hidden + 2 pointers: hidden layers as above, then lin_final W [N,H], b [N].  n_hidden = 0 is the reference's
@@ -153,7 +154,7 @@ int fumi_hip_am3_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w,
         float* loss, int64_t* preds_q, float* lamda_s, float* correct,
-        float* const* g_w, float* stats);
+        float* const* g_w, float* stats, float* g_text);
 /* The same step with the adjoints of the image rows as extra outputs (need_grad): dx_s [B,S,D], dx_q [B,Qn,D] = imbar Wi.  An
  * image encoder in front of the step (the Conv4 backbone at the image_encoder seam, am3.py:41-46) continues from them. */
 int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
@@ -162,7 +163,7 @@ int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
         const float* x_s, const int64_t* y_s, const float* x_q, const int64_t* y_q, const float* text_s,
         const float* const* w,
         float* loss, int64_t* preds_q, float* lamda_s, float* correct,
-        float* const* g_w, float* stats, float* dx_s, float* dx_q);
+        float* const* g_w, float* stats, float* dx_s, float* dx_q, float* g_text);
 /* ---- AM3 step on text rows (am3.py:118-126 with text_encoder = 'rand', then :160-200) ---------------------------------------
  * The same step with the text prototypes handed over as rows of the prototype space: tx = text rows, g is not applied,
  * l1 = dropout(relu(tx H0^T + h0)), lamda = sigmoid(l1 H1^T + h1); prototypes, loss, predictions, stats, dx and lamda_fixed as above.
@@ -173,8 +174,8 @@ int fumi_hip_am3_step_dx(fumi_ws_t* ws, fumi_stream_t stream,
  *   tx_out   [B*S, P] receives the rows the step used (optional when text_s is given, required when it is NULL);
  *   w / g_w  keep the 10-entry layout; entries 2..5 (G0, g0, G1, g1) may be NULL and are never read or written.  Dt is not used.
  * dropout_p > 0 acts in h only, with the mask fumi_hip_am3_step draws for h at the same seed (tag 2, element row * Ht + col).
- * The backward forms gWi, gbi, gH0, gh0, gH1, gh1 (h's as zeros under a fixed lamda) and nothing of g or of the text rows; with
- * fumi_hip_want_text_grad armed the call disarms it and returns FUMI_EINVAL. */
+ * The backward forms gWi, gbi, gH0, gh0, gH1, gh1 (h's as zeros under a fixed lamda) and nothing of g or of the text rows: these
+ * forms have no text adjoint and take no g_text. */
 int fumi_hip_am3_step_tx(fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int D, int Dt, int Ht, int P, int lamda_fixed, int need_grad, float grad_scale,
         float dropout_p, uint64_t seed,
@@ -330,7 +331,7 @@ int fumi_hip_fumi_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi);
+        float* const* g_theta, float* const* g_phi, float* g_cls_text);
 int fumi_hip_maml_conv4_step(fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int Cin, int H, int W, int nblk,
         int T, float alpha, int first_order, int need_grad, float grad_scale,
@@ -385,7 +386,7 @@ int fumi_hip_fumi_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi);
+        float* const* g_theta, float* const* g_phi, float* g_cls_text);
 int fumi_hip_maml_resnet12_step(fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int Cin, int H, int W, int nblk, const int* channels,
         int T, float alpha, int first_order, int need_grad, float grad_scale, int chunk,
@@ -693,12 +694,12 @@ int fumi_hip_lstm_bidir_train(fumi_ws_t* ws, fumi_stream_t stream, int R, int L,
 int fumi_hip_lstm_bidir_bwd(fumi_ws_t* ws, fumi_stream_t stream, int R, int L, int E, int H,
         const int64_t* tokens, int64_t pad_id, const float* const* w, int use_cell, const float* tape, const float* d_out,
         float* const* g_w);
-/* Arms the NEXT meta-step with need_grad != 0 on this workspace to also write the adjoint of its text input, what autograd hands
- * a trainable text encoder in the reference: fumi_hip_fumi_step / _indexed / fumi_hip_fumi_conv4_step / fumi_hip_fumi_resnet12_step
- * write g_text [B*N, Dt] = d(grad_scale * sum_b loss_b) / d(class text rows) (get_hyper_params, fumi.py:196-215);
- * fumi_hip_am3_step / _dx write g_text [B*S, Dt] = d loss / d text_s (every support row feeds its class prototype, am3.py:113-126).
- * One-shot: the step clears it.  NULL disarms. */
-int fumi_hip_want_text_grad(fumi_ws_t* ws, float* g_text);
+/* The text gradient, what autograd hands a trainable text encoder in the reference, is the last argument of every step that has
+ * one: fumi_hip_fumi_step / _indexed / fumi_hip_fumi_conv4_step / fumi_hip_fumi_resnet12_step write g_cls_text [B*N, Dt] =
+ * d(grad_scale * sum_b loss_b) / d(class text rows) (get_hyper_params, fumi.py:196-215), whether the rows came as cls_text or were
+ * selected from text_s; fumi_hip_am3_step / _dx write g_text [B*S, Dt] = d loss / d text_s (every support row feeds its class
+ * prototype, am3.py:113-126).  NULL = not wanted.  Written only when need_grad != 0; with need_grad == 0 a given buffer is ignored
+ * and left untouched.  Never retained past the call. */
 
 /* FuMI meta-step on ZERO-COPY episodes: identical to fumi_hip_fumi_step except that the image rows are not handed over as
  * x_s [B,S,D] / x_q [B,Qn,D] but addressed in an HBM-resident table [n_rows, D] through idx_s [B,S] / idx_q [B,Qn] (what
@@ -712,7 +713,7 @@ int fumi_hip_fumi_step_indexed(fumi_ws_t* ws, fumi_stream_t stream,
         const float* cls_text, const float* text_s,
         const float* const* theta, const float* const* phi,
         float* logits_q, int64_t* preds_q, float* preds_q_f32, float* loss_b, float* acc_b, float* stats,
-        float* const* g_theta, float* const* g_phi);
+        float* const* g_theta, float* const* g_phi, float* g_cls_text);
 
 /* ---- GPU-resident episode sampler (replaces fumi/dataset/data.py:294-581 + the torchmeta loader for
  * precomputed embeddings held in HBM) ---------------------------------------------------------------------------------

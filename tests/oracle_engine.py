@@ -16,9 +16,9 @@ class OracleEngine:
         return R.word_embedding_pool(rows, table, pad_id, mode)
 
     def fumi_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                  g_theta=None, g_phi=None, cls_text=None, stats=None, dropout_p=0.0, seed=0):
+                  g_theta=None, g_phi=None, cls_text=None, stats=None, dropout_p=0.0, seed=0, g_cls_text=None):
         B = x_s.shape[0]
-        want, extra = self._take_text_grad(need_grad), None
+        want, extra = (g_cls_text if need_grad else None), None
         if cls_text is not None:                # expand the per-class rows back to per-sample rows for the oracle
             if want is not None:
                 cls_text = cls_text.detach().clone().requires_grad_(True)
@@ -53,7 +53,7 @@ class OracleEngine:
         return dict(logits=out["logits"], preds=out["preds"], preds_f=out["preds"].float(), loss_b=out["loss_b"], acc_b=out["acc_b"])
 
     def am3_step(self, x_s, y_s, x_q, y_q, text_s, w, n_way, lamda_fixed, need_grad, grad_scale, g_w=None, dropout_p=0.0, seed=0,
-                 want_dx=False):
+                 want_dx=False, g_text=None):
         from fumi_amd.hip import AM3_KEYS
         B, Qn = x_q.shape[0], x_q.shape[1]
         wd = {k: t.detach().clone().requires_grad_(True) for k, t in zip(AM3_KEYS, w)}
@@ -86,7 +86,7 @@ class OracleEngine:
             from helpers import dropout_mask_flat
             Rs, Ht = x_s.shape[0] * x_s.shape[1], w[2].shape[0]
             masks = (dropout_mask_flat(seed, dropout_p, 1, Rs, Ht), dropout_mask_flat(seed, dropout_p, 2, Rs, Ht))
-        want, extra = self._take_text_grad(need_grad), None
+        want, extra = (g_text if need_grad else None), None
         if want is not None:
             text_s = text_s.detach().clone().requires_grad_(True)
             extra = [text_s]
@@ -125,10 +125,10 @@ class OracleEngine:
         return g_theta
 
     def fumi_conv4_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                        g_theta=None, g_phi=None, cls_text=None, stats=None):
+                        g_theta=None, g_phi=None, cls_text=None, stats=None, g_cls_text=None):
         from oracle import conv4_ref as C
         B = x_s.shape[0]
-        want, extra = self._take_text_grad(need_grad), None
+        want, extra = (g_cls_text if need_grad else None), None
         if cls_text is not None:
             if want is not None:
                 cls_text = cls_text.detach().clone().requires_grad_(True)
@@ -163,10 +163,10 @@ class OracleEngine:
         return torch.stack([C.conv4_features(x[g], theta) for g in range(x.shape[0])])
 
     def fumi_resnet12_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
-                           g_theta=None, g_phi=None, cls_text=None, stats=None):
+                           g_theta=None, g_phi=None, cls_text=None, stats=None, g_cls_text=None):
         from oracle import resnet12_ref as C
         B = x_s.shape[0]
-        want, extra = self._take_text_grad(need_grad), None
+        want, extra = (g_cls_text if need_grad else None), None
         if cls_text is not None:
             if want is not None:
                 cls_text = cls_text.detach().clone().requires_grad_(True)
@@ -222,16 +222,6 @@ class OracleEngine:
 
     def class_rows_select(self, rows_s, y_s, n_way):
         return torch.stack([R.class_text_select(rows_s[b], y_s[b], n_way) for b in range(rows_s.shape[0])])
-
-    def want_text_grad(self, device, g_text):
-        self._text_grad = g_text
-
-    def _take_text_grad(self, need_grad):
-        """The armed text-adjoint buffer, consumed by the next step with need_grad (fumi_hip_want_text_grad's contract)."""
-        if not need_grad:
-            return None
-        want, self._text_grad = getattr(self, "_text_grad", None), None
-        return want
 
     def glove_bag(self, tokens, table, pad_id, mode):
         return R.word_embedding_pool(tokens, table, pad_id, mode)

@@ -196,15 +196,16 @@ def test_dropout_hits_h_only(dev, ws):
     assert not torch.equal(a["lamda_s"], b["lamda_s"])
 
 
-def test_armed_text_grad_is_refused_and_disarmed(dev, ws):
+def test_text_grad_buffer_is_refused_and_not_kept(dev, ws):
     from fumi_amd import hip
     c, ep, w, _, _ = A.reference("small_p", "given")
     g = lambda t: t.to(dev).contiguous()
     canary = torch.full((c["B"], c["N"] * c["K"], c["P"]), SENTINEL, device=dev)
-    hip.want_text_grad(ws, canary)
     with pytest.raises(hip.FumiHipError, match="invalid argument"):
-        _step("small_p", "given", dev, ws)
-    # disarmed: the next plain step runs as if nothing had been armed and writes no text adjoint
+        _step("small_p", "given", dev, ws, g_text=canary)
+    torch.cuda.synchronize()
+    assert bool((canary == SENTINEL).all())
+    # nothing was kept: the next plain step runs as if no buffer had been given and writes no text adjoint
     from oracle import casegen as cg
     wf = cg.make_am3_params(c["ep_seed"], c["D"], c["P"], c["Ht"], c["P"])         # a g of h's own hidden width for the plain step
     full = [wf[k].to(dev).contiguous() for k in hip.AM3_KEYS]

@@ -1,6 +1,6 @@
 """GPU parity of the trainable bi-LSTM text encoder (--fine_tune with --text_encoder RNN / RNNhid, fumi/models/fumi.py:46-67):
 the tape-keeping forward and back-propagation through time of csrc/textenc.hip, the text adjoint the FuMI meta-step hands back
-(fumi_hip_want_text_grad), and FUMI.evaluate(train) end to end against the reference's own gradients
+(its g_cls_text / g_text argument), and FUMI.evaluate(train) end to end against the reference's own gradients
 (tests/golden/fumi_rnn_finetune.npz, oracle/refharness/gen_golden.py)."""
 from types import SimpleNamespace
 
@@ -84,7 +84,7 @@ def test_lstm_backward_matches_oracle(dev, ws, use_cell):
 
 @pytest.mark.parametrize("shape", ["golden", "gemm_fallback", "bench"])
 def test_fumi_step_text_gradient_matches_oracle(dev, ws, shape):
-    """fumi_hip_want_text_grad: d(grad_scale * sum_b loss_b) / d cls_text of the very next FuMI step against autograd through
+    """g_cls_text of fumi_hip_fumi_step: d(grad_scale * sum_b loss_b) / d cls_text of that FuMI step against autograd through
     the oracle's meta-step, in the three forms of the hypernetwork backward (fused rider; plain GEMMs for a text width the
     LDS-resident kernels do not take; the bench's widths) -- and the step's other outputs are unchanged by the request."""
     from fumi_amd import hip
@@ -104,8 +104,7 @@ def test_fumi_step_text_gradient_matches_oracle(dev, ws, shape):
     thd, phd = [_g(t, dev) for t in theta], [_g(t, dev) for t in phi]
     plain = hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
     g_ct = torch.full((B, N, Dt), float("nan"), device=dev)
-    hip.want_text_grad(ws, g_ct)
-    out = hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
+    out = hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), grad_scale=1.0 / B, g_cls_text=g_ct)
     assert rel_to_max(g_ct.cpu(), ref["g_extra"][0]) <= 1e-4
     for a, b in zip(out["g_theta"] + out["g_phi"], plain["g_theta"] + plain["g_phi"]):
         assert rel_to_max(a.cpu(), b.cpu()) <= 1e-6
@@ -113,17 +112,38 @@ def test_fumi_step_text_gradient_matches_oracle(dev, ws, shape):
     floor = 1e-2 * max(float(b.abs().max()) for b in ref["g_theta"] + ref["g_phi"])
     for i, (a, b) in enumerate(zip(out["g_theta"] + out["g_phi"], ref["g_theta"] + ref["g_phi"])):
         assert rel_to_max(a.cpu(), b, floor) <= 2e-4, (i, rel_to_max(a.cpu(), b, floor), float(b.abs().max()))
-    # one-shot: the next step does not write it again
+    # a step without the argument does not write it again
     g_ct.fill_(7.0)
     hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
     torch.cuda.synchronize()
     assert float(g_ct.min()) == 7.0 and float(g_ct.max()) == 7.0
-    # an evaluation step (need_grad = 0) leaves the request armed for the training step that follows
-    hip.want_text_grad(ws, g_ct)
-    hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), need_grad=False)
+    # an evaluation step (need_grad = 0) ignores a given buffer and leaves it untouched
+    hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=_g(cls_text, dev), need_grad=False, g_cls_text=g_ct)
     torch.cuda.synchronize()
     assert float(g_ct.min()) == 7.0
-    hip.want_text_grad(ws, None)
+    assert ws.read_status() == 0
+
+
+def test_failed_step_does_not_keep_the_text_gradient_buffer(dev, ws):
+    """A step that is refused after its buffers exist and before its launch (a phi tensor of the wrong shape: the binding raises)
+    keeps nothing of the g_cls_text it was given: the plain need_grad step that follows on the same workspace leaves the buffer at
+    its fill value.  With the text gradient armed on the workspace by a call of its own (before it became an argument) the
+    equivalent sequence -- arm, failing step, plain step -- overwrote the buffer, which the caller may have freed by then."""
+    from fumi_amd import hip
+    B, N, K, Q, D, hid, Dt, Ht, T, tanh = 3, 4, 2, 3, 40, [24], 16, 32, 2, True
+    ep = cg.make_episodes(77, B, N, K, Q, D, Dt)
+    theta, phi = cg.make_fumi_params(77, D, hid, Dt, Ht)
+    cls_text = _g(torch.randn(B, N, Dt, generator=torch.Generator().manual_seed(3)), dev)
+    args = [_g(ep[k], dev) for k in ("x_s", "y_s", "x_q", "y_q")]
+    thd, phd = [_g(t, dev) for t in theta], [_g(t, dev) for t in phi]
+    bad_phi = phd[:3] + [torch.zeros(hid[-1] + 2, device=dev)]
+    canary = torch.full((B, N, Dt), 7.0, device=dev)
+    with pytest.raises(hip.FumiHipError, match="phi"):
+        hip.fumi_step(ws, *args, thd, bad_phi, T, cg.ALPHA, tanh, cls_text=cls_text, grad_scale=1.0 / B, g_cls_text=canary)
+    out = hip.fumi_step(ws, *args, thd, phd, T, cg.ALPHA, tanh, cls_text=cls_text, grad_scale=1.0 / B)
+    torch.cuda.synchronize()
+    assert float(canary.min()) == 7.0 and float(canary.max()) == 7.0
+    assert bool(torch.isfinite(out["g_phi"][0]).all())
     assert ws.read_status() == 0
 
 
@@ -187,7 +207,7 @@ def _text_adjoint_identity(g_text, cls_text, phi, g_phi):
 
 @pytest.mark.parametrize("encoder", ["conv4", "resnet12"])
 def test_conv_encoder_steps_hand_back_the_text_adjoint(dev, ws, encoder):
-    """fumi_hip_fumi_conv4_step / fumi_hip_fumi_resnet12_step with an armed fumi_hip_want_text_grad: the adjoint of the class text rows
+    """fumi_hip_fumi_conv4_step / fumi_hip_fumi_resnet12_step with a g_cls_text buffer: the adjoint of the class text rows
     is tied to the (separately verified) hypernetwork gradients by exact identities -- g_text = s ubar A0, g_phi[0] = s ubar^T c,
     g_phi[1] = s colsum(ubar) -- which determine it when the B*N text rows are linearly independent."""
     from fumi_amd import hip
@@ -209,14 +229,13 @@ def test_conv_encoder_steps_hand_back_the_text_adjoint(dev, ws, encoder):
     args = [N] + [_g(ep[k], dev) for k in ("x_s", "y_s", "x_q", "y_q")] + [[_g(t, dev) for t in theta], [_g(t, dev) for t in phi], T, 0.05, True]
     plain = step(ws, *args, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
     g_ct = torch.full((B, N, Dt), float("nan"), device=dev)
-    hip.want_text_grad(ws, g_ct)
-    out = step(ws, *args, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
+    out = step(ws, *args, cls_text=_g(cls_text, dev), grad_scale=1.0 / B, g_cls_text=g_ct)
     assert ws.read_status() == 0 and bool(torch.isfinite(g_ct).all()) and float(g_ct.abs().max()) > 0
     for a, b in zip(out["g_theta"] + out["g_phi"], plain["g_theta"] + plain["g_phi"]):
         assert torch.equal(a, b)                                  # the request changes nothing else
     e1, e2 = _text_adjoint_identity(g_ct, cls_text, phi, out["g_phi"])
     assert e1 <= 1e-4 and e2 <= 1e-4, (e1, e2)
-    g_ct.fill_(7.0)                                                # one-shot
+    g_ct.fill_(7.0)                                                # nothing is kept: a step without the argument leaves it alone
     step(ws, *args, cls_text=_g(cls_text, dev), grad_scale=1.0 / B)
     torch.cuda.synchronize()
     assert float(g_ct.min()) == 7.0 and float(g_ct.max()) == 7.0
@@ -224,7 +243,7 @@ def test_conv_encoder_steps_hand_back_the_text_adjoint(dev, ws, encoder):
 
 @pytest.mark.parametrize("lamda_fixed", [None, 1])
 def test_am3_step_text_gradient_matches_oracle(dev, ws, lamda_fixed):
-    """fumi_hip_am3_step with an armed text adjoint: d loss / d text_s of all B*S rows against autograd through the oracle's step
+    """fumi_hip_am3_step with a g_text buffer: d loss / d text_s of all B*S rows against autograd through the oracle's step
     (am3.py:113-126: every support row's encoding feeds its class prototype), in the fused and the GEMM form of the text MLPs'
     backward, and with lamda overridden (h out of the graph)."""
     from fumi_amd import hip
@@ -239,8 +258,7 @@ def test_am3_step_text_gradient_matches_oracle(dev, ws, lamda_fixed):
         wd = [_g(w[k], dev) for k in hip.AM3_KEYS]
         args = [_g(ep[k], dev) for k in ("x_s", "y_s", "x_q", "y_q")] + [_g(text, dev), wd, N, lamda_fixed]
         g_t = torch.full((B, N * K, Dt), float("nan"), device=dev)
-        hip.want_text_grad(ws, g_t)
-        out = hip.am3_step(ws, *args, grad_scale=1.0 / B)
+        out = hip.am3_step(ws, *args, grad_scale=1.0 / B, g_text=g_t)
         assert abs(float(out["loss"]) - float(ref["loss"])) <= 1e-4 * max(1.0, float(ref["loss"]))
         assert rel_to_max(g_t.cpu(), ref["g_extra"][0]) <= 2e-4, rel_to_max(g_t.cpu(), ref["g_extra"][0])
         g_t.fill_(7.0)
@@ -311,10 +329,9 @@ def test_fumi_conv4_finetunes_the_bilstm(dev):
     tok_cls = eng.class_rows_select(ep["text_s"].to(dev), y_s, N)
     cls_text, tape = m.text_encoder.forward_train(tok_cls)
     g_ct = torch.empty_like(cls_text)
-    hip.want_text_grad(ws, g_ct)
     theta, phi = [p.detach() for p in m._theta()], [p.detach() for p in m._phi()]
     hip.fumi_conv4_step(ws, N, ep["x_s"].to(dev), y_s, ep["x_q"].to(dev), ep["y_q"].to(dev), theta, phi, 1, 0.05, m.norm_hypernet,
-                        cls_text=cls_text, grad_scale=1.0 / B)
+                        cls_text=cls_text, grad_scale=1.0 / B, g_cls_text=g_ct)
     lw = [w.detach().contiguous() for w in m.text_encoder.lstm_weights()]
     want = hip.lstm_bidir_bwd(ws, tok_cls, m.text_encoder.embed.weight.detach(), lw, 0, False, tape, g_ct)
     before = [p.detach().clone() for p in m.text_encoder.rnn.parameters()]
