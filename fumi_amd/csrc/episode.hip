@@ -19,6 +19,7 @@
 #include "common.h"
 #include <algorithm>
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -1716,9 +1717,11 @@ inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b > 2048 
 
 struct Carver {      // computes the layout twice: once to size the workspace, once to hand out pointers
     fumi_ws* ws; size_t bytes;
+    char* fake;      // no workspace: the addresses a slab at this base would give (fumi_hip_epi_plan_query), or NULL for none
     float* take(size_t n) {
+        const size_t at = bytes;
         bytes += ws_align(n * sizeof(float));
-        return ws ? ws_f(ws, n) : nullptr;
+        return ws ? ws_f(ws, n) : fake ? (float*)(fake + at) : nullptr;
     }
 };
 
@@ -1810,6 +1813,9 @@ struct EpiPlan {
     bool drop;
     int fixed_last;                                          // what fumi_hip_epi_fixed_last() reports
 };
+// what the plan depends on besides the problem, the carved arrays and the knobs: facts of the workspace, passed as values so that
+// fumi_hip_epi_plan_query can state them without a workspace
+struct EpiFacts { bool side, profiling; };                   // side: the second stream and its two fork / join events exist
 
 inline bool a16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 inline bool stage_ok(const StageTab& tb) { return !tb.bad && tb.nunits <= 64 * 8; }     // wg_stage_rows: one unit per lane and wave
@@ -1903,8 +1909,9 @@ bool stage_reverse_step(StageTab& ts, const EpisodeProblem& p, const EpiDims& d,
 }
 
 // Decides every phase's form, each in its fall-back order: a form that fails its size cap or its table check (stage_*: false)
-// falls to the next.  Runs after carve: the fixed-shape reverse form depends on the alignment of carved arrays.
-void plan_episodes(EpiPlan& pl, const fumi_ws* ws, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w) {
+// falls to the next.  Runs after carve: the fixed-shape reverse form depends on the alignment of carved arrays.  Makes no HIP call
+// and dereferences no pointer: addresses only count through their alignment.
+void plan_episodes(EpiPlan& pl, const EpiFacts& f, const EpisodeProblem& p, const EpiDims& d, const EpiBuf& w) {
     const EpiKnobs& k = epi_knobs();
     const int h0 = p.h[0];
     pl.drop = d.drop_thr != 0;
@@ -1917,7 +1924,7 @@ void plan_episodes(EpiPlan& pl, const fumi_ws* ws, const EpisodeProblem& p, cons
     // At T = 1 the sweep is one 42 us launch on half of the CUs and the query-row part takes the other half for about as long: the
     // headline step 0.2200 -> 0.2153 ms without phase timing; not adopted -- the pass is the bench's roofline kernel, timed as ONE
     // launch on the caller's stream, and +2 % does not pay for a second population of that kernel in every profile)
-    pl.two_part = k.overlap && p.need_grad && p.T >= 2 && ws->side && ws->evx[0] && ws->evx[1] && !ws->profiling && !p.after_reverse &&
+    pl.two_part = k.overlap && p.need_grad && p.T >= 2 && f.side && !f.profiling && !p.after_reverse &&
                   xpanel_bwd_two_part_ok(p.D, h0) && p.second_order && ((long)p.B * p.Qn >= 2048 || k.overlap == 2);      // (2: tests)
     if (pl.two_part) xpanel_bwd_two_part_split(p.B, p.S, p.Qn, p.D, h0, &pl.nsq, &pl.kcq, &pl.nss, &pl.kcs);
     // the reference shape of a training step: the query and reverse kernels compiled for it (REF_*; FUMI_EPI_FIXED=0: the
@@ -2046,27 +2053,36 @@ extern "C" int fumi_hip_set_trace_buffer(int which, void* p) {
 // which fixed-shape kernels the last run_episodes launched: 1 = query_lds_kernel<true, true, *>, 2 = reverse_lds_kernel<true, *>
 static int g_epi_fixed_last = 0;
 extern "C" int fumi_hip_epi_fixed_last() { return g_epi_fixed_last; }
-extern "C" int fumi_hip_set_spin_limit(int polls) { const int old = g_spin_limit; g_spin_limit = polls < 0 ? 0 : polls; return old; }
 
-size_t episode_workspace_bytes(const EpisodeProblem& p) {
-    Carver c{nullptr, 0};
-    EpiBuf w;
-    w.trace = nullptr;
-    carve(c, p, w);
-    if (p.need_grad) c.bytes += ws_align(bwd_slab_count(p) * p.h[0] * (size_t)p.D * sizeof(float));
-    return c.bytes;
+// ---- the plan as integers (include/fumi_hip.h: fumi_hip_epi_plan; named once by hip.EPI_PLAN_KEYS).  An entry of a form that was
+// not taken is 0: the plan leaves that form's layout and tables unset.
+constexpr int EPI_PLAN_N = 18;
+static int g_epi_plan_last[EPI_PLAN_N];
+static void plan_entries(const EpiPlan& pl, int* o) {
+    const bool alds = pl.adapt == AdaptForm::lds, fusedq = pl.query == QueryForm::fused_fixed || pl.query == QueryForm::fused;
+    const bool rlds = pl.reverse != ReverseForm::global;
+    o[0] = (int)pl.adapt; o[1] = pl.AP; o[2] = (int)pl.query; o[3] = (int)pl.reverse; o[4] = rlds ? pl.P : 0;
+    o[5] = pl.two_part ? 1 : 0; o[6] = pl.two_part ? pl.nsq : 0; o[7] = pl.two_part ? pl.nss : 0;
+    o[8] = pl.drop ? 1 : 0; o[9] = pl.fixed_last;
+    o[10] = pl.query != QueryForm::global ? pl.ql.total : 0; o[11] = alds ? pl.al.total : 0; o[12] = rlds ? pl.rl.total : 0;
+    o[13] = alds ? pl.stg_adapt.nunits : 0;
+    o[14] = pl.query == QueryForm::lds ? pl.stg.nunits : 0; o[15] = fusedq ? pl.stg_sup.nunits : 0;
+    o[16] = rlds ? pl.stg_init.nunits : 0; o[17] = rlds ? pl.stg_step.nunits : 0;
 }
+static int copy_plan(const int* src, int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    for (int i = 0; i < n && i < EPI_PLAN_N; ++i) plan[i] = src[i];
+    return FUMI_OK;
+}
+extern "C" int fumi_hip_epi_plan(int* plan, int n) { return copy_plan(g_epi_plan_last, plan, n); }
 
-int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
+static int check_problem(const EpisodeProblem& p) {
     if (p.L < 1 || p.L > MAXL || p.B < 1 || p.N < 1 || p.S < 1 || p.Qn < 1 || p.D < 1 || p.T < 0) return FUMI_EINVAL;
     for (int i = 0; i < p.L; ++i) if (p.h[i] < 1) return FUMI_EINVAL;
-    EpiBuf w;
-    Carver c{ws, 0};
-    carve(c, p, w);
-    w.trace = g_epi_trace;
-    w.status = ws->status; w.spin_limit = g_spin_limit;
-    w.acnt = ws->acnt;                           // persistent arrival counters of the split adapt kernel (zero between steps)
-    EpiDims d;
+    return FUMI_OK;
+}
+// the dimensions and the dropout constants the kernels (and the plan) read
+static int fill_dims(EpiDims& d, const EpisodeProblem& p) {
     d.B = p.B; d.N = p.N; d.S = p.S; d.Qn = p.Qn; d.L = p.L; d.T = p.T; d.H = p.h[p.L - 1];
     for (int i = 0; i < MAXL; ++i) d.h[i] = i < p.L ? p.h[i] : 0;
     d.alpha = p.alpha; d.need_grad = p.need_grad; d.second_order = p.second_order;
@@ -2078,9 +2094,68 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
         if (d.drop_thr == 0) d.drop_thr = 1;
         d.mscale = 1.f / (1.f - p.dropout_p);
     }
+    return FUMI_OK;
+}
+
+// The plan of a shape, without a workspace and without a HIP call.  The carved arrays get the addresses a 16-byte-aligned slab
+// would give them (every array starts on a multiple of ws_align = 256 bytes in it, as in a real slab); the parameters get made-up
+// addresses that are 16-byte aligned or one float past such a boundary, as the flags word says.  No address is dereferenced.
+extern "C" int fumi_hip_epi_plan_query(int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int T, int need_grad,
+                                       int second_order, int dropout, int flags, int* plan, int n) {
+    if (!hid || n_hidden < 1 || n_hidden > MAXL) return FUMI_EINVAL;
+    EpisodeProblem p;
+    memset(&p, 0, sizeof(p));
+    p.B = B; p.N = N; p.S = S; p.Qn = Qn; p.D = D; p.L = n_hidden; p.T = T; p.alpha = 0.f;
+    p.need_grad = need_grad ? 1 : 0; p.second_order = second_order ? 1 : 0; p.dropout_p = dropout ? 0.5f : 0.f;
+    for (int i = 0; i < n_hidden; ++i) p.h[i] = hid[i];
+    int rc = check_problem(p);
+    if (rc) return rc;
+    char* const fake = (char*)(uintptr_t)(1u << 20);
+    for (int i = 0; i < n_hidden; ++i) {
+        p.W[i] = (const float*)(fake + 4096 * (2 * i)) + ((flags >> (FUMI_EPI_Q_W_OFF_SHIFT + i)) & 1);
+        p.b[i] = (const float*)(fake + 4096 * (2 * i + 1)) + ((flags >> (FUMI_EPI_Q_B_OFF_SHIFT + i)) & 1);
+    }
+    if (flags & FUMI_EPI_Q_HEAD) p.head = (const float*)(fake + 4096 * 2 * MAXL);
+    if (flags & FUMI_EPI_Q_AFTER_REVERSE) p.after_reverse = (hipEvent_t)fake;          // (only compared with NULL)
+    EpiBuf w{};
+    Carver c{nullptr, 0, fake + (1u << 20)};
+    carve(c, p, w);
+    w.acnt = (int*)fake;                                                             // every workspace has its arrival counters
+    EpiDims d;
+    if ((rc = fill_dims(d, p))) return rc;
+    const EpiFacts f = {(flags & FUMI_EPI_Q_SIDE) != 0, (flags & FUMI_EPI_Q_PROFILING) != 0};
+    EpiPlan pl;
+    plan_episodes(pl, f, p, d, w);
+    int v[EPI_PLAN_N];
+    plan_entries(pl, v);
+    return copy_plan(v, plan, n);
+}
+extern "C" int fumi_hip_set_spin_limit(int polls) { const int old = g_spin_limit; g_spin_limit = polls < 0 ? 0 : polls; return old; }
+
+size_t episode_workspace_bytes(const EpisodeProblem& p) {
+    Carver c{nullptr, 0, nullptr};
+    EpiBuf w{};
+    carve(c, p, w);
+    if (p.need_grad) c.bytes += ws_align(bwd_slab_count(p) * p.h[0] * (size_t)p.D * sizeof(float));
+    return c.bytes;
+}
+
+int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
+    int rc;
+    if ((rc = check_problem(p))) return rc;
+    EpiBuf w{};                                  // (zeroed: without need_grad carve leaves the adjoint arrays unset, and the plan looks at their alignment)
+    Carver c{ws, 0, nullptr};
+    carve(c, p, w);
+    w.trace = g_epi_trace;
+    w.status = ws->status; w.spin_limit = g_spin_limit;
+    w.acnt = ws->acnt;                           // persistent arrival counters of the split adapt kernel (zero between steps)
+    EpiDims d;
+    if ((rc = fill_dims(d, p))) return rc;
     EpiPlan pl;                                  // (filled in place: its five staging tables are about a kilobyte each)
-    plan_episodes(pl, ws, p, d, w);
+    const EpiFacts facts = {ws->side && ws->evx[0] && ws->evx[1], ws->profiling != 0};
+    plan_episodes(pl, facts, p, d, w);
     g_epi_fixed_last = pl.fixed_last;
+    plan_entries(pl, g_epi_plan_last);
     const int h0 = p.h[0];
     const long slab = (long)h0 * p.D;
     const XRows* rows = p.rows.table ? &p.rows : nullptr;
@@ -2088,7 +2163,6 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
         w.ldsr = pl.two_part ? p.S : p.S + p.Qn; w.ldq = pl.two_part ? p.Qn : p.S + p.Qn;
         w.A0bar_q = pl.two_part ? w.A0bar + (size_t)p.B * p.S * h0 : w.A0bar + (size_t)p.S * h0;
     } else { w.A0bar_q = nullptr; w.ldsr = w.ldq = 0; }
-    int rc;
 
     // ---- shared pass 1 over X: [A0 | G] = [Xs;Xq] [W0;Xs]^T for every episode, one launch (xpanel.hip)
     if (p.inputs_ready) HIP_TRY(hipEventRecord(p.inputs_ready, st));

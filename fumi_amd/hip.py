@@ -23,6 +23,7 @@ SYMBOLS = [
     "fumi_hip_set_profiling", "fumi_hip_set_profiling_every", "fumi_hip_get_profile", "fumi_hip_phase_name",
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
     "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
+    "fumi_hip_epi_plan", "fumi_hip_epi_plan_query",
     "fumi_hip_reduce_segments",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
@@ -159,6 +160,8 @@ def lib():
         L.fumi_hip_xpanel_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5
         L.fumi_hip_xpanel_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [c_float, c_void_p]
         L.fumi_hip_xpanel_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_epi_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_epi_plan_query.argtypes = [c_int] * 6 + [POINTER(c_int)] + [c_int] * 5 + [POINTER(c_int), c_int]
         L.fumi_hip_reduce_segments.argtypes = [c_void_p, c_void_p, c_int, PP, POINTER(c_int), POINTER(ctypes.c_long),
                                                POINTER(ctypes.c_long), PP, c_float]
         L.fumi_hip_adam_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
@@ -592,6 +595,42 @@ def maml_step(ws, x_s, y_s, x_q, y_q, params, T, alpha, first_order=False, *, ne
         _parr(g_params, "g_params") if need_grad else None)
     _check(rc, "fumi_hip_maml_step")
     return dict(logits=logits, preds=preds, preds_f=preds_f, loss_b=loss_b, acc_b=acc_b, g_params=g_params, stats=stats)
+
+
+# the plan of the episode chain (csrc/episode.hip: plan_episodes), in the order fumi_hip_epi_plan writes it.  An entry of a form the
+# plan did not take is 0.
+EPI_PLAN_KEYS = ("adapt", "AP", "query", "reverse", "P", "two_part", "nsq", "nss", "drop", "fixed_last",
+                 "ql_total", "al_total", "rl_total", "nu_adapt", "nu_query", "nu_fused", "nu_rev_init", "nu_rev_step")
+EPI_ADAPT_FORMS = {0: "none", 1: "lds", 2: "global"}
+EPI_QUERY_FORMS = {0: "fused_fixed", 1: "fused", 2: "lds", 3: "global"}
+EPI_REVERSE_FORMS = {0: "lds_fixed", 1: "lds", 2: "global"}
+# flags of fumi_hip_epi_plan_query (include/fumi_hip.h: FUMI_EPI_Q_*)
+EPI_Q_HEAD, EPI_Q_SIDE, EPI_Q_PROFILING, EPI_Q_AFTER_REVERSE, EPI_Q_W_OFF_SHIFT, EPI_Q_B_OFF_SHIFT = 1, 2, 4, 8, 8, 16
+
+
+def epi_plan():
+    """dict over EPI_PLAN_KEYS: the forms the episode chain of the last FuMI / MAML step of this process took (fumi_hip_epi_plan;
+    the form ids are named by EPI_ADAPT_FORMS / EPI_QUERY_FORMS / EPI_REVERSE_FORMS)."""
+    v = (c_int * len(EPI_PLAN_KEYS))()
+    _check(lib().fumi_hip_epi_plan(v, len(EPI_PLAN_KEYS)), "fumi_hip_epi_plan")
+    return {k: int(x) for k, x in zip(EPI_PLAN_KEYS, v)}
+
+
+def epi_plan_query(B, N, S, Qn, D, hid, T, *, need_grad=True, second_order=True, dropout=False, head=True, side=True,
+                   profiling=False, after_reverse=False, w_off=(), b_off=()):
+    """The same dict for a shape (fumi_hip_epi_plan_query): host arithmetic only, runs without a GPU.  ``w_off`` / ``b_off``: the
+    hidden layers whose weight / bias starts one float past a 16-byte boundary.  The environment knobs are the process's own."""
+    flags = ((EPI_Q_HEAD if head else 0) | (EPI_Q_SIDE if side else 0) | (EPI_Q_PROFILING if profiling else 0)
+             | (EPI_Q_AFTER_REVERSE if after_reverse else 0))
+    for i in w_off:
+        flags |= 1 << (EPI_Q_W_OFF_SHIFT + int(i))
+    for i in b_off:
+        flags |= 1 << (EPI_Q_B_OFF_SHIFT + int(i))
+    hid_arr = (c_int * len(hid))(*[int(x) for x in hid])
+    v = (c_int * len(EPI_PLAN_KEYS))()
+    _check(lib().fumi_hip_epi_plan_query(B, N, S, Qn, D, len(hid), hid_arr, int(T), int(bool(need_grad)), int(bool(second_order)),
+                                         int(bool(dropout)), flags, v, len(EPI_PLAN_KEYS)), "fumi_hip_epi_plan_query")
+    return {k: int(x) for k, x in zip(EPI_PLAN_KEYS, v)}
 
 
 AM3_KEYS = ["Wi", "bi", "G0", "g0", "G1", "g1", "H0", "h0", "H1", "h1"]

@@ -237,6 +237,29 @@ int fumi_hip_reduce_segments(fumi_ws_t* ws, fumi_stream_t stream, int n, const f
  *    blocks, rider rode, bwd kernel (1 64x64 guarded, 2 64x64 fast, 3 wide fp32, 4 wide split, 5 narrow swapped split), NB, SK,
  *    nsplit, kchunk, rider rode].  Host-side record only: no launch reads it. */
 int fumi_hip_xpanel_plan(int* plan, int n);
+/* The plan of the episode chain (csrc/episode.hip: plan_episodes; DESIGN.md sections 29 and 40) of the last FuMI / MAML step of this
+ * process that ran the chain, up to 18 ints:
+ *   [adapt form (0 none: the inner step runs inside the fused query kernel, 1 LDS-resident, 2 generic), adapt column parts AP,
+ *    query form (0 fused fixed-shape, 1 fused, 2 LDS-resident, 3 generic), reverse form (0 LDS-resident fixed-shape, 1 LDS-resident,
+ *    2 generic), reverse column parts P, backward X-panel pass in two launches (0 / 1), slabs of its query-row part, slabs of its
+ *    support-row part, inner-loop dropout (0 / 1), what fumi_hip_epi_fixed_last reports, floats of LDS of the query layout, of the
+ *    adapt layout, of the reverse layout, staging units of the adapt table, the query table, the fused query table, the reverse
+ *    sweep's first table, its per-step table].
+ * An entry that belongs to a form the plan did not take is 0.  Host-side record only: no launch reads it. */
+int fumi_hip_epi_plan(int* plan, int n);
+/* The same entries for a shape: host arithmetic only -- no workspace, no HIP call, runs without a GPU.  `dropout`: inner-loop
+ * dropout on (1) or off (0).  `flags` states what the shape cannot: FUMI_EPI_Q_HEAD the caller passes an initial head (every entry
+ * point of this header does), _SIDE the workspace has its second stream and fork / join events, _PROFILING phase timing is on,
+ * _AFTER_REVERSE the caller asks for an event after the reverse sweep (FUMI_OVERLAP bit 1); bit _W_OFF_SHIFT + i (_B_OFF_SHIFT + i):
+ * the weight (bias) of hidden layer i starts one float past a 16-byte boundary.  The environment knobs are the process's own. */
+#define FUMI_EPI_Q_HEAD 1
+#define FUMI_EPI_Q_SIDE 2
+#define FUMI_EPI_Q_PROFILING 4
+#define FUMI_EPI_Q_AFTER_REVERSE 8
+#define FUMI_EPI_Q_W_OFF_SHIFT 8
+#define FUMI_EPI_Q_B_OFF_SHIFT 16
+int fumi_hip_epi_plan_query(int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int T, int need_grad,
+        int second_order, int dropout, int flags, int* plan, int n);
 /* One fused launch of torch.optim.Adam's update (coupled L2 weight decay, bias correction; fumi/utils/utils.py:280-283) for
  * up to 32 tensors.  Pointer/size arrays are HOST arrays; `step` is the 1-based step count. */
 int fumi_hip_adam_step(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,
