@@ -147,6 +147,13 @@ class HipEngine:
                                          ce_weight=ce_weight, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
                                          grad_scale=grad_scale, dfeats=dfeats, gW=gW, gb=gb)
 
+    def cos_cls_head_step(self, feats, y_a, W, tau, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,
+                          gW=None, dtau=None):
+        """Fused cosine classifier head of supervised pre-training: mean cross-entropy of tau * cos(feats_m,
+        W_c) against the soft target, with tau [1] on the device; its predictions and the gradients for feats, W and tau."""
+        return hip.cos_cls_head_step(self._ws(feats), feats, y_a, W, tau, y_b=y_b, lam=lam, smoothing=smoothing, need_grad=need_grad,
+                                     grad_scale=grad_scale, dfeats=dfeats, gW=gW, dtau=dtau)
+
     def cos_proto_step(self, feats_s, y_s, feats_q, y_q, tau, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
                        dfeats_q=None, dtau=None, n_way=None):
         """Fused cosine nearest-centroid head with the temperature tau [1] on the device: mean cross-entropy of

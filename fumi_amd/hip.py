@@ -46,6 +46,7 @@ SYMBOLS = [
     "fumi_hip_euclid_proto_step", "fumi_hip_trans_proto_step",
     "fumi_hip_cls_head_step_distill",
     "fumi_hip_svm_head_step", "fumi_hip_svm_set_form", "fumi_hip_svm_get_fit",
+    "fumi_hip_cos_cls_head_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -252,6 +253,8 @@ def lib():
                                              + [c_void_p] * 8)
         L.fumi_hip_svm_set_form.argtypes = [c_int]
         L.fumi_hip_svm_get_fit.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2
+        L.fumi_hip_cos_cls_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
+                                                 + [c_float] + [c_void_p] * 6)
         _lib = L
     return _lib
 
@@ -1866,6 +1869,40 @@ def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0
                                              _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
            "fumi_hip_cls_head_step_soft")
     return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+
+
+def cos_cls_head_step(ws, feats, y_a, W, tau, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,
+                      gW=None, dtau=None, want_preds=True):
+    """The fused cosine classifier head (csrc/coshead.hip): mean cross-entropy of tau * cos(feats_m, W_c) against
+    the soft target of ``cls_head_step_soft`` (``y_b`` None: y_b = y_a, and lam must be 1), with ``tau`` [1] on the device.  Returns a
+    dict of GPU tensors: loss [1], correct [1] (count against y_a, float), preds [M] (first arg-max; None without want_preds) and, with
+    need_grad, dfeats [M,F], gW [C,F], dtau [1] = gradients of grad_scale * loss (written into the tensors given, else into new ones)."""
+    dev = _dev(feats)
+    if feats.dim() != 2 or W.dim() != 2:
+        raise FumiHipError("cos_cls_head_step: feats [M,F] and W [C,F] expected")
+    M, F = (int(v) for v in feats.shape)
+    C = int(W.shape[0])
+    _shape(W, (C, F), "W"); _shape(tau, (1,), "tau"); _shape(y_a, (M,), "y_a")
+    if y_b is not None:
+        _shape(y_b, (M,), "y_b")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.float32)
+    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
+    if need_grad:
+        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
+        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
+        dtau = torch.empty(1, device=dev, dtype=torch.float32) if dtau is None else dtau
+        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(dtau, (1,), "dtau")
+        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(dtau, "dtau")]
+    else:
+        dfeats = gW = dtau = None
+        grads = [None, None, None]
+    _check(lib().fumi_hip_cos_cls_head_step(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
+                                            _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
+                                            _f32(W, "W"), _f32(tau, "tau"), float(grad_scale), _f32(loss, "loss"),
+                                            _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
+           "fumi_hip_cos_cls_head_step")
+    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, dtau=dtau)
 
 
 def cls_head_step_distill(ws, feats, y_a, W, b, feats_t, W_t, b_t, *, temp, alpha, ce_weight, y_b=None, lam=1.0, smoothing=0.0,

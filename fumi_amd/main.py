@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.cli_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.run_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -282,6 +282,19 @@ def check_supported(args):
         raise ValueError(f"--distill_temp {d_temp} must be positive and finite")
     if not 0.0 <= d_alpha < float("inf") or not 0.0 <= d_ce < float("inf"):
         raise ValueError(f"--distill_alpha {d_alpha} and --distill_ce_weight {d_ce} must not be negative")
+    c_head, c_scale, c_fixed = (getattr(args, k, d) for k, d in (("pretrain_head", "linear"), ("pretrain_head_scale", 10.0),
+                                                                  ("pretrain_head_scale_fixed", False)))
+    if family != "pretrain" and (c_head != "linear" or c_scale != 10.0 or c_fixed):
+        raise ValueError("--pretrain_head, --pretrain_head_scale and --pretrain_head_scale_fixed choose the classifier of the "
+                         "supervised stage: they need --model pretrain")
+    if not (c_scale > 0.0 and c_scale < float("inf")):
+        raise ValueError(f"--pretrain_head_scale {c_scale} must be positive and finite")
+    if c_head != "cosine" and (c_scale != 10.0 or c_fixed):
+        raise ValueError("--pretrain_head_scale and --pretrain_head_scale_fixed set the scale of the cosine classifier: they need "
+                         "--pretrain_head cosine")
+    if c_head == "cosine" and d_ckpt:
+        raise NotImplementedError("--distill_checkpoint with --pretrain_head cosine: the distillation head is a form of the linear "
+                                  "head, a cosine student or teacher is not implemented")
     if d_ckpt and not os.path.isfile(d_ckpt):
         raise ValueError(f"--distill_checkpoint {d_ckpt} does not exist")
     if getattr(args, "encoder_checkpoint", None) and (family == "clip" or not raw):

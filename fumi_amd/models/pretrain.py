@@ -15,7 +15,13 @@ produce: the checkpoint with the best few-shot validation loss wins.  ``--encode
 
 Born-again distillation: ``Pretrain(distill=dict(temp=, alpha=, ce_weight=))`` with ``load_teacher(state_dict)``
 trains the classifier as the student of a frozen copy of an earlier generation.  Every step encodes the batch with the teacher first
-(no tape), then with the student (taped), and the distillation form of the head (``cls_head_step_distill``) takes both feature sets."""
+(no tape), then with the student (taped), and the distillation form of the head (``cls_head_step_distill``) takes both feature sets.
+
+The cosine classifier: ``Pretrain(head="cosine")`` (``--pretrain_head cosine``) trains the backbone in the metric a
+cosine few-shot stage compares in: ``classifier = nn.Linear(feature_dim, n_classes, bias=False)`` and one scale ``cls_scale`` [1], a
+parameter, or with ``head_scale_fixed`` a persistent buffer; the logits are ``cls_scale * cos(feats_m, classifier.weight_c)``.  Every
+training step runs the fused cosine head (``cos_cls_head_step``, csrc/coshead.hip), whose soft form covers label smoothing and the
+two-label mixes.  ``head="linear"`` is the model it was."""
 import math
 import os
 
@@ -36,8 +42,18 @@ from .common import _loss_acc
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
                  metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0,
-                 distill=None, svm=None):
+                 distill=None, svm=None, head="linear", head_scale=10.0, head_scale_fixed=False):
         super().__init__()
+        if head not in ("linear", "cosine"):
+            raise ValueError(f"the classifier head must be linear or cosine, got {head}")
+        if not (math.isfinite(float(head_scale)) and float(head_scale) > 0.0):
+            raise ValueError(f"the scale of the cosine classifier must be positive, got {head_scale}")
+        if head != "cosine" and (head_scale_fixed or float(head_scale) != 10.0):
+            raise ValueError(f"the classifier scale belongs to the cosine head, got head {head}")
+        if head == "cosine" and distill is not None:
+            raise NotImplementedError("the distillation head is a form of the linear head: a cosine student or teacher is not implemented")
+        self.head = head                                   # the training classifier (section 41); the few-shot metric is chosen apart
+        self.head_scale_fixed = bool(head_scale_fixed)
         self.svm_cfg = utils.svm_config(svm)               # fixed hyper-parameters of the SVM metric (section 39)
         self._svm = None
         self.distill = distill_config(distill)             # None, or the weights of the distillation loss (section 37)
@@ -76,7 +92,12 @@ class Pretrain(nn.Module):
         self.n_classes = int(n_classes)
         self.bn_group = int(bn_group)          # R: images per batch-statistics group of a training step
         self.num_ways = num_ways               # N of the validation / test episodes (None: read from the labels)
-        self.classifier = nn.Linear(self.conv.feature_dim, self.n_classes)
+        self.classifier = nn.Linear(self.conv.feature_dim, self.n_classes, bias=head == "linear")
+        if head == "cosine" and self.head_scale_fixed:
+            self.register_buffer("cls_scale", torch.tensor([float(head_scale)]))
+        elif head == "cosine":
+            self.cls_scale = nn.Parameter(torch.tensor([float(head_scale)]))
+        self._dscale = None
         self._image = (int(image_channels), int(image_size))
         self._flat = None
         self._pcache = None
@@ -84,19 +105,30 @@ class Pretrain(nn.Module):
     def backbone_module(self):
         return self.conv
 
+    def _head_params(self):
+        """The classifier's own parameters, in the order of the flat gradient buffer: weight and bias of the linear head; weight and
+        ``cls_scale`` of the cosine head, the weight alone where that scale is fixed (a buffer)."""
+        if self.head == "linear":
+            return [self.classifier.weight, self.classifier.bias]
+        return [self.classifier.weight] + ([] if self.head_scale_fixed else [self.cls_scale])
+
     def _step_params(self, need_grad):
-        """(detached classifier weight and bias, detached backbone tensors, flat gradient buffer | None), the same objects from step
-        to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
+        """(detached classifier weight and bias | weight and scale, detached backbone tensors, flat gradient buffer | None), the same
+        objects from step to step; rebuilt when a parameter object was replaced or moved (``_apply``)."""
         c = self._pcache
-        if c is None or not c[0].valid():
-            w, th = [self.classifier.weight, self.classifier.bias], self.conv.theta()
-            c = self._pcache = (ParamWatch(self, w + th), [p.detach() for p in w], [p.detach() for p in th])
+        fixed = self.head == "cosine" and self.head_scale_fixed
+        if c is None or not c[0].valid() or (fixed and c[1][1] is not self._buffers["cls_scale"]):
+            w, th = self._head_params(), self.conv.theta()
+            c = self._pcache = (ParamWatch(self, w + th), [p.detach() for p in w] + ([self._buffers["cls_scale"]] if fixed else []),
+                                [p.detach() for p in th])
             self._flat = None
         fg = None
         if need_grad:
             fg = self._flat
             if fg is None:
-                fg = self._flat = FlatGrads([self.classifier.weight, self.classifier.bias] + self.conv.theta(), extra=2)
+                fg = self._flat = FlatGrads(self._head_params() + self.conv.theta(), extra=2)
+                # the fixed scale has no slot in the flat buffer: its gradient is written beside it and read by nobody
+                self._dscale = torch.empty(1, device=fg.flat.device, dtype=torch.float32) if fixed else None
         return c[1], c[2], fg
 
     def _apply(self, fn, recurse=True):
@@ -122,6 +154,9 @@ class Pretrain(nn.Module):
         ``state_dict()``, the flat gradient buffer nor the optimizer."""
         if self.distill is None:
             raise ValueError("load_teacher needs a model built with distill=dict(temp=, alpha=, ce_weight=)")
+        if "cls_scale" in state_dict:
+            raise ValueError("the teacher's state_dict holds cls_scale: it was trained with the cosine classifier, which the "
+                             "distillation head (a form of the linear head) cannot take as a teacher")
         conv_t = self._new_backbone()
         own = {"conv." + k: v for k, v in conv_t.state_dict().items()}
         own["classifier.weight"], own["classifier.bias"] = self.classifier.weight, self.classifier.bias
@@ -177,8 +212,11 @@ class Pretrain(nn.Module):
             feats_t = torch.cat((t_s.view(half, -1), t_q.view(half, -1)))
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         feats = torch.cat((f_s.view(half, -1), f_q.view(half, -1)))                 # [M, F], the images' order
-        g_w, g_theta = fg.split(2)
-        if feats_t is not None:
+        g_w, g_theta = fg.split(len(w) - 1 if self.head == "cosine" and self.head_scale_fixed else len(w))
+        if self.head == "cosine":
+            out = eng.cos_cls_head_step(feats, y, w[0], w[1], y_b=y_b, lam=float(lam), smoothing=self.label_smoothing, need_grad=True,
+                                        grad_scale=1.0, gW=g_w[0], dtau=self._dscale if self.head_scale_fixed else g_w[1])
+        elif feats_t is not None:
             out = eng.cls_head_step_distill(feats, y, w[0], w[1], feats_t, w_t[0], w_t[1], temp=self.distill["temp"],
                                             alpha=self.distill["alpha"], ce_weight=self.distill["ce_weight"], y_b=y_b,
                                             lam=float(lam), smoothing=self.label_smoothing, need_grad=True, grad_scale=1.0,
@@ -287,6 +325,13 @@ def distill_config(cfg):
     return c
 
 
+def head_log(model):
+    """cls_scale of the cosine classifier, else nothing."""
+    if getattr(model, "head", "linear") != "cosine":
+        return {}
+    return {"cls_scale": float(model.cls_scale.detach()[0])}
+
+
 def distill_log(model):
     """train/loss_ce, train/loss_kd and train/teacher_agree (a fraction of the batch) of the last distillation step, else nothing."""
     out = getattr(model, "last_out", None)
@@ -313,7 +358,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
                 if is_best:
                     best_loss, best_batch_idx = val_loss, batch_idx
                 trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
-                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **trans, **clip_log(opt), **distill_log(model)}, step=batch_idx)
+                wandb.log({"val/acc": val_acc, "val/loss": val_loss, **trans, **clip_log(opt), **distill_log(model), **head_log(model)}, step=batch_idx)
                 utils.save_checkpoint({"batch_idx": batch_idx, "state_dict": model.state_dict(), "best_loss": best_loss,
                                        "optimizer": opt.state_dict(), "args": vars(args)}, is_best)
                 print(f"\nBatch {batch_idx + 1}/{args.epochs}: \ntrain/loss: {tl}, train/acc: {ta}"

@@ -134,6 +134,11 @@ _PRETRAIN_MIX_FLAGS = [     # regularisers of --model pretrain (DESIGN.md sectio
     ("--cutmix_alpha", dict(type=float, default=0.0, help="[--model pretrain] CutMix: box area fraction 1 - lam, lam ~ Beta(alpha, alpha) per training batch (0: off; with --mixup_alpha too, one of the two per batch)")),
     ("--mix_prob", dict(type=float, default=1.0, help="[--model pretrain] probability that a training batch is mixed at all")),
 ]
+_PRETRAIN_HEAD_FLAGS = [    # the cosine classifier of --model pretrain; a list of its own that run_parser() appends to cli_parser()'s
+    ("--pretrain_head", dict(type=str, choices=["linear", "cosine"], default="linear", help="[--model pretrain] the classifier the backbone is trained with: nn.Linear on the raw features, or a cosine classifier, --pretrain_head_scale * cos(feature, class weight), without a bias")),
+    ("--pretrain_head_scale", dict(type=float, default=10.0, help="[--pretrain_head cosine] the scale of the cosine logits: its initial value (learned), or with --pretrain_head_scale_fixed its value (positive)")),
+    ("--pretrain_head_scale_fixed", dict(action="store_true", help="[--pretrain_head cosine] keep --pretrain_head_scale fixed")),
+]
 
 
 def parser():
@@ -152,6 +157,15 @@ def cli_parser():
         if act.dest == "fewshot_head":
             act.choices = list(act.choices) + ["svm"]
     for flag, kw in _SVM_FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
+def run_parser():
+    """``cli_parser()`` and after every flag of it the --pretrain_head* flags: what ``main.parse_args`` reads.  ``cli_parser()`` and
+    ``parser()`` keep the flag sequences the earlier heads were written against."""
+    p = cli_parser()
+    for flag, kw in _PRETRAIN_HEAD_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -223,7 +237,10 @@ def init_model(args, dictionary, watch=True):
                                   transductive_steps=getattr(args, "transductive_steps", 0),
                                   distill=(dict(temp=getattr(args, "distill_temp", 4.0), alpha=getattr(args, "distill_alpha", 0.5),
                                                 ce_weight=getattr(args, "distill_ce_weight", 0.5))
-                                           if getattr(args, "distill_checkpoint", None) else None))
+                                           if getattr(args, "distill_checkpoint", None) else None),
+                                  **(dict(head="cosine", head_scale=getattr(args, "pretrain_head_scale", 10.0),
+                                          head_scale_fixed=getattr(args, "pretrain_head_scale_fixed", False))
+                                     if getattr(args, "pretrain_head", "linear") == "cosine" else {}))
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,

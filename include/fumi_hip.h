@@ -527,6 +527,29 @@ int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, i
         const float* W, const float* b, const float* feats_t, const float* W_t, const float* b_t,
         float kd_temp, float kd_alpha, float ce_weight, float grad_scale,
         float* loss, float* loss_parts, float* correct, float* agree, int64_t* preds, float* dfeats, float* gW, float* gb);
+/* The cosine classifier head of supervised pre-training (csrc/coshead.hip): the linear head above on unit
+ * vectors with a learned scale and no bias.  feats [M,F], y_a, y_b [M], W [C,F], tau [1] on the device.  With
+ * u_m = feats_m / max(|feats_m|, 1e-12), v_c = W_c / max(|W_c|, 1e-12) (norms in fp32), k[m,c] = u_m . v_c and t the soft target of
+ * fumi_hip_cls_head_step_soft (y_b == NULL means y_b = y_a, and lam must be 1; the hard target is y_b == NULL, lam = 1, smoothing = 0),
+ *     z = tau k,   loss = mean_m (lse(z_m) - sum_c t z),   dz = grad_scale / M * (softmax(z) - t),
+ *     dtau     = sum_{m,c} dz k,
+ *     dfeats_m = tau / |feats_m| * (sum_c dz[m,c] v_c - (sum_c dz[m,c] k[m,c]) u_m),
+ *     gW_c     = tau / |W_c|     * (sum_m dz[m,c] u_m - (sum_m dz[m,c] k[m,c]) v_c).
+ * loss [1], correct [1] = number of rows whose first arg-max equals y_a (float), preds [M] = first arg-max (may be NULL);
+ * dfeats [M,F], gW [C,F], dtau [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training form) or
+ * all three NULL (forward form: loss, correct and preds are bit-identical to the training form's).  Three launches: the reciprocal
+ * norms of the C + M rows, then the two launches of the linear head; k of a 16-row tile stays in LDS from the product through the
+ * softmax to dz and dfeats, dz / |feats_m| and dz k go to memory (workspace, 2 [M,C] floats) for gW.  Every sum has a fixed order and
+ * there are no floating-point atomics: two calls on the same inputs give the same bits.
+ * A row of feats or W whose norm is below 1e-12 is the zero direction: k = 0 along it and its gradient row is zero; nothing else is
+ * affected.  A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or any
+ * gradient, the divisor stays M.
+ * 1 <= M <= 4096, F % 32 == 0, 32 <= F <= 2048, 2 <= C <= 1024: FUMI_ENOTSUP / FUMI_EINVAL otherwise, before any launch; FUMI_EINVAL
+ * also for smoothing outside [0, 1), lam outside [0, 1], y_b == NULL with lam != 1, a NULL tau. */
+int fumi_hip_cos_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
+        const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
+        const float* W, const float* tau, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* dtau);
 /* ---- The episode heads (fumi_hip_cos_proto_step ... fumi_hip_trans_proto_step; shared code in csrc/fewshot_head.h) ----
  * LABELS, for all five: a label outside [0,N) sets FUMI_ST_LABEL_RANGE.  Such a query row adds nothing to the loss, the count or any
  * gradient while the divisor stays B * Qn; such a support row is left out exactly (of every mean, count, sum and fit) and gets a zero
