@@ -218,6 +218,13 @@ int fumi_hip_read_status(fumi_ws_t* ws, fumi_stream_t stream, int* status_out) {
 // ------------------------------------------------------------------------------------------------------------
 // FuMI
 // ------------------------------------------------------------------------------------------------------------
+// FUMI_OVERLAP bit 0: hypernetwork forward on the side stream beside xpanel_fwd, bit 1: its backward beside xpanel_bwd
+static void hyper_step_forks(bool side, int need_grad, bool* fork, bool* fork_bwd) {
+    static const int overlap = getenv("FUMI_OVERLAP") ? atoi(getenv("FUMI_OVERLAP")) : 0;
+    *fork_bwd = side && (overlap & 2) && need_grad;
+    *fork = side && (overlap & 1);
+}
+
 static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int Dt, int Ht,
         int T, float alpha, int tanh_head, int need_grad, float grad_scale, float dropout_p, uint64_t seed,
@@ -303,9 +310,9 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     // Off by default.  Measured at the bench shapes (ms per step): 0 -> 0.3605, 1 -> 0.366, 2 -> 0.361, 3 -> 0.3533: a cross-
     // stream fork + join costs ~15 us of event latency on this platform, about what hiding the small kernels saves, and the
     // hypernetwork's workgroups stretch the matrix pass they run beside (80 -> 87 us).  Kept as a knob for larger text towers.
-    static const int overlap = getenv("FUMI_OVERLAP") ? atoi(getenv("FUMI_OVERLAP")) : 0;
-    const bool fork_bwd = ws->side && (overlap & 2) && need_grad;
-    const bool fork = ws->side && (overlap & 1);       // forward fork
+    bool fork, fork_bwd;                               // forward fork, backward fork
+    hyper_step_forks(ws->side != nullptr, need_grad, &fork, &fork_bwd);
+    g_hyper_plan = HyperPlanRec{HYP_FWD_GEMM, 0, (R + 15) / 16, Ht % 64 ? 0 : Ht / 64, HYP_BWD_NONE, 0, 0};
     hipStream_t sh = fork ? ws->side : st;             // stream of the hypernetwork forward
     const HyperHead hd = {R, Dt, Ht, H1, tanh_head, phi, c, u, ub, h, hbar, hpb, ctext};      // (own carving: ws_f above)
     auto hyper_forward = [&]() -> int {
@@ -314,7 +321,10 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         {
             ProfScope ps(ws, sh, FUMI_PH_HYPER_FWD);
             r2 = hyper_lds ? launch_hyper_fwd(sh, R, Dt, Ht, H1, tanh_head, ctext, phi[0], phi[1], phi[2], phi[3], u, h, hfp, ws->hcnt) : FUMI_ENOTSUP;
-            if (r2 == FUMI_ENOTSUP) r2 = hyper_head_fwd_gemm(sh, hd);   // shapes outside the LDS-resident kernels: plain GEMMs
+            if (r2 == FUMI_ENOTSUP) {                                   // shapes outside the LDS-resident kernels: plain GEMMs
+                g_hyper_plan.fwd_form = HYP_FWD_GEMM; g_hyper_plan.fwd_inst = 0;
+                r2 = hyper_head_fwd_gemm(sh, hd);
+            }
             if (r2) return r2;
         }
         if (fork) HIP_TRY(hipEventRecord(ws->ev[1], sh));
@@ -354,6 +364,7 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         hyper_bwd_fused_args(R, Dt, Ht, H1, tanh_head, 1.f, ctext, u, h, hbar, phi[2], hbf, g_phi[0], g_phi[1], g_phi[2], g_phi[3],
                              &fin, &brider, text_grad ? ub : nullptr)) {
         fused_bwd = true;
+        g_hyper_plan.bwd_form = HYP_BWD_FUSED; g_hyper_plan.bwd_dpasses = hyper_bwd_dpasses(Dt);     // (HYP_BWD_RODE where xpanel_bwd carries it)
         p.bwd_rider = &brider;
         p.bwd_rider_fallback = [](void* c) -> int { BwdCtx* x = (BwdCtx*)c; return launch_hyper_bwd_fused(x->st, *x->a); };
         p.hook_ctx2 = &bctx;
@@ -370,12 +381,14 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
     if (hyper_lds) {
         int rc2 = launch_hyper_bwd(sh, R, Dt, Ht, H1, tanh_head, grad_scale, ctext, u, h, hbar, phi[2], ub, hpart,
                                    g_phi[0], g_phi[1], g_phi[2], g_phi[3], &fin);
-        if (rc2 != FUMI_ENOTSUP) return rc2;
+        if (rc2 != FUMI_ENOTSUP) { g_hyper_plan.bwd_form = HYP_BWD_TWO_LAUNCH; return rc2; }
     }
     text_gemm_here = false;
+    g_hyper_plan.bwd_form = HYP_BWD_GEMM;
     return hyper_head_bwd_gemm(sh, hd, grad_scale, g_phi, text_grad);    // plain GEMMs (the text-gradient GEMM among them)
     }();
     if (rc) return rc;
+    g_hyper_plan.text_grad = !text_grad ? 0 : text_gemm_here ? 1 : 2;
     if (text_gemm_here && (rc = hyper_head_text_grad_gemm(sh, hd, grad_scale, text_grad))) return rc;
     if (fork_bwd) {                                                  // join: the caller's stream owns every result again
         HIP_TRY(hipEventRecord(ws->ev[3], sh));
@@ -386,6 +399,66 @@ static int fumi_step_impl(fumi_ws_t* ws, fumi_stream_t stream,
         if ((rc = launch_reduce_multi_final(ws, st, fin))) return rc;      // (+ a deferred optimizer step and publication)
     }
     return FUMI_OK;
+}
+
+constexpr int HYPER_PLAN_N = 7;
+static int hyper_plan_out(const HyperPlanRec& r, int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    const int v[HYPER_PLAN_N] = {r.fwd_form, r.fwd_inst, r.nrb, r.nch, r.bwd_form, r.bwd_dpasses, r.text_grad};
+    for (int i = 0; i < n && i < HYPER_PLAN_N; ++i) plan[i] = v[i];
+    return FUMI_OK;
+}
+int fumi_hip_hyper_plan(int* plan, int n) { return hyper_plan_out(g_hyper_plan, plan, n); }
+
+// The record fumi_step_impl leaves for a shape, by the predicates it and the launchers decide with, in the order they are asked.
+// Workspace arrays are aligned and present, the X-panel operands are aligned, no embedding bag is pending, the per-layer and
+// two-launch forms' staging tables are taken to fit.
+int fumi_hip_hyper_plan_query(int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int Dt, int Ht, int T, int need_grad,
+                              int flags, int* plan, int n) {
+    if (!hid || n_hidden < 1 || n_hidden > FUMI_MAX_HIDDEN || B < 1 || N < 1 || S < 1 || Qn < 1 || D < 1 || Dt < 1 || Ht < 1 || T < 0)
+        return FUMI_EINVAL;
+    for (int i = 0; i < n_hidden; ++i) if (hid[i] < 1) return FUMI_EINVAL;
+    const int h0 = hid[0], R = B * N, H1 = hid[n_hidden - 1] + 1;
+    const bool side = (flags & FUMI_HYPER_Q_SIDE) != 0, want_text = need_grad && (flags & FUMI_HYPER_Q_TEXT_GRAD);
+    const bool c_off = (flags & FUMI_HYPER_Q_CLS_TEXT_OFF) != 0;
+    bool off[4];
+    for (int i = 0; i < 4; ++i) off[i] = ((flags >> (FUMI_HYPER_Q_PHI_OFF_SHIFT + i)) & 1) != 0;
+    const bool al_fwd = !(c_off || off[0] || off[2] || off[1]);        // c | A0 | A1 | b0 | u
+    const bool al_bwd = !(c_off || off[2]);                            // c | u | A1 | part | ub_out
+    bool fork, fork_bwd;
+    hyper_step_forks(side, need_grad, &fork, &fork_bwd);
+    HyperPlanRec r{HYP_FWD_GEMM, 0, (R + 15) / 16, Ht % 64 ? 0 : Ht / 64, HYP_BWD_NONE, 0, 0};
+    const bool hyper_lds = hyper_lds_fits(R, Dt, Ht, H1) != 0;
+    const int nblk = 8 * (Ht / 64) * ((r.nrb + 7) / 8);                // (hyper_fwd_split_args / hyper_bwd_fused_args)
+    // forward: the rider where the step offers one and the forward X-panel launch carries it, else the own launch
+    bool rode = false;
+    if (!fork && hyper_lds && hyper_fwd_split_ok(R, Dt, Ht, H1, al_fwd, true)) {
+        const int kernel = xpanel_fwd_kernel_id(D, h0, true, xpanel_fwd_has_planes(D, h0), 1);
+        if (xpanel_fwd_carries_rider(kernel, nblk, Dt, fwd_ldx(Dt))) {
+            rode = true;
+            r.fwd_form = kernel == 5 ? HYP_FWD_RODE_PRESPLIT : HYP_FWD_RODE_SPLIT; r.fwd_inst = HF_RIDER_KS;
+        }
+    }
+    if (!rode) r.fwd_form = hyper_fwd_own_form(R, Dt, Ht, H1, al_fwd, true, &r.fwd_inst);
+    if (!need_grad) return hyper_plan_out(r, plan, n);
+    // backward: the fused form (segments of the final reduction: none yet) as a rider or alone, else two launches, else GEMMs
+    if (!fork_bwd && hyper_bwd_fused_ok(R, Dt, Ht, H1, al_bwd, true, 0)) {
+        int ep[18];
+        const int rc = fumi_hip_epi_plan_query(B, N, S, Qn, D, n_hidden, hid, T, 1, 1, 0,
+                                               FUMI_EPI_Q_HEAD | (side ? FUMI_EPI_Q_SIDE : 0), ep, 18);
+        if (rc) return rc;
+        int kc, nsq, kcq, nss;
+        if (ep[5]) xpanel_bwd_two_part_split(B, S, Qn, D, h0, &nsq, &kcq, &nss, &kc);       // the rider sits in the support-row launch
+        else (void)xpanel_bwd_nsplit(B, S, Qn, D, h0, &kc);
+        r.bwd_form = xpanel_bwd_carries_rider(D, h0, true, kc, nblk, Dt, H1) ? HYP_BWD_RODE : HYP_BWD_FUSED;
+        r.bwd_dpasses = hyper_bwd_dpasses(Dt);
+        r.text_grad = want_text ? 1 : 0;
+    } else if (hyper_lds) {
+        r.bwd_form = HYP_BWD_TWO_LAUNCH; r.text_grad = want_text ? 1 : 0;
+    } else {
+        r.bwd_form = HYP_BWD_GEMM; r.text_grad = want_text ? 2 : 0;
+    }
+    return hyper_plan_out(r, plan, n);
 }
 
 int fumi_hip_fumi_step(fumi_ws_t* ws, fumi_stream_t stream,

@@ -348,6 +348,25 @@ int launch_hyper_bwd(hipStream_t st, int R, int Dt, int Ht, int H1, int tanh_hea
                      const float* u, const float* h, const float* hbar, const float* A1, float* ub, float* part,
                      float* gA0, float* gb0, float* gA1, float* gb1, ReduceSegs* defer = nullptr);
 
+// ---- the hypernetwork's plan record (include/fumi_hip.h: fumi_hip_hyper_plan; named once by hip.HYPER_PLAN_KEYS): what the
+// hypernetwork of the last FuMI step took, written on the host where each decision is taken, never read by a launch.
+enum { HYP_FWD_GEMM = 0, HYP_FWD_PER_LAYER = 1, HYP_FWD_FUSED = 2, HYP_FWD_SPLIT = 3, HYP_FWD_RODE_SPLIT = 4, HYP_FWD_RODE_PRESPLIT = 5 };
+enum { HYP_BWD_NONE = 0, HYP_BWD_GEMM = 1, HYP_BWD_TWO_LAUNCH = 2, HYP_BWD_FUSED = 3, HYP_BWD_RODE = 4 };
+struct HyperPlanRec { int fwd_form, fwd_inst, nrb, nch, bwd_form, bwd_dpasses, text_grad; };
+extern HyperPlanRec g_hyper_plan;      // (hyper.hip)
+// the predicates the launch path decides with; fumi_hip_hyper_plan_query (api.hip) asks the same ones.  `al`: the pointers the form
+// reads as float4 are 16-byte aligned; `have_ws`: partial-product room and arrival counters (forward), slab room (backward) exist
+bool hyper_fwd_split_ok(int R, int Dt, int Ht, int H1, bool al, bool have_ws);
+int hyper_fwd_own_form(int R, int Dt, int Ht, int H1, bool al, bool have_ws, int* inst);   // HYP_FWD_GEMM .. HYP_FWD_SPLIT
+bool hyper_bwd_fused_ok(int R, int Dt, int Ht, int H1, bool al, bool have_ws, int segs_n);
+int hyper_bwd_dpasses(int Dt);
+// the forward X-panel kernel a shape takes (XpPlan.fwd_kernel: 1 .. 5) and whether it carries a forward rider of nblk workgroups;
+// the wide backward kernel a shape takes and whether it carries a backward rider
+int xpanel_fwd_kernel_id(int D, int h0, bool aligned, bool planes, int ksplit);
+bool xpanel_fwd_carries_rider(int kernel, int nblk, int Dt, int ldx);
+bool xpanel_bwd_carries_rider(int D, int h0, bool aligned, int kchunk, int nblk, int Dt, int H1);
+bool xpanel_fwd_has_planes(int D, int h0);        // xpanel_planes() gives room for this shape (allocation aside)
+
 // small kernels shared by the entry points (episode.hip)
 int launch_class_text_select(hipStream_t st, int B, int N, int S, int Dt, const float* text_s, const int64_t* y_s,
                              float* out, int* status);

@@ -2171,6 +2171,7 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
         int rider_done = 0;
         if ((rc = launch_xpanel_fwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, p.W[0], w.A0, w.G, rows, p.fwd_rider, &rider_done,
                                     nullptr, nullptr, xpanel_planes(ws, p.B, p.S, p.D, h0), p.glove))) return rc;
+        // (not carried: the producer's own launch -- launch_hyper_fwd records the form it takes in g_hyper_plan)
         if (p.fwd_rider && !rider_done && p.fwd_rider_fallback && (rc = p.fwd_rider_fallback(p.hook_ctx))) return rc;
     }
     if (p.after_xpanel_fwd && (rc = p.after_xpanel_fwd(p.hook_ctx))) return rc;
@@ -2232,7 +2233,10 @@ int run_episodes(fumi_ws* ws, hipStream_t st, const EpisodeProblem& p) {
             if ((rc = launch_xpanel_bwd(st, p.B, p.S, p.Qn, p.D, h0, p.x_s, p.x_q, w.A0bar, slabs, kc, ns, rows, p.bwd_rider,
                                         &rider_done))) return rc;
         }
-        if (p.bwd_rider && !rider_done && p.bwd_rider_fallback && (rc = p.bwd_rider_fallback(p.hook_ctx2))) return rc;
+        if (p.bwd_rider && !rider_done && p.bwd_rider_fallback) {                  // not carried: the same grid as its own launch
+            g_hyper_plan.bwd_form = HYP_BWD_FUSED;
+            if ((rc = p.bwd_rider_fallback(p.hook_ctx2))) return rc;
+        }
         if (p.defer_reduce && p.defer_reduce->n < 24 && p.defer_reduce->scale == p.grad_scale) p.defer_reduce->add(slabs, ns, slab, slab, p.gW[0]);
         else if ((rc = launch_reduce_slabs(st, slabs, ns, slab, slab, p.grad_scale, p.gW[0]))) return rc;
     }

@@ -329,12 +329,21 @@ size_t hyper_fwd_workspace_floats(int R, int Ht, int H1) {
     return (size_t)((R + HB - 1) / HB) * (Ht / 64 + 1) * HB * H1 + 64;
 }
 
+HyperPlanRec g_hyper_plan = {};
+
+// the split forward's shapes: float4 rows, whole 64-column chunks, at most two 16-column tiles of layer 1 per wave, a counter per row block
+bool hyper_fwd_split_ok(int R, int Dt, int Ht, int H1, bool al, bool have_ws) {
+    if ((Dt & 3) || (Ht & 63) || R < 1 || H1 < 1) return false;
+    const int nrb = (R + HB - 1) / HB;
+    return have_ws && al && Dt <= 768 && H1 <= 128 && nrb <= FUMI_HCNT;
+}
+static int hyper_fwd_split_ks(int Dt) { return Dt <= 320 ? 20 : 48; }      // register steps of the own launch's instance
+
 int hyper_fwd_split_args(int R, int Dt, int Ht, int H1, int tanh_head, const float* c, const float* A0, const float* b0,
                          const float* A1, const float* b1, float* u, float* h, float* hpart, int* cnt, HyperFwdArgs* a) {
-    if ((Dt & 3) || (Ht & 63) || R < 1 || H1 < 1) return 0;
     const bool al16_ = (((uintptr_t)c | (uintptr_t)A0 | (uintptr_t)A1 | (uintptr_t)b0 | (uintptr_t)u) & 15) == 0;
+    if (!hyper_fwd_split_ok(R, Dt, Ht, H1, al16_, hpart && cnt)) return 0;
     const int nrb = (R + HB - 1) / HB, nch = Ht / 64;
-    if (!(hpart && cnt && al16_ && Dt <= 768 && H1 <= 128 && nrb <= FUMI_HCNT)) return 0;
     a->d = FwdDims{R, Dt, Ht, H1, fwd_ldx(Dt), tanh_head, 0u, 0u, 1.f};
     a->c = c; a->A0 = A0; a->b0 = b0; a->A1 = A1; a->b1 = b1; a->u = u; a->h = h; a->hpart = hpart; a->cnt = cnt;
     a->nrb = nrb; a->nblk = 8 * nch * ((nrb + 7) / 8);
@@ -343,7 +352,7 @@ int hyper_fwd_split_args(int R, int Dt, int Ht, int H1, int tanh_head, const flo
 
 int launch_hyper_fwd_split(hipStream_t st, const HyperFwdArgs& a) {
     const size_t lds = hyper_fwd_split_lds_bytes(a.d.ldx);
-    if (a.d.Dt <= 320) {
+    if (hyper_fwd_split_ks(a.d.Dt) == 20) {
         FUMI_SET_DYN_LDS(hyper_fwd_split_kernel<20>, lds);
         hipLaunchKernelGGL(hyper_fwd_split_kernel<20>, dim3(a.nblk), dim3(256), lds, st, a);
     } else {
@@ -354,21 +363,35 @@ int launch_hyper_fwd_split(hipStream_t st, const HyperFwdArgs& a) {
     return FUMI_OK;
 }
 
-int launch_hyper_fwd(hipStream_t st, int R, int Dt, int Ht, int H1, int tanh_head, const float* c, const float* A0,
-                     const float* b0, const float* A1, const float* b1, float* u, float* h, float* hpart, int* cnt) {
-    if (!hyper_lds_fits(R, Dt, Ht, H1)) return FUMI_ENOTSUP;
+// The form the hypernetwork forward takes as its own launch(es), and the instance of that form (fumi_hip_hyper_plan's fwd_inst):
+// split KS; fused 10 NT + NCH; per layer the column chunk of layer 0; 0 for plain GEMMs (FUMI_ENOTSUP to the caller).
+int hyper_fwd_own_form(int R, int Dt, int Ht, int H1, bool al, bool have_ws, int* inst) {
+    *inst = 0;
+    if (!hyper_lds_fits(R, Dt, Ht, H1)) return HYP_FWD_GEMM;
     // FUMI_HYPER_FWD: 2 (default) one launch, layer-0 columns split over workgroups; 1 one launch, a workgroup per row block;
     // 0 one launch per layer
     static const int hsplit = getenv("FUMI_HYPER_FWD") ? atoi(getenv("FUMI_HYPER_FWD")) : 2;
-    {
-        HyperFwdArgs a;
-        if (hsplit == 2 && hyper_fwd_split_args(R, Dt, Ht, H1, tanh_head, c, A0, b0, A1, b1, u, h, hpart, cnt, &a))
-            return launch_hyper_fwd_split(st, a);
-    }
-    const int no_fuse = hsplit == 0;
-    const bool al = (((uintptr_t)c | (uintptr_t)A0 | (uintptr_t)A1 | (uintptr_t)b0 | (uintptr_t)u) & 15) == 0;
+    if (hsplit == 2 && hyper_fwd_split_ok(R, Dt, Ht, H1, al, have_ws)) { *inst = hyper_fwd_split_ks(Dt); return HYP_FWD_SPLIT; }
     const int nch = (Dt + FCH * 16 - 1) / (FCH * 16);
-    if (!no_fuse && Ht <= 256 && nch <= 4 && al) {
+    if (hsplit != 0 && Ht <= 256 && nch <= 4 && al) { *inst = 10 * (Ht <= 128 ? 1 : 2) + nch; return HYP_FWD_FUSED; }
+    *inst = lin_chunk(Dt);
+    return HYP_FWD_PER_LAYER;
+}
+
+int launch_hyper_fwd(hipStream_t st, int R, int Dt, int Ht, int H1, int tanh_head, const float* c, const float* A0,
+                     const float* b0, const float* A1, const float* b1, float* u, float* h, float* hpart, int* cnt) {
+    const bool al = (((uintptr_t)c | (uintptr_t)A0 | (uintptr_t)A1 | (uintptr_t)b0 | (uintptr_t)u) & 15) == 0;
+    int inst;
+    const int form = hyper_fwd_own_form(R, Dt, Ht, H1, al, hpart && cnt, &inst);
+    g_hyper_plan.fwd_form = form; g_hyper_plan.fwd_inst = inst;
+    if (form == HYP_FWD_GEMM) return FUMI_ENOTSUP;
+    if (form == HYP_FWD_SPLIT) {
+        HyperFwdArgs a;
+        if (!hyper_fwd_split_args(R, Dt, Ht, H1, tanh_head, c, A0, b0, A1, b1, u, h, hpart, cnt, &a)) return FUMI_EINVAL;
+        return launch_hyper_fwd_split(st, a);
+    }
+    const int nch = (Dt + FCH * 16 - 1) / (FCH * 16);
+    if (form == HYP_FWD_FUSED) {
         FwdDims d{R, Dt, Ht, H1, fwd_ldx(Dt), tanh_head};
         const size_t lds = (size_t)HB * (d.ldx + wg_ld(Ht)) * sizeof(float);
         const int nrb = (R + HB - 1) / HB;
@@ -442,13 +465,18 @@ size_t hyper_bwd_fused_workspace_floats(int R, int Dt, int Ht, int H1) {
     return nrb * ((size_t)H1 * Ht + H1 + Ht + (size_t)Ht * Dt) + 256;        // (Dt = 0: without the layer-0 weight slabs)
 }
 
+bool hyper_bwd_fused_ok(int R, int Dt, int Ht, int H1, bool al, bool have_ws, int segs_n) {
+    static const int on = getenv("FUMI_HYPER_BWD") ? atoi(getenv("FUMI_HYPER_BWD")) : 1;     // 0: the two-launch form (bwd1 + bwd0)
+    if (!on || R < 1 || (Dt & 3) || (Ht & 63) || H1 < 1 || !have_ws || segs_n + 4 > 24 || !al) return false;
+    return (size_t)hyper_bwd_lds_floats(Dt, H1) * 4 <= 150 * 1024;
+}
+int hyper_bwd_dpasses(int Dt) { return (Dt + HBW_DC - 1) / HBW_DC; }       // passes of hyper_bwd_body over the layer-0 slab's columns
+
 int hyper_bwd_fused_args(int R, int Dt, int Ht, int H1, int tanh_head, float mscale, const float* c, const float* u, const float* h,
                          const float* hbar, const float* A1, float* part, float* gA0, float* gb0, float* gA1, float* gb1,
                          ReduceSegs* segs, HyperBwdArgs* a, float* ub_out) {
-    static const int on = getenv("FUMI_HYPER_BWD") ? atoi(getenv("FUMI_HYPER_BWD")) : 1;     // 0: the two-launch form (bwd1 + bwd0)
-    if (!on || R < 1 || (Dt & 3) || (Ht & 63) || H1 < 1 || !part || !segs || segs->n + 4 > 24) return 0;
-    if ((((uintptr_t)c | (uintptr_t)u | (uintptr_t)A1 | (uintptr_t)part | (uintptr_t)ub_out) & 15) != 0) return 0;
-    if ((size_t)hyper_bwd_lds_floats(Dt, H1) * 4 > 150 * 1024) return 0;
+    const bool al = (((uintptr_t)c | (uintptr_t)u | (uintptr_t)A1 | (uintptr_t)part | (uintptr_t)ub_out) & 15) == 0;
+    if (!segs || !hyper_bwd_fused_ok(R, Dt, Ht, H1, al, part != nullptr, segs->n)) return 0;
     const int nrb = (R + HB - 1) / HB, nch = Ht / 64;
     a->R = R; a->Dt = Dt; a->Ht = Ht; a->H1 = H1; a->tanh_head = tanh_head; a->mscale = mscale;
     a->c = c; a->u = u; a->h = h; a->hbar = hbar; a->A1 = A1;

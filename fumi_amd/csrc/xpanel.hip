@@ -1310,6 +1310,25 @@ bool xpanel_fwd_presplits(int B, int S, int Qn, int D, int h0, const float* x_s,
     return aligned && planes && xpanel_fwd_ps_ok(D, h0) && D / SBK >= PS_MIN_SLABS;
 }
 
+static int xp_use_sb() { static const int v = getenv("FUMI_XP_SB") ? atoi(getenv("FUMI_XP_SB")) : 1; return v; }
+static int xp_sbn() { static const int v = getenv("FUMI_XP_SBN") ? atoi(getenv("FUMI_XP_SBN")) : 2; return v; }      // ring depth (tuning knob)
+static int xp_ride() { static const int v = getenv("FUMI_XP_RIDER") ? atoi(getenv("FUMI_XP_RIDER")) : 1; return v; }  // 0: never carry the hypernetwork
+bool xpanel_fwd_has_planes(int D, int h0) { return xpanel_fwd_ps_ok(D, h0); }
+// the kernel launch_xpanel_fwd takes (XpPlan.fwd_kernel): 5 pre-split, 4 per-tile split, 3 fp32 MFMA, 2 generic fast, 1 generic guarded
+int xpanel_fwd_kernel_id(int D, int h0, bool aligned, bool planes, int ksplit) {
+    if (aligned && planes && ksplit == 1 && xpanel_fwd_ps_ok(D, h0) && D / SBK >= PS_MIN_SLABS) return 5;
+    if (aligned && D % SBK == 0 && xp_use_sb()) return 4;
+    if (aligned && D % FBK == 0) return 3;
+    return aligned && D % BK == 0 ? 2 : 1;
+}
+// the split hypernetwork forward (hyper_fwd.h) rides in the two split-bf16 kernels, in the LDS their staging rings leave it
+bool xpanel_fwd_carries_rider(int kernel, int nblk, int Dt, int ldx) {
+    if (!xp_ride() || nblk <= 0 || nblk % 8 != 0 || Dt > HF_RIDER_MAXDT) return false;
+    if (kernel == 5) return hyper_fwd_split_lds_bytes(ldx) <= sizeof(unsigned short) * 2 * 3 * 128 * SROW;
+    if (kernel == 4) return hyper_fwd_split_lds_bytes(ldx) <= sizeof(unsigned short) * 2 * 2 * 3 * SPLANE && xp_sbn() <= 2;
+    return false;
+}
+
 int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const float* x_s, const float* x_q,
                       const float* W0, float* A0, float* G, const XRows* rows, const HyperFwdArgs* rider, int* rider_done,
                       float* parts, int* parts_unreduced, unsigned short* planes, GlovePending* glove) {
@@ -1323,14 +1342,16 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
     const int nper = (B + 7) / 8;
     const int gram_tiles = tiles_n - h0 / 64;        // (plan record: 64-column tiles that hold a Gram column; the pre-split form counts 32s)
     const bool aligned = al16(p.x_s) && al16(p.x_q) && al16(W0);
-    static const int use_sb = getenv("FUMI_XP_SB") ? atoi(getenv("FUMI_XP_SB")) : 1;
+    const int use_sb = xp_use_sb();
     const int ks = xpanel_fwd_ksplit(B, S, Qn, D, h0, G != nullptr);
     if (ks > 1 && parts && aligned && D % SBK == 0 && use_sb) { p.ksplit = ks; p.part_stride = (long)B * (S + Qn) * h0; A0 = parts; }
     const dim3 grid(8 * nper * tiles_m * tiles_n * p.ksplit);
     static const int nst = getenv("FUMI_XP_NST") ? atoi(getenv("FUMI_XP_NST")) : 2;      // staging ring depth (tuning knob)
     // Default: split-bf16 (error against fp64 at the fp32 MFMA kernel's level: DESIGN.md) -- with the column operand split once per
     // step where the shape allows (50 + 6 us at the bench shapes), else per tile (70 us).  FUMI_XP_SB=0: the fp32 MFMA kernel (78 us).
-    const bool presplit = aligned && planes && p.ksplit == 1 && xpanel_fwd_ps_ok(D, h0) && D / SBK >= PS_MIN_SLABS;
+    const int kernel = xpanel_fwd_kernel_id(D, h0, aligned, planes != nullptr, p.ksplit);
+    const bool presplit = kernel == 5;
+    const bool ridden = rider && rider_done && xpanel_fwd_carries_rider(kernel, rider->nblk, rider->d.Dt, rider->d.ldx);
     if (glove && !presplit) {                                   // (callers check xpanel_fwd_presplits first: not expected)
         glove->on = 0;
         if (glove->vec) hipLaunchKernelGGL(xpanel_presplit_glove_kernel<true>, dim3((unsigned)glove->a.R), dim3(512), glove->lds, st, p, 0, nullptr, nullptr, glove->a, glove->a.R);
@@ -1340,7 +1361,6 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
     if (presplit) {      // (split contractions: the 64 x 64 kernel)
         // column operands split once (bf16 planes in fragment order), then tiles that only split X: 64 x 128 against W0, 128 x 32
         // against the support rows
-        static const int ride = getenv("FUMI_XP_RIDER") ? atoi(getenv("FUMI_XP_RIDER")) : 1;
         const int cbg = (p.gcols + 31) / 32;
         unsigned short* Wp = planes; unsigned short* Xp = planes + ps_w0_bytes(D, h0) / sizeof(unsigned short);
         const long nfrag = ((long)h0 / 32 + (long)B * cbg) * (D / 16);      // one wave per fragment
@@ -1354,33 +1374,32 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         const int tm = (S + Qn + 63) / 64, tg = (S + Qn + 127) / 128;
         const unsigned nwg = 8u * nper * (tm * (h0 / 128) * p.ksplit + tg * cbg);
         HyperFwdArgs none; memset(&none, 0, sizeof(none));
-        if (ride && rider && rider_done && rider->nblk > 0 && rider->nblk % 8 == 0 && rider->d.Dt <= HF_RIDER_MAXDT &&
-            hyper_fwd_split_lds_bytes(rider->d.ldx) <= sizeof(unsigned short) * 2 * 3 * 128 * SROW) {
+        if (ridden) {
             hipLaunchKernelGGL((xpanel_fwd_ps_kernel<2, true>), dim3(nwg + rider->nblk), dim3(256), 0, st, p, Wp, Xp, A0, G, tm, tg, cbg, *rider, g_trace);
             *rider_done = 1;
+            g_hyper_plan.fwd_form = HYP_FWD_RODE_PRESPLIT; g_hyper_plan.fwd_inst = HF_RIDER_KS;
         } else {
             hipLaunchKernelGGL((xpanel_fwd_ps_kernel<2, false>), dim3(nwg), dim3(256), 0, st, p, Wp, Xp, A0, G, tm, tg, cbg, none, g_trace);
         }
         xp_plan_fwd(5, 2, p.ksplit, cbg, rider_done && *rider_done);
-    } else if (aligned && D % SBK == 0 && use_sb) {
-        static const int sbn = getenv("FUMI_XP_SBN") ? atoi(getenv("FUMI_XP_SBN")) : 2;          // ring depth (tuning knob)
-        static const int ride = getenv("FUMI_XP_RIDER") ? atoi(getenv("FUMI_XP_RIDER")) : 1;     // 0: never carry the hypernetwork forward
+    } else if (kernel == 4) {
+        const int sbn = xp_sbn();
         HyperFwdArgs none; memset(&none, 0, sizeof(none));
-        if (ride && rider && rider_done && rider->nblk > 0 && rider->nblk % 8 == 0 && rider->d.Dt <= HF_RIDER_MAXDT &&
-            hyper_fwd_split_lds_bytes(rider->d.ldx) <= sizeof(unsigned short) * 2 * 2 * 3 * SPLANE && sbn <= 2) {
+        if (ridden) {
             hipLaunchKernelGGL((xpanel_fwd_sb_kernel<2, true>), dim3(grid.x + rider->nblk), dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, *rider);
             *rider_done = 1;
+            g_hyper_plan.fwd_form = HYP_FWD_RODE_SPLIT; g_hyper_plan.fwd_inst = HF_RIDER_KS;
         }
         else if (sbn <= 2) hipLaunchKernelGGL((xpanel_fwd_sb_kernel<2, false>), grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, none);
         else hipLaunchKernelGGL((xpanel_fwd_sb_kernel<4, false>), grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, none);
         xp_plan_fwd(4, sbn <= 2 ? 2 : 4, p.ksplit, gram_tiles, rider_done && *rider_done);
-    } else if (aligned && D % FBK == 0) {
+    } else if (kernel == 3) {
         if (nst == 1) hipLaunchKernelGGL(xpanel_fwd_kernel<1>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
         else if (nst == 2) hipLaunchKernelGGL(xpanel_fwd_kernel<2>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
         else hipLaunchKernelGGL(xpanel_fwd_kernel<3>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, g_trace);
         xp_plan_fwd(3, nst == 1 ? 1 : nst == 2 ? 2 : 3, p.ksplit, gram_tiles, 0);
     }
-    else if (aligned && D % BK == 0) {
+    else if (kernel == 2) {
         hipLaunchKernelGGL(xpanel_fwd_generic_kernel<true>, grid, dim3(256), 0, st, p, A0, G, tiles_m, tiles_n, 0);
         xp_plan_fwd(2, 2, p.ksplit, gram_tiles, 0);
     } else {
@@ -1445,6 +1464,30 @@ void xpanel_bwd_two_part_split(int B, int S, int Qn, int D, int h0, int* nsq, in
     *kcs = (int)kc; *nss = (int)((K + kc - 1) / kc);
 }
 
+// the wide backward kernel launch_xpanel_bwd takes for aligned operands (XpPlan.bwd_kernel: 4 split with NB / SK, 3 fp32; 0: neither,
+// which carries no rider) and the dynamic LDS it is launched with
+struct XpBwdWide { int kernel, NB, SK; size_t lds; };
+static XpBwdWide xpanel_bwd_wide_form(int D, int h0, int kchunk) {
+    static const int bsb = getenv("FUMI_XPB_SB") ? atoi(getenv("FUMI_XPB_SB")) : 1;          // 0: the fp32-MFMA kernel
+    if (xpanel_bwd_narrow(D, h0) && kchunk % BSK == 0) return {0, 1, 16, 0};
+    if (!xpanel_bwd_wide(D, h0)) return {0, 1, 32, 0};
+    if (bsb && kchunk % BSK == 0) {
+        static const int bnb = getenv("FUMI_XPB_NB") ? atoi(getenv("FUMI_XPB_NB")) : 2;      // 2: 256 x 128 tiles (default), 1: 256 x 64
+        static const int bsk = getenv("FUMI_XPB_SK") ? atoi(getenv("FUMI_XPB_SK")) : 16;     // 32: two k-steps per slab (NB = 1)
+        const int NB = (bnb == 2 && D % 128 == 0) ? 2 : 1;
+        const int SKv = (NB == 1 && bsk == 32 && kchunk % 32 == 0) ? 32 : 16;
+        return {4, NB, SKv, 2 * (size_t)bsb_buf_ushorts(NB, SKv) * sizeof(unsigned short)};
+    }
+    return {3, 1, 32, 2 * (32 * 256 + 32 * 64) * sizeof(float)};
+}
+static bool xpanel_bwd_rider_fits(const XpBwdWide& f, int nblk, int Dt, int H1) {
+    return xp_ride() && f.kernel && nblk > 0 && nblk % 8 == 0 && (size_t)hyper_bwd_lds_floats(Dt, H1) * 4 <= f.lds;
+}
+bool xpanel_bwd_carries_rider(int D, int h0, bool aligned, int kchunk, int nblk, int Dt, int H1) {
+    const bool fast = (D % 64 == 0) && (h0 % 64 == 0) && aligned;
+    return fast && xpanel_bwd_rider_fits(xpanel_bwd_wide_form(D, h0, kchunk), nblk, Dt, H1);
+}
+
 int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const float* x_s, const float* x_q,
                       const float* Abar, float* slabs, int kchunk, int nsplit, const XRows* rows, const HyperBwdArgs* rider,
                       int* rider_done) {
@@ -1464,20 +1507,16 @@ int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         return FUMI_OK;
     }
     if (fast && xpanel_bwd_wide(D, h0)) {
+        const XpBwdWide wf = xpanel_bwd_wide_form(D, h0, kchunk);
         const size_t lds_bytes = 2 * (32 * 256 + 32 * 64) * sizeof(float);
         const int tn = D / 64, tm = h0 / 256;
         const unsigned nwg = 8 * ((nsplit + 7) / 8) * tn * tm;
-        static const int ride = getenv("FUMI_XP_RIDER") ? atoi(getenv("FUMI_XP_RIDER")) : 1;     // 0: never carry the hypernetwork backward
-        static const int bsb = getenv("FUMI_XPB_SB") ? atoi(getenv("FUMI_XPB_SB")) : 1;          // 0: the fp32-MFMA kernel
-        if (bsb && kchunk % BSK == 0) {
-            static const int bnb = getenv("FUMI_XPB_NB") ? atoi(getenv("FUMI_XPB_NB")) : 2;      // 2: 256 x 128 tiles (default), 1: 256 x 64
-            static const int bsk = getenv("FUMI_XPB_SK") ? atoi(getenv("FUMI_XPB_SK")) : 16;     // 32: two k-steps per slab (NB = 1)
-            const int NB = (bnb == 2 && D % 128 == 0) ? 2 : 1;
-            const int SKv = (NB == 1 && bsk == 32 && kchunk % 32 == 0) ? 32 : 16;
-            const size_t lds_sb = 2 * (size_t)bsb_buf_ushorts(NB, SKv) * sizeof(unsigned short);
+        const bool ridden = rider && rider_done && xpanel_bwd_rider_fits(wf, rider->nblk, rider->Dt, rider->H1);
+        if (ridden) g_hyper_plan.bwd_form = HYP_BWD_RODE;
+        if (wf.kernel == 4) {
+            const int NB = wf.NB, SKv = wf.SK;
+            const size_t lds_sb = wf.lds;
             const unsigned nwg2 = 8 * ((nsplit + 7) / 8) * (D / (64 * NB)) * tm;
-            const bool ridden = ride && rider && rider_done && rider->nblk > 0 && rider->nblk % 8 == 0 &&
-                                (size_t)hyper_bwd_lds_floats(rider->Dt, rider->H1) * 4 <= lds_sb;
             HyperBwdArgs none; memset(&none, 0, sizeof(none));
 #define BSB_LAUNCH(RID_, NB_, SK_)                                                                                      \
             do {                                                                                                        \
@@ -1492,8 +1531,7 @@ int launch_xpanel_bwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
             LAUNCH_CHECK();
             return FUMI_OK;
         }
-        if (ride && rider && rider_done && rider->nblk > 0 && rider->nblk % 8 == 0 &&
-            (size_t)hyper_bwd_lds_floats(rider->Dt, rider->H1) * 4 <= lds_bytes) {
+        if (ridden) {
             FUMI_SET_DYN_LDS(xpanel_bwd256_kernel<true>, lds_bytes);
             hipLaunchKernelGGL(xpanel_bwd256_kernel<true>, dim3(nwg + rider->nblk), dim3(512), lds_bytes, st, p, Abar, slabs,
                                kchunk, nsplit, tn, tm, *rider);

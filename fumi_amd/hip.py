@@ -23,7 +23,7 @@ SYMBOLS = [
     "fumi_hip_set_profiling", "fumi_hip_set_profiling_every", "fumi_hip_get_profile", "fumi_hip_phase_name",
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
     "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
-    "fumi_hip_epi_plan", "fumi_hip_epi_plan_query",
+    "fumi_hip_epi_plan", "fumi_hip_epi_plan_query", "fumi_hip_hyper_plan", "fumi_hip_hyper_plan_query",
     "fumi_hip_reduce_segments",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
     "fumi_hip_adamw_step", "fumi_hip_adamw_step_deferred", "fumi_hip_sgd_step", "fumi_hip_sgd_step_deferred",
@@ -163,6 +163,8 @@ def lib():
         L.fumi_hip_xpanel_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_epi_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_epi_plan_query.argtypes = [c_int] * 6 + [POINTER(c_int)] + [c_int] * 5 + [POINTER(c_int), c_int]
+        L.fumi_hip_hyper_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_hyper_plan_query.argtypes = [c_int] * 6 + [POINTER(c_int)] + [c_int] * 5 + [POINTER(c_int), c_int]
         L.fumi_hip_reduce_segments.argtypes = [c_void_p, c_void_p, c_int, PP, POINTER(c_int), POINTER(ctypes.c_long),
                                                POINTER(ctypes.c_long), PP, c_float]
         L.fumi_hip_adam_step.argtypes = [c_void_p, c_void_p, c_int, PP, PP, PP, PP, POINTER(ctypes.c_long)] + [c_float] * 5 + [c_int]
@@ -634,6 +636,38 @@ def epi_plan_query(B, N, S, Qn, D, hid, T, *, need_grad=True, second_order=True,
     _check(lib().fumi_hip_epi_plan_query(B, N, S, Qn, D, len(hid), hid_arr, int(T), int(bool(need_grad)), int(bool(second_order)),
                                          int(bool(dropout)), flags, v, len(EPI_PLAN_KEYS)), "fumi_hip_epi_plan_query")
     return {k: int(x) for k, x in zip(EPI_PLAN_KEYS, v)}
+
+
+# what the hypernetwork of the last FuMI step took (csrc/hyper.hip, the rider branches of csrc/xpanel.hip), in the order
+# fumi_hip_hyper_plan writes it
+HYPER_PLAN_KEYS = ("fwd_form", "fwd_inst", "nrb", "nch", "bwd_form", "bwd_dpasses", "text_grad")
+HYPER_FWD_FORMS = {0: "gemm", 1: "per_layer", 2: "fused", 3: "split", 4: "rode_split", 5: "rode_presplit"}
+HYPER_BWD_FORMS = {0: "none", 1: "gemm", 2: "two_launch", 3: "fused", 4: "rode"}
+HYPER_TEXT_GRAD = {0: "none", 1: "gemm_after", 2: "in_fallback"}
+# flags of fumi_hip_hyper_plan_query (include/fumi_hip.h: FUMI_HYPER_Q_*)
+HYPER_Q_SIDE, HYPER_Q_TEXT_GRAD, HYPER_Q_CLS_TEXT_OFF, HYPER_Q_PHI_OFF_SHIFT = 1, 2, 4, 8
+
+
+def hyper_plan():
+    """dict over HYPER_PLAN_KEYS: the forms the hypernetwork of the last FuMI step of this process took (fumi_hip_hyper_plan)."""
+    v = (c_int * len(HYPER_PLAN_KEYS))()
+    _check(lib().fumi_hip_hyper_plan(v, len(HYPER_PLAN_KEYS)), "fumi_hip_hyper_plan")
+    return {k: int(x) for k, x in zip(HYPER_PLAN_KEYS, v)}
+
+
+def hyper_plan_query(B, N, S, Qn, D, hid, Dt, Ht, T, *, need_grad=True, want_text_grad=False, side=True, cls_text_off=False,
+                     phi_off=()):
+    """The same dict for a shape (fumi_hip_hyper_plan_query): host arithmetic only, runs without a GPU.  ``cls_text_off`` /
+    ``phi_off``: the class text rows / the hypernetwork tensors (indices into phi) that start one float past a 16-byte boundary.
+    The environment knobs are the process's own."""
+    flags = (HYPER_Q_SIDE if side else 0) | (HYPER_Q_TEXT_GRAD if want_text_grad else 0) | (HYPER_Q_CLS_TEXT_OFF if cls_text_off else 0)
+    for i in phi_off:
+        flags |= 1 << (HYPER_Q_PHI_OFF_SHIFT + int(i))
+    hid_arr = (c_int * len(hid))(*[int(x) for x in hid])
+    v = (c_int * len(HYPER_PLAN_KEYS))()
+    _check(lib().fumi_hip_hyper_plan_query(B, N, S, Qn, D, len(hid), hid_arr, int(Dt), int(Ht), int(T), int(bool(need_grad)), flags,
+                                           v, len(HYPER_PLAN_KEYS)), "fumi_hip_hyper_plan_query")
+    return {k: int(x) for k, x in zip(HYPER_PLAN_KEYS, v)}
 
 
 AM3_KEYS = ["Wi", "bi", "G0", "g0", "G1", "g1", "H0", "h0", "H1", "h1"]

@@ -260,6 +260,28 @@ int fumi_hip_epi_plan(int* plan, int n);
 #define FUMI_EPI_Q_B_OFF_SHIFT 16
 int fumi_hip_epi_plan_query(int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int T, int need_grad,
         int second_order, int dropout, int flags, int* plan, int n);
+/* What the hypernetwork (hyper_net = Linear -> ReLU -> Linear [-> Tanh], csrc/hyper.hip) of the last
+ * fumi_hip_fumi_step* of this process took, up to 7 ints:
+ *   [forward form (0 plain GEMMs, 1 one launch per layer, 2 one launch with a workgroup per row block, 3 one launch with layer 0's
+ *    columns split over workgroups, 4 that split form riding in the per-tile split forward X-panel launch, 5 riding in the pre-split
+ *    one), instance of the form (register steps KS 20 / 48 / 24 for 3, 4, 5; 10 NT + NCH for 2; the column chunk of layer 0 for 1;
+ *    else 0), 16-row blocks, 64-column hidden chunks (0: the hidden width is no multiple of 64), backward form (0 none: no gradients
+ *    asked for, 1 plain GEMMs, 2 two launches, 3 one launch, 4 that launch riding in the backward X-panel launch), passes over the
+ *    text width of the layer-0 weight slab (forms 3, 4; else 0), text gradient (0 none, 1 a GEMM after the backward's own launches,
+ *    2 inside the plain-GEMM backward)].
+ * Host-side record only: no launch reads it. */
+int fumi_hip_hyper_plan(int* plan, int n);
+/* The same entries for a shape: host arithmetic only -- no workspace, no HIP call, runs without a GPU; it asks the predicates the
+ * launch path asks.  `flags`: FUMI_HYPER_Q_SIDE the workspace has its second stream (FUMI_OVERLAP then moves the hypernetwork
+ * there), _TEXT_GRAD the caller passes g_cls_text, _CLS_TEXT_OFF the class text rows start one float past a 16-byte boundary,
+ * bit _PHI_OFF_SHIFT + i: phi[i] does.  The X-panel operands and every workspace array count as aligned; the environment knobs
+ * are the process's own. */
+#define FUMI_HYPER_Q_SIDE 1
+#define FUMI_HYPER_Q_TEXT_GRAD 2
+#define FUMI_HYPER_Q_CLS_TEXT_OFF 4
+#define FUMI_HYPER_Q_PHI_OFF_SHIFT 8
+int fumi_hip_hyper_plan_query(int B, int N, int S, int Qn, int D, int n_hidden, const int* hid, int Dt, int Ht, int T, int need_grad,
+        int flags, int* plan, int n);
 /* One fused launch of torch.optim.Adam's update (coupled L2 weight decay, bias correction; fumi/utils/utils.py:280-283) for
  * up to 32 tensors.  Pointer/size arrays are HOST arrays; `step` is the 1-based step count. */
 int fumi_hip_adam_step(fumi_ws_t* ws, fumi_stream_t stream, int n_tensors, float* const* params,

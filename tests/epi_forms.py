@@ -319,8 +319,15 @@ def query_plan(name, **grow):
 
 
 # ---- inputs, the oracle, the step ------------------------------------------------------------------------------------------------
+def _case(name):
+    """A row of this table by id, or a row of another table that shares these helpers (tests/hyper_forms.py), passed as the row itself
+    with its seed under 'seed'."""
+    return CASES[name] if isinstance(name, str) else name
+
+
 def make_inputs(name):
-    c, seed = CASES[name], SEEDS[name]
+    c = _case(name)
+    seed = SEEDS[name] if isinstance(name, str) else c["seed"]
     ep = cg.make_episodes(seed, c["B"], c["N"], c["K"], c["Q"], c["D"], c["Dt"], blocked=bool(seed & 1))
     if c["entry"] == "fumi":
         theta, phi = cg.make_fumi_params(seed, c["D"], c["hid"], c["Dt"], c["Ht"])
@@ -335,18 +342,22 @@ def names(c):
     return [f"net.lin_{i}.{k}" for i in range(len(c["hid"])) for k in ("weight", "bias")] + ["net.lin_final.weight", "net.lin_final.bias"]
 
 
-def oracle(name, inputs, dtype):
-    """oracle.fumi_ref on the CPU in ``dtype``: dict(logits, loss_b, preds, grads or None)."""
-    c = CASES[name]
+def oracle(name, inputs, dtype, text_grad=False):
+    """oracle.fumi_ref on the CPU in ``dtype``: dict(logits, loss_b, preds, grads or None); ``text_grad`` (FuMI rows with gradients):
+    also g_text_s [B,S,Dt], the gradient of the same loss with respect to the support text rows."""
+    c = _case(name)
     ep, a, b = inputs
     f = lambda t: t.to(dtype)
     leaf = lambda ts: [t.clone().to(dtype).requires_grad_(True) for t in ts]
     if c["entry"] == "fumi":
         p = c["dropout"]
         drop = (lambda bb, call, layer, rows, width: dropout_mask(DROP_SEED, p, bb, call, layer, rows, width).to(dtype)) if p > 0 else None
-        r = R.fumi_meta_step(leaf(a), leaf(b), f(ep["text_s"]), f(ep["x_s"]), ep["y_s"], f(ep["x_q"]), ep["y_q"], c["N"], c["T"], cg.ALPHA,
-                             c["tanh"], need_grad=c["need_grad"], dropout=drop)
+        text = f(ep["text_s"]).clone().requires_grad_(True) if text_grad and c["need_grad"] else f(ep["text_s"])
+        r = R.fumi_meta_step(leaf(a), leaf(b), text, f(ep["x_s"]), ep["y_s"], f(ep["x_q"]), ep["y_q"], c["N"], c["T"], cg.ALPHA,
+                             c["tanh"], need_grad=c["need_grad"], dropout=drop, extra=[text] if text.requires_grad else None)
         grads = (r["g_theta"] + r["g_phi"]) if c["need_grad"] else None
+        if text.requires_grad:
+            return dict(logits=r["logits"], loss_b=r["loss_b"], preds=r["preds"], grads=grads, g_text_s=r["g_extra"][0])
     else:
         r = R.maml_meta_step(leaf(a), f(ep["x_s"]), ep["y_s"], f(ep["x_q"]), ep["y_q"], c["T"], cg.ALPHA, c["first_order"],
                              need_grad=c["need_grad"])
@@ -391,7 +402,7 @@ def errors(name, got, ref):
     e = {"logits": rel_to_max(got["logits"].cpu(), ref["logits"]), "loss_b": rel_to_max(got["loss_b"].cpu(), ref["loss_b"])}
     if ref["grads"] is not None:
         fl = grad_floor(ref["grads"])
-        for n, a, r in zip(names(CASES[name]), got["grads"], ref["grads"]):
+        for n, a, r in zip(names(_case(name)), got["grads"], ref["grads"]):
             e[n] = rel_to_max(a.cpu(), r, fl)
     return e
 

@@ -61,7 +61,8 @@ def test_argtypes_agree_with_the_header_argument_by_argument():
     L = hip.lib()
     protos = _prototypes()
     assert sorted(protos) == _declared_symbols(), "a declaration of include/fumi_hip.h was not parsed as a prototype"
-    assert sum(1 for a in protos.values() if a) >= 89
+    assert sum(1 for a in protos.values() if a) >= 91
+    assert {"fumi_hip_hyper_plan", "fumi_hip_hyper_plan_query"} <= set(protos)
     for name, want in protos.items():
         argtypes = getattr(L, name).argtypes
         if not want:
@@ -90,3 +91,20 @@ def test_product_path_fails_loudly_without_gpu_tensors():
         hip.Workspace("cpu")
     with pytest.raises(hip.FumiHipError):
         hip.glove_bag(None, torch.zeros(1, 2, dtype=torch.int64), torch.zeros(3, 4), 0)
+
+
+def test_hyper_plan_entry_points_without_gpu():
+    """fumi_hip_hyper_plan copies at most n entries and refuses a NULL array; the query is host arithmetic: it answers without a GPU
+    and refuses, before anything else, what the step itself refuses."""
+    from fumi_amd import hip
+    L = hip.lib()
+    v = (ctypes.c_int * 9)(*([-7] * 9))
+    assert L.fumi_hip_hyper_plan(v, 3) == 0 and list(v)[3:] == [-7] * 6
+    assert L.fumi_hip_hyper_plan(None, 7) != 0 and L.fumi_hip_hyper_plan(v, -1) != 0
+    assert len(hip.HYPER_PLAN_KEYS) == 7 and set(hip.hyper_plan()) == set(hip.HYPER_PLAN_KEYS)
+    p = hip.hyper_plan_query(2, 5, 5, 5, 24, [8, 16], 20, 64, 1, want_text_grad=True)
+    assert p == dict(fwd_form=3, fwd_inst=20, nrb=1, nch=1, bwd_form=3, bwd_dpasses=1, text_grad=1)
+    hid = (ctypes.c_int * 1)(0)
+    assert L.fumi_hip_hyper_plan_query(2, 5, 5, 5, 24, 0, hid, 20, 64, 1, 1, 0, v, 7) != 0          # no hidden layer
+    assert L.fumi_hip_hyper_plan_query(2, 5, 5, 5, 24, 1, hid, 0, 64, 1, 1, 0, v, 7) != 0           # Dt = 0
+    assert L.fumi_hip_hyper_plan_query(2, 5, 5, 5, 24, 1, None, 20, 64, 1, 1, 0, v, 7) != 0
