@@ -18,9 +18,9 @@ from oracle import conv4_manual as M
 from oracle import conv4_ref as C
 from oracle import fumi_ref as R
 from helpers import rel_to_max, safe_margin_mask
+from conv4_forms import (GRAD_TOL, LOGIT_TOL, MARGIN, _case, _check_grads, _g, _match_episodes, check_every_intermediate)
 
 pytestmark = pytest.mark.gpu
-LOGIT_TOL, GRAD_TOL, MARGIN = 1e-4, 1e-3, 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -35,13 +35,13 @@ def ws(dev):
     return hip.Workspace.get(dev)
 
 
-def _g(t, dev):
-    return t.to(dev).contiguous()
-
-
 # ---- the three convolution products ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("Mi,H,W", [(3, 10, 10), (2, 21, 21), (5, 42, 42), (1, 7, 13), (40, 5, 5)])
+@pytest.mark.parametrize("Mi,H,W", [(3, 10, 10), (2, 21, 21), (5, 42, 42), (1, 7, 13), (40, 5, 5),
+                                    (2, 6, 6), (4, 6, 6), (1, 1, 1), (3, 2, 37)])
 def test_conv3x3_products_match_torch(Mi, H, W, dev, ws):
+    """The last four rows sit on the pixel tiling (128 padded pixels per workgroup, slab = tile + 2 (W + 3) halo pixels):
+    2 x 8 x 8 = 128 padded pixels = exactly one full tile; 4 x 8 x 8 = two full tiles, the second one's halo past the end of the
+    tensor; a single pixel (9 padded pixels); a short wide map with a halo of 40 pixels on 3 x 4 x 39 = 468 pixels."""
     from fumi_amd import hip
     g = torch.Generator().manual_seed(Mi * 100 + H)
     x = torch.randn(Mi, 64, H, W, generator=g)
@@ -89,85 +89,6 @@ def test_small_exported_ops(dev, ws):
 
 
 # ---- every intermediate of a meta-step ------------------------------------------------------------------------------------
-def _unpad(flat, B, Mi, H, W):
-    """padded channels-last [B*M][(H+2)(W+2)][64] -> NCHW [B, M, 64, H, W]; also returns the largest |border| value."""
-    t = flat.reshape(B, Mi, H + 2, W + 2, 64)
-    inner = t[:, :, 1:-1, 1:-1, :]
-    frame = t.clone()
-    frame[:, :, 1:-1, 1:-1, :] = 0
-    return inner.permute(0, 1, 4, 2, 3), float(frame.abs().max())
-
-
-def _case(seed, B, N, K, Q, Cin, H, W, nblk):
-    ep = C.make_image_episodes(seed, B, N, K, Q, Cin, H, W, 12)
-    theta = C.make_conv4_params(seed, Cin, 64, nblk)
-    Fd = C.feature_dim(H, W, 64, nblk)
-    return ep, theta, Fd
-
-
-def _slab_to_torch(slab, Cin, nblk):
-    """One episode's parameter slab in the engine's canonical layouts (csrc/conv4.hip: W1 [64][32], W_l [tap][co][ci], BN weight,
-    BN bias per block) -> tensors in torch layouts."""
-    out, off = [], 0
-    for l in range(nblk):
-        if l == 0:
-            out.append(slab[off:off + 2048].reshape(64, 32)[:, :Cin * 9].reshape(64, Cin, 3, 3)); off += 2048
-        else:
-            out.append(slab[off:off + 36864].reshape(9, 64, 64).permute(1, 2, 0).reshape(64, 64, 3, 3)); off += 36864
-        out += [slab[off:off + 64], slab[off + 64:off + 128]]; off += 128
-    return out
-
-
-TIE_TOL = 3e-6
-
-
-def _match_episodes(hip, ws, dev, logits, theta, heads, ep, T, alpha, first_order, need_grad=True):
-    """Per episode: the float64 autograd-free sweep (oracle/conv4_manual.py, tied to autograd at 1e-9) against the engine's query
-    logits and its per-episode meta-gradients (fumi_hip_conv4_probe).  A ReLU / arg-max decision within fp32 noise of a tie may
-    fall either way in two correct fp32 implementations: the forward value does not move, but the gradient routed through that
-    unit switches on or off and moves a weight gradient by O(1/sqrt(#terms)) (tests/dev/probe_conv4_flip.py).  With ~5e5
-    decisions per case such a tie (margin < 3e-6) is present in most cases, so the checker enumerates the decisions of the
-    float64 sweep that lie within TIE_TOL of a tie (at most 6) and requires the engine to agree with ONE assignment of them, at
-    the usual tolerances.  Returns the matched per-episode (logits, loss, d theta, d head, trace)."""
-    import itertools
-    B, Cin, nblk = logits.shape[0], ep["x_s"].shape[2], len(theta) // 3
-    th64 = [t.double() for t in theta]
-    if need_grad:
-        bar = hip.conv4_probe(ws, dev, -1, 4).cpu().reshape(B, -1)
-        barh = hip.conv4_probe(ws, dev, -1, 5).cpu().reshape(B, heads.shape[1], -1)
-    out = []
-    for b in range(B):
-        args = (th64, heads[b].double(), ep["x_s"][b].double(), ep["y_s"][b], ep["x_q"][b].double(), ep["y_q"][b], T, alpha, first_order)
-        tr0 = {}
-        M.episode_grads(*args, trace=tr0)
-        amb = M.ambiguous_decisions(tr0, TIE_TOL, limit=6)
-        subsets = [()] + [c for k in range(1, len(amb) + 1) for c in itertools.combinations(amb, k)]
-        got = _slab_to_torch(bar[b], Cin, nblk) + [barh[b]] if need_grad else None
-        errs = None
-        for sub in subsets:
-            tr = {}
-            zq, loss, bth, bh = M.episode_grads(*args, trace=tr, flips=M.flips_of(sub))
-            e_log = rel_to_max(logits[b], zq)
-            e_g = 0.0
-            if need_grad:
-                ref = bth + [bh]
-                floor = max(0.02 * max(float(r.abs().max()) for r in ref), 1e-9)
-                e_g = max(rel_to_max(a, r, floor) for a, r in zip(got, ref))
-            errs = errs or (e_log, e_g)
-            if e_log <= LOGIT_TOL and e_g <= GRAD_TOL:
-                out.append((zq, loss, bth, bh, tr))
-                break
-        else:
-            raise AssertionError(f"episode {b}: logits / gradient error {errs[0]:.2e} / {errs[1]:.2e} against the float64 sweep, and no "
-                                 f"assignment of its {len(amb)} near-tie decisions (margins {[f'{m[0]:.1e}' for m in amb]}) explains it")
-    return out
-
-
-def _cmp(name, got, ref, tol=2e-4):
-    e = rel_to_max(got, ref, floor=1e-6)
-    assert e <= tol, f"{name}: rel-to-max error {e:.3e}"
-
-
 @pytest.fixture(params=["fused-block1", "plain"])
 def c1mode(request):
     """Block 1 either recomputed band by band (csrc/conv_first.hip, the default) or through the plain passes."""
@@ -180,87 +101,10 @@ def c1mode(request):
 @pytest.mark.parametrize("shape", [(3, 12, 12, 2), (1, 20, 20, 3)])
 def test_every_intermediate_matches_the_manual_sweep(shape, dev, ws, c1mode):
     from fumi_amd import hip
-    Cin, H, W, nblk = shape
-    fused = c1mode == "fused-block1"
-    B, N, K, Q, T, alpha = 2, 3, 2, 3, 2, 0.05
-
-    ep, theta, Fd = _case(11, B, N, K, Q, Cin, H, W, nblk)
-    S, Qn = N * K, N * Q
-    g = torch.Generator().manual_seed(5)
-    head = torch.cat([torch.randn(N, Fd, generator=g) * 0.2, torch.rand(N, 1, generator=g) * 0.2 - 0.1], 1)
-    p = theta + [head[:, :-1].contiguous(), head[:, -1].contiguous()]
-    out = hip.maml_conv4_step(ws, _g(ep["x_s"], dev), _g(ep["y_s"], dev), _g(ep["x_q"], dev), _g(ep["y_q"], dev),
-                              [_g(t, dev) for t in p], T, alpha)
-    assert ws.read_status() == 0
-    probe = lambda pa, kind, blk=0: hip.conv4_probe(ws, dev, pa, kind, blk).cpu()
-    # the float64 sweep of each episode, with its near-tie decisions taken the way the engine took them
-    traces = [m[4] for m in _match_episodes(hip, ws, dev, out["logits"].cpu(), theta, head[None].expand(B, -1, -1), ep, T, alpha, False)]
-    geo = [(H >> l, W >> l) for l in range(nblk + 1)]
-    for t in range(T + 1):                                              # support steps, then the query pass
-        Mi = S if t < T else Qn
-        tapes = [tr["tapes"][t] if t < T else tr["query"] for tr in traces]
-        for l in range(nblk):
-            Hl, Wl = geo[l]
-            if not (fused and l == 0):                              # (the fused path never stores block 1's maps)
-                u, bu = _unpad(probe(t, 0, l), B, Mi, Hl, Wl)
-                _cmp(f"pass {t} block {l} u", u, torch.stack([tp["blocks"][l]["u"] for tp in tapes]))
-                assert bu == 0.0, f"pass {t} block {l}: conv output border not zero"
-            xo = probe(t, 1, l)
-            ref_xo = torch.stack([tp["blocks"][l]["xo"] for tp in tapes])
-            if l + 1 < nblk:
-                xo, bx = _unpad(xo, B, Mi, *geo[l + 1])
-                assert bx == 0.0
-            else:
-                xo = xo.reshape(B, Mi, -1); ref_xo = ref_xo.reshape(B, Mi, -1)
-            _cmp(f"pass {t} block {l} pooled", xo, ref_xo)
-        _cmp(f"pass {t} p", probe(t, 5).reshape(B, Mi, N), torch.stack([tp["p"] for tp in tapes]))
-        _cmp(f"pass {t} dz", probe(t, 6).reshape(B, Mi, N), torch.stack([tp["dz"] for tp in tapes]))
-        for l in reversed(range(nblk)):
-            Hl, Wl = geo[l]
-            dxo = probe(t, 3, l)
-            ref = torch.stack([tp["blocks"][l]["dxo"] for tp in tapes])
-            if l + 1 < nblk:
-                dxo, _ = _unpad(dxo, B, Mi, *geo[l + 1])
-            else:
-                dxo = dxo.reshape(ref.shape)
-            _cmp(f"pass {t} block {l} dxo", dxo, ref)
-            if fused and l == 0:
-                continue
-            du, bd = _unpad(probe(t, 2, l), B, Mi, Hl, Wl)
-            _cmp(f"pass {t} block {l} du", du, torch.stack([tp["blocks"][l]["du"] for tp in tapes]))
-            assert bd == 0.0, f"pass {t} block {l}: du border not zero"
-    # tangent scratch of the last Hessian-vector product (inner step 0)
-    tp0 = [tr["tapes"][0] for tr in traces]
-    for l in range(nblk):
-        Hl, Wl = geo[l]
-        if not (fused and l == 0):
-            ud, _ = _unpad(probe(T + 1, 0, l), B, S, Hl, Wl)
-            _cmp(f"tangent block {l} u'", ud, torch.stack([tp["blocks"][l]["ud"] for tp in tp0]))
-        xod = probe(T + 1, 1, l)
-        ref = torch.stack([tp["blocks"][l]["xod"] for tp in tp0])
-        xod = _unpad(xod, B, S, *geo[l + 1])[0] if l + 1 < nblk else xod.reshape(ref.shape)
-        _cmp(f"tangent block {l} x'", xod, ref)
-    for l in reversed(range(nblk)):
-        Hl, Wl = geo[l]
-        dxod = probe(T + 1, 3, l)
-        ref = torch.stack([tp["blocks"][l]["dxod"] for tp in tp0])
-        dxod = _unpad(dxod, B, S, *geo[l + 1])[0] if l + 1 < nblk else dxod.reshape(ref.shape)
-        _cmp(f"tangent block {l} dxo'", dxod, ref)
-        if fused and l == 0:
-            continue
-        dud, bd = _unpad(probe(T + 1, 2, l), B, S, Hl, Wl)
-        _cmp(f"tangent block {l} du'", dud, torch.stack([tp["blocks"][l]["dud"] for tp in tp0]))
-        assert bd == 0.0
+    check_every_intermediate(hip, ws, dev, shape, 2, 3, 2, 3, 2, 0.05, 11, c1mode == "fused-block1")
 
 
 # ---- whole meta-steps --------------------------------------------------------------------------------------
-def _check_grads(names, got, ref):
-    floor = max(0.02 * max(float(r.abs().max()) for r in ref), 1e-7)
-    for n, a, r in zip(names, got, ref):
-        e = rel_to_max(a.cpu(), r, floor)
-        assert e <= GRAD_TOL, f"grad {n}: rel-to-max error {e:.3e}"
-
-
 @pytest.mark.parametrize("T,first_order,need_grad", [(1, False, True), (3, False, True), (2, True, True), (0, False, True), (2, False, False)])
 def test_maml_conv4_step_matches_the_float64_sweep(T, first_order, need_grad, dev, ws, c1mode):
     from fumi_amd import hip

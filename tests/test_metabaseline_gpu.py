@@ -70,7 +70,7 @@ def _check_step(model, batch, encode, encode_bwd, dev, plan=None):
         if plan_a == plan_b:
             assert torch.equal(g, w), n                                           # the same launches on the same inputs: the same bits
         else:                                                                     # another encoder plan: the composition, 1e-2 of the
-            e = rel_to_max(g.cpu(), w.cpu())                                      # tensor's scale (tests/test_conv4_gpu.py:533-536)
+            e = rel_to_max(g.cpu(), w.cpu())                                      # tensor's scale (test_am3_conv4_step_matches_autograd)
             print(f"{n}: plans {plan_a} / {plan_b}, rel-to-max difference {e:.3e}")
             assert e <= 1e-2, (n, e)
     assert float(got[0].abs()) > 0.0

@@ -40,7 +40,7 @@ def _model(backbone, conv, C, R, dev):
 def test_conv4_training_step_equals_the_composition_of_the_unit_ops(dev):
     """Encoder gradients, gW and gb of one step (16 x 16 images, 2 blocks, M = 16, R = 4, C = 6) against conv4_encode -> linear_fwd /
     ce_fwd_bwd / linear_bwd_data / linear_bwd_weight -> conv4_encode_bwd on the same batch, at the tolerance tests/test_conv4_gpu.py
-    applies to parameter gradients (1e-2 of the tensor's scale, tests/test_conv4_gpu.py:533-536)."""
+    applies to parameter gradients (1e-2 of the tensor's scale, test_am3_conv4_step_matches_autograd there)."""
     from fumi_amd import hip
     from fumi_amd.models.conv4 import Conv4
     M, R, C = 16, 4, 6
