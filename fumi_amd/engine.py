@@ -168,6 +168,15 @@ class HipEngine:
         return hip.euclid_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, alpha, need_grad=need_grad, grad_scale=grad_scale,
                                      want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dalpha=dalpha, n_way=n_way)
 
+    def feat_adapt_fwd(self, feats_s, y_s, w, n_way=None, keep_tape=False):
+        """Set-to-set prototype adaptation (FEAT): (adapted prototypes [B,N,F], tape | None) of the class means
+        of feats_s through one self-attention block, a residual and a LayerNorm; w = (wqkv, wo, bo, ln_weight, ln_bias)."""
+        return hip.feat_adapt_fwd(self._ws(feats_s), feats_s, y_s, w, n_way=n_way, keep_tape=keep_tape)
+
+    def feat_adapt_bwd(self, feats_s, y_s, w, tape, dprotos, n_way=None, dfeats_s=None, g_w=None):
+        """(dfeats_s [B,S,F], g_w) for dprotos [B,N,F], the head's gradient for the adapted prototypes."""
+        return hip.feat_adapt_bwd(self._ws(feats_s), feats_s, y_s, w, tape, dprotos, n_way=n_way, dfeats_s=dfeats_s, g_w=g_w)
+
     def ridge_head_step(self, feats_s, y_s, feats_q, y_q, params, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
                         dfeats_q=None, dparams=None, n_way=None):
         """Fused ridge-regression head with params [2] = (log lambda, logit scale) on the device: mean

@@ -47,6 +47,7 @@ SYMBOLS = [
     "fumi_hip_cls_head_step_distill",
     "fumi_hip_svm_head_step", "fumi_hip_svm_set_form", "fumi_hip_svm_get_fit",
     "fumi_hip_cos_cls_head_step",
+    "fumi_hip_feat_adapt_tape_floats", "fumi_hip_feat_adapt_fwd", "fumi_hip_feat_adapt_bwd",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -247,6 +248,10 @@ def lib():
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_euclid_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_feat_adapt_tape_floats.argtypes = [c_int] * 3
+        L.fumi_hip_feat_adapt_tape_floats.restype = c_int64
+        L.fumi_hip_feat_adapt_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 9
+        L.fumi_hip_feat_adapt_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 15
         L.fumi_hip_logreg_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4 + [c_int] + [c_float] * 3 + [c_int]
                                                 + [c_void_p] * 4)
         L.fumi_hip_logreg_set_form.argtypes = [c_int]
@@ -1776,6 +1781,62 @@ def euclid_proto_step(ws, feats_s, y_s, feats_q, y_q, alpha, *, need_grad=True, 
     _check(lib().fumi_hip_euclid_proto_step(ws.handle, _stream(dev), *lead, _f32(alpha, "alpha"), float(grad_scale), *tail, *grads),
            "fumi_hip_euclid_proto_step")
     return out
+
+
+FEAT_PARAMS = ("wqkv", "wo", "bo", "ln_weight", "ln_bias")      # the adaptation's tensors, in the order of the entries' arguments
+
+
+def _feat_adapt_io(name, feats_s, y_s, w, n_way):
+    """The checks the two adaptation entries share: feats_s [B,S,F], y_s [B,S], w = (wqkv [3F,F], wo [F,F], bo, ln_weight, ln_bias
+    [F]).  Returns (dev, (B, S, N, F), the ctypes arguments from feats_s to ln_bias)."""
+    dev = _dev(feats_s)
+    if feats_s.dim() != 3:
+        raise FumiHipError(f"{name}: feats_s [B,S,F] expected")
+    if len(w) != len(FEAT_PARAMS):
+        raise FumiHipError(f"{name}: w = ({', '.join(FEAT_PARAMS)}) expected, got {len(w)} tensors")
+    B, S, F = (int(v) for v in feats_s.shape)
+    N = int(n_way) if n_way is not None else int(y_s.max().item()) + 1
+    _shape(y_s, (B, S), "y_s")
+    for t, shape, nm in zip(w, ((3 * F, F), (F, F), (F,), (F,), (F,)), FEAT_PARAMS):
+        _shape(t, shape, nm)
+    args = (_f32(feats_s, "feats_s"), _i64(y_s, "y_s"), *(_f32(t, nm) for t, nm in zip(w, FEAT_PARAMS)))
+    return dev, (B, S, N, F), args
+
+
+def feat_adapt_fwd(ws, feats_s, y_s, w, *, n_way=None, keep_tape=False):
+    """The set-to-set prototype adaptation (csrc/featadapt.hip): the class means of feats_s [B,S,F] by y_s [B,S]
+    through one self-attention block over the N prototypes of each episode, a residual and a LayerNorm.  ``w`` = (wqkv [3F,F], wo
+    [F,F], bo [F], ln_weight [F], ln_bias [F]); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises.  Returns (protos
+    [B,N,F], tape): the adapted prototypes -- an N-way 1-shot support set with labels 0..N-1 for cos_proto_step / euclid_proto_step --
+    and, with keep_tape, what feat_adapt_bwd needs (None otherwise: the forward form, same bits)."""
+    dev, (B, S, N, F), args = _feat_adapt_io("feat_adapt_fwd", feats_s, y_s, w, n_way)
+    protos = torch.empty(B, N, F, device=dev, dtype=torch.float32)
+    tape = torch.empty(int(lib().fumi_hip_feat_adapt_tape_floats(B, N, F)), device=dev, dtype=torch.float32) if keep_tape else None
+    _check(lib().fumi_hip_feat_adapt_fwd(ws.handle, _stream(dev), B, S, N, F, *args, _f32(protos, "protos"),
+                                         _f32(tape, "tape") if keep_tape else None), "fumi_hip_feat_adapt_fwd")
+    return protos, tape
+
+
+def feat_adapt_bwd(ws, feats_s, y_s, w, tape, dprotos, *, n_way=None, dfeats_s=None, g_w=None):
+    """The backward of feat_adapt_fwd for dprotos [B,N,F] (the head's dfeats_s): returns (dfeats_s [B,S,F], g_w) with g_w the
+    gradients of ``w`` in its order, written into the tensors given (``g_w`` may be slices of one flat buffer), else into new ones."""
+    dev, (B, S, N, F), args = _feat_adapt_io("feat_adapt_bwd", feats_s, y_s, w, n_way)
+    if tape is None or tape.numel() != int(lib().fumi_hip_feat_adapt_tape_floats(B, N, F)):
+        raise FumiHipError("feat_adapt_bwd: tape: not the tape of a feat_adapt_fwd call of these shapes")
+    _shape(dprotos, (B, N, F), "dprotos")
+    if dfeats_s is None:
+        dfeats_s = torch.empty(B, S, F, device=dev, dtype=torch.float32)
+    _shape(dfeats_s, (B, S, F), "dfeats_s")
+    if g_w is None:
+        g_w = [torch.empty_like(t) for t in w]
+    if len(g_w) != len(FEAT_PARAMS):
+        raise FumiHipError(f"feat_adapt_bwd: g_w: {len(FEAT_PARAMS)} tensors expected, got {len(g_w)}")
+    for g, t, nm in zip(g_w, w, FEAT_PARAMS):
+        _shape(g, tuple(t.shape), "d" + nm)
+    _check(lib().fumi_hip_feat_adapt_bwd(ws.handle, _stream(dev), B, S, N, F, *args, _f32(tape, "tape"), _f32(dprotos, "dprotos"),
+                                         _f32(dfeats_s, "dfeats_s"), *(_f32(g, "d" + nm) for g, nm in zip(g_w, FEAT_PARAMS))),
+           "fumi_hip_feat_adapt_bwd")
+    return dfeats_s, g_w
 
 
 def ridge_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,

@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.run_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.main_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -258,6 +258,23 @@ def check_supported(args):
             raise NotImplementedError(f"the transductive head holds an episode's soft assignments in LDS: S + Qn = --num_ways * "
                                       f"(--num_shots + --num_shots_test) = {S + Qn} must not exceed 512 and Qn * --num_ways = "
                                       f"{Qn * args.num_ways} must not exceed 8192")
+    adapt = getattr(args, "fewshot_adapt", "none")
+    if adapt not in ("none", "feat"):
+        raise ValueError(f"--fewshot_adapt {adapt} must be none or feat")
+    if adapt == "feat":
+        if family != "metabaseline":
+            raise ValueError("--fewshot_adapt adapts the class prototypes of the Meta-Baseline stage: feat needs --model metabaseline")
+        if head not in ("cosine", "proto"):
+            raise ValueError(f"--fewshot_adapt feat adapts class prototypes: it goes with --fewshot_head cosine or proto, not {head} "
+                             "(the ridge and the SVM head fit on the support rows, not on prototypes)")
+        if e_head == "logreg":
+            raise ValueError("--fewshot_adapt feat classifies against the adapted prototypes: --eval_head logreg fits on the support "
+                             "rows and would not see them")
+        if t_steps > 0:
+            raise ValueError("--fewshot_adapt feat is inductive: the transductive refinement starts from the plain class means, so "
+                             "--transductive_steps must be 0")
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the prototype adaptation takes 2 to 64 classes, got --num_ways {args.num_ways}")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):

@@ -28,7 +28,14 @@ not a parameter: ``state_dict`` is the same either way.
 
 ``transductive_steps > 0`` (``--transductive_steps``) classifies validation and test episodes transductively:
 ``trans_proto_step`` (csrc/transproto.hip) refines the class prototypes by that many soft k-means steps on the episode's queries, in the
-cosine metric at ``temp`` or the Euclidean one at ``proto_scale``.  Training and ``state_dict`` are the same either way."""
+cosine metric at ``temp`` or the Euclidean one at ``proto_scale``.  Training and ``state_dict`` are the same either way.
+
+``adapt="feat"`` (``--fewshot_adapt feat``) is FEAT (Ye et al. 2020): the class prototypes of an episode are made
+task-specific by one self-attention block over the set of prototypes, a residual and a LayerNorm (``feat_adapt_fwd`` /
+``feat_adapt_bwd``, csrc/featadapt.hip), and the cosine or the prototypical head classifies against the adapted prototypes as an
+N-way 1-shot support set with labels 0..N-1.  The model then owns the submodule ``feat`` (``wqkv``, ``wo``, ``bo``, ``ln_weight``,
+``ln_bias``), whose gradients join the flat buffer.  A training step is five engine calls: ``encode``, ``feat_adapt_fwd``, the head,
+``feat_adapt_bwd`` and ``encode_bwd``.  With ``adapt="none"`` nothing changes: same ``state_dict`` keys, engine calls and bits."""
 import math
 import os
 
@@ -45,11 +52,37 @@ from ..utils.wandb_compat import wandb
 from .common import _loss_acc
 
 
+class FeatAdapt(nn.Module):
+    """The parameters of the set-to-set adaptation at feature width F: the Q, K and V projections as one [3F,F] tensor (each block
+    normal with std sqrt(2 / (F + F)), as FEAT initialises them), the output projection (Xavier-normal, zero bias) and the LayerNorm."""
+
+    def __init__(self, F):
+        super().__init__()
+        if F % 32 != 0 or not 32 <= F <= 2048:
+            raise ValueError(f"the prototype adaptation takes feature widths in multiples of 32 from 32 to 2048, got {F}")
+        self.wqkv = nn.Parameter(torch.empty(3 * F, F).normal_(0.0, math.sqrt(2.0 / (F + F))))
+        self.wo = nn.Parameter(nn.init.xavier_normal_(torch.empty(F, F)))
+        self.bo = nn.Parameter(torch.zeros(F))
+        self.ln_weight = nn.Parameter(torch.ones(F))
+        self.ln_bias = nn.Parameter(torch.zeros(F))
+
+    def tensors(self):
+        """In the order of the engine's arguments (hip.FEAT_PARAMS)."""
+        return [self.wqkv, self.wo, self.bo, self.ln_weight, self.ln_bias]
+
+
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
                  ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0,
-                 svm=None):
+                 svm=None, adapt="none"):
         super().__init__()
+        if adapt not in ("none", "feat"):
+            raise ValueError(f"the prototype adaptation must be none or feat, got {adapt}")
+        if adapt == "feat" and (head not in ("cosine", "proto") or eval_head == "logreg" or int(transductive_steps) > 0):
+            raise ValueError("the prototype adaptation goes with the cosine and the prototypical head, the training head at evaluation "
+                             f"and no transductive refinement, got head {head}, evaluation head {eval_head}, {transductive_steps} "
+                             "transductive steps")
+        self.adapt = adapt
         if head not in ("cosine", "ridge", "proto", "svm"):
             raise ValueError(f"the few-shot head must be cosine, ridge, proto or svm, got {head}")
         if head == "svm" and svm is None:
@@ -97,9 +130,22 @@ class MetaBaseline(nn.Module):
             self.proto_scale = nn.Parameter(torch.tensor([float(proto_scale)]))
         else:
             self.temp = nn.Parameter(torch.tensor([float(init_temp)]))
+        if adapt == "feat":
+            self.feat = FeatAdapt(self.conv.feature_dim)
         self._flat = None
         self._pcache = None
         self._dscale = None
+        self._arange = None
+
+    def _feat_tensors(self):
+        return self.feat.tensors() if self.adapt == "feat" else []
+
+    def _class_labels(self, B, N, device):
+        """y [B,N] = 0..N-1 per episode: the labels of the adapted prototypes as a 1-shot support set"""
+        a = self._arange
+        if a is None or a.shape != (B, N) or a.device != device:
+            a = self._arange = torch.arange(N, device=device, dtype=torch.int64).repeat(B, 1).contiguous()
+        return a
 
     def backbone_module(self):
         return self.conv
@@ -119,16 +165,16 @@ class MetaBaseline(nn.Module):
         c = self._pcache
         if c is None or not c[0].valid() or (self.proto_scale_fixed and c[1] is not self._buffers["proto_scale"]):
             th, hp = self.conv.theta(), self.head_param()
-            own = [] if hp is None else [hp]
+            own = ([] if hp is None else [hp]) + self._feat_tensors()
             c = self._pcache = (ParamWatch(self, own + th), self._buffers["proto_scale"] if hp is None else hp.detach(),
-                                [p.detach() for p in th])
+                                [p.detach() for p in th], [p.detach() for p in self._feat_tensors()])
             self._flat = None
         fg = None
         if need_grad:
             fg = self._flat
             if fg is None:
                 hp = self.head_param()
-                fg = self._flat = FlatGrads(([] if hp is None else [hp]) + self.conv.theta(), extra=2)
+                fg = self._flat = FlatGrads(([] if hp is None else [hp]) + self._feat_tensors() + self.conv.theta(), extra=2)
                 # the fixed scale has no slot in the flat buffer: its gradient is written beside it and read by nobody
                 self._dscale = torch.empty(1, device=fg.flat.device, dtype=torch.float32) if hp is None else None
         return c[1], c[2], fg
@@ -160,18 +206,26 @@ class MetaBaseline(nn.Module):
         temp, theta, fg = self._step_params(True)
         encode, encode_bwd = self._encoders(eng)
         f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
-        g_t, g_theta = fg.split(0 if self.proto_scale_fixed else 1)
+        featw = self._pcache[3]                 # [] without the adaptation
+        g_t, g_theta = fg.split((0 if self.proto_scale_fixed else 1) + len(featw))   # g_t: [head parameter | feat.*]
+        h_s, h_y, tape = f_s, y_s, None         # what the head takes for its support set
+        if self.adapt == "feat":                # the adapted prototypes, an N-way 1-shot support set with labels 0..N-1
+            h_s, tape = eng.feat_adapt_fwd(f_s, y_s, featw, n_way=N, keep_tape=True)
+            h_y = self._class_labels(h_s.shape[0], N, h_s.device)
         if self.head == "proto":
-            out = eng.euclid_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0,
+            out = eng.euclid_proto_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0,
                                         dalpha=self._dscale if self.proto_scale_fixed else g_t[0], n_way=N)
         elif self.head == "ridge":
-            out = eng.ridge_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dparams=g_t[0], n_way=N)
+            out = eng.ridge_head_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dparams=g_t[0], n_way=N)
         elif self.head == "svm":
-            out = eng.svm_head_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dscale=g_t[0], n_way=N, **self._svm_kw())
+            out = eng.svm_head_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dscale=g_t[0], n_way=N, **self._svm_kw())
             self.svm_stats = out["stats"].amax(dim=0)
         else:
-            out = eng.cos_proto_step(f_s, y_s, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
-        encode_bwd(x_s, x_q, out["dfeats_s"], out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
+            out = eng.cos_proto_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
+        dfeats_s = out["dfeats_s"]
+        if self.adapt == "feat":                # the head's gradient for the prototypes, back to the support features
+            dfeats_s, _ = eng.feat_adapt_bwd(f_s, y_s, featw, tape, dfeats_s, n_way=N, g_w=g_t[len(g_t) - len(featw):])
+        encode_bwd(x_s, x_q, dfeats_s, out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
         _loss_acc(out, y_q, into=fg.tail)
         if optimizer is not None:
             optimizer.zero_grad()
@@ -188,6 +242,9 @@ class MetaBaseline(nn.Module):
         x_s, x_q, y_s, y_q, N = self._episode(batch, device)
         temp, theta, _ = self._step_params(False)
         f_s, f_q = self._encoders(eng)[0](x_s, x_q, theta, keep_tape=False)
+        if self.adapt == "feat":                # the forward forms: the head classifies against the adapted prototypes
+            f_s, _ = eng.feat_adapt_fwd(f_s, y_s, self._pcache[3], n_way=N, keep_tape=False)
+            y_s = self._class_labels(f_s.shape[0], N, f_s.device)
         if self.eval_head == "logreg":
             out = eng.logreg_head_step(f_s, y_s, f_q, y_q, n_way=N, **self.logreg)
             return _loss_acc(out, y_q)

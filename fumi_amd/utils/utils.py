@@ -139,6 +139,9 @@ _PRETRAIN_HEAD_FLAGS = [    # the cosine classifier of --model pretrain (DESIGN.
     ("--pretrain_head_scale", dict(type=float, default=10.0, help="[--pretrain_head cosine] the scale of the cosine logits: its initial value (learned), or with --pretrain_head_scale_fixed its value (positive)")),
     ("--pretrain_head_scale_fixed", dict(action="store_true", help="[--pretrain_head cosine] keep --pretrain_head_scale fixed")),
 ]
+_ADAPT_FLAGS = [            # the set-to-set prototype adaptation; a list of its own that main_parser() appends to run_parser()'s
+    ("--fewshot_adapt", dict(type=str, choices=["none", "feat"], default="none", help="[--model metabaseline, --fewshot_head cosine | proto] adapt the class prototypes of an episode to the task before the head classifies against them: feat is FEAT's one-head self-attention block over the set of prototypes, with a residual and a LayerNorm")),
+]
 
 
 def parser():
@@ -162,10 +165,19 @@ def cli_parser():
 
 
 def run_parser():
-    """``cli_parser()`` and after every flag of it the --pretrain_head* flags: what ``main.parse_args`` reads.  ``cli_parser()`` and
-    ``parser()`` keep the flag sequences the earlier heads were written against."""
+    """``cli_parser()`` and after every flag of it the --pretrain_head* flags.  ``cli_parser()`` and ``parser()`` keep the flag
+    sequences the earlier heads were written against."""
     p = cli_parser()
     for flag, kw in _PRETRAIN_HEAD_FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
+def main_parser():
+    """``run_parser()`` and after every flag of it --fewshot_adapt: what ``main.parse_args`` reads.  ``run_parser()`` keeps the flag
+    sequence the cosine classifier was written against."""
+    p = run_parser()
+    for flag, kw in _ADAPT_FLAGS:
         p.add_argument(flag, **kw)
     return p
 
@@ -251,7 +263,8 @@ def init_model(args, dictionary, watch=True):
                                           proto_scale=getattr(args, "proto_scale", 1.0),
                                           proto_scale_fixed=getattr(args, "proto_scale_fixed", False),
                                           transductive_steps=getattr(args, "transductive_steps", 0),
-                                          svm=svm_config(args) if getattr(args, "fewshot_head", "cosine") == "svm" else None)
+                                          svm=svm_config(args) if getattr(args, "fewshot_head", "cosine") == "svm" else None,
+                                          **(dict(adapt="feat") if getattr(args, "fewshot_adapt", "none") == "feat" else {}))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

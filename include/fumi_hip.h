@@ -723,6 +723,40 @@ int fumi_hip_svm_get_fit(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int 
 int fumi_hip_trans_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* scale, int metric, int steps,
         float* loss, float* correct, int64_t* preds, float* logits);
+/* Set-to-set prototype adaptation in front of the prototype heads (csrc/featadapt.hip): FEAT (Ye et al., CVPR
+ * 2020), one self-attention block over the set of an episode's class prototypes, one head with d_k = d_v = F.  Per episode b:
+ *     P  = mean of the rows of feats_s[b] with y_s == n (count clamped to >= 1, as fumi_hip_proto_reduce)      [N,F]
+ *     Q  = P Wq^T,  K = P Wk^T,  V = P Wv^T          (Wqkv [3F,F] = the rows of Wq, Wk, Wv in this order; no bias)
+ *     A  = softmax_rows(Q K^T / sqrt(F))             [N,N]   (the row maximum is subtracted before exp)
+ *     O  = A V,   U = O Wo^T + bo,   R = P + U       (Wo [F,F], bo [F])
+ *     P' = gamma * (R - mean_f R) / sqrt(var_f R + 1e-5) + beta                  (LayerNorm over F, biased variance; gamma, beta [F])
+ * protos_out [B,N,F] = P'.  It is an N-way 1-shot support set with the labels 0..N-1 of every episode: fumi_hip_cos_proto_step and
+ * fumi_hip_euclid_proto_step classify against it unchanged, and their dfeats_s is dprotos of the backward.
+ * K and V are formed from P - m, m the episode's mean prototype, and O = A V + m Wv^T: the same numbers in exact arithmetic, without the
+ * round-off that an offset common to all features (post-ReLU features have one) costs the softmax and its backward.
+ * tape: caller memory of fumi_hip_feat_adapt_tape_floats(B, N, F) floats that receives what the backward needs (P, Q|K|V, A, O, R, the
+ * mean and 1 / std of every row, the class counts), or NULL (forward form: protos_out is bit-identical to the taped form's).
+ * fumi_hip_feat_adapt_bwd, given the tape of the forward call on the same inputs and dprotos [B,N,F] = d(grad_scale * loss) / dP',
+ * writes (never accumulates) dfeats_s [B,S,F], dWqkv [3F,F], dWo [F,F], dbo [F], dgamma [F], dbeta [F]: through the LayerNorm (dR,
+ * dgamma = sum_rows dP' xhat, dbeta = sum_rows dP'), the output projection, the attention (dV = A^T dO, dA = dO V^T,
+ * dS = A (dA - sum_n dA A) / sqrt(F), dQ = dS K, dK = dS^T Q), the three projections and the residual; every support row of class n
+ * receives dP_n / count_n.  The gradient outputs need no alignment beyond a float's (they may be slices of one flat buffer).
+ * fp32 with fp32 accumulation on the f32 MFMA.  Forward: eight launches (class means; three products for Q, K | V and m Wv^T; scores and softmax, one workgroup per
+ * episode, the contraction over F streamed through LDS; A V per 128 features; O Wo^T + bo; residual and LayerNorm, one wave per row).
+ * Backward: ten launches.  The four F x F projections and their gradients run on the dense GEMM behind fumi_hip_linear_*.  ORDER as
+ * for the episode heads: fixed summation orders, no floating-point atomics, equal inputs give equal bits.
+ * LABELS: a support label outside [0,N) sets FUMI_ST_LABEL_RANGE; that row is left out of the mean and gets a zero gradient.  A class
+ * without a support row sets FUMI_ST_CLASS_MISSING, has P_n = 0 and still takes part in the attention.  The forward raises the flags.
+ * B >= 1, 1 <= S <= 1024, 2 <= N <= 64, B * N <= 65536, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise (the tape size is 0
+ * there); FUMI_EINVAL for a NULL required pointer (every pointer but the forward's tape); both before any launch. */
+int64_t fumi_hip_feat_adapt_tape_floats(int B, int N, int F);
+int fumi_hip_feat_adapt_fwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int N, int F, const float* feats_s,
+        const int64_t* y_s, const float* Wqkv, const float* Wo, const float* bo, const float* gamma, const float* beta,
+        float* protos_out, float* tape);
+int fumi_hip_feat_adapt_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int N, int F, const float* feats_s,
+        const int64_t* y_s, const float* Wqkv, const float* Wo, const float* bo, const float* gamma, const float* beta,
+        const float* tape, const float* dprotos, float* dfeats_s, float* dWqkv, float* dWo, float* dbo, float* dgamma,
+        float* dbeta);
 /* mix_images (csrc/immix.hip): the blend of a gathered batch x float [M,C,H,W] with the rows partner [M]
  * (device int64) names, into out (same shape; must not overlap x, row i reads row partner[i]: FUMI_EINVAL).
  *   mode 0, mixup:   out[i] = lam * x[i] + (1.0f - lam) * x[partner[i]], each operation rounded on its own; the box is ignored.
