@@ -577,6 +577,20 @@ int fumi_hip_xpanel_fwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
                              xpanel_planes(ws, B, S, D, h0));
 }
 
+int fumi_hip_xpanel_fwd_rows(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
+        const float* table, int64_t n_rows, const int64_t* idx_s, const int64_t* idx_q, const float* W0, float* A0, float* G) {
+    if (!ws || !table || !idx_s || !idx_q || !W0 || !A0 || n_rows < 1 || B < 1 || S < 1 || Qn < 1 || D < 1 || h0 < 1) return FUMI_EINVAL;
+    HIP_TRY(hipSetDevice(ws->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = launch_index_range_check(st, idx_s, (long)B * S, (long)n_rows, ws->status))) return rc;
+    if ((rc = launch_index_range_check(st, idx_q, (long)B * Qn, (long)n_rows, ws->status))) return rc;
+    XRows rows{table, idx_s, idx_q, (long)n_rows};
+    ProfScope ps(ws, st, FUMI_PH_XPANEL_FWD);
+    return launch_xpanel_fwd(st, B, S, Qn, D, h0, table, table, W0, A0, G, &rows, nullptr, nullptr, nullptr, nullptr,
+                             xpanel_planes(ws, B, S, D, h0));
+}
+
 int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
         const float* x_s, const float* x_q, const float* Abar, float scale, float* gW0) {
     // a one-sided panel (S == 0 or Qn == 0, not both; the absent side's pointer is not read and may be NULL) is what the two-launch

@@ -522,6 +522,8 @@ __global__ __launch_bounds__(256, 2) void xpanel_fwd_sb_kernel(XPanel p, float* 
 // for the support rows of 32 episodes: L2 / MALL resident) -- no LDS, no vector work on the column side.  A workgroup computes
 // 32 RB rows x (32 columns per wave); every wave owns one 32-column block -- W0 columns or Gram columns alike -- and RB
 // accumulators that share each B fragment.  Only the slab of X is split and staged through LDS.
+// Since DESIGN.md section 45 only W0 is pre-split by default: a Gram tile splits its 32 support rows itself (GS in xpanel_ps_tile);
+// FUMI_XP_GSPLIT=0 writes and reads the support planes described here.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void xpanel_presplit_kernel(XPanel p, int cbg, unsigned short* __restrict__ Wp, unsigned short* __restrict__ Xp) {
     const int bid = blockIdx.x;
@@ -597,11 +599,16 @@ __global__ __launch_bounds__(512) void xpanel_presplit_glove_kernel(XPanel p, in
 // (from tile row `wrow`) of ONE 32-column block whose fragments it reads at `bq` (+ plane per piece, + kstride per 16-deep step).
 // W0 tiles: RB = SR = 2, the four waves sit side by side on the same 64 rows.  Gram tiles: RB = 1, SR = 4, the four waves sit
 // one above the other on 128 rows of the same column block (equal work per wave either way: 12 RB MFMAs a slab).
-template <int NST, int RB, int SR>
+//
+// GS (Gram tiles, FUMI_XP_GSPLIT=1, the default): no planes.  The tile's 32 columns are 32 support rows: a slab of them is 256 float4,
+// one per thread, fetched at `brow` (the thread's row, clamped, + its k offset) beside the thread's SR float4 of X, zeroed where the
+// column is past S (`bok`; the planes hold zeros there), split once per tile and staged as rows 32 SR .. 32 SR + 31 of the same LDS
+// image; every wave reads its B fragments there exactly as it reads its A fragments.  Same pieces, same MFMA order: the same bits.
+template <int NST, int RB, int SR, bool GS = false>
 __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, int wrow, const u32x4* __restrict__ bq, long plane, long kstride,
                                                int kbeg, int nslab, unsigned short* lds, float* __restrict__ out, int ld, int n, bool nok,
-                                               unsigned long long* trace) {
-    constexpr int PLN = SR * 32 * SROW;                         // ushorts per LDS plane; lds: [buffer][piece][row][k]
+                                               unsigned long long* trace, const float* __restrict__ brow = nullptr, bool bok = false) {
+    constexpr int PLN = (SR + (GS ? 1 : 0)) * 32 * SROW;        // ushorts per LDS plane; lds: [buffer][piece][row][k]
     const int tid = threadIdx.x, lane = tid & 63;
     unsigned long long t0 = 0, t1 = 0, t2 = 0;                  // dev tracing (tests/dev/trace_xpanel_wg.py): 100 MHz wall ticks
     if (trace && tid == 0) t0 = __builtin_amdgcn_s_memrealtime();
@@ -615,7 +622,11 @@ __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, i
     }
     const int li = lane & 31, hh = lane >> 5;
     const int aoff = (wrow + li) * SROW + 8 * hh;
+    const int boff = (SR * 32 + li) * SROW + 8 * hh;            // GS: the column block's rows sit behind the SR x 32 rows of X
+    const int bsto = (SR * 32 + (tid >> 3)) * SROW + ((tid & 7) << 2);
     f32x4 ga[NST][SR];
+    f32x4 gbv[NST];                              // GS: the thread's float4 of the column block, ring slot as ga
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     bf16x8 fb[2][2][3];                          // [slot = slab & 1][step][piece]
     f32x16 acc[RB];
 #pragma unroll
@@ -627,9 +638,11 @@ __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, i
         constexpr int ST = decltype(sc)::value;
 #pragma unroll
         for (int i = 0; i < SR; ++i) ga[ST][i] = *(const f32x4*)(arow[i] + k0);
+        if constexpr (GS) gbv[ST] = *(const f32x4*)(brow + k0);
     };
     auto bload = [&](auto sc, auto stc, int slab_) {                             // the fragments of one 16-deep step of slab `slab_`
         constexpr int SL = decltype(sc)::value & 1, st = decltype(stc)::value;
+        if constexpr (GS) return;
         const u32x4* q = bq + (long)(2 * slab_ + st) * kstride;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) fb[SL][st][pl] = __builtin_bit_cast(bf16x8, q[pl * plane]);
@@ -644,11 +657,26 @@ __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, i
             unsigned short* d = lds + buf * 3 * PLN + off;
             *(u32x2*)d = h; *(u32x2*)(d + PLN) = m; *(u32x2*)(d + 2 * PLN) = l;
         }
+        if constexpr (GS) {
+            u32x2 h, m, l;
+            split3(bok ? gbv[ST] : z4, h, m, l);
+            unsigned short* d = lds + buf * 3 * PLN + bsto;
+            *(u32x2*)d = h; *(u32x2*)(d + PLN) = m; *(u32x2*)(d + 2 * PLN) = l;
+        }
+    };
+    auto bfrag = [&](auto sc, int buf) {                                         // GS: the slab's B fragments from its LDS image
+        constexpr int SL = decltype(sc)::value & 1;
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                fb[SL][st][pl] = __builtin_bit_cast(bf16x8, *(const f32x4*)(lds + (buf * 3 + pl) * PLN + boff + 16 * st));
     };
     // piece pairs in accumulation order (smallest first): (h,l) (l,h) (m,m) (h,m) (m,h) (h,h)
     constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
     auto mma_slab = [&](auto sc, int buf) {
         constexpr int SL = decltype(sc)::value & 1;
+        if constexpr (GS) bfrag(sc, buf);
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
             bf16x8 f[RB][3];
@@ -682,14 +710,22 @@ __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, i
         const int cur = s & 1, nxt = cur ^ 1;
         bf16x8 fa[RB][2][3];
 #pragma unroll
-        for (int st = 0; st < 2; ++st)
+        for (int st = 0; st < 2; ++st) {
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
                     fa[rb][st][pl] = __builtin_bit_cast(bf16x8, *(const f32x4*)(lds + (cur * 3 + pl) * PLN + aoff + rb * 32 * SROW + 16 * st));
+            if constexpr (GS) {                                    // (step 0's six fragments first: its MFMAs wait for them alone)
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+                    fb[SL][st][pl] = __builtin_bit_cast(bf16x8, *(const f32x4*)(lds + (cur * 3 + pl) * PLN + boff + 16 * st));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         unsigned hp[2], mp[2], lp[2];
+        unsigned hb[2], mb[2], lb[2];                              // GS: the column block's float4 rides in segments 0..2
         xp_static_for<0, NSEG>([&](auto gc) {                      // segment g: MFMAs MPS g .. + MPS - 1 of the slab's 12 RB, work item g
             constexpr int g = decltype(gc)::value, q = g / 3, part = g % 3;
 #pragma unroll
@@ -706,6 +742,17 @@ __device__ __forceinline__ void xpanel_ps_tile(const XPanel& p, int b, int m0, i
                 *(u32x2*)d = (u32x2){hp[0], hp[1]};
                 *(u32x2*)(d + PLN) = (u32x2){mp[0], mp[1]};
                 *(u32x2*)(d + 2 * PLN) = (u32x2){lp[0], lp[1]};
+            }
+            if constexpr (GS && g < 3) {
+                if constexpr (g < 2) {
+                    const f32x4 vb = bok ? gbv[ST] : z4;
+                    split_pair(vb[2 * g], vb[2 * g + 1], hb[g], mb[g], lb[g]);
+                } else {
+                    unsigned short* d = lds + nxt * 3 * PLN + bsto;
+                    *(u32x2*)d = (u32x2){hb[0], hb[1]};
+                    *(u32x2*)(d + PLN) = (u32x2){mb[0], mb[1]};
+                    *(u32x2*)(d + 2 * PLN) = (u32x2){lb[0], lb[1]};
+                }
             }
             if constexpr (MPS > 1) {            // inside a segment: one MFMA, then a share of the item's vector operations / LDS writes
 #pragma unroll
@@ -764,7 +811,7 @@ template <int NST, bool RIDER>
 __global__ __launch_bounds__(256, 2) void xpanel_fwd_ps_kernel(XPanel p, const unsigned short* __restrict__ Wp, const unsigned short* __restrict__ Xp,
                                                                 float* __restrict__ A0, float* __restrict__ G, int tiles_m, int tiles_g, int cbg,
                                                                 HyperFwdArgs rider, unsigned long long* trace) {
-    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * 3 * 128 * SROW];
+    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * 3 * 160 * SROW];      // (Gram tiles: 128 rows of X + 32 support rows)
     int bid = blockIdx.x;
     if constexpr (RIDER) {
         __shared__ int s_last;
@@ -786,6 +833,12 @@ __global__ __launch_bounds__(256, 2) void xpanel_fwd_ps_kernel(XPanel p, const u
         const int jj = j - nheavy, per = max(1, tiles_g * cbg);
         const int b = xcd + 8 * (jj / per), t = jj % per, g = t % cbg;
         if (b >= p.B) return;
+        if (!Xp) {                                     // the tile splits its own column block (uniform over the launch)
+            const int c = g * 32 + (threadIdx.x >> 3);
+            xpanel_ps_tile<NST, 1, 4, true>(p, b, (t / cbg) * 128, wave * 32, nullptr, 0, 0, 0, K / SBK, lds, G + (long)b * R * p.S, p.S,
+                                            g * 32 + li, g * 32 + li < p.S, trace, xrow(p, b, c < p.S ? c : 0) + ((threadIdx.x & 7) << 2), c < p.S);
+            return;
+        }
         const long plane = (long)cbg * 32 * (K >> 3);
         xpanel_ps_tile<NST, 1, 4>(p, b, (t / cbg) * 128, wave * 32, (const u32x4*)Xp + (long)b * 3 * plane + (long)g * 64 + lane,
                                   plane, cbg * 64L, 0, K / SBK, lds, G + (long)b * R * p.S, p.S, g * 32 + li, g * 32 + li < p.S, trace);
@@ -1243,11 +1296,14 @@ unsigned long long* g_trace = nullptr;      // dev tracing only (tools/trace_xpa
 // decisions of the last launch_xpanel_fwd / launch_xpanel_bwd of this process (fumi_hip_xpanel_plan): written on the host beside the
 // launches, never read by one.  Kernel ids -- forward: 1 generic guarded, 2 generic fast, 3 fp32 MFMA, 4 per-tile split, 5 pre-split;
 // backward: 1 64 x 64 guarded, 2 64 x 64 fast, 3 wide fp32, 4 wide split, 5 narrow swapped split.
-struct XpPlan { int fwd_kernel, fwd_ring, fwd_ksplit, fwd_gram_blocks, fwd_rode, bwd_kernel, bwd_nb, bwd_sk, bwd_nsplit, bwd_kchunk, bwd_rode; };
+// fwd_gram_split (where the pre-split form splits the support rows of its Gram tiles): 0 not the pre-split form, 1 planes written by the
+// pre-split launch (FUMI_XP_GSPLIT=0), 2 inside the Gram tiles.  g_xp_planes_bytes: bytes of operand planes that launch wrote and read.
+struct XpPlan { int fwd_kernel, fwd_ring, fwd_ksplit, fwd_gram_blocks, fwd_rode, bwd_kernel, bwd_nb, bwd_sk, bwd_nsplit, bwd_kchunk, bwd_rode, fwd_gram_split; };
 XpPlan g_xp_last = {};
-inline void xp_plan_fwd(int kernel, int ring, int ksplit, int gram_blocks, int rode) {
+size_t g_xp_planes_bytes = 0;
+inline void xp_plan_fwd(int kernel, int ring, int ksplit, int gram_blocks, int rode, int gram_split = 0, size_t planes_bytes = 0) {
     g_xp_last.fwd_kernel = kernel; g_xp_last.fwd_ring = ring; g_xp_last.fwd_ksplit = ksplit; g_xp_last.fwd_gram_blocks = gram_blocks;
-    g_xp_last.fwd_rode = rode;
+    g_xp_last.fwd_rode = rode; g_xp_last.fwd_gram_split = gram_split; g_xp_planes_bytes = planes_bytes;
 }
 inline void xp_plan_bwd(int kernel, int nb, int sk, int nsplit, int kchunk, int rode) {
     g_xp_last.bwd_kernel = kernel; g_xp_last.bwd_nb = nb; g_xp_last.bwd_sk = sk; g_xp_last.bwd_nsplit = nsplit; g_xp_last.bwd_kchunk = kchunk;
@@ -1258,11 +1314,14 @@ inline void xp_plan_bwd(int kernel, int nb, int sk, int nsplit, int kchunk, int 
 
 extern "C" int fumi_hip_xpanel_plan(int* plan, int n) {
     if (!plan || n < 0) return FUMI_EINVAL;
-    const int v[11] = {g_xp_last.fwd_kernel, g_xp_last.fwd_ring, g_xp_last.fwd_ksplit, g_xp_last.fwd_gram_blocks, g_xp_last.fwd_rode,
-                       g_xp_last.bwd_kernel, g_xp_last.bwd_nb, g_xp_last.bwd_sk, g_xp_last.bwd_nsplit, g_xp_last.bwd_kchunk, g_xp_last.bwd_rode};
-    for (int i = 0; i < n && i < 11; ++i) plan[i] = v[i];
+    const int v[12] = {g_xp_last.fwd_kernel, g_xp_last.fwd_ring, g_xp_last.fwd_ksplit, g_xp_last.fwd_gram_blocks, g_xp_last.fwd_rode,
+                       g_xp_last.bwd_kernel, g_xp_last.bwd_nb, g_xp_last.bwd_sk, g_xp_last.bwd_nsplit, g_xp_last.bwd_kchunk, g_xp_last.bwd_rode,
+                       g_xp_last.fwd_gram_split};
+    for (int i = 0; i < n && i < 12; ++i) plan[i] = v[i];
     return FUMI_OK;
 }
+
+extern "C" size_t fumi_hip_xpanel_planes_bytes(void) { return g_xp_planes_bytes; }
 
 void set_xpanel_trace(void* p) { g_trace = (unsigned long long*)p; }
 
@@ -1288,10 +1347,12 @@ static bool xpanel_fwd_ps_ok(int D, int h0) {
 }
 static size_t ps_w0_bytes(int D, int h0) { return (size_t)3 * h0 * D * sizeof(unsigned short); }
 static size_t ps_xs_bytes(int B, int S, int D) { return (size_t)B * 3 * ((S + 31) / 32 * 32) * D * sizeof(unsigned short); }
+// 1 (default): a Gram tile splits its 32 support rows itself, slab by slab; 0: the pre-split launch writes them as planes too
+static int xp_gsplit() { static const int v = getenv("FUMI_XP_GSPLIT") ? atoi(getenv("FUMI_XP_GSPLIT")) : 1; return v; }
 
 unsigned short* xpanel_planes(fumi_ws* ws, int B, int S, int D, int h0) {
     if (!ws || !xpanel_fwd_ps_ok(D, h0)) return nullptr;
-    const size_t need = ps_w0_bytes(D, h0) + ps_xs_bytes(B, S, D);
+    const size_t need = ps_w0_bytes(D, h0) + (xp_gsplit() ? 0 : ps_xs_bytes(B, S, D));
     if (ws->w0p_cap < need) {
         if (ws->w0p) (void)hipFree(ws->w0p);          // (hipFree waits for the device: nothing in flight reads the old planes)
         ws->w0p = nullptr; ws->w0p_cap = 0;
@@ -1356,21 +1417,24 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         glove->on = 0;
         if (glove->vec) hipLaunchKernelGGL(xpanel_presplit_glove_kernel<true>, dim3((unsigned)glove->a.R), dim3(512), glove->lds, st, p, 0, nullptr, nullptr, glove->a, glove->a.R);
         else hipLaunchKernelGGL(xpanel_presplit_glove_kernel<false>, dim3((unsigned)glove->a.R), dim3(512), glove->lds, st, p, 0, nullptr, nullptr, glove->a, glove->a.R);
+        LAUNCH_CHECK();
         glove = nullptr;
     }
     if (presplit) {      // (split contractions: the 64 x 64 kernel)
         // column operands split once (bf16 planes in fragment order), then tiles that only split X: 64 x 128 against W0, 128 x 32
         // against the support rows
         const int cbg = (p.gcols + 31) / 32;
-        unsigned short* Wp = planes; unsigned short* Xp = planes + ps_w0_bytes(D, h0) / sizeof(unsigned short);
-        const long nfrag = ((long)h0 / 32 + (long)B * cbg) * (D / 16);      // one wave per fragment
+        const bool gsplit = xp_gsplit() != 0;                               // the Gram tiles split their own column block: W0 planes only
+        const int cbp = gsplit ? 0 : cbg;
+        unsigned short* Wp = planes; unsigned short* Xp = gsplit ? nullptr : planes + ps_w0_bytes(D, h0) / sizeof(unsigned short);
+        const long nfrag = ((long)h0 / 32 + (long)B * cbp) * (D / 16);      // one wave per fragment
         if (glove) {                                                        // the pending embedding bag rides in front (its rows first)
             const unsigned ng = (unsigned)glove->a.R, nb = (unsigned)((nfrag + 7) / 8);
-            if (glove->vec) hipLaunchKernelGGL(xpanel_presplit_glove_kernel<true>, dim3(ng + nb), dim3(512), glove->lds, st, p, cbg, Wp, Xp, glove->a, (int)ng);
-            else hipLaunchKernelGGL(xpanel_presplit_glove_kernel<false>, dim3(ng + nb), dim3(512), glove->lds, st, p, cbg, Wp, Xp, glove->a, (int)ng);
+            if (glove->vec) hipLaunchKernelGGL(xpanel_presplit_glove_kernel<true>, dim3(ng + nb), dim3(512), glove->lds, st, p, cbp, Wp, Xp, glove->a, (int)ng);
+            else hipLaunchKernelGGL(xpanel_presplit_glove_kernel<false>, dim3(ng + nb), dim3(512), glove->lds, st, p, cbp, Wp, Xp, glove->a, (int)ng);
             glove->on = 0; glove = nullptr;
         } else
-        hipLaunchKernelGGL(xpanel_presplit_kernel, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, st, p, cbg, Wp, Xp);
+        hipLaunchKernelGGL(xpanel_presplit_kernel, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, st, p, cbp, Wp, Xp);
         const int tm = (S + Qn + 63) / 64, tg = (S + Qn + 127) / 128;
         const unsigned nwg = 8u * nper * (tm * (h0 / 128) * p.ksplit + tg * cbg);
         HyperFwdArgs none; memset(&none, 0, sizeof(none));
@@ -1381,7 +1445,8 @@ int launch_xpanel_fwd(hipStream_t st, int B, int S, int Qn, int D, int h0, const
         } else {
             hipLaunchKernelGGL((xpanel_fwd_ps_kernel<2, false>), dim3(nwg), dim3(256), 0, st, p, Wp, Xp, A0, G, tm, tg, cbg, none, g_trace);
         }
-        xp_plan_fwd(5, 2, p.ksplit, cbg, rider_done && *rider_done);
+        xp_plan_fwd(5, 2, p.ksplit, cbg, rider_done && *rider_done, gsplit ? 2 : 1,
+                    ps_w0_bytes(D, h0) + (size_t)B * 3 * cbp * 32 * D * sizeof(unsigned short));
     } else if (kernel == 4) {
         const int sbn = xp_sbn();
         HyperFwdArgs none; memset(&none, 0, sizeof(none));

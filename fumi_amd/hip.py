@@ -22,7 +22,7 @@ SYMBOLS = [
     "fumi_hip_set_spin_limit", "fumi_hip_set_trace_buffer",
     "fumi_hip_set_profiling", "fumi_hip_set_profiling_every", "fumi_hip_get_profile", "fumi_hip_phase_name",
     "fumi_hip_fumi_step", "fumi_hip_fumi_step_indexed", "fumi_hip_maml_step", "fumi_hip_am3_step",
-    "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan",
+    "fumi_hip_glove_bag", "fumi_hip_glove_bag_select", "fumi_hip_glove_bag_select_deferred", "fumi_hip_glove_flush", "fumi_hip_class_text_select", "fumi_hip_xpanel_fwd", "fumi_hip_xpanel_bwd", "fumi_hip_xpanel_plan", "fumi_hip_xpanel_planes_bytes", "fumi_hip_xpanel_fwd_rows",
     "fumi_hip_epi_plan", "fumi_hip_epi_plan_query", "fumi_hip_hyper_plan", "fumi_hip_hyper_plan_query",
     "fumi_hip_reduce_segments",
     "fumi_hip_adam_step", "fumi_hip_adam_step_deferred", "fumi_hip_adam_flush",
@@ -162,6 +162,9 @@ def lib():
         L.fumi_hip_xpanel_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5
         L.fumi_hip_xpanel_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [c_float, c_void_p]
         L.fumi_hip_xpanel_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_xpanel_fwd_rows.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int64] + [c_void_p] * 5
+        L.fumi_hip_xpanel_planes_bytes.argtypes = []
+        L.fumi_hip_xpanel_planes_bytes.restype = c_size_t
         L.fumi_hip_epi_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_epi_plan_query.argtypes = [c_int] * 6 + [POINTER(c_int)] + [c_int] * 5 + [POINTER(c_int), c_int]
         L.fumi_hip_hyper_plan.argtypes = [POINTER(c_int), c_int]
@@ -908,6 +911,22 @@ def xpanel_fwd(ws, x_s, x_q, W0, out=None):
     return A0, G
 
 
+def xpanel_fwd_rows(ws, table, idx_s, idx_q, W0, gram=True, out=None):
+    """xpanel_fwd over rows of ``table`` [n_rows, D]: row r of episode b is table[idx_s[b, r]] (r < S) or table[idx_q[b, r - S]]
+    (int64 indices).  ``gram=False``: A0 only (G is None; no Gram tile runs).  ``out``: (A0, G) tensors to write."""
+    dev = _dev(table)
+    (B, S), Qn, h0, D = idx_s.shape, idx_q.shape[1], W0.shape[0], table.shape[1]
+    for t, name in ((idx_s, "idx_s"), (idx_q, "idx_q")):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != table.device:
+            raise FumiHipError(f"xpanel_fwd_rows: {name} must be a contiguous int64 tensor on the table's device")
+    A0 = _out(out[0] if out is not None else None, (B, S + Qn, h0), dev, "A0")
+    G = _out(out[1] if out is not None else None, (B, S + Qn, S), dev, "G") if gram else None
+    _check(lib().fumi_hip_xpanel_fwd_rows(ws.handle, _stream(dev), B, S, Qn, D, h0, _f32(table, "table"), table.shape[0],
+                                          c_void_p(idx_s.data_ptr()), c_void_p(idx_q.data_ptr()), _f32(W0, "W0"), _f32(A0, "A0"),
+                                          _f32(G, "G") if gram else c_void_p(None)), "fumi_hip_xpanel_fwd_rows")
+    return A0, G
+
+
 def xpanel_bwd(ws, x_s, x_q, Abar, scale=1.0, out=None):
     """gW0 [h0, D].  ``x_s`` or ``x_q`` (not both) may be None: a one-sided panel over the rows of the other (Abar [B, rows, h0]).
     ``out``: the tensor to write instead of a fresh one."""
@@ -949,8 +968,9 @@ def reduce_segments(ws, segs, scale=1.0):
 
 
 XPANEL_PLAN_KEYS = ("fwd_kernel", "fwd_ring", "fwd_ksplit", "fwd_gram_blocks", "fwd_rode",
-                    "bwd_kernel", "bwd_nb", "bwd_sk", "bwd_nsplit", "bwd_kchunk", "bwd_rode")
+                    "bwd_kernel", "bwd_nb", "bwd_sk", "bwd_nsplit", "bwd_kchunk", "bwd_rode", "fwd_gram_split")
 XPANEL_FWD_KERNELS = {1: "generic", 2: "generic_fast", 3: "fp32", 4: "split", 5: "presplit"}
+XPANEL_GRAM_SPLIT = {0: "none", 1: "planes", 2: "tile"}      # where the pre-split forward splits the support rows of its Gram tiles
 XPANEL_BWD_KERNELS = {1: "guarded64", 2: "fast64", 3: "wide_fp32", 4: "wide_split", 5: "narrow_split"}
 
 
@@ -960,6 +980,12 @@ def xpanel_plan():
     v = (c_int * len(XPANEL_PLAN_KEYS))()
     _check(lib().fumi_hip_xpanel_plan(v, len(XPANEL_PLAN_KEYS)), "fumi_hip_xpanel_plan")
     return {k: int(x) for k, x in zip(XPANEL_PLAN_KEYS, v)}
+
+
+def xpanel_planes_bytes():
+    """Bytes of bf16 operand planes the last forward X-panel launch of this process wrote and read (fumi_hip_xpanel_planes_bytes):
+    3 * h0 * D * 2 for W0, plus the padded support rows of every episode under FUMI_XP_GSPLIT=0."""
+    return int(lib().fumi_hip_xpanel_planes_bytes())
 
 
 class AdamArgs:

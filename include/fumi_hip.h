@@ -232,11 +232,19 @@ int fumi_hip_xpanel_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Q
 int fumi_hip_reduce_segments(fumi_ws_t* ws, fumi_stream_t stream, int n, const float* const* src, const int* nslab,
         const long* stride, const long* count, float* const* dst, float scale);
 /* bwd also takes a one-sided panel: S == 0 (x_s may be NULL) or Qn == 0 (x_q may be NULL), not both.
- * Which kernel form the last fwd / bwd X-panel launch of this process took, up to 11 ints:
+ * Which kernel form the last fwd / bwd X-panel launch of this process took, up to 12 ints:
  *   [fwd kernel (1 generic guarded, 2 generic fast, 3 fp32 MFMA, 4 per-tile split, 5 pre-split), ring depth, ksplit, Gram column
  *    blocks, rider rode, bwd kernel (1 64x64 guarded, 2 64x64 fast, 3 wide fp32, 4 wide split, 5 narrow swapped split), NB, SK,
- *    nsplit, kchunk, rider rode].  Host-side record only: no launch reads it. */
+ *    nsplit, kchunk, rider rode, where the pre-split fwd form splits its Gram operand (0 another form, 1 planes written by the
+ *    pre-split launch, 2 inside the Gram tiles: DESIGN.md section 45)].  Host-side record only: no launch reads it. */
 int fumi_hip_xpanel_plan(int* plan, int n);
+/* The forward X-panel pass over rows of a table [n_rows, D]: row r of episode b is table[idx_s[b, r]] (r < S) or table[idx_q[b, r - S]]
+ * (what the zero-copy sampler passes).  G may be NULL: A0 only, and no Gram tile runs (AM3's image encoder).  An index outside
+ * [0, n_rows) sets the workspace status and reads row 0. */
+int fumi_hip_xpanel_fwd_rows(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int D, int h0,
+        const float* table, int64_t n_rows, const int64_t* idx_s, const int64_t* idx_q, const float* W0, float* A0, float* G);
+/* Bytes of bf16 operand planes the last fwd X-panel launch of this process wrote and read (0: a form without planes). */
+size_t fumi_hip_xpanel_planes_bytes(void);
 /* The plan of the episode chain (csrc/episode.hip: plan_episodes; DESIGN.md sections 29 and 40) of the last FuMI / MAML step of this
  * process that ran the chain, up to 18 ints:
  *   [adapt form (0 none: the inner step runs inside the fused query kernel, 1 LDS-resident, 2 generic), adapt column parts AP,
