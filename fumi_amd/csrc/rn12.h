@@ -120,3 +120,12 @@ int launch_rn_avgpool(hipStream_t st, int BM, int C, const RnGeom& g, const rbf1
 int launch_rn_avgpool_bwd(hipStream_t st, int BM, int C, const RnGeom& g, const float* df, rbf16* dout);
 // images fp32 [BM][Cin][H][W] -> bf16 padded channels-last with 16 channels
 int launch_rn_img_prep(hipStream_t st, long BM, int Cin, const RnGeom& g, const float* img, rbf16* out);
+
+// ---- rn12_drop.hip -----------------------------------------------------------------------------------------------------------------
+// DropBlock (block > 1) / dropout (block == 1) of a pooled map [B][M Pp][C] in place: map = keep * scale * map, the mask a pure
+// function of (seed, blk, set, global episode b0 + b, image, channel, position), scale = total / kept per group b.  count: the launch
+// that writes kept [B] (64-bit integers) and scale [B] (ticket [B]: its arrival counters); apply: the launch that scales the map.
+// FUMI_EINVAL (nothing launched): rate outside [0, 1), block outside 1..8, block > 1 with H or W beyond 64.
+int rn_drop_plan(int H, int W, float rate, int block, int* bs_out, unsigned* thr_out);
+int launch_rn_drop(hipStream_t st, int B, int M, const RnGeom& g, int C, float rate, int block, unsigned long long seed, int blk,
+                   int set, int b0, rbf16* map, unsigned long long* kept, unsigned* ticket, float* scale, bool count, bool apply);

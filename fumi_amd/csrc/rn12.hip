@@ -156,8 +156,12 @@ size_t scratch_sizes(const RnNet& n, int S, int Qn, RnScratch& sc) {
 // the pass joins (ev[1]) before it returns.  Their partial-sum scratch is touched by that stream only.  Measured: 568.8 -> 551.7 ms
 // per 8-episode step (3 %: the convolutions and the weight gradients each hold 2 x 240 of a SIMD's 512 registers per lane, so the
 // element-wise waves cannot sit beside them -- the gain is the tails of the launches filling up, not true co-residency).
+// DropBlock / dropout on the pooled block outputs (the first-order encoder pair's _drop entries; off everywhere else): the rates,
+// block sizes and seed as the caller passed them; set / b0 name the groups of the pass in flight (support 0 / query 1, the global
+// index of the chunk's first episode)
+struct RnDrop { bool on; float rate[RN_MAXBLK]; int block[RN_MAXBLK]; unsigned long long seed; int set, b0; };
 struct RnCtx { fumi_ws* ws; hipStream_t st; RnNet n; RnScratch sc; hipStream_t side = nullptr; bool forked = false;
-               hipEvent_t ev_fork = nullptr, ev_join = nullptr; };
+               hipEvent_t ev_fork = nullptr, ev_join = nullptr; RnDrop drop = {}; };
 
 static hipStream_t rn_side_stream(fumi_ws* ws) {
     static const int on = getenv("FUMI_RN_SIDE") ? atoi(getenv("FUMI_RN_SIDE")) : 1;
@@ -252,6 +256,20 @@ RnJoin join_of(const RnNet& n, int M, int l, const RnPass& pb, const RnTan* tb) 
     return j;
 }
 
+// map <- keep * scale * map for block l's pooled output (forward) or its adjoint (backward): a count launch, then the apply launch.
+// The counters sit at the head of the backward's reduction scratch, idle at both places (the forward never uses it; in the backward
+// the join's reduction, next on this stream, overwrites it).  Blocks with rate 0 launch nothing.
+int drop_map(RnCtx& c, int M, int l, rbf16* map) {
+    const RnDrop& d = c.drop;
+    if (!d.on || !(d.rate[l] > 0.f)) return FUMI_OK;
+    const RnNet& n = c.n;
+    if ((size_t)4 * n.B > c.sc.rpart_n) return FUMI_ENOMEM;                      // (cannot happen: 5 C floats per episode and slab)
+    unsigned long long* kept = (unsigned long long*)c.sc.rpart;
+    TRYP(FUMI_PH_RN_EW, launch_rn_drop(c.st, n.B, M, n.g[l + 1], n.C[l], d.rate[l], d.block[l], d.seed, l, d.set, d.b0, map, kept,
+                                       (unsigned*)(kept + n.B), c.sc.rpart + 3 * (size_t)n.B, true, true));
+    return FUMI_OK;
+}
+
 int forward_pass(RnCtx& c, int M, const rbf16* img16, const float* params, const rbf16* frags, RnPass& pb, const float* head,
                  const int64_t* y, float scale, float* logits, int64_t* preds, float* preds_f, float* loss_b, float* acc_b) {
     const RnNet& n = c.n;
@@ -272,6 +290,7 @@ int forward_pass(RnCtx& c, int M, const rbf16* img16, const float* params, const
         s[0] = src_of(xin, xs, frags + L[3].fF, n.FSZ, L[3].Cin, 1);
         TRY(conv_bn(c, M, l, 1, s, pb.u[l][3], nullptr, RCM_FWD, pb.coef[l][3], params + L[3].offG, params + L[3].offB, n.PSZ));
         TRYP(FUMI_PH_RN_EW, launch_rn_join_fwd(c.st, join_of(n, M, l, pb, nullptr), pb.out[l], 0));
+        TRY(drop_map(c, M, l, pb.out[l]));
     }
     TRYP(FUMI_PH_RN_EW, launch_rn_avgpool(c.st, n.B * M, n.F, n.g[n.nblk], pb.out[n.nblk - 1], pb.f));
     if (!head) return FUMI_OK;
@@ -311,6 +330,7 @@ int backward_pass(RnCtx& c, int M, const rbf16* img16, const rbf16* frags, RnPas
         const RnMap m = map_of(n, M, l);
         const int nt = rn_red_nt(m);
         const RnJoin j = join_of(n, M, l, pb, nullptr);
+        TRY(drop_map(c, M, l, pb.dout[l]));                // (the join's backward reads u3 / us and dout, never out[l])
         TRYP(FUMI_PH_RN_EW, launch_rn_join_reduce(c.st, j, pb.dout[l], nullptr, c.sc.rpart, 0));
         TRY(coef_bwd(c, M, l, nt, 3, 0, 1, 0, RCM_BWD, pb.coef[l][2], nullptr, G + L[2].offG, G + L[2].offB));
         TRY(coef_bwd(c, M, l, nt, 3, 0, 2, 0, RCM_BWD, pb.coef[l][3], nullptr, G + L[3].offG, G + L[3].offB));
@@ -694,7 +714,7 @@ int side_reserve(fumi_ws* ws, size_t floats, float** out) {
 // forms and every chunking give bit-identical features and gradients.
 namespace {
 struct RnEncPlan { int lanes, Bc, nchunks, taped; size_t glob, lane, tape, total; };
-struct RnEncToken { bool valid; fumi_ws* ws; char* base; int B, S, Qn, Cin, H, W, nblk; int ch[RN_MAXBLK]; RnEncPlan pl; };
+struct RnEncToken { bool valid; fumi_ws* ws; char* base; int B, S, Qn, Cin, H, W, nblk; int ch[RN_MAXBLK]; RnEncPlan pl; RnDrop drop; };
 RnEncToken g_rn_enc = {};
 RnEncPlan g_rn_enc_last = {};                         // plan of the last encode (fumi_hip_resnet12_encode_plan)
 
@@ -775,6 +795,31 @@ void with_bwd_maps(RnPass& p, const RnPass& b) {
         for (int k = 0; k < 2; ++k) p.da[l][k] = b.da[l][k];
         p.dout[l] = b.dout[l];
     }
+}
+// the drop arguments of a call, checked (FUMI_EINVAL: a rate outside [0, 1), or a block size / map the kernels refuse at a dropped
+// block).  With no rate > 0 the result is the all-zero `off` record whatever the block sizes and the seed were.
+int enc_drop_args(const RnNet& n, const float* rate, const int* block, unsigned long long seed, RnDrop& d) {
+    memset(&d, 0, sizeof(d));
+    if (!rate && !block) return FUMI_OK;                                  // the entries without drop
+    if (!rate || !block) return FUMI_EINVAL;
+    bool on = false;
+    for (int l = 0; l < n.nblk; ++l) {
+        if (!(rate[l] >= 0.f) || !(rate[l] < 1.f)) return FUMI_EINVAL;
+        if (rate[l] > 0.f) {
+            int bs; unsigned thr;
+            TRY(rn_drop_plan(n.g[l + 1].H, n.g[l + 1].W, rate[l], block[l], &bs, &thr));
+            on = true;
+        }
+    }
+    if (!on) return FUMI_OK;
+    d.on = true; d.seed = seed;
+    for (int l = 0; l < n.nblk; ++l) { d.rate[l] = rate[l]; d.block[l] = block[l]; }
+    return FUMI_OK;
+}
+bool enc_drop_same(const RnDrop& a, const RnDrop& b, int nblk) {
+    if (a.on != b.on || a.seed != b.seed) return false;
+    for (int l = 0; l < nblk; ++l) if (memcmp(&a.rate[l], &b.rate[l], sizeof(float)) || a.block[l] != b.block[l]) return false;
+    return true;
 }
 bool enc_shape_ok(const RnEncToken& t, fumi_ws* ws, int B, int S, int Qn, int Cin, int H, int W, int nblk, const int* channels) {
     if (!t.valid || t.ws != ws || t.base != ws->base || t.B != B || t.S != S || t.Qn != Qn || t.Cin != Cin || t.H != H || t.W != W ||
@@ -963,9 +1008,9 @@ int fumi_hip_resnet12_features(fumi_ws_t* ws, fumi_stream_t stream, int G, int M
 }
 
 // ---- first-order encoder pair ---------------------------------------------------------------------------------------------------------
-int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+static int rn_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
         int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
-        float* feats_s, float* feats_q, int keep_tape) {
+        float* feats_s, float* feats_q, int keep_tape, const float* drop_rate, const int* drop_block, unsigned long long drop_seed) {
     if (!ws || !x_s || !x_q || !theta || !feats_s || !feats_q || !channels || B < 1 || S < 1 || Qn < 1) return FUMI_EINVAL;
     if (nblk < 1 || nblk > RN_MAXBLK) return FUMI_EINVAL;
     for (int i = 0; i < 12 * nblk; ++i) if (!theta[i]) return FUMI_EINVAL;
@@ -975,6 +1020,7 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
     RnCtx c0; c0.ws = ws; c0.st = st;
     int rc = net_init(c0.n, B, nblk, Cin, 1, H, W, channels);
     if (rc) return rc;
+    if ((rc = enc_drop_args(c0.n, drop_rate, drop_block, drop_seed, c0.drop))) return rc;
     RnEncPlan pl;
     enc_plan(ws, c0.n, B, S, Qn, keep_tape != 0, pl);
     if ((rc = ws_reserve(ws, pl.total))) return rc;
@@ -1003,7 +1049,9 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
             TRY(launch_rn_img_prep(c.st, (long)bc * S, Cin, c.n.g[0], x_s + (size_t)b0 * S * img, img_s));
             TRY(launch_rn_img_prep(c.st, (long)bc * Qn, Cin, c.n.g[0], x_q + (size_t)b0 * Qn * img, img_q));
             ps.f = feats_s + (size_t)b0 * S * F; pq.f = feats_q + (size_t)b0 * Qn * F;     // the pooled features land in the caller's tensors
+            c.drop.b0 = b0; c.drop.set = 0;
             TRY(forward_pass(c, S, img_s, L[lane].params, L[lane].frags, ps, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
+            c.drop.set = 1;
             TRY(forward_pass(c, Qn, img_q, L[lane].params, L[lane].frags, pq, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
         }
         return ws_join_lanes(ws, st, pl.lanes);
@@ -1014,25 +1062,42 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
         RnEncToken& t = g_rn_enc;
         t.ws = ws; t.base = ws->base; t.B = B; t.S = S; t.Qn = Qn; t.Cin = Cin; t.H = H; t.W = W; t.nblk = nblk;
         for (int l = 0; l < nblk; ++l) t.ch[l] = channels[l];
-        t.pl = pl; t.valid = true;
+        t.pl = pl; t.drop = c0.drop; t.valid = true;
     }
     return FUMI_OK;
 }
 
-int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
+        float* feats_s, float* feats_q, int keep_tape) {
+    return rn_encode(ws, stream, B, S, Qn, Cin, H, W, nblk, channels, x_s, x_q, theta, feats_s, feats_q, keep_tape, nullptr, nullptr, 0);
+}
+
+int fumi_hip_resnet12_encode_drop(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
+        float* feats_s, float* feats_q, int keep_tape, const float* drop_rate, const int* drop_block, uint64_t drop_seed) {
+    if (!drop_rate || !drop_block) return FUMI_EINVAL;
+    return rn_encode(ws, stream, B, S, Qn, Cin, H, W, nblk, channels, x_s, x_q, theta, feats_s, feats_q, keep_tape, drop_rate, drop_block,
+                     drop_seed);
+}
+
+static int rn_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
         int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
-        const float* dfeats_q, float scale, float* const* g_theta) {
+        const float* dfeats_q, float scale, float* const* g_theta, const float* drop_rate, const int* drop_block,
+        unsigned long long drop_seed) {
     if (!ws || !x_s || !x_q || !dfeats_s || !dfeats_q || !g_theta || !channels || nblk < 1 || nblk > RN_MAXBLK) return FUMI_EINVAL;
     const RnEncToken t = g_rn_enc;
     if (!enc_shape_ok(t, ws, B, S, Qn, Cin, H, W, nblk, channels)) return FUMI_EINVAL;     // no tape of this shape in this workspace
     for (int i = 0; i < 12 * nblk; ++i) if (!g_theta[i]) return FUMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(ws->device));
-    g_rn_enc.valid = false;                                               // the backward pass overwrites the BN tables of the tape
-    const RnEncPlan pl = t.pl;                                            // the layout the forward call left
     RnCtx c0; c0.ws = ws; c0.st = st;
     int rc = net_init(c0.n, B, nblk, Cin, 1, H, W, channels);
     if (rc) return rc;
+    if ((rc = enc_drop_args(c0.n, drop_rate, drop_block, drop_seed, c0.drop))) return rc;
+    if (!enc_drop_same(c0.drop, t.drop, nblk)) return FUMI_EINVAL;        // the tape was written under another mask (it stays valid)
+    HIP_TRY(hipSetDevice(ws->device));
+    g_rn_enc.valid = false;                                               // the backward pass overwrites the BN tables of the tape
+    const RnEncPlan pl = t.pl;                                            // the layout the forward call left
     if ((rc = ws_reserve(ws, pl.total))) return rc;
     if (ws->base != t.base) return FUMI_EINVAL;
     for (int i = 1; i < pl.lanes; ++i) if (!ws_lane_stream(ws, i)) return FUMI_EHIP;
@@ -1062,12 +1127,14 @@ int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int
             ps.df = const_cast<float*>(dfeats_s) + (size_t)b0 * S * F;   // read straight into the average-pool backward
             pq.df = const_cast<float*>(dfeats_q) + (size_t)b0 * Qn * F;
             const float* xs = x_s + (size_t)b0 * S * img; const float* xq = x_q + (size_t)b0 * Qn * img;
+            c.drop.b0 = b0; c.drop.set = 0;
             if (!pl.taped) {
                 TRY(launch_rn_img_prep(c.st, (long)bc * S, Cin, c.n.g[0], xs, img_s));
                 ps.f = L[lane].f;
                 TRY(forward_pass(c, S, img_s, L[lane].params, L[lane].frags, ps, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr));
             }
             TRY(backward_pass(c, S, img_s, L[lane].frags, ps, nullptr, Gs + (size_t)b0 * n0.PSZ, nullptr));
+            c.drop.set = 1;
             if (!pl.taped) {
                 TRY(launch_rn_img_prep(c.st, (long)bc * Qn, Cin, c.n.g[0], xq, img_q));
                 pq.f = L[lane].f;
@@ -1082,6 +1149,37 @@ int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int
     };
     if ((rc = run())) { ws_abandon_lanes(ws); return rc; }
     return FUMI_OK;
+}
+
+int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
+        const float* dfeats_q, float scale, float* const* g_theta) {
+    return rn_encode_bwd(ws, stream, B, S, Qn, Cin, H, W, nblk, channels, x_s, x_q, dfeats_s, dfeats_q, scale, g_theta, nullptr, nullptr, 0);
+}
+
+int fumi_hip_resnet12_encode_bwd_drop(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
+        const float* dfeats_q, float scale, float* const* g_theta, const float* drop_rate, const int* drop_block, uint64_t drop_seed) {
+    if (!drop_rate || !drop_block) return FUMI_EINVAL;
+    return rn_encode_bwd(ws, stream, B, S, Qn, Cin, H, W, nblk, channels, x_s, x_q, dfeats_s, dfeats_q, scale, g_theta, drop_rate,
+                         drop_block, drop_seed);
+}
+
+// DropBlock / dropout of one raw map in place (unit parity of rn12_drop.hip): the count launch, then the apply launch.
+// map [B][M (H+2)(W+2)][C] bf16; kept_out [B] int64, scale_out [B] fp32 (device).  rate == 0 still runs both launches (nothing drops).
+int fumi_hip_rn12_drop_apply(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, float rate, int block,
+        uint64_t seed, int block_index, int set, int b0, void* map_in_out, int64_t* kept_out, float* scale_out) {
+    if (!ws || !map_in_out || !kept_out || !scale_out || B < 1 || M < 1 || C < 1) return FUMI_EINVAL;
+    int bs; unsigned thr;
+    TRY(rn_drop_plan(H, W, rate, block, &bs, &thr));                     // (every refusal before the workspace is touched)
+    if (block_index < 0 || set < 0 || set > 1 || b0 < 0) return FUMI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ws->device));
+    int rc = ws_reserve(ws, ws_align((size_t)B * 4));
+    if (rc) return rc;
+    unsigned* ticket = (unsigned*)ws_f(ws, (size_t)B);
+    return launch_rn_drop(st, B, M, rn_geom(H, W), C, rate, block, seed, block_index, set, b0, (rbf16*)map_in_out,
+                          (unsigned long long*)kept_out, ticket, scale_out, true, true);
 }
 
 // plan of the last fumi_hip_resnet12_encode: *taped (1 taped, 0 recompute), *chunk (episodes per chunk), *lanes

@@ -68,6 +68,16 @@ class HipEngine:
         return hip.resnet12_encode_bwd(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, dfeats_s, dfeats_q, theta_like,
                                        scale=scale, g_theta=g_theta)
 
+    def resnet12_encode_drop(self, x_s, x_q, theta, drop_rate, drop_block, drop_seed, keep_tape=False):
+        """``resnet12_encode`` with DropBlock / dropout on the block outputs (training steps only; per-block rates and block sizes)."""
+        return hip.resnet12_encode_drop(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, theta, drop_rate, drop_block, drop_seed,
+                                        keep_tape=keep_tape)
+
+    def resnet12_encode_bwd_drop(self, x_s, x_q, dfeats_s, dfeats_q, theta_like, drop_rate, drop_block, drop_seed, scale=1.0,
+                                 g_theta=None):
+        return hip.resnet12_encode_bwd_drop(hip.Workspace.get(x_s.device, "encoder"), x_s, x_q, dfeats_s, dfeats_q, theta_like,
+                                            drop_rate, drop_block, drop_seed, scale=scale, g_theta=g_theta)
+
     def fumi_conv4_step(self, n_way, x_s, y_s, x_q, y_q, text_s, theta, phi, T, alpha, tanh_head, need_grad, grad_scale,
                         g_theta=None, g_phi=None, cls_text=None, stats=None, g_cls_text=None):
         """FuMI with the Conv4 encoder at the im_net seam: x_s [B,S,C,H,W], x_q [B,Qn,C,H,W]."""

@@ -48,6 +48,7 @@ SYMBOLS = [
     "fumi_hip_svm_head_step", "fumi_hip_svm_set_form", "fumi_hip_svm_get_fit",
     "fumi_hip_cos_cls_head_step",
     "fumi_hip_feat_adapt_tape_floats", "fumi_hip_feat_adapt_fwd", "fumi_hip_feat_adapt_bwd",
+    "fumi_hip_resnet12_encode_drop", "fumi_hip_resnet12_encode_bwd_drop", "fumi_hip_rn12_drop_apply",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -212,6 +213,11 @@ def lib():
                                                                                   c_int])
         L.fumi_hip_resnet12_encode_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [PI] + [c_void_p] * 4 + [c_float, PP]
         L.fumi_hip_resnet12_encode_plan.argtypes = [POINTER(c_int)] * 3
+        rn_drop = [POINTER(c_float), PI, ctypes.c_uint64]                                     # drop_rate, drop_block, drop_seed
+        L.fumi_hip_resnet12_encode_drop.argtypes = L.fumi_hip_resnet12_encode.argtypes + rn_drop
+        L.fumi_hip_resnet12_encode_bwd_drop.argtypes = L.fumi_hip_resnet12_encode_bwd.argtypes + rn_drop
+        L.fumi_hip_rn12_drop_apply.argtypes = ([c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_int, ctypes.c_uint64] + [c_int] * 3 +
+                                               [c_void_p] * 3)
         L.fumi_hip_am3_step_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_rn12_conv.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4
         L.fumi_hip_rn12_wgrad.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3
@@ -1419,19 +1425,27 @@ def _enc_features(enc, ws, x, theta):
     return feats
 
 
-def _enc_encode(enc, ws, x_s, x_q, theta, keep_tape):
+def _drop_args(nblk, drop_rate, drop_block, drop_seed):
+    """(rate [nblk] fp32, block [nblk] int, seed uint64) as the ``_drop`` entry points take them (host values)."""
+    if len(drop_rate) != nblk or len(drop_block) != nblk:
+        raise FumiHipError("drop_rate / drop_block must hold one value per block")
+    return ((c_float * nblk)(*[float(r) for r in drop_rate]), _ci(drop_block), ctypes.c_uint64(int(drop_seed) & 0xFFFFFFFFFFFFFFFF))
+
+
+def _enc_encode(enc, ws, x_s, x_q, theta, keep_tape, drop=None):
     dev = _dev(x_s)
     dims, F, extra = enc.shapes(x_s, None, x_q, None, theta)
     B, S, Qn = dims[:3]
     fs = torch.empty(B, S, F, device=dev, dtype=torch.float32)
     fq = torch.empty(B, Qn, F, device=dev, dtype=torch.float32)
-    sym = f"fumi_hip_{enc.name}_encode"
+    sym = f"fumi_hip_{enc.name}_encode" + ("_drop" if drop is not None else "")
+    tail = _drop_args(dims[-1], *drop) if drop is not None else ()
     _check(getattr(lib(), sym)(ws.handle, _stream(dev), *dims, *extra, _f32(x_s, "x_s"), _f32(x_q, "x_q"), _parr(theta, "theta"),
-                               _f32(fs, "feats_s"), _f32(fq, "feats_q"), int(bool(keep_tape))), sym)
+                               _f32(fs, "feats_s"), _f32(fq, "feats_q"), int(bool(keep_tape)), *tail), sym)
     return fs, fq
 
 
-def _enc_encode_bwd(enc, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta):
+def _enc_encode_bwd(enc, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta, drop=None):
     dev = _dev(x_s)
     dims, F, extra = enc.shapes(x_s, None, x_q, None, theta_like)
     B, S, Qn = dims[:3]
@@ -1443,9 +1457,10 @@ def _enc_encode_bwd(enc, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_
     else:
         for i, (g, t) in enumerate(zip(g_theta, theta_like)):
             _shape(g, tuple(t.shape), f"g_theta[{i}]")
-    sym = f"fumi_hip_{enc.name}_encode_bwd"
+    sym = f"fumi_hip_{enc.name}_encode_bwd" + ("_drop" if drop is not None else "")
+    tail = _drop_args(dims[-1], *drop) if drop is not None else ()
     _check(getattr(lib(), sym)(ws.handle, _stream(dev), *dims, *extra, _f32(x_s, "x_s"), _f32(x_q, "x_q"), _f32(dfeats_s, "dfeats_s"),
-                               _f32(dfeats_q, "dfeats_q"), float(scale), _parr(g_theta, "g_theta")), sym)
+                               _f32(dfeats_q, "dfeats_q"), float(scale), _parr(g_theta, "g_theta"), *tail), sym)
     return g_theta
 
 
@@ -1511,6 +1526,32 @@ def resnet12_encode_bwd(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale=1.0,
     """Gradient of sum <dfeats, ResNet12(x)> w.r.t. the encoder's parameters (summed over episodes, times ``scale``) from what the
     last ``resnet12_encode(..., keep_tape=True)`` left in ``ws``."""
     return _enc_encode_bwd(_RESNET12, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta)
+
+
+def resnet12_encode_drop(ws, x_s, x_q, theta, drop_rate, drop_block, drop_seed, keep_tape=False):
+    """``resnet12_encode`` with DropBlock / dropout on every block's pooled output: ``drop_rate`` / ``drop_block`` hold one value per
+    block (block size 1: element-wise dropout, 2..8: DropBlock; rate 0: nothing at that block), ``drop_seed`` is the step's 64-bit
+    seed.  The mask is regenerated from (seed, block, set, global episode, image, channel, position) wherever it is needed."""
+    return _enc_encode(_RESNET12, ws, x_s, x_q, theta, keep_tape, (drop_rate, drop_block, drop_seed))
+
+
+def resnet12_encode_bwd_drop(ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, drop_rate, drop_block, drop_seed, scale=1.0, g_theta=None):
+    """``resnet12_encode_bwd`` for a tape ``resnet12_encode_drop`` left: the three drop arguments must be the tape's (FUMI_EINVAL)."""
+    return _enc_encode_bwd(_RESNET12, ws, x_s, x_q, dfeats_s, dfeats_q, theta_like, scale, g_theta, (drop_rate, drop_block, drop_seed))
+
+
+def rn12_drop_apply(ws, x, H, W, rate, block, seed, block_index=0, set_index=0, b0=0):
+    """Unit op: x [B, M*(H+2)*(W+2), C] bf16 padded channels-last is scaled IN PLACE by keep * total / kept; returns (kept [B] int64,
+    scale [B] fp32)."""
+    dev = _dev(x)
+    B, npix, C = x.shape
+    M = npix // ((H + 2) * (W + 2))
+    kept = torch.empty(B, device=dev, dtype=torch.int64)
+    scale = torch.empty(B, device=dev, dtype=torch.float32)
+    _check(lib().fumi_hip_rn12_drop_apply(ws.handle, _stream(dev), B, M, H, W, C, float(rate), int(block),
+                                          ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(block_index), int(set_index), int(b0),
+                                          _bf16ptr(x, "x"), _i64(kept, "kept"), _f32(scale, "scale")), "fumi_hip_rn12_drop_apply")
+    return kept, scale
 
 
 def resnet12_set_budget(gigabytes):

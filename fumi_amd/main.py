@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.main_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.drop_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -275,6 +275,32 @@ def check_supported(args):
                              "--transductive_steps must be 0")
         if not 2 <= args.num_ways <= 64:
             raise NotImplementedError(f"the prototype adaptation takes 2 to 64 classes, got --num_ways {args.num_ways}")
+    d_rate, d_bs, d_nb, d_an = (getattr(args, k, d) for k, d in (("drop_rate", 0.0), ("drop_block_size", 5), ("drop_blocks", 2),
+                                                                   ("drop_anneal_steps", 40000)))
+    if not 0.0 <= d_rate < 1.0:
+        raise ValueError(f"--drop_rate {d_rate} must lie in [0, 1)")
+    if d_rate == 0.0 and (d_bs != 5 or d_nb != 2 or d_an != 40000):
+        raise ValueError("--drop_block_size, --drop_blocks and --drop_anneal_steps shape the DropBlock / dropout regulariser: they "
+                         "need --drop_rate > 0")
+    if d_rate > 0.0:
+        if family in ("fumi", "maml"):
+            raise NotImplementedError(f"--drop_rate with --model {family}: DropBlock / dropout is built into the first-order encoder "
+                                      "pair; the second-order FuMI / MAML ResNet-12 steps are out of scope and run without it")
+        if family not in ("pretrain", "metabaseline"):
+            raise NotImplementedError(f"--drop_rate with --model {args.model}: the regulariser is wired into the training steps of "
+                                      "--model pretrain and metabaseline only")
+        if args.im_encoder != "resnet12":
+            raise NotImplementedError(f"--drop_rate is DropBlock / dropout inside the ResNet-12 encoder: it needs --im_encoder resnet12, "
+                                      f"got {args.im_encoder}")
+        if not 1 <= d_bs <= 8:
+            raise ValueError(f"--drop_block_size {d_bs} must lie in [1, 8]")
+        if not 0 <= d_nb <= 4:
+            raise ValueError(f"--drop_blocks {d_nb} must lie in [0, 4]")
+        if d_an < 0:
+            raise ValueError(f"--drop_anneal_steps {d_an} must not be negative")
+        if d_bs > 1 and d_nb > 0 and (args.image_size >> (4 - d_nb + 1)) > 64:
+            raise NotImplementedError(f"DropBlock holds a row of the map in one 64-bit word: the first DropBlock block's pooled map "
+                                      f"({args.image_size >> (4 - d_nb + 1)} wide at --image_size {args.image_size}) must be at most 64 wide")
     eps, a_mix, a_cut, p_mix = (getattr(args, k, d) for k, d in (("label_smoothing", 0.0), ("mixup_alpha", 0.0),
                                                                     ("cutmix_alpha", 0.0), ("mix_prob", 1.0)))
     if family != "pretrain" and (eps != 0.0 or a_mix != 0.0 or a_cut != 0.0 or p_mix != 1.0):

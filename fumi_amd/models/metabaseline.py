@@ -74,8 +74,13 @@ class FeatAdapt(nn.Module):
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
                  ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0,
-                 svm=None, adapt="none"):
+                 svm=None, adapt="none", drop=None):
         super().__init__()
+        if drop is not None and im_encoder != "resnet12":
+            raise NotImplementedError("DropBlock / dropout on the block outputs is built into the ResNet-12 encoder pair: drop= needs "
+                                      "im_encoder resnet12")
+        self.drop = None                       # DropSchedule of the training steps, None: no drop
+        self.drop_step = 0                     # the training loop's step index: the mask seed and the annealed rate follow it
         if adapt not in ("none", "feat"):
             raise ValueError(f"the prototype adaptation must be none or feat, got {adapt}")
         if adapt == "feat" and (head not in ("cosine", "proto") or eval_head == "logreg" or int(transductive_steps) > 0):
@@ -119,6 +124,9 @@ class MetaBaseline(nn.Module):
             self.conv = ResNet12(image_channels, CHANNELS, image_size)
         else:
             raise NameError(f"{im_encoder} not allowed as image encoder of --model metabaseline (conv4, resnet12)")
+        if drop is not None:
+            from .resnet12 import DropSchedule
+            self.drop = DropSchedule(n_blocks=self.conv.n_blocks, **drop)
         self.num_ways = num_ways               # N of the episodes (None: read from the support labels, which synchronises)
         if head == "ridge":
             self.ridge = nn.Parameter(torch.tensor([math.log(float(ridge_lambda)), float(ridge_scale)]))
@@ -205,7 +213,12 @@ class MetaBaseline(nn.Module):
         x_s, x_q, y_s, y_q, N = self._episode(batch, device)
         temp, theta, fg = self._step_params(True)
         encode, encode_bwd = self._encoders(eng)
-        f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
+        # the training encode alone drops (validation, test and few_shot never do)
+        drop = self.drop.args(self.drop_step) if self.drop is not None and self.drop.rate_at(self.drop_step) > 0.0 else None
+        if drop is not None:
+            f_s, f_q = eng.resnet12_encode_drop(x_s, x_q, theta, *drop, keep_tape=True)
+        else:
+            f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         featw = self._pcache[3]                 # [] without the adaptation
         g_t, g_theta = fg.split((0 if self.proto_scale_fixed else 1) + len(featw))   # g_t: [head parameter | feat.*]
         h_s, h_y, tape = f_s, y_s, None         # what the head takes for its support set
@@ -225,7 +238,10 @@ class MetaBaseline(nn.Module):
         dfeats_s = out["dfeats_s"]
         if self.adapt == "feat":                # the head's gradient for the prototypes, back to the support features
             dfeats_s, _ = eng.feat_adapt_bwd(f_s, y_s, featw, tape, dfeats_s, n_way=N, g_w=g_t[len(g_t) - len(featw):])
-        encode_bwd(x_s, x_q, dfeats_s, out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
+        if drop is not None:
+            eng.resnet12_encode_bwd_drop(x_s, x_q, dfeats_s, out["dfeats_q"], theta, *drop, scale=1.0, g_theta=g_theta)
+        else:
+            encode_bwd(x_s, x_q, dfeats_s, out["dfeats_q"], theta, scale=1.0, g_theta=g_theta)
         _loss_acc(out, y_q, into=fg.tail)
         if optimizer is not None:
             optimizer.zero_grad()
@@ -303,6 +319,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
     opt, scheduler = optimizer if type(optimizer) == tuple else (optimizer, None)
     try:
         for batch_idx, batch in enumerate(train_loader):
+            model.drop_step = batch_idx            # (--drop_rate: the step's mask seed and annealed rate)
             tl, ta = model.evaluate(batch=batch, optimizer=opt, scheduler=scheduler, device=args.device, task="train")
             wandb.log({"train/acc": ta, "train/loss": tl, "num_episodes": (batch_idx + 1) * args.batch_size}, step=batch_idx)
             if batch_idx % args.eval_freq == 0:

@@ -42,8 +42,13 @@ from .common import _loss_acc
 class Pretrain(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, n_classes=64, bn_group=64, num_ways=None, label_smoothing=0.0,
                  metric="euclidean", metric_temp=10.0, ridge_lambda=50.0, ridge_scale=1.0, logreg=None, transductive_steps=0,
-                 distill=None, svm=None, head="linear", head_scale=10.0, head_scale_fixed=False):
+                 distill=None, svm=None, head="linear", head_scale=10.0, head_scale_fixed=False, drop=None):
         super().__init__()
+        if drop is not None and im_encoder != "resnet12":
+            raise NotImplementedError("DropBlock / dropout on the block outputs is built into the ResNet-12 encoder pair: drop= needs "
+                                      "im_encoder resnet12")
+        self.drop = None                                   # DropSchedule of the training steps, None: no drop
+        self.drop_step = 0                                 # the training loop's step index: the mask seed and the annealed rate follow it
         if head not in ("linear", "cosine"):
             raise ValueError(f"the classifier head must be linear or cosine, got {head}")
         if not (math.isfinite(float(head_scale)) and float(head_scale) > 0.0):
@@ -89,6 +94,9 @@ class Pretrain(nn.Module):
             self.conv = ResNet12(image_channels, CHANNELS, image_size)
         else:
             raise NameError(f"{im_encoder} not allowed as image encoder of --model pretrain (conv4, resnet12)")
+        if drop is not None:
+            from .resnet12 import DropSchedule
+            self.drop = DropSchedule(n_blocks=self.conv.n_blocks, **drop)
         self.n_classes = int(n_classes)
         self.bn_group = int(bn_group)          # R: images per batch-statistics group of a training step
         self.num_ways = num_ways               # N of the validation / test episodes (None: read from the labels)
@@ -210,7 +218,12 @@ class Pretrain(nn.Module):
             w_t, theta_t = self._teacher_params()
             t_s, t_q = encode(x_s, x_q, theta_t, keep_tape=False)
             feats_t = torch.cat((t_s.view(half, -1), t_q.view(half, -1)))
-        f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
+        # the student's training encode alone drops (the teacher above, validation, test and few_shot never do)
+        drop = self.drop.args(self.drop_step) if self.drop is not None and self.drop.rate_at(self.drop_step) > 0.0 else None
+        if drop is not None:
+            f_s, f_q = eng.resnet12_encode_drop(x_s, x_q, theta, *drop, keep_tape=True)
+        else:
+            f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         feats = torch.cat((f_s.view(half, -1), f_q.view(half, -1)))                 # [M, F], the images' order
         g_w, g_theta = fg.split(len(w) - 1 if self.head == "cosine" and self.head_scale_fixed else len(w))
         if self.head == "cosine":
@@ -227,7 +240,11 @@ class Pretrain(nn.Module):
         else:
             out = eng.cls_head_step(feats, y, w[0], w[1], need_grad=True, grad_scale=1.0, gW=g_w[0], gb=g_w[1])
         df = out["dfeats"]
-        encode_bwd(x_s, x_q, df[:half].view(B, R, -1), df[half:].view(B, R, -1), theta, scale=1.0, g_theta=g_theta)
+        if drop is not None:
+            eng.resnet12_encode_bwd_drop(x_s, x_q, df[:half].view(B, R, -1), df[half:].view(B, R, -1), theta, *drop, scale=1.0,
+                                         g_theta=g_theta)
+        else:
+            encode_bwd(x_s, x_q, df[:half].view(B, R, -1), df[half:].view(B, R, -1), theta, scale=1.0, g_theta=g_theta)
         torch.cat((out["loss"], out["correct"] / M), out=fg.tail)
         if optimizer is not None:
             optimizer.zero_grad()
@@ -350,6 +367,7 @@ def training_run(args, model, optimizer, train_loader, val_loader, max_test_batc
     opt, scheduler = optimizer if type(optimizer) == tuple else (optimizer, None)
     try:
         for batch_idx, batch in enumerate(train_loader):
+            model.drop_step = batch_idx                    # (--drop_rate: the step's mask seed and annealed rate)
             tl, ta = model.evaluate(batch=batch, optimizer=opt, scheduler=scheduler, device=args.device, task="train")
             wandb.log({"train/acc": ta, "train/loss": tl, "num_images": (batch_idx + 1) * args.pretrain_batch}, step=batch_idx)
             if batch_idx % args.eval_freq == 0:

@@ -2,8 +2,9 @@
 meta_named_parameters()"; ``--im_encoder resnet`` is a ``# TODO`` in the reference, fumi/models/am3.py:41-46).
 
 BASELINE.json configs[4] words a configuration the reference never implements: FuMI 20-way 5-shot with a ResNet-12 backbone in
-bf16, 5 inner steps, second-order outer gradients.  This module is the few-shot literature's ResNet-12 (TADAM / MetaOptNet form
-without DropBlock): four residual blocks of channels (64, 160, 320, 640),
+bf16, 5 inner steps, second-order outer gradients.  This module is the few-shot literature's ResNet-12 (TADAM / MetaOptNet form;
+DropBlock and dropout on the block outputs are a training-time option of the first-order encoder pair, ``DropSchedule`` below and
+DESIGN.md section 46; the second-order steps run without them): four residual blocks of channels (64, 160, 320, 640),
 
     a1 = lrelu(BN(conv3x3(x))),  a2 = lrelu(BN(conv3x3(a1))),  out = maxpool2(lrelu(BN(conv3x3(a2)) + BN(conv1x1(x)))),
 
@@ -21,6 +22,50 @@ from ..meta import MetaModule
 from .conv4 import MetaBatchNorm2d, MetaConv2d
 
 CHANNELS = (64, 160, 320, 640)
+
+
+def drop_rate_at(rate, step, anneal_steps):
+    """The literature's schedule: the drop probability of training step ``step`` is ``rate * min(1, step / anneal_steps)`` (the keep
+    rate annealed from 1 down to 1 - rate); ``anneal_steps == 0`` gives the full rate from step 0."""
+    if anneal_steps <= 0:
+        return float(rate)
+    return float(rate) * min(1.0, max(int(step), 0) / float(anneal_steps))
+
+
+def drop_step_seed(seed, step):
+    """The 64-bit mask seed of a training step from --seed and the step index (splitmix64 of their combination, on the host)."""
+    m = (1 << 64) - 1
+    z = ((int(seed) & m) * 0x9E3779B97F4A7C15 + (int(step) & m) + 0xD1B54A32D192ED03) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+class DropSchedule:
+    """--drop_rate and its companions for a ResNet-12 of ``n_blocks`` blocks: the last ``blocks`` blocks use DropBlock of size
+    ``block_size``, the earlier ones element-wise dropout, all at the annealed rate of the step.  ``args(step)`` is what the engine's
+    ``resnet12_encode_drop`` / ``resnet12_encode_bwd_drop`` take after theta: (rates, block sizes, seed of the step)."""
+
+    def __init__(self, rate, block_size=5, blocks=2, anneal_steps=40000, seed=0, n_blocks=4):
+        if not 0.0 <= float(rate) < 1.0:
+            raise ValueError(f"--drop_rate {rate} must lie in [0, 1)")
+        if not 1 <= int(block_size) <= 8:
+            raise ValueError(f"--drop_block_size {block_size} must lie in [1, 8] (the kernel keeps the last rows' masks in registers)")
+        if not 0 <= int(blocks) <= int(n_blocks):
+            raise ValueError(f"--drop_blocks {blocks} must lie in [0, {n_blocks}]")
+        if int(anneal_steps) < 0:
+            raise ValueError(f"--drop_anneal_steps {anneal_steps} must not be negative")
+        self.rate, self.block_size, self.blocks = float(rate), int(block_size), int(blocks)
+        self.anneal_steps, self.seed, self.n_blocks = int(anneal_steps), int(seed), int(n_blocks)
+
+    def rate_at(self, step):
+        return drop_rate_at(self.rate, step, self.anneal_steps)
+
+    def block_sizes(self):
+        return [self.block_size if l >= self.n_blocks - self.blocks else 1 for l in range(self.n_blocks)]
+
+    def args(self, step):
+        return [self.rate_at(step)] * self.n_blocks, self.block_sizes(), drop_step_seed(self.seed, step)
 
 
 class ResBlock(MetaModule):

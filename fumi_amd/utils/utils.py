@@ -142,6 +142,12 @@ _PRETRAIN_HEAD_FLAGS = [    # the cosine classifier of --model pretrain (DESIGN.
 _ADAPT_FLAGS = [            # the set-to-set prototype adaptation; a list of its own that main_parser() appends to run_parser()'s
     ("--fewshot_adapt", dict(type=str, choices=["none", "feat"], default="none", help="[--model metabaseline, --fewshot_head cosine | proto] adapt the class prototypes of an episode to the task before the head classifies against them: feat is FEAT's one-head self-attention block over the set of prototypes, with a residual and a LayerNorm")),
 ]
+_DROP_FLAGS = [             # DropBlock / dropout inside the ResNet-12; a list of its own that drop_parser() appends to main_parser()'s
+    ("--drop_rate", dict(type=float, default=0.0, help="[--model pretrain | metabaseline, --im_encoder resnet12] final drop probability of the regulariser on the block outputs of the ResNet-12 in training steps (the MetaOptNet / RFS network: 0.1); 0: off")),
+    ("--drop_block_size", dict(type=int, default=5, help="[--drop_rate > 0] block size of the DropBlock blocks (1 to 8)")),
+    ("--drop_blocks", dict(type=int, default=2, help="[--drop_rate > 0] the last this-many blocks use DropBlock, the earlier ones element-wise dropout")),
+    ("--drop_anneal_steps", dict(type=int, default=40000, help="[--drop_rate > 0] the rate at training step t is --drop_rate * min(1, t / this); 0: the full rate from step 0")),
+]
 
 
 def parser():
@@ -180,6 +186,23 @@ def main_parser():
     for flag, kw in _ADAPT_FLAGS:
         p.add_argument(flag, **kw)
     return p
+
+
+def drop_parser():
+    """``main_parser()`` and after every flag of it the --drop_* flags: what ``main.parse_args`` reads.  ``main_parser()`` keeps the
+    flag sequence the prototype adaptation was written against."""
+    p = main_parser()
+    for flag, kw in _DROP_FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
+def drop_config(args):
+    """None (--drop_rate 0), or the keyword arguments of ``resnet12.DropSchedule`` from an argparse namespace."""
+    if not getattr(args, "drop_rate", 0.0) > 0.0:
+        return None
+    return dict(rate=float(args.drop_rate), block_size=int(getattr(args, "drop_block_size", 5)), blocks=int(getattr(args, "drop_blocks", 2)),
+                anneal_steps=int(getattr(args, "drop_anneal_steps", 40000)), seed=int(getattr(args, "seed", 0) or 0))
 
 
 def logreg_config(cfg=None):
@@ -252,7 +275,8 @@ def init_model(args, dictionary, watch=True):
                                            if getattr(args, "distill_checkpoint", None) else None),
                                   **(dict(head="cosine", head_scale=getattr(args, "pretrain_head_scale", 10.0),
                                           head_scale_fixed=getattr(args, "pretrain_head_scale_fixed", False))
-                                     if getattr(args, "pretrain_head", "linear") == "cosine" else {}))
+                                     if getattr(args, "pretrain_head", "linear") == "cosine" else {}),
+                                  **(dict(drop=drop_config(args)) if drop_config(args) else {}))
     elif args.model == "metabaseline":
         from ..models import metabaseline
         model = metabaseline.MetaBaseline(im_encoder=args.im_encoder, image_size=args.image_size, image_channels=args.image_channels,
@@ -264,7 +288,8 @@ def init_model(args, dictionary, watch=True):
                                           proto_scale_fixed=getattr(args, "proto_scale_fixed", False),
                                           transductive_steps=getattr(args, "transductive_steps", 0),
                                           svm=svm_config(args) if getattr(args, "fewshot_head", "cosine") == "svm" else None,
-                                          **(dict(adapt="feat") if getattr(args, "fewshot_adapt", "none") == "feat" else {}))
+                                          **(dict(adapt="feat") if getattr(args, "fewshot_adapt", "none") == "feat" else {}),
+                                          **(dict(drop=drop_config(args)) if drop_config(args) else {}))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

@@ -464,6 +464,26 @@ int fumi_hip_resnet12_encode(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, 
 int fumi_hip_resnet12_encode_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
         int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
         const float* dfeats_q, float scale, float* const* g_theta);
+/* The pair with DropBlock / dropout on every block's pooled output (the MetaOptNet / RFS ResNet-12; fumi_amd/csrc/rn12_drop.hip).
+ * Arguments as above, then drop_rate [nblk] (each in [0, 1); 0: the block launches nothing), drop_block [nblk] (1: element-wise
+ * dropout; 2..8: DropBlock with block size min(drop_block, H_l, W_l) on the block's pooled H_l x W_l map, which must then be at most
+ * 64 x 64) and the step's 64-bit seed (host pointers / values; nothing is armed on the workspace).  The mask is a pure function of
+ * (seed, block, support / query, GLOBAL episode, image, channel, position), regenerated wherever it is needed and never stored; the
+ * kept cells are rescaled by total / kept counted per batch-statistics group (one episode's support or query set).  Both forms and
+ * every chunking give the same bits.  The tape records the three arguments: encode_bwd_drop returns FUMI_EINVAL when its own differ
+ * (the tape stays).  With every rate 0 the launches and bits are those of the pair above. */
+int fumi_hip_resnet12_encode_drop(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* const* theta,
+        float* feats_s, float* feats_q, int keep_tape, const float* drop_rate, const int* drop_block, uint64_t drop_seed);
+int fumi_hip_resnet12_encode_bwd_drop(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int Cin, int H, int W,
+        int nblk, const int* channels, const float* x_s, const float* x_q, const float* dfeats_s,
+        const float* dfeats_q, float scale, float* const* g_theta, const float* drop_rate, const int* drop_block, uint64_t drop_seed);
+/* The two drop launches on one raw map (unit parity): map [B][M (H+2)(W+2)][C] bf16 is scaled in place, kept_out [B] int64 and
+ * scale_out [B] fp32 (device) receive each group's kept count and total / kept (0 when nothing is kept).  block_index, set (0 | 1)
+ * and b0 (global index of the map's first episode) enter the mask as in the pair above.  FUMI_EINVAL (nothing launched): rate
+ * outside [0, 1), block outside 1..8, block > 1 with H or W beyond 64. */
+int fumi_hip_rn12_drop_apply(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, float rate, int block,
+        uint64_t seed, int block_index, int set, int b0, void* map_in_out, int64_t* kept_out, float* scale_out);
 /* Plan of the last fumi_hip_resnet12_encode: *taped = 1 (taped form) or 0 (recompute form), *chunk = episodes per chunk,
  * *lanes = streams the chunks were spread over. */
 int fumi_hip_resnet12_encode_plan(int* taped, int* chunk, int* lanes);
