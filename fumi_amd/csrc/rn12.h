@@ -100,6 +100,20 @@ size_t rn_coef_scratch_floats(int B, int nt, int K, int C);
 int launch_rn_coef(hipStream_t st, const RnCoefArgs& a, float* scratch);
 
 struct RnMap { int B, M, C; RnGeom g; };         // M images per episode
+// what an element-wise launch decides from its shape (rn_ew_plan: host arithmetic only, shared by the launchers and the query).
+// nch 8-channel chunks, nrg pixel groups of a workgroup's 256 threads (active = nch nrg of them work; unit = 1: one unit of work per
+// thread instead, all 256 active); rb pixels per reduction workgroup and nt slabs per episode; map_rb pixels per workgroup of a
+// walking map pass; wb join windows per workgroup; ncy x ncx cells per image, cb cells per workgroup (walking form) or cell = 1 (one
+// cell per thread); first = 1: the coefficient pass behind the reduction adds groups of 64 slabs first, nt2 slabs reach
+// rn_coef_kernel; lds dynamic LDS bytes; gx x gy workgroups.
+enum { RN_EW_ACT = 0, RN_EW_BWD_REDUCE, RN_EW_BWD_APPLY, RN_EW_JOIN_FWD, RN_EW_JOIN_REDUCE, RN_EW_JOIN_APPLY, RN_EW_AVGPOOL,
+       RN_EW_AVGPOOL_BWD, RN_EW_IMG_PREP, RN_EW_NKIND };
+constexpr int RN_EW_NPLAN = 17;
+struct RnEwPlan { int nch, nrg, active, unit, rb, nt, map_rb, wb, ncy, ncx, cb, cell, first, nt2, lds, gx, gy; };
+struct RnCoefPlan { int first, nt2, gx1, gy1, gx, gy; };            // first stage grid gx1 x gy1 x B (0: none), rn_coef_kernel gx x gy
+// AVGPOOL / AVGPOOL_BWD / IMG_PREP: B M images (C: the image's channels for IMG_PREP).  form: RN_EW_JOIN_APPLY only, 1 = the cell form
+int rn_ew_plan(int B, int M, int H, int W, int C, int kind, int tangent, int form, RnEwPlan* p);
+int rn_coef_plan(int B, int nt, int K, int C, int has_scratch, RnCoefPlan* p);
 // a = lrelu(A u + C0)            | tangent: a' = lrelu'(v) (A u' + TB xh + TC)
 int launch_rn_act(hipStream_t st, const RnMap& m, const rbf16* u, const rbf16* ud, const float* coef, rbf16* out);
 // partial sums of (dv, dv xh) | tangent (dv', dv' xh, dv xh'), dv = da lrelu'(v): part [B][nt][K][C]
@@ -114,7 +128,9 @@ struct RnJoin { RnMap m; RnGeom gn; int Ho, Wo; const rbf16* u3; const rbf16* us
 int launch_rn_join_fwd(hipStream_t st, const RnJoin& j, rbf16* o, int tangent);
 // sums (ds, ds xh3, ds xhs) | tangent (ds', ds' xh3, ds xh3', ds' xhs, ds xhs'): part [B][nt][K = 3 | 5][C]
 int launch_rn_join_reduce(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, float* part, int tangent);
-int launch_rn_join_apply(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, rbf16* du3, rbf16* dus, int tangent);
+// form 1 (test hook): the plain pass on rn_join_apply_cell_kernel, which the launcher takes for the tangent pass only
+int launch_rn_join_apply(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, rbf16* du3, rbf16* dus, int tangent,
+                         int form = 0);
 // global average pool of the last block's output map and its adjoint
 int launch_rn_avgpool(hipStream_t st, int BM, int C, const RnGeom& g, const rbf16* o, float* f);
 int launch_rn_avgpool_bwd(hipStream_t st, int BM, int C, const RnGeom& g, const float* df, rbf16* dout);

@@ -1291,4 +1291,97 @@ int fumi_hip_rn12_wgrad_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M,
     return launch_rn_wgrad_reduce(st, B, a.nsplit, ntaps, Cout, Cin, Cin_real, a.part, dW, (long)dw_stride);
 }
 
+// ---- unit ops of the element-wise passes on raw buffers (tests/rn12_ew_forms.py) ---------------------------------
+// Every launcher of rn12_ew.hip as the engine calls it: maps bf16 [B][M (H+2)(W+2)][C] padded channels-last, coefficient tables fp32
+// [B][RCF_N][C], partial sums fp32 [B][nt][K][C] (nt: fumi_hip_rn12_ew_query).  Every refusal comes before anything is launched.
+static int ew_map_of(int B, int M, int H, int W, int C, int kind, int tangent, int form, RnMap* m) {
+    RnEwPlan p;
+    TRY(rn_ew_plan(B, M, H, W, C, kind, tangent, form, &p));
+    m->B = B; m->M = M; m->C = C; m->g = rn_geom(H, W);
+    return FUMI_OK;
+}
+
+// out = lrelu(A u + C0); ud != NULL: the tangent form
+int fumi_hip_rn12_ew_act(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, const void* u, const void* ud,
+        const float* coef, void* out) {
+    if (!ws || !u || !coef || !out) return FUMI_EINVAL;
+    RnMap m;
+    TRY(ew_map_of(B, M, H, W, C, RN_EW_ACT, ud != nullptr, 0, &m));
+    HIP_TRY(hipSetDevice(ws->device));
+    return launch_rn_act((hipStream_t)stream, m, (const rbf16*)u, (const rbf16*)ud, coef, (rbf16*)out);
+}
+
+// apply = 0: the partial sums of the BN backward -> out fp32 [B][nt][K = 2 | 3][C]; apply = 1: du -> out bf16 map
+int fumi_hip_rn12_ew_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, int apply, int tangent, const void* u,
+        const void* ud, const void* da, const void* dad, const float* coef, void* out) {
+    if (!ws || !u || !da || !coef || !out || apply < 0 || apply > 1 || tangent < 0 || tangent > 1) return FUMI_EINVAL;
+    if (tangent && (!ud || !dad)) return FUMI_EINVAL;
+    RnMap m;
+    TRY(ew_map_of(B, M, H, W, C, apply ? RN_EW_BWD_APPLY : RN_EW_BWD_REDUCE, tangent, 0, &m));
+    HIP_TRY(hipSetDevice(ws->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (apply) return launch_rn_bwd_apply(st, m, (const rbf16*)u, (const rbf16*)ud, (const rbf16*)da, (const rbf16*)dad, coef, (rbf16*)out, tangent);
+    return launch_rn_bwd_reduce(st, m, (const rbf16*)u, (const rbf16*)ud, (const rbf16*)da, (const rbf16*)dad, coef, (float*)out, tangent);
+}
+
+// pass_ 0: o = maxpool(lrelu(BN3(u3) + BNs(us))) -> out0 bf16 [B][M (H/2+2)(W/2+2)][C]; 1: partial sums -> out0 fp32 [B][nt][K = 3 | 5][C];
+// 2: du3 -> out0, dus -> out1 (bf16 maps); form 1 (pass 2, plain): the cell form
+int fumi_hip_rn12_ew_join(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, int pass_, int tangent, int form,
+        const void* u3, const void* us, const void* u3d, const void* usd, const float* coef3, const float* coefs, const void* dout,
+        const void* doutd, void* out0, void* out1) {
+    if (!ws || !u3 || !us || !coef3 || !coefs || !out0 || pass_ < 0 || pass_ > 2 || tangent < 0 || tangent > 1) return FUMI_EINVAL;
+    if (tangent && (!u3d || !usd)) return FUMI_EINVAL;
+    if (pass_ && (!dout || (tangent && !doutd))) return FUMI_EINVAL;
+    if (pass_ == 2 && !out1) return FUMI_EINVAL;
+    RnJoin j; memset(&j, 0, sizeof(j));
+    TRY(ew_map_of(B, M, H, W, C, pass_ == 0 ? RN_EW_JOIN_FWD : pass_ == 1 ? RN_EW_JOIN_REDUCE : RN_EW_JOIN_APPLY, tangent, form, &j.m));
+    j.Ho = H / 2; j.Wo = W / 2; j.gn = rn_geom(j.Ho, j.Wo);
+    j.u3 = (const rbf16*)u3; j.us = (const rbf16*)us; j.coef3 = coef3; j.coefs = coefs; j.u3d = (const rbf16*)u3d; j.usd = (const rbf16*)usd;
+    HIP_TRY(hipSetDevice(ws->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (pass_ == 0) return launch_rn_join_fwd(st, j, (rbf16*)out0, tangent);
+    if (pass_ == 1) return launch_rn_join_reduce(st, j, (const rbf16*)dout, (const rbf16*)doutd, (float*)out0, tangent);
+    return launch_rn_join_apply(st, j, (const rbf16*)dout, (const rbf16*)doutd, (rbf16*)out0, (rbf16*)out1, tangent, form);
+}
+
+// the coefficient pass (RnCoefArgs, rn12.h) with caller-given slab count, slices and strides; scratch (optional): at least
+// rn_coef_scratch_floats = B ceil(nt / 64) K C floats (fumi_hip_rn12_coef_query), NULL: rn_coef_kernel alone whatever nt
+int fumi_hip_rn12_ew_coef(fumi_ws_t* ws, fumi_stream_t stream, int B, int C, int mode, int nt, int K, int k0, int k1, int k2, float n,
+        const float* part, float* coef, const float* g, const float* beta, long long pstride, const float* gd, const float* betad,
+        long long dstride, float* dg, float* dbeta, long long gstride, float* scratch) {
+    if (!ws || !part || !coef || mode < RCM_FWD || mode > RCM_TBWD || K < 1 || !(n > 0.f)) return FUMI_EINVAL;
+    if (k0 < 0 || k0 >= K || k1 < 0 || k1 >= K || k2 < 0 || k2 >= K) return FUMI_EINVAL;
+    if (mode == RCM_FWD && (!g || !beta || pstride < C)) return FUMI_EINVAL;
+    if (mode == RCM_TFWD && (!gd || !betad || dstride < C)) return FUMI_EINVAL;
+    if ((mode == RCM_BWD || mode == RCM_TBWD) && (!dg || !dbeta || gstride < C)) return FUMI_EINVAL;
+    if (mode == RCM_TBWD && (!gd || dstride < C)) return FUMI_EINVAL;
+    RnCoefPlan p;
+    TRY(rn_coef_plan(B, nt, K, C, scratch != nullptr, &p));
+    RnCoefArgs a; memset(&a, 0, sizeof(a));
+    a.B = B; a.C = C; a.mode = mode; a.nt = nt; a.K = K; a.k0 = k0; a.k1 = k1; a.k2 = k2; a.n = n; a.part = part; a.coef = coef;
+    a.g = g; a.beta = beta; a.pstride = (long)pstride; a.gd = gd; a.betad = betad; a.dstride = (long)dstride;
+    a.dg = dg; a.dbeta = dbeta; a.gstride = (long)gstride;
+    HIP_TRY(hipSetDevice(ws->device));
+    return launch_rn_coef((hipStream_t)stream, a, scratch);
+}
+
+// adjoint = 0: f fp32 [BM][C] = mean over the interior of in bf16 [BM][(H+2)(W+2)][C]; 1: out bf16 map = in fp32 [BM][C] / (H W), border 0
+int fumi_hip_rn12_ew_avgpool(fumi_ws_t* ws, fumi_stream_t stream, int BM, int H, int W, int C, int adjoint, const void* in, void* out) {
+    if (!ws || !in || !out || adjoint < 0 || adjoint > 1) return FUMI_EINVAL;
+    RnEwPlan p;
+    TRY(rn_ew_plan(1, BM, H, W, C, adjoint ? RN_EW_AVGPOOL_BWD : RN_EW_AVGPOOL, 0, 0, &p));
+    HIP_TRY(hipSetDevice(ws->device));
+    if (adjoint) return launch_rn_avgpool_bwd((hipStream_t)stream, BM, C, rn_geom(H, W), (const float*)in, (rbf16*)out);
+    return launch_rn_avgpool((hipStream_t)stream, BM, C, rn_geom(H, W), (const rbf16*)in, (float*)out);
+}
+
+// img fp32 [BM][Cin][H][W] -> out bf16 [BM][(H+2)(W+2)][16], channels Cin..15 and the border zero; Cin outside 1..8: FUMI_EINVAL
+int fumi_hip_rn12_ew_img_prep(fumi_ws_t* ws, fumi_stream_t stream, int BM, int Cin, int H, int W, const float* img, void* out) {
+    if (!ws || !img || !out) return FUMI_EINVAL;
+    RnEwPlan p;
+    TRY(rn_ew_plan(1, BM, H, W, Cin, RN_EW_IMG_PREP, 0, 0, &p));
+    HIP_TRY(hipSetDevice(ws->device));
+    return launch_rn_img_prep((hipStream_t)stream, BM, Cin, rn_geom(H, W), img, (rbf16*)out);
+}
+
 }  // extern "C"

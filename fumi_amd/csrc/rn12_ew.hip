@@ -700,143 +700,254 @@ __global__ __launch_bounds__(256) void rn_img_prep_kernel(long BM, int Cin, RnGe
     *(u32x4*)(out + i * 16 + 8) = pack8(hi);
 }
 
-}  // namespace
-size_t rn_coef_scratch_floats(int B, int nt, int K, int C) { return (size_t)B * ((nt + PR_GRP - 1) / PR_GRP) * K * C; }
-namespace {
+
+constexpr int PR_MAX1 = 2 * PR_GRP;                  // longest list of slabs rn_coef_kernel adds on its own
+// what the last element-wise launch of this process decided (fumi_hip_rn12_ew_plan): written on the host beside the launch, never
+// read by one
+RnEwPlan g_rn_ew_last = {};
+
 // pixels per workgroup of the reductions: from PER-EPISODE quantities only, so that an episode's summation order (and with bf16
 // storage everything downstream of it) does not depend on how many episodes share the chunk -- chunks and lanes are bit-neutral
-inline int red_rb(const RnMap& m) {
-    const long npix = (long)m.M * m.g.Pp;
+inline int red_rb(long npix) {
     long rb = npix / 512;
     rb = rb < 64 ? 64 : (rb > 1024 ? 1024 : rb);
     return (int)rb;
 }
+inline int cdiv(long a, long b) { const long q = (a + b - 1) / b; return q > 0x7fffffffL ? 0x7fffffff : (int)q; }   // (saturates: refused below)
 
 }  // namespace
+size_t rn_coef_scratch_floats(int B, int nt, int K, int C) { return (size_t)B * ((nt + PR_GRP - 1) / PR_GRP) * K * C; }
+
+// The coefficient pass of nt slabs: first stage (groups of PR_GRP slabs) or rn_coef_kernel alone.  Host arithmetic only.
+int rn_coef_plan(int B, int nt, int K, int C, int has_scratch, RnCoefPlan* p) {
+    *p = RnCoefPlan{};
+    if (B < 1 || C < 8 || nt < 1) return FUMI_EINVAL;
+    p->first = nt > PR_MAX1 && has_scratch;
+    p->nt2 = p->first ? (nt + PR_GRP - 1) / PR_GRP : nt;
+    p->gx1 = p->first ? p->nt2 : 0; p->gy1 = p->first ? (K * C + 63) / 64 : 0;
+    p->gx = (C + 63) / 64; p->gy = B;
+    return FUMI_OK;
+}
+
+// Every decision of an element-wise launch from its shape alone: no HIP call.  The launchers launch what this returns, and
+// fumi_hip_rn12_ew_query reports it for a shape.  form (RN_EW_JOIN_APPLY only): 0 the launcher's own choice, 1 the cell form.
+int rn_ew_plan(int B, int M, int H, int W, int C, int kind, int tangent, int form, RnEwPlan* p) {
+    *p = RnEwPlan{};
+    if (B < 1 || M < 1 || H < 1 || W < 1 || C < 1 || kind < 0 || kind >= RN_EW_NKIND || form < 0 || form > 1) return FUMI_EINVAL;
+    if (form && kind != RN_EW_JOIN_APPLY) return FUMI_EINVAL;
+    const RnGeom g = rn_geom(H, W);
+    const long npix = (long)M * g.Pp;
+    if (kind == RN_EW_IMG_PREP) {                                     // (C: the image's channels; B M images)
+        if (C > 8) return FUMI_EINVAL;
+        p->unit = 1; p->active = 256; p->gx = cdiv((long)B * npix, 256); p->gy = 1;
+        return FUMI_OK;
+    }
+    if (kind == RN_EW_AVGPOOL || kind == RN_EW_AVGPOOL_BWD) {         // (B M images, one grid row each)
+        if ((long)B * M > 65535) return FUMI_ENOTSUP;
+        p->unit = 1; p->active = 256; p->gy = B * M;
+        p->gx = kind == RN_EW_AVGPOOL ? (C + 255) / 256 : cdiv((long)g.Pp * C, 256);
+        return FUMI_OK;
+    }
+    if (C < 8 || (C & 7)) return FUMI_EINVAL;                         // (a thread owns 8 channels: 16 bytes)
+    if (B > 65535) return FUMI_ENOTSUP;
+    const int nch = C >> 3;
+    const bool join = kind == RN_EW_JOIN_FWD || kind == RN_EW_JOIN_REDUCE || kind == RN_EW_JOIN_APPLY;
+    if (join && (H < 2 || W < 2)) return FUMI_EINVAL;
+    if (kind != RN_EW_JOIN_FWD && nch > 256) return FUMI_ENOTSUP;
+    p->nch = nch; p->nrg = nch <= 256 ? 256 / nch : 0; p->active = p->nch * p->nrg;
+    p->rb = red_rb(npix); p->nt = cdiv(npix, p->rb);
+    p->first = p->nt > PR_MAX1; p->nt2 = p->first ? (p->nt + PR_GRP - 1) / PR_GRP : p->nt;
+    p->gy = B;
+    const long nwin = (long)M * (H / 2) * (W / 2);
+    switch (kind) {
+    case RN_EW_ACT: case RN_EW_BWD_APPLY:
+        if (npix >= (1L << 31)) return FUMI_ENOTSUP;
+        if (kind == RN_EW_ACT && !tangent) { p->unit = 1; p->active = 256; p->gx = cdiv(npix * nch, 256); break; }
+        p->map_rb = p->nrg * 8;                                       // every thread walks ~8 pixels (per-episode quantities only)
+        p->gx = cdiv(npix, p->map_rb);
+        break;
+    case RN_EW_BWD_REDUCE:
+        p->lds = p->nrg * (tangent ? 3 : 2) * C * 4; p->gx = p->nt;
+        break;
+    case RN_EW_JOIN_FWD:
+        p->unit = 1; p->active = 256; p->gx = cdiv((long)M * rn_geom(H / 2, W / 2).Pp * nch, 256);
+        break;
+    case RN_EW_JOIN_REDUCE:
+        if (nwin >= (1L << 31)) return FUMI_ENOTSUP;
+        p->lds = p->nrg * (tangent ? 5 : 3) * C * 4; p->gx = p->nt;  // (the coefficient pass is sized for this many slabs)
+        p->wb = cdiv(nwin, p->nt);                                    // windows per workgroup
+        break;
+    default: {                                                        // RN_EW_JOIN_APPLY
+        p->ncy = g.Hp / 2 + 1; p->ncx = g.Wp / 2 + 1;                 // cells (2 cy - 1 .. 2 cy) cover padded rows 0 .. Hp - 1
+        const long ncell = (long)M * p->ncy * p->ncx;
+        if (ncell * nch >= (1L << 32) - 256) return FUMI_ENOTSUP;
+        if (tangent || form) {                                        // one cell per thread (see rn_join_apply_cell_kernel)
+            p->cell = 1; p->unit = 1; p->active = 256; p->gx = cdiv(ncell * nch, 256);
+            break;
+        }
+        p->cb = p->nrg * 4;                                           // cells per workgroup: every thread walks ~4 cells (16 pixels)
+        p->gx = cdiv(ncell, p->cb);
+    } }
+    if (p->gx == 0x7fffffff) return FUMI_ENOTSUP;                     // (no grid is that wide)
+    return FUMI_OK;
+}
+
+int rn_red_nt(const RnMap& m) { return cdiv((long)m.M * m.g.Pp, red_rb((long)m.M * m.g.Pp)); }
+
+#define EW_PLAN(m_, kind, tangent, form)                                                            \
+    RnEwPlan p;                                                                                     \
+    { const int _rc = rn_ew_plan((m_).B, (m_).M, (m_).g.H, (m_).g.W, (m_).C, kind, tangent, form, &p); if (_rc) return _rc; } \
+    const dim3 grid(p.gx, p.gy)
 
 int launch_rn_coef(hipStream_t st, const RnCoefArgs& a0, float* scratch) {
     RnCoefArgs a = a0;
-    if (a.B < 1 || a.C < 8 || a.nt < 1) return FUMI_EINVAL;
-    if (a.nt > 2 * PR_GRP && scratch) {
-        const int nt2 = (a.nt + PR_GRP - 1) / PR_GRP, KC = a.K * a.C;
-        hipLaunchKernelGGL(rn_partial_reduce_kernel, dim3(nt2, (KC + 63) / 64, a.B), dim3(256), 0, st, a.nt, KC, a.part, scratch);
+    RnCoefPlan p;
+    { const int rc = rn_coef_plan(a.B, a.nt, a.K, a.C, scratch != nullptr, &p); if (rc) return rc; }
+    if (p.first) {
+        hipLaunchKernelGGL(rn_partial_reduce_kernel, dim3(p.gx1, p.gy1, a.B), dim3(256), 0, st, a.nt, a.K * a.C, a.part, scratch);
         LAUNCH_CHECK();
-        a.part = scratch; a.nt = nt2;
+        a.part = scratch; a.nt = p.nt2;
     }
-    hipLaunchKernelGGL(rn_coef_kernel, dim3((a.C + 63) / 64, a.B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rn_coef_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, a);
     LAUNCH_CHECK();
+    g_rn_ew_last.first = p.first; g_rn_ew_last.nt2 = p.nt2;           // (beside the map launch the record already holds)
     return FUMI_OK;
 }
-
-static inline dim3 unit_grid(const RnMap& m, long npix) { return dim3((unsigned)((npix * (m.C >> 3) + 255) / 256), m.B); }
-// pixels per workgroup of the pixel-looped map passes: every thread walks ~8 pixels (per-episode quantities only)
-static inline int map_rb(const RnMap& m) { return (256 / (m.C >> 3)) * 8; }
 
 int launch_rn_act(hipStream_t st, const RnMap& m, const rbf16* u, const rbf16* ud, const float* coef, rbf16* out) {
-    const long npix = (long)m.M * m.g.Pp;
-    if ((m.C >> 3) > 256 || npix >= (1L << 31)) return FUMI_ENOTSUP;
-    const int rb = map_rb(m);
-    const dim3 grid((unsigned)((npix + rb - 1) / rb), m.B);
-    if (ud) hipLaunchKernelGGL(rn_act_kernel<true>, grid, dim3(256), 0, st, m, u, ud, coef, out, rb);
-    else hipLaunchKernelGGL(rn_act1_kernel, unit_grid(m, npix), dim3(256), 0, st, m, u, coef, out);
+    EW_PLAN(m, RN_EW_ACT, ud != nullptr, 0);
+    if (ud) hipLaunchKernelGGL(rn_act_kernel<true>, grid, dim3(256), 0, st, m, u, ud, coef, out, p.map_rb);
+    else hipLaunchKernelGGL(rn_act1_kernel, grid, dim3(256), 0, st, m, u, coef, out);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
-}
-
-int rn_red_nt(const RnMap& m) {
-    const long npix = (long)m.M * m.g.Pp;
-    const int rb = red_rb(m);
-    return (int)((npix + rb - 1) / rb);
 }
 
 int launch_rn_bwd_reduce(hipStream_t st, const RnMap& m, const rbf16* u, const rbf16* ud, const rbf16* da, const rbf16* dad,
                          const float* coef, float* part, int tangent) {
-    if ((m.C >> 3) > 256) return FUMI_ENOTSUP;
-    const int nrg = 256 / (m.C >> 3), K = tangent ? 3 : 2;
-    const size_t lds = (size_t)nrg * K * m.C * 4;
-    const dim3 grid(rn_red_nt(m), m.B);
+    EW_PLAN(m, RN_EW_BWD_REDUCE, tangent, 0);
+    const size_t lds = (size_t)p.lds;
     if (tangent) {
         FUMI_SET_DYN_LDS(rn_bwd_reduce_kernel<true>, lds);
-        hipLaunchKernelGGL(rn_bwd_reduce_kernel<true>, grid, dim3(256), lds, st, m, u, ud, da, dad, coef, part, red_rb(m));
+        hipLaunchKernelGGL(rn_bwd_reduce_kernel<true>, grid, dim3(256), lds, st, m, u, ud, da, dad, coef, part, p.rb);
     } else {
         FUMI_SET_DYN_LDS(rn_bwd_reduce_kernel<false>, lds);
-        hipLaunchKernelGGL(rn_bwd_reduce_kernel<false>, grid, dim3(256), lds, st, m, u, ud, da, dad, coef, part, red_rb(m));
+        hipLaunchKernelGGL(rn_bwd_reduce_kernel<false>, grid, dim3(256), lds, st, m, u, ud, da, dad, coef, part, p.rb);
     }
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
 int launch_rn_bwd_apply(hipStream_t st, const RnMap& m, const rbf16* u, const rbf16* ud, const rbf16* da, const rbf16* dad,
                         const float* coef, rbf16* du, int tangent) {
-    const long npix = (long)m.M * m.g.Pp;
-    if ((m.C >> 3) > 256 || npix >= (1L << 31)) return FUMI_ENOTSUP;
-    const int rb = map_rb(m);
-    const dim3 grid((unsigned)((npix + rb - 1) / rb), m.B);
-    if (tangent) hipLaunchKernelGGL(rn_bwd_apply_kernel<true>, grid, dim3(256), 0, st, m, u, ud, da, dad, coef, du, rb);
-    else hipLaunchKernelGGL(rn_bwd_apply_kernel<false>, grid, dim3(256), 0, st, m, u, ud, da, dad, coef, du, rb);
+    EW_PLAN(m, RN_EW_BWD_APPLY, tangent, 0);
+    if (tangent) hipLaunchKernelGGL(rn_bwd_apply_kernel<true>, grid, dim3(256), 0, st, m, u, ud, da, dad, coef, du, p.map_rb);
+    else hipLaunchKernelGGL(rn_bwd_apply_kernel<false>, grid, dim3(256), 0, st, m, u, ud, da, dad, coef, du, p.map_rb);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
+// (the plan takes the pooled geometry from the map's: a join is always the 2 x 2 / stride 2 pool of its block)
+static inline bool join_geom_ok(const RnJoin& j) {
+    return j.Ho == j.m.g.H / 2 && j.Wo == j.m.g.W / 2 && j.gn.H == j.Ho && j.gn.W == j.Wo;
+}
+
 int launch_rn_join_fwd(hipStream_t st, const RnJoin& j, rbf16* o, int tangent) {
-    const long npo = (long)j.m.M * j.gn.Pp;
-    if (tangent) hipLaunchKernelGGL(rn_join_fwd_kernel<true>, unit_grid(j.m, npo), dim3(256), 0, st, j, o);
-    else hipLaunchKernelGGL(rn_join_fwd_kernel<false>, unit_grid(j.m, npo), dim3(256), 0, st, j, o);
+    if (!join_geom_ok(j)) return FUMI_EINVAL;
+    EW_PLAN(j.m, RN_EW_JOIN_FWD, tangent, 0);
+    if (tangent) hipLaunchKernelGGL(rn_join_fwd_kernel<true>, grid, dim3(256), 0, st, j, o);
+    else hipLaunchKernelGGL(rn_join_fwd_kernel<false>, grid, dim3(256), 0, st, j, o);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
 int launch_rn_join_reduce(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, float* part, int tangent) {
-    if ((j.m.C >> 3) > 256) return FUMI_ENOTSUP;
-    const int nrg = 256 / (j.m.C >> 3), K = tangent ? 5 : 3;
-    const size_t lds = (size_t)nrg * K * j.m.C * 4;
-    const int nt = rn_red_nt(j.m);                                    // (the coefficient pass is sized for this many slabs)
-    const long nwin = (long)j.m.M * j.Ho * j.Wo;
-    if (nwin >= (1L << 31)) return FUMI_ENOTSUP;
-    const unsigned wb = (unsigned)((nwin + nt - 1) / nt);             // windows per workgroup
-    const dim3 grid(nt, j.m.B);
+    if (!join_geom_ok(j)) return FUMI_EINVAL;
+    EW_PLAN(j.m, RN_EW_JOIN_REDUCE, tangent, 0);
+    const size_t lds = (size_t)p.lds;
     if (tangent) {
         FUMI_SET_DYN_LDS(rn_join_reduce_kernel<true>, lds);
-        hipLaunchKernelGGL(rn_join_reduce_kernel<true>, grid, dim3(256), lds, st, j, dout, doutd, part, wb);
+        hipLaunchKernelGGL(rn_join_reduce_kernel<true>, grid, dim3(256), lds, st, j, dout, doutd, part, (unsigned)p.wb);
     } else {
         FUMI_SET_DYN_LDS(rn_join_reduce_kernel<false>, lds);
-        hipLaunchKernelGGL(rn_join_reduce_kernel<false>, grid, dim3(256), lds, st, j, dout, doutd, part, wb);
+        hipLaunchKernelGGL(rn_join_reduce_kernel<false>, grid, dim3(256), lds, st, j, dout, doutd, part, (unsigned)p.wb);
     }
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
-int launch_rn_join_apply(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, rbf16* du3, rbf16* dus, int tangent) {
-    const int ncy = j.m.g.Hp / 2 + 1, ncx = j.m.g.Wp / 2 + 1;          // cells (2 cy - 1 .. 2 cy) cover padded rows 0 .. Hp - 1
-    const long ncell = (long)j.m.M * ncy * ncx;
-    if ((j.m.C >> 3) > 256 || ncell * (j.m.C >> 3) >= (1L << 32) - 256) return FUMI_ENOTSUP;
-    if (tangent) {                                                       // one cell per thread (see rn_join_apply_cell_kernel)
-        hipLaunchKernelGGL(rn_join_apply_cell_kernel<true>, unit_grid(j.m, ncell), dim3(256), 0, st, j, dout, doutd, du3, dus, ncy, ncx);
-        LAUNCH_CHECK();
-        return FUMI_OK;
-    }
-    const unsigned cb = (unsigned)(256 / (j.m.C >> 3)) * 4;              // cells per workgroup: every thread walks ~4 cells (16 pixels)
-    const dim3 grid((unsigned)((ncell + cb - 1) / cb), j.m.B);
-    hipLaunchKernelGGL(rn_join_apply_kernel<false>, grid, dim3(256), 0, st, j, dout, doutd, du3, dus, ncy, ncx, cb);
+int launch_rn_join_apply(hipStream_t st, const RnJoin& j, const rbf16* dout, const rbf16* doutd, rbf16* du3, rbf16* dus, int tangent,
+                         int form) {
+    if (!join_geom_ok(j)) return FUMI_EINVAL;
+    EW_PLAN(j.m, RN_EW_JOIN_APPLY, tangent, form);
+    if (p.cell) {
+        if (tangent) hipLaunchKernelGGL(rn_join_apply_cell_kernel<true>, grid, dim3(256), 0, st, j, dout, doutd, du3, dus, p.ncy, p.ncx);
+        else hipLaunchKernelGGL(rn_join_apply_cell_kernel<false>, grid, dim3(256), 0, st, j, dout, doutd, du3, dus, p.ncy, p.ncx);
+    } else
+        hipLaunchKernelGGL(rn_join_apply_kernel<false>, grid, dim3(256), 0, st, j, dout, doutd, du3, dus, p.ncy, p.ncx, (unsigned)p.cb);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
 int launch_rn_avgpool(hipStream_t st, int BM, int C, const RnGeom& g, const rbf16* o, float* f) {
-    hipLaunchKernelGGL(rn_avgpool_kernel, dim3((C + 255) / 256, BM), dim3(256), 0, st, C, g, o, f);
+    RnEwPlan p;
+    { const int rc = rn_ew_plan(1, BM, g.H, g.W, C, RN_EW_AVGPOOL, 0, 0, &p); if (rc) return rc; }
+    hipLaunchKernelGGL(rn_avgpool_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, C, g, o, f);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
 int launch_rn_avgpool_bwd(hipStream_t st, int BM, int C, const RnGeom& g, const float* df, rbf16* dout) {
-    hipLaunchKernelGGL(rn_avgpool_bwd_kernel, dim3((unsigned)(((long)g.Pp * C + 255) / 256), BM), dim3(256), 0, st, C, g, df, dout);
+    RnEwPlan p;
+    { const int rc = rn_ew_plan(1, BM, g.H, g.W, C, RN_EW_AVGPOOL_BWD, 0, 0, &p); if (rc) return rc; }
+    hipLaunchKernelGGL(rn_avgpool_bwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, C, g, df, dout);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
     return FUMI_OK;
 }
 
 int launch_rn_img_prep(hipStream_t st, long BM, int Cin, const RnGeom& g, const float* img, rbf16* out) {
-    if (Cin < 1 || Cin > 8) return FUMI_EINVAL;
-    hipLaunchKernelGGL(rn_img_prep_kernel, dim3((unsigned)((BM * g.Pp + 255) / 256)), dim3(256), 0, st, BM, Cin, g, img, out);
+    if (BM < 1 || BM >= (1L << 31)) return FUMI_EINVAL;
+    RnEwPlan p;
+    { const int rc = rn_ew_plan(1, (int)BM, g.H, g.W, Cin, RN_EW_IMG_PREP, 0, 0, &p); if (rc) return rc; }
+    hipLaunchKernelGGL(rn_img_prep_kernel, dim3(p.gx), dim3(256), 0, st, BM, Cin, g, img, out);
     LAUNCH_CHECK();
+    g_rn_ew_last = p;
+    return FUMI_OK;
+}
+
+// ---- the plan, reported (host arithmetic: no HIP call) ---------------------------------------------------------------------------------
+static void ew_plan_out(const RnEwPlan& p, int* plan, int n) {
+    const int v[RN_EW_NPLAN] = {p.nch, p.nrg, p.active, p.unit, p.rb, p.nt, p.map_rb, p.wb, p.ncy, p.ncx, p.cb, p.cell, p.first, p.nt2,
+                                p.lds, p.gx, p.gy};
+    for (int i = 0; i < n && i < RN_EW_NPLAN; ++i) plan[i] = v[i];
+}
+extern "C" int fumi_hip_rn12_ew_plan(int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    ew_plan_out(g_rn_ew_last, plan, n);
+    return FUMI_OK;
+}
+extern "C" int fumi_hip_rn12_ew_query(int B, int M, int H, int W, int C, int kind, int tangent, int form, int* plan, int n) {
+    if (!plan || n < 0) return FUMI_EINVAL;
+    RnEwPlan p;
+    const int rc = rn_ew_plan(B, M, H, W, C, kind, tangent, form, &p);
+    if (rc) return rc;
+    ew_plan_out(p, plan, n);
+    return FUMI_OK;
+}
+extern "C" int fumi_hip_rn12_coef_query(int B, int nt, int K, int C, int has_scratch, int* plan, int n) {
+    if (!plan || n < 0 || K < 1) return FUMI_EINVAL;
+    RnCoefPlan p;
+    const int rc = rn_coef_plan(B, nt, K, C, has_scratch, &p);
+    if (rc) return rc;
+    const size_t sf = rn_coef_scratch_floats(B, nt, K, C);
+    const int v[7] = {p.first, p.nt2, p.gx1, p.gy1, p.gx, p.gy, sf > 0x7fffffffu ? -1 : (int)sf};
+    for (int i = 0; i < n && i < 7; ++i) plan[i] = v[i];
     return FUMI_OK;
 }

@@ -36,7 +36,10 @@ SYMBOLS = [
     "fumi_hip_resnet12_set_budget", "fumi_hip_fumi_resnet12_step", "fumi_hip_maml_resnet12_step", "fumi_hip_resnet12_features",
     "fumi_hip_resnet12_encode", "fumi_hip_resnet12_encode_bwd", "fumi_hip_resnet12_encode_plan",
     "fumi_hip_rn12_conv", "fumi_hip_rn12_wgrad", "fumi_hip_rn12_conv_multi", "fumi_hip_rn12_wgrad_multi",
-    "fumi_hip_rn12_conv_plan", "fumi_hip_rn12_conv_query", "fumi_hip_rn12_wgrad_query", "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
+    "fumi_hip_rn12_conv_plan", "fumi_hip_rn12_conv_query", "fumi_hip_rn12_wgrad_query", 
+    "fumi_hip_rn12_ew_act", "fumi_hip_rn12_ew_bwd", "fumi_hip_rn12_ew_join", "fumi_hip_rn12_ew_coef", "fumi_hip_rn12_ew_avgpool",
+    "fumi_hip_rn12_ew_img_prep", "fumi_hip_rn12_ew_query", "fumi_hip_rn12_ew_plan", "fumi_hip_rn12_coef_query",
+    "fumi_hip_resnet12_set_option", "fumi_hip_rn12_probe",
     "fumi_hip_conv3x3_fwd", "fumi_hip_conv3x3_bwd_data", "fumi_hip_conv3x3_bwd_weight",
     "fumi_hip_sgd_axpy", "fumi_hip_ce_fwd_bwd", "fumi_hip_proto_reduce", "fumi_hip_clip_step", "fumi_hip_lstm_bidir", "fumi_hip_lstm_tape_floats", "fumi_hip_lstm_bidir_train", "fumi_hip_lstm_bidir_bwd",
     "fumi_hip_am3_step_tx", "fumi_hip_am3_step_tx_dx",
@@ -228,6 +231,16 @@ def lib():
         L.fumi_hip_rn12_conv_plan.argtypes = [POINTER(c_int), c_int]
         L.fumi_hip_rn12_conv_query.argtypes = [c_int] * 6 + [POINTER(c_int), POINTER(c_int), c_int]
         L.fumi_hip_rn12_wgrad_query.argtypes = [c_int] * 9 + [POINTER(c_int), c_int]
+        L.fumi_hip_rn12_ew_act.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4
+        L.fumi_hip_rn12_ew_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 6
+        L.fumi_hip_rn12_ew_join.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 10
+        L.fumi_hip_rn12_ew_coef.argtypes = ([c_void_p, c_void_p] + [c_int] * 8 + [c_float] + [c_void_p] * 4 + [LL] + [c_void_p] * 2 + [LL]
+                                            + [c_void_p] * 2 + [LL, c_void_p])
+        L.fumi_hip_rn12_ew_avgpool.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 2
+        L.fumi_hip_rn12_ew_img_prep.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 2
+        L.fumi_hip_rn12_ew_query.argtypes = [c_int] * 8 + [POINTER(c_int), c_int]
+        L.fumi_hip_rn12_ew_plan.argtypes = [POINTER(c_int), c_int]
+        L.fumi_hip_rn12_coef_query.argtypes = [c_int] * 5 + [POINTER(c_int), c_int]
         L.fumi_hip_resnet12_set_option.argtypes = [c_int, c_int]
         L.fumi_hip_rn12_probe.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, POINTER(c_size_t),
                                           POINTER(c_int)]
@@ -1650,6 +1663,91 @@ def rn12_wgrad_query(B, M, H, W, Cin, Cout, ntaps, npair=1, nsplit=0):
     v = (c_int * 6)()
     _check(lib().fumi_hip_rn12_wgrad_query(B, M, H, W, Cin, Cout, ntaps, npair, nsplit, v, 6), "fumi_hip_rn12_wgrad_query")
     return dict(zip(RN12_WGRAD_KEYS, v[:]))
+
+
+RN12_EW_KINDS = ("act", "bwd_reduce", "bwd_apply", "join_fwd", "join_reduce", "join_apply", "avgpool", "avgpool_bwd", "img_prep")
+RN12_EW_KEYS = ("nch", "nrg", "active", "unit", "rb", "nt", "map_rb", "wb", "ncy", "ncx", "cb", "cell", "first", "nt2", "lds", "gx", "gy")
+RN12_COEF_KEYS = ("first", "nt2", "gx1", "gy1", "gx", "gy", "scratch")
+RN12_COEF_MODES = {"fwd": 0, "bwd": 1, "tfwd": 2, "tbwd": 3}
+RN12_COEF_FIELDS = ("mu", "r", "a", "c0", "d1", "d2", "tb", "tc", "m1", "m2", "k0", "dd1", "e12")
+
+
+def rn12_ew_query(B, M, H, W, C, kind, tangent=False, form=0):
+    """The decisions an element-wise launcher of csrc/rn12_ew.hip takes for a shape: host arithmetic only, no GPU.  kind: a name of
+    RN12_EW_KINDS (avgpool / avgpool_bwd / img_prep: B * M images; img_prep: C is the image's channel count)."""
+    v = (c_int * 17)()
+    _check(lib().fumi_hip_rn12_ew_query(B, M, H, W, C, RN12_EW_KINDS.index(kind), int(bool(tangent)), int(form), v, 17), "fumi_hip_rn12_ew_query")
+    return dict(zip(RN12_EW_KEYS, v[:]))
+
+
+def rn12_ew_plan():
+    """What the last element-wise launch of this process decided (keys RN12_EW_KEYS; a coefficient launch updates first / nt2)."""
+    v = (c_int * 17)()
+    _check(lib().fumi_hip_rn12_ew_plan(v, 17), "fumi_hip_rn12_ew_plan")
+    return dict(zip(RN12_EW_KEYS, v[:]))
+
+
+def rn12_coef_query(B, nt, K, C, has_scratch=True):
+    v = (c_int * 7)()
+    _check(lib().fumi_hip_rn12_coef_query(B, nt, K, C, int(bool(has_scratch)), v, 7), "fumi_hip_rn12_coef_query")
+    return dict(zip(RN12_COEF_KEYS, v[:]))
+
+
+def _rawptr(t, name, dtype):
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise FumiHipError(f"{name}: expected a contiguous {dtype} GPU tensor")
+    return c_void_p(t.data_ptr())
+
+
+def rn12_ew_act(ws, B, M, H, W, C, u, ud, coef, out):
+    """fumi_hip_rn12_ew_act on raw buffers (flat bf16 maps, fp32 table [B, 13, C]); ud None: the plain form."""
+    bf, f4 = torch.bfloat16, torch.float32
+    _check(lib().fumi_hip_rn12_ew_act(ws.handle, _stream(_dev(out)), B, M, H, W, C, _rawptr(u, "u", bf), _rawptr(ud, "ud", bf),
+                                      _rawptr(coef, "coef", f4), _rawptr(out, "out", bf)), "fumi_hip_rn12_ew_act")
+
+
+def rn12_ew_bwd(ws, B, M, H, W, C, apply, u, ud, da, dad, coef, out):
+    """fumi_hip_rn12_ew_bwd: apply False -> out fp32 partial sums [B, nt, 2 | 3, C]; True -> out bf16 du.  ud / dad None: plain."""
+    bf, f4 = torch.bfloat16, torch.float32
+    _check(lib().fumi_hip_rn12_ew_bwd(ws.handle, _stream(_dev(out)), B, M, H, W, C, int(bool(apply)), int(ud is not None),
+                                      _rawptr(u, "u", bf), _rawptr(ud, "ud", bf), _rawptr(da, "da", bf), _rawptr(dad, "dad", bf),
+                                      _rawptr(coef, "coef", f4), _rawptr(out, "out", bf if apply else f4)), "fumi_hip_rn12_ew_bwd")
+
+
+def rn12_ew_join(ws, B, M, H, W, C, pass_, u3, us, u3d, usd, coef3, coefs, dout, doutd, out0, out1=None, form=0):
+    """fumi_hip_rn12_ew_join: pass_ 0 forward (out0 the pooled map), 1 reduce (out0 fp32 [B, nt, 3 | 5, C]), 2 apply (out0 du3, out1
+    dus).  u3d / usd (and doutd) None: plain.  form 1: the plain apply on the cell kernel."""
+    bf, f4 = torch.bfloat16, torch.float32
+    _check(lib().fumi_hip_rn12_ew_join(ws.handle, _stream(_dev(out0)), B, M, H, W, C, int(pass_), int(u3d is not None), int(form),
+                                       _rawptr(u3, "u3", bf), _rawptr(us, "us", bf), _rawptr(u3d, "u3d", bf), _rawptr(usd, "usd", bf),
+                                       _rawptr(coef3, "coef3", f4), _rawptr(coefs, "coefs", f4), _rawptr(dout, "dout", bf),
+                                       _rawptr(doutd, "doutd", bf), _rawptr(out0, "out0", f4 if pass_ == 1 else bf),
+                                       _rawptr(out1, "out1", bf)), "fumi_hip_rn12_ew_join")
+
+
+def rn12_ew_coef(ws, B, C, mode, nt, K, ks, n, part, coef, g=None, beta=None, pstride=0, gd=None, betad=None, dstride=0, dg=None,
+                 dbeta=None, gstride=0, scratch=None):
+    """fumi_hip_rn12_ew_coef: mode a name of RN12_COEF_MODES, ks = (k0, k1, k2) slices of the K partial sums, all buffers flat fp32."""
+    f4 = torch.float32
+    P = lambda t, name: _rawptr(t, name, f4)
+    _check(lib().fumi_hip_rn12_ew_coef(ws.handle, _stream(_dev(coef)), B, C, RN12_COEF_MODES[mode], nt, K, int(ks[0]), int(ks[1]), int(ks[2]),
+                                       float(n), P(part, "part"), P(coef, "coef"), P(g, "g"), P(beta, "beta"), int(pstride), P(gd, "gd"),
+                                       P(betad, "betad"), int(dstride), P(dg, "dg"), P(dbeta, "dbeta"), int(gstride), P(scratch, "scratch")),
+           "fumi_hip_rn12_ew_coef")
+
+
+def rn12_ew_avgpool(ws, BM, H, W, C, adjoint, src, out):
+    """fumi_hip_rn12_ew_avgpool: adjoint False src bf16 map -> out fp32 [BM, C]; True src fp32 [BM, C] -> out bf16 map."""
+    bf, f4 = torch.bfloat16, torch.float32
+    _check(lib().fumi_hip_rn12_ew_avgpool(ws.handle, _stream(_dev(out)), BM, H, W, C, int(bool(adjoint)), _rawptr(src, "in", f4 if adjoint else bf),
+                                          _rawptr(out, "out", bf if adjoint else f4)), "fumi_hip_rn12_ew_avgpool")
+
+
+def rn12_ew_img_prep(ws, BM, Cin, H, W, img, out):
+    _check(lib().fumi_hip_rn12_ew_img_prep(ws.handle, _stream(_dev(out)), BM, Cin, H, W, _rawptr(img, "img", torch.float32),
+                                           _rawptr(out, "out", torch.bfloat16)), "fumi_hip_rn12_ew_img_prep")
 
 
 def resnet12_set_option(key, value):

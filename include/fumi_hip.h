@@ -516,6 +516,42 @@ int fumi_hip_rn12_wgrad_multi(fumi_ws_t* ws, fumi_stream_t stream, int B, int M,
 int fumi_hip_rn12_conv_plan(int* plan, int n);
 int fumi_hip_rn12_conv_query(int B, int M, int H, int W, int Cout, int nsrc, const int* Cin, int* plan, int n);
 int fumi_hip_rn12_wgrad_query(int B, int M, int H, int W, int Cin, int Cout, int ntaps, int npair, int nsplit, int* plan, int n);
+/* The element-wise passes between the convolutions on raw buffers (unit parity; tests/rn12_ew_forms.py): every
+ * launcher as the engine calls it.  Maps are bf16 [B][M (H+2)(W+2)][C] padded channels-last, C a multiple of 8 up to 2048; a
+ * coefficient table is fp32 [B][13][C] (fields MU, R, A, C0, D1, D2, TB, TC, M1, M2, K0, DD1, E12); partial sums are fp32
+ * [B][nt][K][C] with nt of the query below.  act: out = lrelu(A u + C0), with ud its tangent.  bwd: apply = 0 the partial sums
+ * (K = 2, tangent 3), apply = 1 du.  join: pass_ 0 the pooled map out0 [B][M (H/2+2)(W/2+2)][C], 1 the partial sums (K = 3, tangent 5),
+ * 2 du3 -> out0 and dus -> out1; form = 1 runs the plain pass 2 on the one-cell-per-thread kernel the tangent pass takes.  coef: the
+ * coefficient pass in mode 0 FWD (part slices k0 = sum, k1 = sum of squares; g, beta with pstride floats between episodes), 1 BWD
+ * (D1, D2; dbeta = slice k0, dg = slice k1, gstride), 2 TFWD (gd, betad, dstride), 3 TBWD (slices k0, k1 + k2; gd, dg, dbeta); n =
+ * interior pixels per channel; scratch (optional, B ceil(nt / 64) K C floats): lists beyond 128 slabs are first added in groups of 64.
+ * avgpool: adjoint = 0 out fp32 [BM][C] = interior mean of in; 1 out bf16 map = in fp32 [BM][C] / (H W).  img_prep: img fp32
+ * [BM][Cin][H][W] -> out bf16 [BM][(H+2)(W+2)][16].  Refusals, before anything is launched: FUMI_EINVAL for a missing buffer, C % 8,
+ * a join of a map below 2 x 2, Cin outside 1..8, a slice outside K, a stride below C; FUMI_ENOTSUP for C above 2048 and for index
+ * ranges beyond 32 bits. */
+int fumi_hip_rn12_ew_act(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, const void* u, const void* ud,
+        const float* coef, void* out);
+int fumi_hip_rn12_ew_bwd(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, int apply, int tangent, const void* u,
+        const void* ud, const void* da, const void* dad, const float* coef, void* out);
+int fumi_hip_rn12_ew_join(fumi_ws_t* ws, fumi_stream_t stream, int B, int M, int H, int W, int C, int pass_, int tangent, int form,
+        const void* u3, const void* us, const void* u3d, const void* usd, const float* coef3, const float* coefs, const void* dout,
+        const void* doutd, void* out0, void* out1);
+int fumi_hip_rn12_ew_coef(fumi_ws_t* ws, fumi_stream_t stream, int B, int C, int mode, int nt, int K, int k0, int k1, int k2, float n,
+        const float* part, float* coef, const float* g, const float* beta, long long pstride, const float* gd, const float* betad,
+        long long dstride, float* dg, float* dbeta, long long gstride, float* scratch);
+int fumi_hip_rn12_ew_avgpool(fumi_ws_t* ws, fumi_stream_t stream, int BM, int H, int W, int C, int adjoint, const void* in, void* out);
+int fumi_hip_rn12_ew_img_prep(fumi_ws_t* ws, fumi_stream_t stream, int BM, int Cin, int H, int W, const float* img, void* out);
+/* What an element-wise launch decides from its shape -- host arithmetic only, no HIP call (the launchers launch what it returns).
+ * kind: 0 act, 1 bwd reduce, 2 bwd apply, 3 join fwd, 4 join reduce, 5 join apply, 6 avgpool, 7 its adjoint, 8 image prep (6..8: B M
+ * images; 8: C is the image's channel count).  plan[0..16] = 8-channel chunks nch, pixel groups nrg, active threads, unit (1: one unit
+ * of work per thread), pixels per reduction workgroup rb, slabs per episode nt, pixels per workgroup of a walking map pass, join
+ * windows per workgroup, cells per image ncy, ncx, cells per workgroup, cell (1: one cell per thread), first (1: the coefficient
+ * pass behind the reduction adds groups of 64 slabs first), slabs nt2 that reach the coefficient kernel, dynamic LDS bytes, grid x, y.
+ * ew_plan: the same record of the last launch of this process (the coefficient launcher updates first and nt2 only).  coef_query:
+ * plan[0..6] = first, nt2, the first stage's grid x, y (0: none), the coefficient kernel's grid x, y, floats of scratch. */
+int fumi_hip_rn12_ew_query(int B, int M, int H, int W, int C, int kind, int tangent, int form, int* plan, int n);
+int fumi_hip_rn12_ew_plan(int* plan, int n);
+int fumi_hip_rn12_coef_query(int B, int nt, int K, int C, int has_scratch, int* plan, int n);
 /* The three 3x3 / pad 1 / stride 1 convolution products on 64 -> 64 channels (the set is closed under differentiation: the
  * second-order sweep uses nothing else).  Dense channels-last tensors x, y, dy [M,H,W,64]; weights W, dW [64,64,3,3] (OIHW). */
 int fumi_hip_conv3x3_fwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int H, int W, const float* x, const float* Wt, float* y);
