@@ -11,9 +11,11 @@
 //       one further workgroup adds part[0..ntile) in index order: loss = sum / M, correct = count.
 //   The forward form (no gradient pointers) is launch 1 without its backward half and launch 2 with that last workgroup alone: the
 //   same instructions produce loss, correct and preds in both forms.
-// Every sum has a fixed order (MFMA chains over k, butterflies inside a 16-lane group, index-ordered loops across tiles): equal
-// inputs give equal bits.  No floating-point atomics; the only atomic is the OR into the status word.
-// A label outside [0, C) sets FUMI_ST_LABEL_RANGE; its row adds nothing to the loss, the count or the gradients (the divisor stays M).
+// The heads' common contract (fixed order of every sum, first arg-max, the label rule, no floating-point atomics) is stated in
+// cls_head.h, which also holds what this file shares with coshead.hip: the tile constants, ClsHead and ClsSoft, the host's checks,
+// the soft-target builder and launch geometry, and the tile sums.  Still copies, here and on z = tau k in coshead.hip, each marked
+// "(cls_head.h: a copy)": the row arg-max (twice here: teacher and student), the row sums, the label rule, the soft target, the
+// final sum over the tiles and the column sum -- through a helper each changed an instruction stream.
 //
 // Soft-target form (fumi_hip_cls_head_step_soft): label smoothing eps and a two-label mix (mixup / CutMix),
 //   t[m,c] = (1 - eps) (lam [c == y_a[m]] + u [c == y_b[m]]) + eps / C,  u = 1 - lam in fp32,
@@ -28,28 +30,13 @@
 // The rows kernel is also a template on KD: that instance first forms the teacher's logits in the same LDS image, takes their first
 // arg-max, lse(z_t / T) and sum_c p z_t / T per row and writes p to the workspace array pt [M, C], every lane the columns c = l + 16 k it
 // reads back itself later; after a barrier the student's logits overwrite the image and the per-row part runs as before with two more
-// strided sums.  The tile's loss_kd and agree sums take part[2 * CH_MAXTILE + tile] and part[3 * CH_MAXTILE + tile]; launch 2 is a
+// strided sums.  The tile's loss_kd and agree sums take part[2 * CL_MAXTILE + tile] and part[3 * CL_MAXTILE + tile]; launch 2 is a
 // template on KD only in its last workgroup.  The instances with KD = false are the code they were.  With alpha = 0, ce_weight = 1 every
 // extra operation is exact, so that call returns the soft form's bits.
 #include <type_traits>
-#include "common.h"
+#include "cls_head.h"
 
 namespace {
-
-constexpr int CH_TM = 16;          // rows per workgroup of launch 1
-constexpr int CH_NB = 128;         // output columns of one wg_mm call: 8 MFMA tiles = one pass of 4 waves x 2 tiles
-constexpr int CH_MM = 16384;       // floats of LDS the products stage their operands in
-constexpr int CH_MAXTILE = 4096 / CH_TM;
-
-struct ClsHead {
-    int M, F, C, ldz, ntile, train;
-    float gs;                      // grad_scale / M
-};
-
-struct ClsSoft {                   // the soft target of a row: t[c] = base + wa [c == y_a] + wb [c == y_b]
-    const int64_t* yb;
-    float wa, wb, base;            // (1 - eps) lam, (1 - eps) (1 - lam), eps / C
-};
 
 struct ClsKD {                     // the teacher of the distillation form and its weights
     const float* ft; const float* Wt; const float* bt;
@@ -69,25 +56,25 @@ __global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, ClsSoft s
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int M = d.M, F = d.F, C = d.C, ldz = d.ldz;
-    const int m0 = blockIdx.x * CH_TM, rows = min(CH_TM, M - m0);
+    const int m0 = blockIdx.x * CL_TM, rows = min(CL_TM, M - m0);
     float* Z = sm;                               // [16, ldz]
-    float* rl = Z + CH_TM * ldz;                 // [16] row losses, [16] row hits (KD: [16] row KL terms, [16] rows agreeing with the teacher)
+    float* rl = Z + CL_TM * ldz;                 // [16] row losses, [16] row hits (KD: [16] row KL terms, [16] rows agreeing with the teacher)
     float* mm = rl + 64;
     const float* ft = feats + (long)m0 * F;
 
     float kt = 0.f; int argt = 0;                // the teacher's row scalars: sum_c p (z_t - max) / T - log sum exp, first arg-max
     if constexpr (KD) {
         const float* ftt = kd.ft + (long)m0 * F;
-        for (int c0 = 0; c0 < C; c0 += CH_NB) {
-            const int nb = min(CH_NB, C - c0);
-            wg_mm(mm, CH_MM, rows, nb, F, ftt, F, 1, kd.Wt + (long)c0 * F, 1, F,
+        for (int c0 = 0; c0 < C; c0 += CL_NB) {
+            const int nb = min(CL_NB, C - c0);
+            wg_mm(mm, CL_MM, rows, nb, F, ftt, F, 1, kd.Wt + (long)c0 * F, 1, F,
                   [&](int m, int n, float acc) { Z[m * ldz + c0 + n] = acc + kd.bt[c0 + n]; });
         }
         __syncthreads();
         const int row = tid >> 4, l = tid & 15;
         if (row < rows) {
             const float* z = Z + row * ldz;
-            float mx = -INFINITY; int arg = C;
+            float mx = -INFINITY; int arg = C;                                           // (cls_head.h: a copy, like the row sums below)
             for (int c = l; c < C; c += 16) { const float v = z[c]; if (v > mx) { mx = v; arg = c; } }
             for (int o = 8; o > 0; o >>= 1) {
                 const float v2 = __shfl_xor(mx, o, 64); const int a2 = __shfl_xor(arg, o, 64);
@@ -110,9 +97,9 @@ __global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, ClsSoft s
         __syncthreads();                         // the student's logits overwrite the image
     }
 
-    for (int c0 = 0; c0 < C; c0 += CH_NB) {
-        const int nb = min(CH_NB, C - c0);
-        wg_mm(mm, CH_MM, rows, nb, F, ft, F, 1, W + (long)c0 * F, 1, F,
+    for (int c0 = 0; c0 < C; c0 += CL_NB) {
+        const int nb = min(CL_NB, C - c0);
+        wg_mm(mm, CL_MM, rows, nb, F, ft, F, 1, W + (long)c0 * F, 1, F,
               [&](int m, int n, float acc) { Z[m * ldz + c0 + n] = acc + bias[c0 + n]; });
     }
     __syncthreads();
@@ -123,13 +110,13 @@ __global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, ClsSoft s
         [[maybe_unused]] float lkd = 0.f, agr = 0.f;
         if (row < rows) {
             float* z = Z + row * ldz;
-            float mx = -INFINITY; int arg = C;
+            float mx = -INFINITY; int arg = C;                                           // (cls_head.h: a copy, like the row sums, the label rule and t below)
             for (int c = l; c < C; c += 16) { const float v = z[c]; if (v > mx) { mx = v; arg = c; } }
             for (int o = 8; o > 0; o >>= 1) {
                 const float v2 = __shfl_xor(mx, o, 64); const int a2 = __shfl_xor(arg, o, 64);
-                if (v2 > mx || (v2 == mx && a2 < arg)) { mx = v2; arg = a2; }           // first arg-max (torch.max)
+                if (v2 > mx || (v2 == mx && a2 < arg)) { mx = v2; arg = a2; }
             }
-            if (arg >= C) arg = 0;                                                       // (a row of NaNs)
+            if (arg >= C) arg = 0;
             float s = 0.f;
             for (int c = l; c < C; c += 16) s += expf(z[c] - mx);
             for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -185,21 +172,13 @@ __global__ __launch_bounds__(256) void cls_head_rows_kernel(ClsHead d, ClsSoft s
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, c = 0.f;
-        for (int r = 0; r < CH_TM; ++r) { a += rl[r]; c += rl[16 + r]; }
-        part[blockIdx.x] = a; part[CH_MAXTILE + blockIdx.x] = c;
-        if constexpr (KD) {
-            float k = 0.f, g = 0.f;
-            for (int r = 0; r < CH_TM; ++r) { k += rl[32 + r]; g += rl[48 + r]; }
-            part[2 * CH_MAXTILE + blockIdx.x] = k; part[3 * CH_MAXTILE + blockIdx.x] = g;
-        }
-    }
+    cl_tile_part<2>(rl, part);                                                       // loss, correct
+    if constexpr (KD) cl_tile_part<2>(rl, part, 2);                                    // KL, agree
     if (!d.train) return;
     // dfeats_tile [rows, F] = dlogits_tile [rows, C] W [C, F]
-    for (int f0 = 0; f0 < F; f0 += CH_NB) {
-        const int nb = min(CH_NB, F - f0);
-        wg_mm(mm, CH_MM, rows, nb, C, Z, ldz, 1, W + f0, F, 1,
+    for (int f0 = 0; f0 < F; f0 += CL_NB) {
+        const int nb = min(CL_NB, F - f0);
+        wg_mm(mm, CL_MM, rows, nb, C, Z, ldz, 1, W + f0, F, 1,
               [&](int m, int n, float acc) { dfeats[(long)(m0 + m) * F + f0 + n] = acc; });
     }
 }
@@ -214,12 +193,12 @@ __global__ __launch_bounds__(256) void cls_head_wgrad_kernel(ClsHead d, int nfb,
     const int tid = threadIdx.x;
     const int M = d.M, F = d.F, C = d.C;
     if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles, in index order
-        if (tid == 0) {
+        if (tid == 0) {                          // (cls_head.h: a copy)
             float a = 0.f, c = 0.f;
-            for (int t = 0; t < d.ntile; ++t) { a += part[t]; c += part[CH_MAXTILE + t]; }
+            for (int t = 0; t < d.ntile; ++t) { a += part[t]; c += part[CL_MAXTILE + t]; }
             if constexpr (KD) {
                 float k = 0.f, g = 0.f;
-                for (int t = 0; t < d.ntile; ++t) { k += part[2 * CH_MAXTILE + t]; g += part[3 * CH_MAXTILE + t]; }
+                for (int t = 0; t < d.ntile; ++t) { k += part[2 * CL_MAXTILE + t]; g += part[3 * CL_MAXTILE + t]; }
                 const float lce = a / (float)M, lkl = k / (float)M;
                 const float lkd = kd.T2 * lkl;
                 kd.parts[0] = lce; kd.parts[1] = lkd;
@@ -231,14 +210,14 @@ __global__ __launch_bounds__(256) void cls_head_wgrad_kernel(ClsHead d, int nfb,
         return;
     }
     const int cb = blockIdx.x / nfb, fb = blockIdx.x - cb * nfb;
-    const int c0 = cb * CH_TM, f0 = fb * CH_NB;
-    const int nc = min(CH_TM, C - c0), nf = min(CH_NB, F - f0);
+    const int c0 = cb * CL_TM, f0 = fb * CL_NB;
+    const int nc = min(CL_TM, C - c0), nf = min(CL_NB, F - f0);
     // gW[c0 + m, f0 + n] = sum_k dlog[k, c0 + m] feats[k, f0 + n]
-    wg_mm(sm, CH_MM, nc, nf, M, dlog + c0, 1, C, feats + f0, F, 1,
+    wg_mm(sm, CL_MM, nc, nf, M, dlog + c0, 1, C, feats + f0, F, 1,
           [&](int m, int n, float acc) { gW[(long)(c0 + m) * F + f0 + n] = acc; });
     if (fb != 0) return;
     __syncthreads();
-    {   // gb[c0 + c] = sum_k dlog[k, c0 + c]: 16 strided partial sums per class, added in index order
+    {   // gb[c0 + c] = sum_k dlog[k, c0 + c]: 16 strided partial sums per class, added in index order (cls_head.h: a copy)
         const int c = tid & 15, j = tid >> 4;
         float s = 0.f;
         if (c < nc) for (int k = j; k < M; k += 16) s += dlog[(long)k * C + c0 + c];
@@ -258,24 +237,20 @@ __global__ __launch_bounds__(256) void cls_head_wgrad_kernel(ClsHead d, int nfb,
 static int cls_head_launch(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C, const float* feats, const int64_t* y,
         const ClsSoft* soft, const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb, const ClsKD* kdp = nullptr) {
-    if (!ws || !feats || !y || !W || !b || !loss || !correct || M < 1 || F < 1 || C < 1) return FUMI_EINVAL;
-    const int ngrad = (dfeats ? 1 : 0) + (gW ? 1 : 0) + (gb ? 1 : 0);
-    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
-    if (M > 4096 || F % 32 != 0 || F < 32 || F > 2048 || C < 2 || C > 1024) return FUMI_ENOTSUP;
+    const int train = cl_grad_form(dfeats, gW, gb);
+    if (int rc = cl_args_check(ws, M, F, C, train, {feats, y, W, b, loss, correct})) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
-    const int train = ngrad == 3;
     ClsHead d;
-    d.M = M; d.F = F; d.C = C; d.ldz = ((C + 15) & ~15) + 4; d.ntile = (M + CH_TM - 1) / CH_TM; d.train = train;
-    d.gs = grad_scale / (float)M;
+    cl_dims_fill(d, M, F, C, train, grad_scale);
     const int nslot = kdp ? 4 : 2;                                                   // index-ordered sums per tile
-    int rc = ws_reserve(ws, ws_align((size_t)nslot * CH_MAXTILE * 4) + (train ? ws_align((size_t)M * C * 4) : 0) +
+    int rc = ws_reserve(ws, ws_align((size_t)nslot * CL_MAXTILE * 4) + (train ? ws_align((size_t)M * C * 4) : 0) +
                             (kdp ? ws_align((size_t)M * C * 4) : 0));
     if (rc) return rc;
-    float* part = ws_f(ws, nslot * CH_MAXTILE);
+    float* part = ws_f(ws, nslot * CL_MAXTILE);
     float* dlog = train ? ws_f(ws, (size_t)M * C) : nullptr;
-    const size_t lds1 = ((size_t)CH_TM * d.ldz + 64 + CH_MM) * 4, lds2 = train ? (size_t)CH_MM * 4 : 0;   // the forward form's one workgroup only adds the tile sums
-    const int nfb = (F + CH_NB - 1) / CH_NB, ncb = (C + CH_TM - 1) / CH_TM;
+    const size_t lds1 = ((size_t)CL_TM * d.ldz + 64 + CL_MM) * 4, lds2 = train ? (size_t)CL_MM * 4 : 0;   // the forward form's one workgroup only adds the tile sums
+    const int nfb = cl_feature_blocks(F);
     if (kdp) {
         ClsKD kd = *kdp;
         kd.pt = ws_f(ws, (size_t)M * C);
@@ -284,7 +259,7 @@ static int cls_head_launch(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, in
                            dlog, dfeats, ws->status, kd);
         LAUNCH_CHECK();
         FUMI_SET_DYN_LDS(cls_head_wgrad_kernel<true>, lds2);
-        hipLaunchKernelGGL(cls_head_wgrad_kernel<true>, dim3((train ? ncb * nfb : 0) + 1), dim3(256), lds2, st, d, nfb, feats, dlog, part,
+        hipLaunchKernelGGL(cls_head_wgrad_kernel<true>, dim3(cl_wgrad_grid(d)), dim3(256), lds2, st, d, nfb, feats, dlog, part,
                            loss, correct, gW, gb, kd);
         LAUNCH_CHECK();
         return FUMI_OK;
@@ -300,7 +275,7 @@ static int cls_head_launch(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, in
     }
     LAUNCH_CHECK();
     FUMI_SET_DYN_LDS(cls_head_wgrad_kernel<false>, lds2);
-    hipLaunchKernelGGL(cls_head_wgrad_kernel<false>, dim3((train ? ncb * nfb : 0) + 1), dim3(256), lds2, st, d, nfb, feats, dlog, part, loss,
+    hipLaunchKernelGGL(cls_head_wgrad_kernel<false>, dim3(cl_wgrad_grid(d)), dim3(256), lds2, st, d, nfb, feats, dlog, part, loss,
                        correct, gW, gb, ClsNoKD{});
     LAUNCH_CHECK();
     return FUMI_OK;
@@ -316,9 +291,8 @@ extern "C" int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, 
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
         const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb) {
-    if (!(smoothing >= 0.f && smoothing < 1.f) || !(lam >= 0.f && lam <= 1.f) || (!y_b && lam != 1.f)) return FUMI_EINVAL;
-    const float u = 1.f - lam, keep = 1.f - smoothing;
-    const ClsSoft soft{y_b ? y_b : y_a, keep * lam, keep * u, smoothing / (float)C};
+    ClsSoft soft;
+    if (int rc = cl_soft_fill(soft, y_a, y_b, lam, smoothing, C)) return rc;
     return cls_head_launch(ws, stream, M, F, C, feats, y_a, &soft, W, b, grad_scale, loss, correct, preds, dfeats, gW, gb);
 }
 
@@ -332,9 +306,8 @@ extern "C" int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t strea
     if (!finite(kd_temp) || !finite(kd_alpha) || !finite(ce_weight) || !(kd_temp > 0.f) || kd_alpha < 0.f || ce_weight < 0.f ||
         !finite(1.f / kd_temp) || !finite(kd_alpha * kd_temp * kd_temp))
         return FUMI_EINVAL;
-    if (!(smoothing >= 0.f && smoothing < 1.f) || !(lam >= 0.f && lam <= 1.f) || (!y_b && lam != 1.f)) return FUMI_EINVAL;
-    const float u = 1.f - lam, keep = 1.f - smoothing;
-    const ClsSoft soft{y_b ? y_b : y_a, keep * lam, keep * u, smoothing / (float)C};
+    ClsSoft soft;
+    if (int rc = cl_soft_fill(soft, y_a, y_b, lam, smoothing, C)) return rc;
     ClsKD kd;
     kd.ft = feats_t; kd.Wt = W_t; kd.bt = b_t; kd.pt = nullptr;
     kd.invT = 1.f / kd_temp; kd.aT = kd_alpha * kd_temp; kd.cw = ce_weight; kd.T2 = kd_temp * kd_temp; kd.alpha = kd_alpha;

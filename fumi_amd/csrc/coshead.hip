@@ -21,32 +21,25 @@
 //       gW = tau rw[c] ((dz rf)^T feats - q_c v_c), the W element of the epilogue loaded before the product;
 //       one further workgroup adds part[0..ntile) in index order: loss, correct, dtau.
 //   The forward form (no gradient pointers) is launches 0 and 1 without the backward half and that last workgroup alone.
-// Every sum has a fixed order; no floating-point atomics; the only atomic is the OR into the status word; the launches hand over
-// through memory.  A label outside [0, C) sets FUMI_ST_LABEL_RANGE; its row adds nothing to the loss, the count or any gradient.
+// The heads' common contract (fixed order of every sum, first arg-max, the label rule, no floating-point atomics) is stated in
+// cls_head.h; the launches hand over through memory.
 //
-// Departures from the plan of the issue, and what is shared:
+// Shared with the linear heads, in cls_head.h: the tile constants, the dims and soft-target fields of CosHead, the host's checks, the
+// soft-target builder and launch geometry, and the tile sums.  Still copies of the linear head's lines, on z = tau k, each marked
+// "(cls_head.h: a copy)": the row arg-max, the log-sum-exp and sum_c z, the label rule, the soft target, the final sum over the tiles
+// and the column sum q_c -- through a helper each changed this file's or clshead.hip's instruction streams.
+// Departures from the plan of the issue:
 //   * q_c comes from a second workspace array (dz k), not from a stored k: either way launch 1 writes and launch 2 reads one more
 //     [M, C] array, and the stored product saves launch 2 the multiplication and the second read of dz.
 //   * there is one instance of the rows kernel, the soft one: with y_b = y_a, lam = 1, smoothing = 0 its extra operations are exact
 //     (a product by 1, a sum with 0), which csrc/clshead.hip already relies on.
-//   * the row arg-max, the log-sum-exp and the soft target are the linear head's lines, duplicated here on z = tau k rather than
-//     moved to a header: clshead.hip is left untouched so that its instances compile to the code they were.
-#include "common.h"
+#include "cls_head.h"
 
 namespace {
 
-constexpr int KH_TM = 16;          // rows per workgroup of launch 1
-constexpr int KH_NB = 128;         // output columns of one wg_mm call
-constexpr int KH_MM = 16384;       // floats of LDS the products stage their operands in
-constexpr int KH_MAXTILE = 4096 / KH_TM;
 constexpr float KH_EPS = 1e-12f;
 
-struct CosHead {
-    int M, F, C, ldz, ntile, train;
-    float gs;                      // grad_scale / M
-    const int64_t* yb;
-    float wa, wb, base;            // (1 - eps) lam, (1 - eps) (1 - lam), eps / C
-};
+struct CosHead : ClsHead { ClsSoft sf; };   // the kernels' one argument: the layout it always had
 
 // rn[0, C) = 1 / |W_c|, rn[C, C + M) = 1 / |feats_m|; 0 where the norm is below eps
 __global__ __launch_bounds__(256) void cos_head_norm_kernel(int M, int F, int C, const float* __restrict__ feats,
@@ -74,21 +67,21 @@ __global__ __launch_bounds__(256) void cos_head_rows_kernel(CosHead d, const flo
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int M = d.M, F = d.F, C = d.C, ldz = d.ldz;
-    const int m0 = blockIdx.x * KH_TM, rows = min(KH_TM, M - m0);
+    const int m0 = blockIdx.x * CL_TM, rows = min(CL_TM, M - m0);
     float* Z = sm;                               // [16, ldz]: k, then dz rw[c]
-    float* rl = Z + KH_TM * ldz;                 // [16] row losses, [16] row hits, [16] r_m, [16] rf
+    float* rl = Z + CL_TM * ldz;                 // [16] row losses, [16] row hits, [16] r_m, [16] rf
     float* rws = rl + 64;                        // [ldz] rw
     float* mm = rws + ldz;
     const float* ft = feats + (long)m0 * F;
     const float tau = taup[0];
 
     for (int c = tid; c < C; c += 256) rws[c] = rn[c];
-    if (tid < KH_TM) rl[48 + tid] = tid < rows ? rn[C + m0 + tid] : 0.f;
+    if (tid < CL_TM) rl[48 + tid] = tid < rows ? rn[C + m0 + tid] : 0.f;
     __syncthreads();
 
-    for (int c0 = 0; c0 < C; c0 += KH_NB) {
-        const int nb = min(KH_NB, C - c0);
-        wg_mm(mm, KH_MM, rows, nb, F, ft, F, 1, W + (long)c0 * F, 1, F,
+    for (int c0 = 0; c0 < C; c0 += CL_NB) {
+        const int nb = min(CL_NB, C - c0);
+        wg_mm(mm, CL_MM, rows, nb, F, ft, F, 1, W + (long)c0 * F, 1, F,
               [&](int m, int n, float acc) { Z[m * ldz + c0 + n] = acc * rl[48 + m] * rws[c0 + n]; });
     }
     __syncthreads();
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void cos_head_rows_kernel(CosHead d, const flo
         float loss = 0.f, hit = 0.f, rsum = 0.f;
         if (row < rows) {
             float* z = Z + row * ldz;
-            float mx = -INFINITY; int arg = C;
+            float mx = -INFINITY; int arg = C;                                           // (cls_head.h: a copy, like the row sums, the label rule and t below)
             for (int c = l; c < C; c += 16) { const float v = tau * z[c]; if (v > mx) { mx = v; arg = c; } }
             for (int o = 8; o > 0; o >>= 1) {
                 const float v2 = __shfl_xor(mx, o, 64); const int a2 = __shfl_xor(arg, o, 64);
@@ -108,15 +101,15 @@ __global__ __launch_bounds__(256) void cos_head_rows_kernel(CosHead d, const flo
             float s = 0.f;
             for (int c = l; c < C; c += 16) s += expf(tau * z[c] - mx);
             for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            long yv = y[m0 + row], yw = d.yb[m0 + row];
+            long yv = y[m0 + row], yw = d.sf.yb[m0 + row];
             const bool ok = yv >= 0 && yv < C && yw >= 0 && yw < C;
             if (!ok) { if (l == 0) atomicOr(status, FUMI_ST_LABEL_RANGE); yv = 0; yw = 0; }
-            float tz = d.wa * (tau * z[yv]) + d.wb * (tau * z[yw]);                      // sum_c t[c] z[c]
-            if (d.base > 0.f) {
+            float tz = d.sf.wa * (tau * z[yv]) + d.sf.wb * (tau * z[yw]);                      // sum_c t[c] z[c]
+            if (d.sf.base > 0.f) {
                 float sz = 0.f;
                 for (int c = l; c < C; c += 16) sz += tau * z[c];
                 for (int o = 8; o > 0; o >>= 1) sz += __shfl_xor(sz, o, 64);
-                tz += d.base * sz;
+                tz += d.sf.base * sz;
             }
             loss = ok ? mx + logf(s) - tz : 0.f;
             hit = (ok && arg == (int)yv) ? 1.f : 0.f;
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void cos_head_rows_kernel(CosHead d, const flo
                 float* kr = dk + (long)(m0 + row) * C;
                 for (int c = l; c < C; c += 16) {
                     const float k = z[c];
-                    const float t = d.base + (c == (int)yv ? d.wa : 0.f) + (c == (int)yw ? d.wb : 0.f);
+                    const float t = d.sf.base + (c == (int)yv ? d.sf.wa : 0.f) + (c == (int)yw ? d.sf.wb : 0.f);
                     const float g = gs * (expf(tau * k - mx) * inv - t), gk = g * k;
                     rsum += gk;
                     z[c] = g * rws[c]; ar[c] = g * rfm; kr[c] = gk;
@@ -138,16 +131,12 @@ __global__ __launch_bounds__(256) void cos_head_rows_kernel(CosHead d, const flo
         if (l == 0) { rl[row] = loss; rl[16 + row] = hit; rl[32 + row] = rsum; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float a = 0.f, c = 0.f, r = 0.f;
-        for (int i = 0; i < KH_TM; ++i) { a += rl[i]; c += rl[16 + i]; r += rl[32 + i]; }
-        part[blockIdx.x] = a; part[KH_MAXTILE + blockIdx.x] = c; part[2 * KH_MAXTILE + blockIdx.x] = r;
-    }
+    cl_tile_part<3>(rl, part);                                                       // loss, correct, r_m
     if (!d.train) return;
     // dfeats_tile [rows, F] = tau rf[m] ((dz rw) [rows, C] W [C, F] - r_m u_m)
-    for (int f0 = 0; f0 < F; f0 += KH_NB) {
-        const int nb = min(KH_NB, F - f0);
-        wg_mm2(mm, KH_MM, rows, nb, C, Z, ldz, 1, W + f0, F, 1,
+    for (int f0 = 0; f0 < F; f0 += CL_NB) {
+        const int nb = min(CL_NB, F - f0);
+        wg_mm2(mm, CL_MM, rows, nb, C, Z, ldz, 1, W + f0, F, 1,
                [&](int m, int n) { return ft[(long)m * F + f0 + n]; },
                [&](int m, int n, float acc, float x) {
                    const float rfm = rl[48 + m];
@@ -165,20 +154,20 @@ __global__ __launch_bounds__(256) void cos_head_wgrad_kernel(CosHead d, int nfb,
     const int tid = threadIdx.x;
     const int M = d.M, F = d.F, C = d.C;
     if (blockIdx.x == gridDim.x - 1) {           // the sums over the row tiles, in index order
-        if (tid == 0) {
+        if (tid == 0) {                          // (cls_head.h: a copy)
             float a = 0.f, c = 0.f, r = 0.f;
-            for (int t = 0; t < d.ntile; ++t) { a += part[t]; c += part[KH_MAXTILE + t]; r += part[2 * KH_MAXTILE + t]; }
+            for (int t = 0; t < d.ntile; ++t) { a += part[t]; c += part[CL_MAXTILE + t]; r += part[2 * CL_MAXTILE + t]; }
             loss[0] = a / (float)M; correct[0] = c;
             if (d.train) dtau[0] = r;
         }
         return;
     }
     const int cb = blockIdx.x / nfb, fb = blockIdx.x - cb * nfb;
-    const int c0 = cb * KH_TM, f0 = fb * KH_NB;
-    const int nc = min(KH_TM, C - c0), nf = min(KH_NB, F - f0);
-    float* ql = sm + KH_MM;                      // [16, 16] partial sums, [16] q_c, [16] rw
+    const int c0 = cb * CL_TM, f0 = fb * CL_NB;
+    const int nc = min(CL_TM, C - c0), nf = min(CL_NB, F - f0);
+    float* ql = sm + CL_MM;                      // [16, 16] partial sums, [16] q_c, [16] rw
     const float tau = taup[0];
-    {   // q[c] = sum_k dk[k, c0 + c]: 16 strided partial sums per class, added in index order
+    {   // q[c] = sum_k dk[k, c0 + c]: 16 strided partial sums per class, added in index order (cls_head.h: a copy)
         const int c = tid & 15, j = tid >> 4;
         float s = 0.f;
         if (c < nc) for (int k = j; k < M; k += 16) s += dk[(long)k * C + c0 + c];
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(256) void cos_head_wgrad_kernel(CosHead d, int nfb,
         __syncthreads();
     }
     // gW[c0 + m, f0 + n] = tau rw[c] (sum_k da[k, c0 + m] feats[k, f0 + n] - q_c v_c)
-    wg_mm2(sm, KH_MM, nc, nf, M, da + c0, 1, C, feats + f0, F, 1,
+    wg_mm2(sm, CL_MM, nc, nf, M, da + c0, 1, C, feats + f0, F, 1,
            [&](int m, int n) { return W[(long)(c0 + m) * F + f0 + n]; },
            [&](int m, int n, float acc, float w) {
                const float rwc = ql[272 + m];
@@ -206,29 +195,22 @@ extern "C" int fumi_hip_cos_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, i
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
         const float* W, const float* tau, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* dtau) {
-    if (!(smoothing >= 0.f && smoothing < 1.f) || !(lam >= 0.f && lam <= 1.f) || (!y_b && lam != 1.f)) return FUMI_EINVAL;
-    if (!ws || !feats || !y_a || !W || !tau || !loss || !correct || M < 1 || F < 1 || C < 1) return FUMI_EINVAL;
-    const int ngrad = (dfeats ? 1 : 0) + (gW ? 1 : 0) + (dtau ? 1 : 0);
-    if (ngrad != 0 && ngrad != 3) return FUMI_EINVAL;
-    if (M > 4096 || F % 32 != 0 || F < 32 || F > 2048 || C < 2 || C > 1024) return FUMI_ENOTSUP;
+    CosHead d;
+    if (int rc = cl_soft_fill(d.sf, y_a, y_b, lam, smoothing, C)) return rc;
+    const int train = cl_grad_form(dfeats, gW, dtau);
+    if (int rc = cl_args_check(ws, M, F, C, train, {feats, y_a, W, tau, loss, correct})) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ws->device));
-    const int train = ngrad == 3;
-    const float u = 1.f - lam, keep = 1.f - smoothing;
-    CosHead d;
-    d.M = M; d.F = F; d.C = C; d.ldz = ((C + 15) & ~15) + 4; d.ntile = (M + KH_TM - 1) / KH_TM; d.train = train;
-    d.gs = grad_scale / (float)M;
-    d.yb = y_b ? y_b : y_a; d.wa = keep * lam; d.wb = keep * u; d.base = smoothing / (float)C;
-    int rc = ws_reserve(ws, ws_align((size_t)3 * KH_MAXTILE * 4) + ws_align((size_t)(C + M) * 4) +
+    cl_dims_fill(d, M, F, C, train, grad_scale);
+    int rc = ws_reserve(ws, ws_align((size_t)3 * CL_MAXTILE * 4) + ws_align((size_t)(C + M) * 4) +
                             (train ? 2 * ws_align((size_t)M * C * 4) : 0));
     if (rc) return rc;
-    float* part = ws_f(ws, 3 * KH_MAXTILE);
+    float* part = ws_f(ws, 3 * CL_MAXTILE);
     float* rn = ws_f(ws, (size_t)C + M);
     float* da = train ? ws_f(ws, (size_t)M * C) : nullptr;
     float* dk = train ? ws_f(ws, (size_t)M * C) : nullptr;
-    const size_t lds1 = ((size_t)KH_TM * d.ldz + 64 + d.ldz + KH_MM) * 4;
-    const size_t lds2 = train ? (size_t)(KH_MM + 288) * 4 : 0;                      // the forward form's one workgroup only adds the tile sums
-    const int nfb = (F + KH_NB - 1) / KH_NB, ncb = (C + KH_TM - 1) / KH_TM;
+    const size_t lds1 = ((size_t)CL_TM * d.ldz + 64 + d.ldz + CL_MM) * 4;
+    const size_t lds2 = train ? (size_t)(CL_MM + 288) * 4 : 0;                      // the forward form's one workgroup only adds the tile sums
     hipLaunchKernelGGL(cos_head_norm_kernel, dim3((C + M + 3) / 4), dim3(256), 0, st, M, F, C, feats, W, rn);
     LAUNCH_CHECK();
     FUMI_SET_DYN_LDS(cos_head_rows_kernel, lds1);
@@ -236,7 +218,7 @@ extern "C" int fumi_hip_cos_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, i
                        ws->status);
     LAUNCH_CHECK();
     FUMI_SET_DYN_LDS(cos_head_wgrad_kernel, lds2);
-    hipLaunchKernelGGL(cos_head_wgrad_kernel, dim3((train ? ncb * nfb : 0) + 1), dim3(256), lds2, st, d, nfb, feats, W, tau, rn, da, dk,
+    hipLaunchKernelGGL(cos_head_wgrad_kernel, dim3(cl_wgrad_grid(d)), dim3(256), lds2, st, d, cl_feature_blocks(F), feats, W, tau, rn, da, dk,
                        part, loss, correct, gW, dtau);
     LAUNCH_CHECK();
     return FUMI_OK;

@@ -260,11 +260,15 @@ def lib():
                                                 c_void_p, c_void_p]
         L.fumi_hip_lstm_bidir_bwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_int64, PP, c_int, c_void_p, c_void_p, PP]
         L.fumi_hip_proto_reduce.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3
-        L.fumi_hip_cls_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_float] + [c_void_p] * 6
-        L.fumi_hip_cls_head_step_soft.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
-                                                  + [c_float] + [c_void_p] * 6)
-        L.fumi_hip_cls_head_step_distill.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2
-                                                     + [c_void_p] * 5 + [c_float] * 4 + [c_void_p] * 8)
+        cls_lead = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2       # ws, stream, M, F, C, feats, y_a
+        cls_soft = [c_void_p] + [c_float] * 2                               # y_b, lam, smoothing
+        cls_tail = [c_void_p] * 3 + [c_void_p] * 3                          # loss, correct, preds, the three gradients
+        L.fumi_hip_cls_head_step.argtypes = cls_lead + [c_void_p] * 2 + [c_float] + cls_tail
+        for fn in (L.fumi_hip_cls_head_step_soft, L.fumi_hip_cos_cls_head_step):
+            fn.argtypes = cls_lead + cls_soft + [c_void_p] * 2 + [c_float] + cls_tail
+        # the teacher and the KD scalars before grad_scale; loss_parts after loss and agree after correct
+        L.fumi_hip_cls_head_step_distill.argtypes = (cls_lead + cls_soft + [c_void_p] * 5 + [c_float] * 4 + [c_void_p] * 2
+                                                     + cls_tail[1:2] + [c_void_p] + cls_tail[2:])
         L.fumi_hip_mix_images.argtypes = ([c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_float] + [c_int] * 4
                                           + [c_void_p])
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
@@ -282,8 +286,6 @@ def lib():
                                              + [c_void_p] * 8)
         L.fumi_hip_svm_set_form.argtypes = [c_int]
         L.fumi_hip_svm_get_fit.argtypes = [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2
-        L.fumi_hip_cos_cls_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_float] * 2 + [c_void_p] * 2
-                                                 + [c_float] + [c_void_p] * 6)
         _lib = L
     return _lib
 
@@ -1844,28 +1846,42 @@ def cls_head_step(ws, feats, y, W, b, *, need_grad=True, grad_scale=1.0, dfeats=
     """The fused classification head (csrc/clshead.hip): F.cross_entropy(feats @ W.T + b, y), mean over the M rows.  Returns a dict
     of GPU tensors: loss [1], correct [1] (count, float), preds [M] (first arg-max; None without want_preds) and, with need_grad,
     dfeats [M,F], gW [C,F], gb [C] = gradients of grad_scale * loss (written into the tensors given, else into new ones)."""
+    dev, (M, F, C), out = _cls_head_io("cls_head_step", feats, W, (b, "b"), (y, "y"), None, want_preds)
+    grads = _head_grads(dev, need_grad, out, dfeats=((M, F), dfeats), gW=((C, F), gW), gb=((C,), gb))
+    _check(lib().fumi_hip_cls_head_step(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y, "y"), _f32(W, "W"), _f32(b, "b"),
+                                        float(grad_scale), *_cls_head_outs(out), *grads), "fumi_hip_cls_head_step")
+    return out
+
+
+def _cls_head_io(name, feats, W, param, y_a, y_b, want_preds, teacher=None):
+    """What the classification heads share before their call: the checks of feats [M,F] and W [C,F], of the head's second parameter
+    ``param`` = (b [C] or tau [1], its name), of the labels ``y_a`` = (tensor [M], its name) and ``y_b`` (tensor [M] or None) and of
+    the distillation head's ``teacher`` = (feats_t [M,F], W_t [C,F], b_t [C]), and the outputs.  Returns (dev, (M, F, C),
+    dict(loss, correct, preds))."""
     dev = _dev(feats)
     if feats.dim() != 2 or W.dim() != 2:
-        raise FumiHipError("cls_head_step: feats [M,F] and W [C,F] expected")
+        raise FumiHipError(f"{name}: feats [M,F] and W [C,F] expected")
     M, F = (int(v) for v in feats.shape)
     C = int(W.shape[0])
-    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y, (M,), "y")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
-    if need_grad:
-        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
-        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
-        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
-        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
-        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
-    else:
-        dfeats = gW = gb = None
-        grads = [None, None, None]
-    _check(lib().fumi_hip_cls_head_step(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y, "y"), _f32(W, "W"), _f32(b, "b"),
-                                        float(grad_scale), _f32(loss, "loss"), _f32(correct, "correct"),
-                                        _i64(preds, "preds") if want_preds else None, *grads), "fumi_hip_cls_head_step")
-    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+    _shape(W, (C, F), "W"); _shape(param[0], (1,) if param[1] == "tau" else (C,), param[1]); _shape(y_a[0], (M,), y_a[1])
+    if teacher is not None:
+        _shape(teacher[0], (M, F), "feats_t"); _shape(teacher[1], (C, F), "W_t"); _shape(teacher[2], (C,), "b_t")
+    if y_b is not None:
+        _shape(y_b, (M,), "y_b")
+    out = dict(loss=torch.empty(1, device=dev, dtype=torch.float32), correct=torch.empty(1, device=dev, dtype=torch.float32),
+               preds=torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None)
+    return dev, (M, F, C), out
+
+
+def _cls_head_outs(out):
+    """The trailing (loss, correct, preds) ctypes arguments of a classification head's entry, with their dtype checks."""
+    return (_f32(out["loss"], "loss"), _f32(out["correct"], "correct"),
+            _i64(out["preds"], "preds") if out["preds"] is not None else None)
+
+
+def _soft_args(y_b, lam, smoothing):
+    """The (y_b, lam, smoothing) ctypes arguments of the soft target; y_b None -> NULL."""
+    return _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing)
 
 
 def _episode_head_io(name, feats_s, y_s, feats_q, y_q, n_way, want_logits, param=None, metric=None):
@@ -2103,32 +2119,12 @@ def cls_head_step_soft(ws, feats, y_a, W, b, *, y_b=None, lam=1.0, smoothing=0.0
     """``cls_head_step`` against the soft target t = (1 - smoothing) (lam onehot(y_a) + (1 - lam) onehot(y_b)) + smoothing / C
     (fumi_hip_cls_head_step_soft: label smoothing, mixup / CutMix labels).  ``y_b`` None: y_b = y_a, and lam must be 1.  ``correct``
     counts against y_a.  The same dict as ``cls_head_step``."""
-    dev = _dev(feats)
-    if feats.dim() != 2 or W.dim() != 2:
-        raise FumiHipError("cls_head_step_soft: feats [M,F] and W [C,F] expected")
-    M, F = (int(v) for v in feats.shape)
-    C = int(W.shape[0])
-    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y_a, (M,), "y_a")
-    if y_b is not None:
-        _shape(y_b, (M,), "y_b")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
-    if need_grad:
-        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
-        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
-        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
-        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
-        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
-    else:
-        dfeats = gW = gb = None
-        grads = [None, None, None]
+    dev, (M, F, C), out = _cls_head_io("cls_head_step_soft", feats, W, (b, "b"), (y_a, "y_a"), y_b, want_preds)
+    grads = _head_grads(dev, need_grad, out, dfeats=((M, F), dfeats), gW=((C, F), gW), gb=((C,), gb))
     _check(lib().fumi_hip_cls_head_step_soft(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
-                                             _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
-                                             _f32(W, "W"), _f32(b, "b"), float(grad_scale), _f32(loss, "loss"),
-                                             _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
-           "fumi_hip_cls_head_step_soft")
-    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb)
+                                             *_soft_args(y_b, lam, smoothing), _f32(W, "W"), _f32(b, "b"), float(grad_scale),
+                                             *_cls_head_outs(out), *grads), "fumi_hip_cls_head_step_soft")
+    return out
 
 
 def cos_cls_head_step(ws, feats, y_a, W, tau, *, y_b=None, lam=1.0, smoothing=0.0, need_grad=True, grad_scale=1.0, dfeats=None,
@@ -2137,32 +2133,12 @@ def cos_cls_head_step(ws, feats, y_a, W, tau, *, y_b=None, lam=1.0, smoothing=0.
     the soft target of ``cls_head_step_soft`` (``y_b`` None: y_b = y_a, and lam must be 1), with ``tau`` [1] on the device.  Returns a
     dict of GPU tensors: loss [1], correct [1] (count against y_a, float), preds [M] (first arg-max; None without want_preds) and, with
     need_grad, dfeats [M,F], gW [C,F], dtau [1] = gradients of grad_scale * loss (written into the tensors given, else into new ones)."""
-    dev = _dev(feats)
-    if feats.dim() != 2 or W.dim() != 2:
-        raise FumiHipError("cos_cls_head_step: feats [M,F] and W [C,F] expected")
-    M, F = (int(v) for v in feats.shape)
-    C = int(W.shape[0])
-    _shape(W, (C, F), "W"); _shape(tau, (1,), "tau"); _shape(y_a, (M,), "y_a")
-    if y_b is not None:
-        _shape(y_b, (M,), "y_b")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
-    if need_grad:
-        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
-        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
-        dtau = torch.empty(1, device=dev, dtype=torch.float32) if dtau is None else dtau
-        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(dtau, (1,), "dtau")
-        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(dtau, "dtau")]
-    else:
-        dfeats = gW = dtau = None
-        grads = [None, None, None]
+    dev, (M, F, C), out = _cls_head_io("cos_cls_head_step", feats, W, (tau, "tau"), (y_a, "y_a"), y_b, want_preds)
+    grads = _head_grads(dev, need_grad, out, dfeats=((M, F), dfeats), gW=((C, F), gW), dtau=((1,), dtau))
     _check(lib().fumi_hip_cos_cls_head_step(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
-                                            _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
-                                            _f32(W, "W"), _f32(tau, "tau"), float(grad_scale), _f32(loss, "loss"),
-                                            _f32(correct, "correct"), _i64(preds, "preds") if want_preds else None, *grads),
-           "fumi_hip_cos_cls_head_step")
-    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, dtau=dtau)
+                                            *_soft_args(y_b, lam, smoothing), _f32(W, "W"), _f32(tau, "tau"), float(grad_scale),
+                                            *_cls_head_outs(out), *grads), "fumi_hip_cos_cls_head_step")
+    return out
 
 
 def cls_head_step_distill(ws, feats, y_a, W, b, feats_t, W_t, b_t, *, temp, alpha, ce_weight, y_b=None, lam=1.0, smoothing=0.0,
@@ -2171,38 +2147,19 @@ def cls_head_step_distill(ws, feats, y_a, W, b, feats_t, W_t, b_t, *, temp, alph
     z_t = feats_t @ W_t.T + b_t and T = ``temp``, loss = ce_weight * loss_ce + alpha * loss_kd, loss_kd = T^2 KL(softmax(z_t / T) ||
     softmax(z / T)) (batch mean).  The dict of ``cls_head_step_soft`` plus loss_ce [1], loss_kd [1] (views of loss_parts [2]) and
     agree [1] (rows whose arg-max equals the teacher's, float)."""
-    dev = _dev(feats)
-    if feats.dim() != 2 or W.dim() != 2:
-        raise FumiHipError("cls_head_step_distill: feats [M,F] and W [C,F] expected")
-    M, F = (int(v) for v in feats.shape)
-    C = int(W.shape[0])
-    _shape(W, (C, F), "W"); _shape(b, (C,), "b"); _shape(y_a, (M,), "y_a")
-    _shape(feats_t, (M, F), "feats_t"); _shape(W_t, (C, F), "W_t"); _shape(b_t, (C,), "b_t")
-    if y_b is not None:
-        _shape(y_b, (M,), "y_b")
-    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    dev, (M, F, C), out = _cls_head_io("cls_head_step_distill", feats, W, (b, "b"), (y_a, "y_a"), y_b, want_preds,
+                                       teacher=(feats_t, W_t, b_t))
     loss_parts = torch.empty(2, device=dev, dtype=torch.float32)
-    correct = torch.empty(1, device=dev, dtype=torch.float32)
     agree = torch.empty(1, device=dev, dtype=torch.float32)
-    preds = torch.empty(M, device=dev, dtype=torch.int64) if want_preds else None
-    if need_grad:
-        dfeats = torch.empty(M, F, device=dev, dtype=torch.float32) if dfeats is None else dfeats
-        gW = torch.empty(C, F, device=dev, dtype=torch.float32) if gW is None else gW
-        gb = torch.empty(C, device=dev, dtype=torch.float32) if gb is None else gb
-        _shape(dfeats, (M, F), "dfeats"); _shape(gW, (C, F), "gW"); _shape(gb, (C,), "gb")
-        grads = [_f32(dfeats, "dfeats"), _f32(gW, "gW"), _f32(gb, "gb")]
-    else:
-        dfeats = gW = gb = None
-        grads = [None, None, None]
+    grads = _head_grads(dev, need_grad, out, dfeats=((M, F), dfeats), gW=((C, F), gW), gb=((C,), gb))
+    loss, correct, preds = _cls_head_outs(out)
     _check(lib().fumi_hip_cls_head_step_distill(ws.handle, _stream(dev), M, F, C, _f32(feats, "feats"), _i64(y_a, "y_a"),
-                                                _i64(y_b, "y_b") if y_b is not None else None, float(lam), float(smoothing),
-                                                _f32(W, "W"), _f32(b, "b"), _f32(feats_t, "feats_t"), _f32(W_t, "W_t"),
-                                                _f32(b_t, "b_t"), float(temp), float(alpha), float(ce_weight), float(grad_scale),
-                                                _f32(loss, "loss"), _f32(loss_parts, "loss_parts"), _f32(correct, "correct"),
-                                                _f32(agree, "agree"), _i64(preds, "preds") if want_preds else None, *grads),
-           "fumi_hip_cls_head_step_distill")
-    return dict(loss=loss, correct=correct, preds=preds, dfeats=dfeats, gW=gW, gb=gb, loss_parts=loss_parts, loss_ce=loss_parts[0:1],
-                loss_kd=loss_parts[1:2], agree=agree)
+                                                *_soft_args(y_b, lam, smoothing), _f32(W, "W"), _f32(b, "b"),
+                                                _f32(feats_t, "feats_t"), _f32(W_t, "W_t"), _f32(b_t, "b_t"), float(temp), float(alpha),
+                                                float(ce_weight), float(grad_scale), loss, _f32(loss_parts, "loss_parts"), correct,
+                                                _f32(agree, "agree"), preds, *grads), "fumi_hip_cls_head_step_distill")
+    out.update(loss_parts=loss_parts, loss_ce=loss_parts[0:1], loss_kd=loss_parts[1:2], agree=agree)
+    return out
 
 
 MIX_MIXUP, MIX_CUTMIX = 0, 1

@@ -566,16 +566,23 @@ int fumi_hip_ce_fwd_bwd(fumi_ws_t* ws, fumi_stream_t stream, int M, int N, const
         int64_t* preds);
 /* get_prototypes (fumi/utils/utils.py:331-376): out[b,n,:] = sum_{s: y[b,s]==n} x[b,s,:] / max(count, 1)  -> [B,N,P] */
 int fumi_hip_proto_reduce(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int N, int P, const float* x, const int64_t* y, float* out);
+/* ---- The classification heads of --model pretrain (fumi_hip_cls_head_step ... fumi_hip_cos_cls_head_step; shared code in
+ * csrc/cls_head.h) ----
+ * PREDICTIONS, for all four: preds is the first arg-max, as torch.max gives it; a row of NaNs predicts class 0.
+ * LABELS, for all four: a label outside [0,C), in y_a or y_b, sets FUMI_ST_LABEL_RANGE; that row adds nothing to any loss, count or
+ * gradient while the divisor stays M.
+ * ORDER, for all four: every sum has a fixed order and there are no floating-point atomics, so two calls on the same inputs give the
+ * same bits.
+ * SHAPES, for all four: 1 <= M <= 4096, F % 32 == 0, 32 <= F <= 2048, 2 <= C <= 1024: FUMI_ENOTSUP / FUMI_EINVAL otherwise, before any
+ * launch.  Each entry says below only what is its own. */
 /* The classification head of supervised pre-training (csrc/clshead.hip), fused: F.cross_entropy(feats W^T + b, y)
  * with mean reduction over the M rows and its backward, in two launches.  feats [M,F], y [M], W [C,F], b [C];  loss [1] = mean NLL,
  * correct [1] = number of rows whose first arg-max equals the label (float), preds [M] = first arg-max (may be NULL);
  * dfeats [M,F], gW [C,F], gb [C] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training form) or all
  * three NULL (forward form: loss, correct and preds are bit-identical to the training form's).  fp32 with fp32 accumulation on
  * v_mfma_f32_16x16x4_f32; the logits of a 16-row tile stay in LDS from the product through the softmax to dlogits and dfeats =
- * dlogits W, only dlogits goes to memory (workspace) for gW = dlogits^T feats and gb = colsum(dlogits).  Every sum has a fixed order
- * and there are no floating-point atomics: two calls on the same inputs give the same bits.
- * A label outside [0,C) sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or the gradients, the divisor stays M.
- * 1 <= M <= 4096, F % 32 == 0, 32 <= F <= 2048, 2 <= C <= 1024: FUMI_ENOTSUP / FUMI_EINVAL otherwise, before any launch. */
+ * dlogits W, only dlogits goes to memory (workspace) for gW = dlogits^T feats and gb = colsum(dlogits).  Predictions,
+ * labels, order and shapes: the common contract above. */
 int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
         const float* feats, const int64_t* y, const float* W, const float* b, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* dfeats, float* gW, float* gb);
@@ -587,7 +594,7 @@ int fumi_hip_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, in
  * y_b == NULL means y_b = y_a (label smoothing alone; lam must be 1).  The same two launches, LDS image, shapes, fixed summation
  * orders and forward form as fumi_hip_cls_head_step; sum_c z[m,c] (needed for eps > 0) is formed by the strided loop and butterfly of
  * the log-sum-exp.  With y_b == NULL, lam = 1, smoothing = 0 all six outputs are bit-identical to fumi_hip_cls_head_step.
- * A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or the gradients.
+ * Labels: the common contract above, for y_a and y_b.
  * FUMI_EINVAL before any launch: smoothing outside [0, 1), lam outside [0, 1], y_b == NULL with lam != 1. */
 int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
@@ -605,7 +612,7 @@ int fumi_hip_cls_head_step_soft(fumi_ws_t* ws, fumi_stream_t stream, int M, int 
  * The same two launches, LDS image, shapes, fixed summation orders and forward form: the teacher's logits of a 16-row tile are formed in
  * the LDS image first, p goes to the workspace ([M,C] floats, the teacher's only trace in memory), then the student's logits overwrite
  * the image.  With kd_alpha = 0, ce_weight = 1 loss, correct, preds, dfeats, gW and gb are bit-identical to fumi_hip_cls_head_step_soft.
- * A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to either loss, correct, agree or the gradients.
+ * Labels: the common contract above; a row left out adds nothing to either loss, correct, agree or the gradients.
  * FUMI_EINVAL before any launch: a NULL teacher pointer, loss_parts or agree; kd_temp, kd_alpha or ce_weight not finite; kd_temp <= 0;
  * a negative kd_alpha or ce_weight; the refusals of the soft entry. */
 int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
@@ -625,12 +632,9 @@ int fumi_hip_cls_head_step_distill(fumi_ws_t* ws, fumi_stream_t stream, int M, i
  * dfeats [M,F], gW [C,F], dtau [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training form) or
  * all three NULL (forward form: loss, correct and preds are bit-identical to the training form's).  Three launches: the reciprocal
  * norms of the C + M rows, then the two launches of the linear head; k of a 16-row tile stays in LDS from the product through the
- * softmax to dz and dfeats, dz / |feats_m| and dz k go to memory (workspace, 2 [M,C] floats) for gW.  Every sum has a fixed order and
- * there are no floating-point atomics: two calls on the same inputs give the same bits.
+ * softmax to dz and dfeats, dz / |feats_m| and dz k go to memory (workspace, 2 [M,C] floats) for gW.
  * A row of feats or W whose norm is below 1e-12 is the zero direction: k = 0 along it and its gradient row is zero; nothing else is
- * affected.  A label outside [0,C) in y_a or y_b sets FUMI_ST_LABEL_RANGE; that row adds nothing to the loss, the count or any
- * gradient, the divisor stays M.
- * 1 <= M <= 4096, F % 32 == 0, 32 <= F <= 2048, 2 <= C <= 1024: FUMI_ENOTSUP / FUMI_EINVAL otherwise, before any launch; FUMI_EINVAL
+ * affected.  Predictions, labels, order and shapes: the common contract above.  FUMI_EINVAL before any launch
  * also for smoothing outside [0, 1), lam outside [0, 1], y_b == NULL with lam != 1, a NULL tau. */
 int fumi_hip_cos_cls_head_step(fumi_ws_t* ws, fumi_stream_t stream, int M, int F, int C,
         const float* feats, const int64_t* y_a, const int64_t* y_b, float lam, float smoothing,
