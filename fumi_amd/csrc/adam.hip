@@ -245,11 +245,13 @@ int step_now(fumi_ws* ws, hipStream_t st, int rule, int n_tensors, float* const*
 }
 int step_later(fumi_ws* ws, int rule, int n_tensors, float* const* params, const float* const* grads, float* const* s0,
                float* const* s1, const long* numel_host, const OptCoef& c) {
-    if (!ws->adam) { ws->adam = new AdamPending(); ws->adam->on = 0; }
-    const int rc = optim_fill(ws->adam, rule, n_tensors, MAX_FOLD, params, grads, s0, s1, numel_host);
+    AdamPending ap{};                             // filled aside: a refused call leaves a step that is already pending as it was
+    const int rc = optim_fill(&ap, rule, n_tensors, MAX_FOLD, params, grads, s0, s1, numel_host);
     if (rc) return rc;
-    ws->adam->c = c;
-    ws->adam->on = 1;
+    ap.c = c;
+    ap.on = 1;
+    if (!ws->adam) ws->adam = new AdamPending();
+    *ws->adam = ap;
     return FUMI_OK;
 }
 
