@@ -178,6 +178,14 @@ class HipEngine:
         return hip.euclid_proto_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, alpha, need_grad=need_grad, grad_scale=grad_scale,
                                      want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dalpha=dalpha, n_way=n_way)
 
+    def match_head_step(self, feats_s, y_s, feats_q, y_q, tau, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                        dfeats_q=None, dtau=None, n_way=None):
+        """Fused Matching Networks head with the temperature tau [1] on the device: mean cross-entropy of the
+        per-class log attention mass of tau * cos(query, support row) over all query rows, its predictions and the gradients for both
+        feature sets and tau."""
+        return hip.match_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, tau, need_grad=need_grad, grad_scale=grad_scale,
+                                   want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau, n_way=n_way)
+
     def feat_adapt_fwd(self, feats_s, y_s, w, n_way=None, keep_tape=False):
         """Set-to-set prototype adaptation (FEAT): (adapted prototypes [B,N,F], tape | None) of the class means
         of feats_s through one self-attention block, a residual and a LayerNorm; w = (wqkv, wo, bo, ln_weight, ln_bias)."""

@@ -52,6 +52,7 @@ SYMBOLS = [
     "fumi_hip_cos_cls_head_step",
     "fumi_hip_feat_adapt_tape_floats", "fumi_hip_feat_adapt_fwd", "fumi_hip_feat_adapt_bwd",
     "fumi_hip_resnet12_encode_drop", "fumi_hip_resnet12_encode_bwd_drop", "fumi_hip_rn12_drop_apply",
+    "fumi_hip_match_head_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -274,6 +275,7 @@ def lib():
         L.fumi_hip_cos_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_euclid_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_match_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_feat_adapt_tape_floats.argtypes = [c_int] * 3
         L.fumi_hip_feat_adapt_tape_floats.restype = c_int64
         L.fumi_hip_feat_adapt_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 9
@@ -1961,6 +1963,26 @@ def euclid_proto_step(ws, feats_s, y_s, feats_q, y_q, alpha, *, need_grad=True, 
     lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
     _check(lib().fumi_hip_euclid_proto_step(ws.handle, _stream(dev), *lead, _f32(alpha, "alpha"), float(grad_scale), *tail, *grads),
            "fumi_hip_euclid_proto_step")
+    return out
+
+
+def match_head_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad_scale=1.0, want_logits=False, dfeats_s=None,
+                    dfeats_q=None, dtau=None, n_way=None):
+    """The fused Matching Networks head (csrc/matchhead.hip): per episode a query row of feats_q [B,Qn,F] attends over the individual
+    rows of feats_s [B,S,F] at tau * cos(query, support row); the logit of class n is the log-sum-exp of those scores over the support
+    rows with y_s == n (the log of the attention mass on the class, up to the row's normaliser), mean softmax cross-entropy against y_q
+    [B,Qn] over all B * Qn rows.  ``tau`` is a GPU tensor [1] (the kernels read it on the device); ``n_way`` defaults to
+    int(y_s.max()) + 1, which synchronises -- callers that know N pass it.  A class without a support row has the logit -inf and a
+    query row labelled with it is left out (FUMI_ST_CLASS_MISSING).  Returns a dict of GPU tensors: loss [1], correct [1] (count, float),
+    preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without want_logits) and, with need_grad, dfeats_s [B,S,F], dfeats_q [B,Qn,F],
+    dtau [1] = gradients of grad_scale * loss (written into the tensors given, else into new ones)."""
+    dev, dims, out = _episode_head_io("match_head_step", feats_s, y_s, feats_q, y_q, n_way, want_logits,
+                                                               param=(tau, (1,), "tau"))
+    B, S, Qn, N, F = dims
+    grads = _head_grads(dev, need_grad, out, dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q), dtau=((1,), dtau))
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    _check(lib().fumi_hip_match_head_step(ws.handle, _stream(dev), *lead, _f32(tau, "tau"), float(grad_scale), *tail, *grads),
+           "fumi_hip_match_head_step")
     return out
 
 

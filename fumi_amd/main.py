@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.drop_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.match_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -191,7 +191,7 @@ def check_supported(args):
     if not temp > 0.0:
         raise ValueError(f"--metric_temp {temp} must be positive")
     head, r_lam, r_scale = (getattr(args, k, d) for k, d in (("fewshot_head", "cosine"), ("ridge_lambda", 50.0), ("ridge_scale", 1.0)))
-    if head in ("ridge", "proto", "svm") and family != "metabaseline":
+    if head in ("ridge", "proto", "svm", "matching") and family != "metabaseline":
         raise ValueError(f"--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: {head} needs --model metabaseline")
     if not r_lam > 0.0:
         raise ValueError(f"--ridge_lambda {r_lam} must be positive")
@@ -243,6 +243,20 @@ def check_supported(args):
     t_steps = getattr(args, "transductive_steps", 0)
     if not 0 <= t_steps <= 100:
         raise ValueError(f"--transductive_steps {t_steps} must lie in [0, 100]")
+    if head == "matching" or metric == "matching":
+        # the limits of fumi_hip_match_head_step (csrc/matchhead.hip): a tile's scores against every support row are held in LDS
+        S = args.num_ways * args.num_shots
+        if not 1 <= S <= 512:
+            raise NotImplementedError(f"the matching head holds a query tile's scores against every support row in LDS: S = --num_ways * "
+                                      f"--num_shots = {S} must lie in [1, 512]")
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the matching head takes 2 to 64 classes, got --num_ways {args.num_ways}")
+        if t_steps > 0:
+            raise ValueError("--fewshot_head matching / --pretrain_metric matching attends over the support rows and has no class "
+                             f"prototypes for the transductive refinement to move: --transductive_steps must be 0, got {t_steps}")
+        if getattr(args, "fewshot_adapt", "none") == "feat":
+            raise ValueError("--fewshot_head matching attends over the support rows and has no class prototypes for --fewshot_adapt "
+                             "feat to adapt: it goes with --fewshot_adapt none")
     if t_steps > 0:
         if family not in ("metabaseline", "pretrain"):
             raise ValueError("--transductive_steps refines the class prototypes of a nearest-centroid few-shot evaluation: it needs "

@@ -22,6 +22,12 @@ parameter ``svm = [logit scale]`` in ``temp``'s place; ``C``, ``eps`` and the tw
 as ``utils.svm_config`` returns it: the head has no silent defaults).  The largest KKT
 residual and conjugate-gradient residual of the last training step are kept on the device (``svm_stats``) and logged at each validation.
 
+``head="matching"`` (``--fewshot_head matching``) is Matching Networks (Vinyals et al. 2016, without the
+full-context embeddings): ``match_head_step`` (csrc/matchhead.hip).  A query attends over the individual support rows at
+``temp * cos(query, support row)`` and a class's logit is the log of the attention mass on it.  It owns ``temp`` exactly as the cosine
+head does (same parameter, initial value and ``state_dict`` key) and coincides with it at one shot per class.  There are no class
+prototypes, so it takes neither ``adapt="feat"`` nor ``transductive_steps > 0``.
+
 ``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
 head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
 not a parameter: ``state_dict`` is the same either way.
@@ -83,13 +89,16 @@ class MetaBaseline(nn.Module):
         self.drop_step = 0                     # the training loop's step index: the mask seed and the annealed rate follow it
         if adapt not in ("none", "feat"):
             raise ValueError(f"the prototype adaptation must be none or feat, got {adapt}")
+        if adapt == "feat" and head == "matching":
+            raise ValueError("the prototype adaptation (adapt=feat) moves class prototypes: the matching head attends over the support "
+                             "rows and has none")
         if adapt == "feat" and (head not in ("cosine", "proto") or eval_head == "logreg" or int(transductive_steps) > 0):
             raise ValueError("the prototype adaptation goes with the cosine and the prototypical head, the training head at evaluation "
                              f"and no transductive refinement, got head {head}, evaluation head {eval_head}, {transductive_steps} "
                              "transductive steps")
         self.adapt = adapt
-        if head not in ("cosine", "ridge", "proto", "svm"):
-            raise ValueError(f"the few-shot head must be cosine, ridge, proto or svm, got {head}")
+        if head not in ("cosine", "ridge", "proto", "svm", "matching"):
+            raise ValueError(f"the few-shot head must be cosine, ridge, proto, svm or matching, got {head}")
         if head == "svm" and svm is None:
             raise ValueError("the SVM head takes its hyper-parameters explicitly: svm=dict(C, eps, scale, steps, bwd_steps) "
                              "(utils.svm_config fills in the defaults of the flags)")
@@ -109,6 +118,9 @@ class MetaBaseline(nn.Module):
             raise ValueError(f"a fixed scale belongs to the prototypical head, got head {head}")
         if not 0 <= int(transductive_steps) <= 100:
             raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
+        if int(transductive_steps) > 0 and head == "matching":
+            raise ValueError("the transductive refinement (transductive_steps > 0) moves class prototypes: the matching head attends "
+                             "over the support rows and has none")
         if int(transductive_steps) > 0 and (head in ("ridge", "svm") or eval_head == "logreg"):
             raise ValueError("the transductive refinement moves class prototypes: it goes with the cosine and the prototypical head, "
                              f"got head {head}, evaluation head {eval_head}")
@@ -233,6 +245,8 @@ class MetaBaseline(nn.Module):
         elif self.head == "svm":
             out = eng.svm_head_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dscale=g_t[0], n_way=N, **self._svm_kw())
             self.svm_stats = out["stats"].amax(dim=0)
+        elif self.head == "matching":
+            out = eng.match_head_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
         else:
             out = eng.cos_proto_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0, dtau=g_t[0], n_way=N)
         dfeats_s = out["dfeats_s"]
@@ -271,7 +285,8 @@ class MetaBaseline(nn.Module):
         if self.head == "svm":
             out = eng.svm_head_step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N, **self._svm_kw())
             return _loss_acc(out, y_q)
-        step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step"}.get(self.head, "cos_proto_step"))
+        step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step",
+                             "matching": "match_head_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
         return _loss_acc(out, y_q)
 

@@ -65,11 +65,11 @@ class Pretrain(nn.Module):
         self.last_out = None                               # the head's output dict of the last training step
         object.__setattr__(self, "_teacher", None)         # (conv module, [W_t, b_t]) once loaded: frozen, outside parameters() / state_dict()
         self._tcache = None
-        if metric not in ("euclidean", "cosine", "ridge", "logreg", "svm"):
-            raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge, logreg or svm, got {metric}")
+        if metric not in ("euclidean", "cosine", "ridge", "logreg", "svm", "matching"):
+            raise ValueError(f"the few-shot metric must be euclidean, cosine, ridge, logreg, svm or matching, got {metric}")
         if not 0 <= int(transductive_steps) <= 100:
             raise ValueError(f"the transductive refinement takes 0 to 100 steps, got {transductive_steps}")
-        if int(transductive_steps) > 0 and metric in ("ridge", "logreg", "svm"):
+        if int(transductive_steps) > 0 and metric in ("ridge", "logreg", "svm", "matching"):
             raise ValueError(f"the transductive refinement moves class prototypes: it goes with the euclidean and the cosine metric, got {metric}")
         self.transductive_steps = int(transductive_steps)   # soft k-means steps of the few-shot evaluation (section 36; 0: inductive)
         self._one = None
@@ -262,7 +262,8 @@ class Pretrain(nn.Module):
         With ``metric == "cosine"``: one forward call of the fused cosine head (cos_proto_step) at the fixed temperature; with
         ``metric == "ridge"``: one forward call of the ridge-regression head (ridge_head_step) at the fixed ridge weight and scale; with
         ``metric == "logreg"``: one forward call of the logistic-regression head (logreg_head_step) at the fixed hyper-parameters; with
-        ``metric == "svm"``: one forward call of the MetaOptNet-SVM head (svm_head_step) at the fixed C, eps, scale and step count.
+        ``metric == "svm"``: one forward call of the MetaOptNet-SVM head (svm_head_step) at the fixed C, eps, scale and step count; with
+        ``metric == "matching"``: one forward call of the Matching Networks head (match_head_step) at the fixed temperature.
         With ``transductive_steps > 0``: one call of the transductive head (trans_proto_step), cosine at the fixed temperature or
         squared Euclidean at scale 1."""
         eng = _engine.get_engine()
@@ -284,10 +285,11 @@ class Pretrain(nn.Module):
                 scale, trans_metric = self._one, "euclid"
             out = eng.trans_proto_step(f_s, y_s, f_q, y_q, scale, metric=trans_metric, steps=self.transductive_steps, n_way=N)
             return _loss_acc(out, y_q)
-        if self.metric == "cosine":
+        if self.metric in ("cosine", "matching"):
             if self._tau is None or self._tau.device != f_s.device:
                 self._tau = torch.tensor([self.metric_temp], device=f_s.device, dtype=torch.float32)
-            out = eng.cos_proto_step(f_s, y_s, f_q, y_q, self._tau, need_grad=False, n_way=N)
+            step = eng.match_head_step if self.metric == "matching" else eng.cos_proto_step
+            out = step(f_s, y_s, f_q, y_q, self._tau, need_grad=False, n_way=N)
             return _loss_acc(out, y_q)
         if self.metric == "ridge":
             if self._ridge is None or self._ridge.device != f_s.device:

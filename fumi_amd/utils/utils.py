@@ -197,6 +197,17 @@ def drop_parser():
     return p
 
 
+def match_parser():
+    """``drop_parser()`` with the choice ``matching`` of --fewshot_head and of --pretrain_metric (the Matching Networks head, DESIGN.md
+    section 47): what ``main.parse_args`` reads.  ``drop_parser()`` keeps the flag sequence and the choices the regulariser was written
+    against."""
+    p = drop_parser()
+    for act in p._actions:
+        if act.dest in ("fewshot_head", "pretrain_metric"):
+            act.choices = list(act.choices) + ["matching"]
+    return p
+
+
 def drop_config(args):
     """None (--drop_rate 0), or the keyword arguments of ``resnet12.DropSchedule`` from an argparse namespace."""
     if not getattr(args, "drop_rate", 0.0) > 0.0:

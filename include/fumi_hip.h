@@ -691,6 +691,34 @@ int fumi_hip_cos_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, i
 int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* alpha, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dalpha);
+/* The Matching Networks head with a learned temperature (csrc/matchhead.hip): Vinyals et al. 2016 without the
+ * full-context embeddings, in the slot of fumi_hip_cos_proto_step.  A query attends over the individual support rows, not over class
+ * means.  Per episode b, with norm(x) = x / max(|x|_2, 1e-12) (F.normalize) and a support row valid when its label is in [0,N):
+ *     cos[q,i] = <norm(feats_q[b,q]), norm(feats_s[b,i])>,   a[q,i] = tau * cos[q,i],
+ *     z[q,n] = logsumexp over the valid rows i with y_s == n of a[q,i]     (the class maximum is subtracted before exp),
+ * loss [1] = mean over all B * Qn query rows of the softmax cross-entropy of z against y_q, which is the Matching Networks negative
+ * log-likelihood -log sum_{i: y_i = y_q} softmax_i(a[q,:]); preds [B,Qn] = first arg-max of z (may be NULL), correct [1] = number of
+ * rows with preds == y_q (float), logits [B,Qn,N] = z (may be NULL).  z is formed per class from the class's own maximum, never as the
+ * log of a sum of globally normalised probabilities: a class far below the row's best keeps a finite, accurate logit.  tau [1] is read
+ * from DEVICE memory: it is a parameter the optimizer updates, no host synchronisation is needed.
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dtau [1] = gradients of grad_scale * loss (written, not accumulated) -- all three given (training
+ * form) or all three NULL (forward form: loss, correct, preds and logits are bit-identical to the training form's).  With gs =
+ * grad_scale / (B Qn), p[q,i] the softmax of a over all valid rows and r[q,i] the softmax within the class y_q (zero outside it):
+ *     da[q,i] = gs (p[q,i] - r[q,i])        (each row of da sums to zero),        dtau = sum da * cos,
+ *     dfeats_q = rq (G_q - norm(f_q) <norm(f_q), G_q>),   G_q = tau sum_i da[q,i] norm(x_i),
+ *     dfeats_s = rs (G_i - norm(x_i) <norm(x_i), G_i>),   G_i = tau sum_q da[q,i] norm(f_q),
+ * rq, rs the reciprocal clamped norms.  Where a norm is below the clamp the gradient is the plain d / 1e-12, as autograd gives it; the
+ * projection onto the tangent space applies only where the norm is at or above the clamp.
+ * fp32 with fp32 accumulation on v_mfma_f32_16x16x4_f32, three launches (support norms, class counts and status; 16-row query tiles with
+ * the [16,S] scores in LDS; [16 support rows x 128 features] blocks of the support gradient plus the final sums).  ORDER as above.
+ * LABELS as above, with one difference the method forces: a class without a valid support row has no zero prototype -- there is no row
+ * to attend to -- so z = -inf for it (it carries no mass and is never predicted unless the whole row is NaN), and a query row
+ * labelled with such a class is left out exactly like a query label outside [0,N).  A row of NaNs predicts class 0.
+ * B >= 1, 1 <= S <= 512, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048: FUMI_ENOTSUP otherwise; FUMI_EINVAL for
+ * a NULL required pointer or for one or two of the three gradient pointers; both before any launch. */
+int fumi_hip_match_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau);
 /* The ridge-regression few-shot head with a backward (csrc/ridgehead.hip): the closed-form base learner of R2-D2
  * and of MetaOptNet's ridge head, in the slot of fumi_hip_cos_proto_step.  params [2] = (rho, alpha) is read from DEVICE memory (both
  * are parameters the optimizer updates); lam = exp(rho) is the ridge weight, alpha the logit scale.  Per episode b, with X = feats_s[b]
