@@ -186,6 +186,15 @@ class HipEngine:
         return hip.match_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, tau, need_grad=need_grad, grad_scale=grad_scale,
                                    want_logits=want_logits, dfeats_s=dfeats_s, dfeats_q=dfeats_q, dtau=dtau, n_way=n_way)
 
+    def relation_head_step(self, feats_s, y_s, feats_q, y_q, params, loss="mse", need_grad=True, grad_scale=1.0, want_logits=False,
+                           want_hidden=False, dfeats_s=None, dfeats_q=None, g_w=None, n_way=None):
+        """Fused Relation Network head with the relation module's tensors params = (w1 [2,H,F], b1, w2 [H], b2 [1]) on the device
+        (DESIGN.md section 51): the ``mse`` or ``ce`` loss of z[q,n] = w2 . relu(W1s mean_n + b1 + W1q query) + b2 over all query rows,
+        its predictions and the gradients for both feature sets and the four tensors (into ``g_w`` where given)."""
+        return hip.relation_head_step(self._ws(feats_s), feats_s, y_s, feats_q, y_q, params, loss=loss, need_grad=need_grad,
+                                      grad_scale=grad_scale, want_logits=want_logits, want_hidden=want_hidden, dfeats_s=dfeats_s,
+                                      dfeats_q=dfeats_q, g_w=g_w, n_way=n_way)
+
     def feat_adapt_fwd(self, feats_s, y_s, w, n_way=None, keep_tape=False):
         """Set-to-set prototype adaptation (FEAT): (adapted prototypes [B,N,F], tape | None) of the class means
         of feats_s through one self-attention block, a residual and a LayerNorm; w = (wqkv, wo, bo, ln_weight, ln_bias)."""

@@ -53,6 +53,7 @@ SYMBOLS = [
     "fumi_hip_feat_adapt_tape_floats", "fumi_hip_feat_adapt_fwd", "fumi_hip_feat_adapt_bwd",
     "fumi_hip_resnet12_encode_drop", "fumi_hip_resnet12_encode_bwd_drop", "fumi_hip_rn12_drop_apply",
     "fumi_hip_match_head_step",
+    "fumi_hip_relation_head_step",
 ]
 
 ST_LABEL_RANGE, ST_CLASS_MISSING, ST_SYNC_TIMEOUT, ST_NOT_POSDEF = 1, 2, 4, 8
@@ -276,6 +277,8 @@ def lib():
         L.fumi_hip_ridge_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_euclid_proto_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
         L.fumi_hip_match_head_step.argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5 + [c_float] + [c_void_p] * 7
+        L.fumi_hip_relation_head_step.argtypes = ([c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 8 + [c_int, c_float]
+                                                  + [c_void_p] * 12)
         L.fumi_hip_feat_adapt_tape_floats.argtypes = [c_int] * 3
         L.fumi_hip_feat_adapt_tape_floats.restype = c_int64
         L.fumi_hip_feat_adapt_fwd.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 9
@@ -1983,6 +1986,49 @@ def match_head_step(ws, feats_s, y_s, feats_q, y_q, tau, *, need_grad=True, grad
     lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
     _check(lib().fumi_hip_match_head_step(ws.handle, _stream(dev), *lead, _f32(tau, "tau"), float(grad_scale), *tail, *grads),
            "fumi_hip_match_head_step")
+    return out
+
+
+RELATION_PARAMS = ("w1", "b1", "w2", "b2")      # the relation module's tensors, in the order of the entry's arguments
+RELATION_LOSSES = {"ce": 0, "mse": 1}
+
+
+def relation_head_step(ws, feats_s, y_s, feats_q, y_q, params, *, loss="mse", need_grad=True, grad_scale=1.0, want_logits=False,
+                       want_hidden=False, dfeats_s=None, dfeats_q=None, g_w=None, n_way=None):
+    """The fused Relation Network head (csrc/relationhead.hip): per episode the class means c_n of feats_s
+    [B,S,F] by y_s [B,S], U = W1s c_n + b1, V = W1q feats_q [B,Qn,F], logits z[q,n] = w2 . relu(U[n] + V[q]) + b2 -- the relation
+    module Linear(2F,H) -> ReLU -> Linear(H,1) on (class mean, query) without the concatenation.  ``params`` = (w1 [2,H,F], b1 [H],
+    w2 [H], b2 [1]) on the device; ``loss`` is ``mse`` (the paper's: mean over B * Qn * N of (sigmoid(z) - onehot)^2) or ``ce`` (softmax
+    cross-entropy over the classes, mean over B * Qn); ``n_way`` defaults to int(y_s.max()) + 1, which synchronises.  Returns a dict of
+    GPU tensors: loss [1], correct [1] (count, float), preds [B,Qn] (first arg-max), logits [B,Qn,N] (None without want_logits), with
+    want_hidden hid_s [B,N,H] = U and hid_q [B,Qn,H] = V (the mask of the backward is hid_s + hid_q > 0 in fp32), and, with need_grad,
+    dfeats_s [B,S,F], dfeats_q [B,Qn,F], dw1, db1, dw2, db2 = gradients of grad_scale * loss.  ``g_w`` = four caller-owned tensors
+    (slices of a flat buffer) that receive dw1, db1, dw2, db2 in place."""
+    if loss not in RELATION_LOSSES:
+        raise FumiHipError(f"relation_head_step: loss must be mse or ce, got {loss}")
+    if len(params) != len(RELATION_PARAMS):
+        raise FumiHipError(f"relation_head_step: params = ({', '.join(RELATION_PARAMS)}) expected, got {len(params)} tensors")
+    if params[0].dim() != 3:
+        raise FumiHipError("relation_head_step: w1 [2,H,F] expected")
+    dev, dims, out = _episode_head_io("relation_head_step", feats_s, y_s, feats_q, y_q, n_way, want_logits)
+    B, S, Qn, N, F = dims
+    H = int(params[0].shape[1])
+    shapes = ((2, H, F), (H,), (H,), (1,))
+    for t, shape, nm in zip(params, shapes, RELATION_PARAMS):
+        _shape(t, shape, nm)
+    out["hid_s"] = torch.empty(B, N, H, device=dev, dtype=torch.float32) if want_hidden else None
+    out["hid_q"] = torch.empty(B, Qn, H, device=dev, dtype=torch.float32) if want_hidden else None
+    if g_w is not None and len(g_w) != len(RELATION_PARAMS):
+        raise FumiHipError(f"relation_head_step: g_w: {len(RELATION_PARAMS)} tensors expected, got {len(g_w)}")
+    given = dict(dfeats_s=((B, S, F), dfeats_s), dfeats_q=((B, Qn, F), dfeats_q))
+    for i, (shape, nm) in enumerate(zip(shapes, RELATION_PARAMS)):
+        given["d" + nm] = (shape, g_w[i] if g_w is not None else None)
+    grads = _head_grads(dev, need_grad, out, **given)
+    lead, tail = _episode_head_args(dims, feats_s, y_s, feats_q, y_q, out)
+    hid = tuple(_f32(out[k], k) if want_hidden else None for k in ("hid_s", "hid_q"))
+    _check(lib().fumi_hip_relation_head_step(ws.handle, _stream(dev), *lead[:5], H, *lead[5:],
+                                             *(_f32(t, nm) for t, nm in zip(params, RELATION_PARAMS)), RELATION_LOSSES[loss],
+                                             float(grad_scale), *tail, *hid, *grads), "fumi_hip_relation_head_step")
     return out
 
 

@@ -149,7 +149,7 @@ def main(args):
 def parse_args(argv=None):
     """Flags -> args (+ args.device, fumi/main.py:141-149).  Pure: nothing here touches the engine, so host-only users of the parser
     (tools, tests, a dry run on a login node) get the same namespace the reference builds."""
-    args = utils.match_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    args = utils.relation_parser().parse_args(sys.argv[1:] if argv is None else argv)
     use_gpu = (not args.disable_cuda) and torch.cuda.is_available()
     local = int(os.environ.get("LOCAL_RANK", "0"))
     args.device = torch.device("cuda", local) if use_gpu else torch.device("cpu")
@@ -191,7 +191,7 @@ def check_supported(args):
     if not temp > 0.0:
         raise ValueError(f"--metric_temp {temp} must be positive")
     head, r_lam, r_scale = (getattr(args, k, d) for k, d in (("fewshot_head", "cosine"), ("ridge_lambda", 50.0), ("ridge_scale", 1.0)))
-    if head in ("ridge", "proto", "svm", "matching") and family != "metabaseline":
+    if head in ("ridge", "proto", "svm", "matching", "relation") and family != "metabaseline":
         raise ValueError(f"--fewshot_head chooses the episodic classifier of the Meta-Baseline stage: {head} needs --model metabaseline")
     if not r_lam > 0.0:
         raise ValueError(f"--ridge_lambda {r_lam} must be positive")
@@ -257,6 +257,28 @@ def check_supported(args):
         if getattr(args, "fewshot_adapt", "none") == "feat":
             raise ValueError("--fewshot_head matching attends over the support rows and has no class prototypes for --fewshot_adapt "
                              "feat to adapt: it goes with --fewshot_adapt none")
+    r_hid, r_loss = getattr(args, "relation_hidden", 256), getattr(args, "relation_loss", "mse")
+    if head != "relation" and (r_hid != 256 or r_loss != "mse"):
+        raise ValueError("--relation_hidden / --relation_loss set the Relation Network head: they need --fewshot_head relation")
+    if head == "relation":
+        # the limits of fumi_hip_relation_head_step (csrc/relationhead.hip)
+        if r_loss not in ("mse", "ce"):
+            raise ValueError(f"--relation_loss {r_loss} must be mse or ce")
+        if t_steps > 0:
+            raise ValueError("--fewshot_head relation scores (class mean, query) pairs with a learned module and has no metric for the "
+                             f"transductive refinement to move prototypes in: --transductive_steps must be 0, got {t_steps}")
+        if getattr(args, "fewshot_adapt", "none") == "feat":
+            raise ValueError("--fewshot_head relation does not take adapted prototypes: it goes with --fewshot_adapt none, not "
+                             "--fewshot_adapt feat")
+        if r_hid % 32 != 0 or not 32 <= r_hid <= 1024:
+            raise NotImplementedError(f"the relation head takes a hidden width in multiples of 32 from 32 to 1024, got --relation_hidden "
+                                      f"{r_hid}")
+        if not 2 <= args.num_ways <= 64:
+            raise NotImplementedError(f"the relation head takes 2 to 64 classes, got --num_ways {args.num_ways}")
+        S = args.num_ways * args.num_shots
+        if not 1 <= S <= 1024:
+            raise NotImplementedError(f"the relation head stages an episode's support labels in LDS: S = --num_ways * --num_shots = {S} "
+                                      "must lie in [1, 1024]")
     if t_steps > 0:
         if family not in ("metabaseline", "pretrain"):
             raise ValueError("--transductive_steps refines the class prototypes of a nearest-centroid few-shot evaluation: it needs "

@@ -28,6 +28,13 @@ full-context embeddings): ``match_head_step`` (csrc/matchhead.hip).  A query att
 head does (same parameter, initial value and ``state_dict`` key) and coincides with it at one shot per class.  There are no class
 prototypes, so it takes neither ``adapt="feat"`` nor ``transductive_steps > 0``.
 
+``head="relation"`` (``--fewshot_head relation``) is the Relation Network (Sung et al. 2018) in its feature-vector
+form: ``relation_head_step`` (csrc/relationhead.hip) scores every (class mean, query) pair with the learned module Linear(2F, H) -> ReLU
+-> Linear(H, 1).  The model owns the submodule ``relation`` with ``w1 [2,H,F]``, ``b1``, ``w2 [H]``, ``b2 [1]`` (``state_dict`` keys
+``relation.*``) and no ``temp``; the four tensors join the flat gradient buffer in front of the backbone, as ``feat.*`` do.
+``relation=dict(hidden, loss)`` chooses H and the loss (``mse``, the paper's, or ``ce``).  It takes neither ``adapt="feat"`` nor
+``transductive_steps > 0``.
+
 ``eval_head="logreg"`` (``--eval_head logreg``) classifies validation and test episodes with the logistic-regression
 head fitted on the backbone features (``logreg_head_step``, csrc/logreghead.hip); training keeps the model's own head.  It is a choice,
 not a parameter: ``state_dict`` is the same either way.
@@ -77,10 +84,32 @@ class FeatAdapt(nn.Module):
         return [self.wqkv, self.wo, self.bo, self.ln_weight, self.ln_bias]
 
 
+class RelationModule(nn.Module):
+    """The parameters of the relation module at feature width F and hidden width H, in torch's [out, in] layout with nn.Linear's default
+    initialisation of the two layers: ``w1 [2,H,F]`` (block 0 applied to the class mean, block 1 to the query) and ``b1 [H]`` uniform in
+    +-1/sqrt(2F), ``w2 [H]`` and ``b2 [1]`` uniform in +-1/sqrt(H)."""
+
+    def __init__(self, F, H):
+        super().__init__()
+        if F % 32 != 0 or not 32 <= F <= 2048:
+            raise ValueError(f"the relation head takes feature widths in multiples of 32 from 32 to 2048, got {F}")
+        if H % 32 != 0 or not 32 <= H <= 1024:
+            raise ValueError(f"the relation head takes hidden widths in multiples of 32 from 32 to 1024, got {H}")
+        k1, k2 = 1.0 / math.sqrt(2.0 * F), 1.0 / math.sqrt(float(H))
+        self.w1 = nn.Parameter(torch.empty(2, H, F).uniform_(-k1, k1))
+        self.b1 = nn.Parameter(torch.empty(H).uniform_(-k1, k1))
+        self.w2 = nn.Parameter(torch.empty(H).uniform_(-k2, k2))
+        self.b2 = nn.Parameter(torch.empty(1).uniform_(-k2, k2))
+
+    def tensors(self):
+        """In the order of the engine's arguments (hip.RELATION_PARAMS)."""
+        return [self.w1, self.b1, self.w2, self.b2]
+
+
 class MetaBaseline(nn.Module):
     def __init__(self, im_encoder, image_size=84, image_channels=3, num_ways=None, init_temp=10.0, head="cosine", ridge_lambda=50.0,
                  ridge_scale=1.0, eval_head="train", logreg=None, proto_scale=1.0, proto_scale_fixed=False, transductive_steps=0,
-                 svm=None, adapt="none", drop=None):
+                 svm=None, adapt="none", drop=None, relation=None):
         super().__init__()
         if drop is not None and im_encoder != "resnet12":
             raise NotImplementedError("DropBlock / dropout on the block outputs is built into the ResNet-12 encoder pair: drop= needs "
@@ -92,13 +121,23 @@ class MetaBaseline(nn.Module):
         if adapt == "feat" and head == "matching":
             raise ValueError("the prototype adaptation (adapt=feat) moves class prototypes: the matching head attends over the support "
                              "rows and has none")
+        if adapt == "feat" and head == "relation":
+            raise ValueError("the prototype adaptation (adapt=feat) goes with the cosine and the prototypical head: the relation head "
+                             "does not take adapted prototypes")
         if adapt == "feat" and (head not in ("cosine", "proto") or eval_head == "logreg" or int(transductive_steps) > 0):
             raise ValueError("the prototype adaptation goes with the cosine and the prototypical head, the training head at evaluation "
                              f"and no transductive refinement, got head {head}, evaluation head {eval_head}, {transductive_steps} "
                              "transductive steps")
         self.adapt = adapt
-        if head not in ("cosine", "ridge", "proto", "svm", "matching"):
-            raise ValueError(f"the few-shot head must be cosine, ridge, proto, svm or matching, got {head}")
+        if head not in ("cosine", "ridge", "proto", "svm", "matching", "relation"):
+            raise ValueError(f"the few-shot head must be cosine, ridge, proto, svm, matching or relation, got {head}")
+        if relation is not None and head != "relation":
+            raise ValueError(f"relation= sets the relation head, got head {head}")
+        rel = dict(hidden=256, loss="mse")
+        rel.update(relation or {})
+        if set(rel) != {"hidden", "loss"} or rel["loss"] not in ("mse", "ce"):
+            raise ValueError(f"relation=dict(hidden, loss) with loss mse or ce expected, got {relation}")
+        self.relation_loss = rel["loss"]
         if head == "svm" and svm is None:
             raise ValueError("the SVM head takes its hyper-parameters explicitly: svm=dict(C, eps, scale, steps, bwd_steps) "
                              "(utils.svm_config fills in the defaults of the flags)")
@@ -121,6 +160,9 @@ class MetaBaseline(nn.Module):
         if int(transductive_steps) > 0 and head == "matching":
             raise ValueError("the transductive refinement (transductive_steps > 0) moves class prototypes: the matching head attends "
                              "over the support rows and has none")
+        if int(transductive_steps) > 0 and head == "relation":
+            raise ValueError("the transductive refinement (transductive_steps > 0) moves class prototypes in a metric: the relation "
+                             "head's comparison is learned and has none")
         if int(transductive_steps) > 0 and (head in ("ridge", "svm") or eval_head == "logreg"):
             raise ValueError("the transductive refinement moves class prototypes: it goes with the cosine and the prototypical head, "
                              f"got head {head}, evaluation head {eval_head}")
@@ -144,6 +186,8 @@ class MetaBaseline(nn.Module):
             self.ridge = nn.Parameter(torch.tensor([math.log(float(ridge_lambda)), float(ridge_scale)]))
         elif head == "svm":
             self.svm = nn.Parameter(torch.tensor([self.svm_cfg["scale"]]))
+        elif head == "relation":
+            self.relation = RelationModule(self.conv.feature_dim, int(rel["hidden"]))
         elif head == "proto" and self.proto_scale_fixed:
             self.register_buffer("proto_scale", torch.tensor([float(proto_scale)]))
         elif head == "proto":
@@ -158,6 +202,9 @@ class MetaBaseline(nn.Module):
         self._arange = None
 
     def _feat_tensors(self):
+        """The tensors the model owns beside the head's scalar and the backbone: ``feat.*`` or ``relation.*`` (never both)."""
+        if self.head == "relation":
+            return self.relation.tensors()
         return self.feat.tensors() if self.adapt == "feat" else []
 
     def _class_labels(self, B, N, device):
@@ -175,6 +222,8 @@ class MetaBaseline(nn.Module):
         ``proto_scale`` [1] of the prototypical head -- None where that scale is fixed (a buffer: the head has no parameter then)."""
         if self.head == "proto":
             return None if self.proto_scale_fixed else self.proto_scale
+        if self.head == "relation":
+            return None
         if self.head == "svm":
             return self.svm
         return self.ridge if self.head == "ridge" else self.temp
@@ -186,7 +235,8 @@ class MetaBaseline(nn.Module):
         if c is None or not c[0].valid() or (self.proto_scale_fixed and c[1] is not self._buffers["proto_scale"]):
             th, hp = self.conv.theta(), self.head_param()
             own = ([] if hp is None else [hp]) + self._feat_tensors()
-            c = self._pcache = (ParamWatch(self, own + th), self._buffers["proto_scale"] if hp is None else hp.detach(),
+            scale = hp.detach() if hp is not None else None if self.head == "relation" else self._buffers["proto_scale"]
+            c = self._pcache = (ParamWatch(self, own + th), scale,
                                 [p.detach() for p in th], [p.detach() for p in self._feat_tensors()])
             self._flat = None
         fg = None
@@ -196,7 +246,7 @@ class MetaBaseline(nn.Module):
                 hp = self.head_param()
                 fg = self._flat = FlatGrads(([] if hp is None else [hp]) + self._feat_tensors() + self.conv.theta(), extra=2)
                 # the fixed scale has no slot in the flat buffer: its gradient is written beside it and read by nobody
-                self._dscale = torch.empty(1, device=fg.flat.device, dtype=torch.float32) if hp is None else None
+                self._dscale = torch.empty(1, device=fg.flat.device, dtype=torch.float32) if self.proto_scale_fixed else None
         return c[1], c[2], fg
 
     def _apply(self, fn, recurse=True):
@@ -232,12 +282,15 @@ class MetaBaseline(nn.Module):
         else:
             f_s, f_q = encode(x_s, x_q, theta, keep_tape=True)
         featw = self._pcache[3]                 # [] without the adaptation
-        g_t, g_theta = fg.split((0 if self.proto_scale_fixed else 1) + len(featw))   # g_t: [head parameter | feat.*]
+        g_t, g_theta = fg.split((0 if self.head_param() is None else 1) + len(featw))   # g_t: [head parameter | feat.* or relation.*]
         h_s, h_y, tape = f_s, y_s, None         # what the head takes for its support set
         if self.adapt == "feat":                # the adapted prototypes, an N-way 1-shot support set with labels 0..N-1
             h_s, tape = eng.feat_adapt_fwd(f_s, y_s, featw, n_way=N, keep_tape=True)
             h_y = self._class_labels(h_s.shape[0], N, h_s.device)
-        if self.head == "proto":
+        if self.head == "relation":
+            out = eng.relation_head_step(h_s, h_y, f_q, y_q, featw, loss=self.relation_loss, need_grad=True, grad_scale=1.0, g_w=g_t,
+                                         n_way=N)
+        elif self.head == "proto":
             out = eng.euclid_proto_step(h_s, h_y, f_q, y_q, temp, need_grad=True, grad_scale=1.0,
                                         dalpha=self._dscale if self.proto_scale_fixed else g_t[0], n_way=N)
         elif self.head == "ridge":
@@ -285,6 +338,9 @@ class MetaBaseline(nn.Module):
         if self.head == "svm":
             out = eng.svm_head_step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N, **self._svm_kw())
             return _loss_acc(out, y_q)
+        if self.head == "relation":
+            out = eng.relation_head_step(f_s, y_s, f_q, y_q, self._pcache[3], loss=self.relation_loss, need_grad=False, n_way=N)
+            return _loss_acc(out, y_q)
         step = getattr(eng, {"ridge": "ridge_head_step", "proto": "euclid_proto_step",
                              "matching": "match_head_step"}.get(self.head, "cos_proto_step"))
         out = step(f_s, y_s, f_q, y_q, temp, need_grad=False, n_way=N)
@@ -313,6 +369,8 @@ def head_log(model):
     trans = {"transductive_steps": model.transductive_steps} if getattr(model, "transductive_steps", 0) > 0 else {}
     if model.head == "proto":
         return {"proto_scale": float(model.proto_scale.detach()), **trans}
+    if model.head == "relation":
+        return {"relation_w2_norm": float(model.relation.w2.detach().norm())}
     if model.head == "svm":
         log = {"svm_scale": float(model.svm.detach())}
         if model.svm_stats is not None:

@@ -208,6 +208,33 @@ def match_parser():
     return p
 
 
+_RELATION_FLAGS = [         # the Relation Network head; a list of its own that relation_parser() appends to match_parser()'s
+    ("--relation_hidden", dict(type=int, default=256, help="[--fewshot_head relation] hidden width H of the relation module Linear(2F, H) -> ReLU -> Linear(H, 1) (a multiple of 32 from 32 to 1024)")),
+    ("--relation_loss", dict(type=str, choices=["mse", "ce"], default="mse", help="[--fewshot_head relation] the training loss: mse regresses sigmoid(score) onto the one-hot label (the paper's), ce is the softmax cross-entropy of the scores over the classes")),
+]
+
+
+def relation_parser():
+    """``match_parser()`` with the choice ``relation`` of --fewshot_head (not of --pretrain_metric: a classifier pre-training has no
+    relation module to evaluate with) and after every flag of it the --relation_* flags (the Relation Network head, DESIGN.md section
+    51): what ``main.parse_args`` reads.  ``match_parser()`` keeps the flag sequence and the choices the matching head was written
+    against."""
+    p = match_parser()
+    for act in p._actions:
+        if act.dest == "fewshot_head":
+            act.choices = list(act.choices) + ["relation"]
+    for flag, kw in _RELATION_FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
+def relation_config(args):
+    """None (another head), or ``MetaBaseline``'s ``relation=`` dict (hidden, loss) from an argparse namespace."""
+    if getattr(args, "fewshot_head", "cosine") != "relation":
+        return None
+    return dict(hidden=int(getattr(args, "relation_hidden", 256)), loss=str(getattr(args, "relation_loss", "mse")))
+
+
 def drop_config(args):
     """None (--drop_rate 0), or the keyword arguments of ``resnet12.DropSchedule`` from an argparse namespace."""
     if not getattr(args, "drop_rate", 0.0) > 0.0:
@@ -300,7 +327,8 @@ def init_model(args, dictionary, watch=True):
                                           transductive_steps=getattr(args, "transductive_steps", 0),
                                           svm=svm_config(args) if getattr(args, "fewshot_head", "cosine") == "svm" else None,
                                           **(dict(adapt="feat") if getattr(args, "fewshot_adapt", "none") == "feat" else {}),
-                                          **(dict(drop=drop_config(args)) if drop_config(args) else {}))
+                                          **(dict(drop=drop_config(args)) if drop_config(args) else {}),
+                                          **(dict(relation=relation_config(args)) if relation_config(args) else {}))
     elif args.model == "clip":
         model = clip.CLIP(text_input_dim=args.text_emb_dim, image_input_dim=args.im_emb_dim, latent_dim=args.clip_latent_dim)
     else:

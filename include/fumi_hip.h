@@ -719,6 +719,47 @@ int fumi_hip_euclid_proto_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S
 int fumi_hip_match_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F,
         const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* tau, float grad_scale,
         float* loss, float* correct, int64_t* preds, float* logits, float* dfeats_s, float* dfeats_q, float* dtau);
+/* The Relation Network head (csrc/relationhead.hip): Sung et al. 2018 in the feature-vector form of the relation
+ * module, Linear(2F,H) -> ReLU -> Linear(H,1) on the concatenation (class mean, query), which is never formed.  It is the one episode
+ * head that owns weight TENSORS, all read from device memory in torch's [out, in] layout: w1 [2,H,F] (block 0 = W1s, applied to the class
+ * mean; block 1 = W1q, applied to the query), b1 [H], w2 [H], b2 [1].  Per episode b, with c_n the mean of the valid support rows of
+ * class n (count clamped to >= 1, the sums in the order of fumi_hip_proto_reduce):
+ *     U[n,:] = W1s c_n + b1,   V[q,:] = W1q feats_q[b,q],   z[q,n] = w2 . relu(U[n,:] + V[q,:]) + b2.
+ * loss_kind 1 (mse, the paper's loss): loss [1] = 1 / (B Qn N) * sum over the valid query rows and the N classes of
+ * (sigmoid(z[q,n]) - onehot(y_q)[n])^2, and with s = sigmoid(z), t the one-hot target, dz = grad_scale * 2 / (B Qn N) * (s - t) s (1 - s).
+ * loss_kind 0 (ce, Chen et al. 2019): loss [1] = mean over all B * Qn rows of the softmax cross-entropy of z over the N classes,
+ * dz = grad_scale / (B Qn) * (softmax - onehot).  In both, preds [B,Qn] = first arg-max of z (may be NULL), correct [1] = number of rows
+ * with preds == y_q (float), logits [B,Qn,N] = z (may be NULL); hid_s [B,N,H] = U and hid_q [B,Qn,H] = V (either may be NULL).
+ * dfeats_s [B,S,F], dfeats_q [B,Qn,F], dw1 [2,H,F], db1 [H], dw2 [H], db2 [1] = gradients of grad_scale * loss (written, not
+ * accumulated) -- all six given (training form) or all six NULL (forward form: loss, correct, preds, logits, hid_s and hid_q are
+ * bit-identical to the training form's).  With the mask m[q,n,h] = (U[n,h] + V[q,h] > 0):
+ *     dV[q,h] = w2[h] sum_n dz[q,n] m,   dU[n,h] = w2[h] sum_q dz[q,n] m,   dw2[h] = sum_{b,q,n} dz relu(U + V),   db2 = sum dz,
+ *     db1 = column sum of dU over all B N rows,   dW1q = dV^T F_q over all B Qn rows,   dW1s = dU^T C over all B N rows,
+ *     dfeats_q = dV W1q,   dc = dU W1s,   every valid support row of class n receives dc_n / count_n.
+ * THE MASK is part of the interface, the ReLU's kink being the one place where fp32 and a float64 restatement may legitimately
+ * disagree: it is fl32(U[n,h] + V[q,h]) > 0, ONE fp32 addition of the stored fp32 U and V, in the forward and in the backward.  A
+ * correctly rounded sum keeps the sign of the exact sum, so the mask can be rebuilt exactly from hid_s and hid_q.
+ * fp32 throughout; U, V and the five products of the backward on the dense GEMM (v_mfma_f32_32x32x2_f32), the pair terms on the VALU.
+ * Launches: class means, counts and status; U; V; 16-row query tiles that walk H in chunks of 128 with the episode's U chunk [N,128]
+ * and the tile's V chunk [16,128] in LDS (z, the loss, and in the training form dz and dV); training form only: one workgroup per
+ * (group of episodes, 128 hidden units) for dU, dw2 and db1 over all Qn rows (three fixed levels: 8 rows, 64 rows, the blocks) with the
+ * mask rebuilt from U and V, then
+ * dfeats_q, dc, dW1q, dW1s (the last two split over their rows into at most 8 slabs and summed in slab order where the rows are
+ * many); last, the scatter of dc to the support rows and the final sums.  5 launches in the forward form, 10 to 12 in the training form.
+ * Workspace, in floats, M = B Qn: B N F + B N + 3 ceil-tiles + (B N H without hid_s) + (M H without hid_q); training form in addition
+ * M N + M H + B N H + B N F + 2 min(B,256) H + the slabs, at most 4 M floats each.  No mask and no per-tile [N,H] image is stored: at
+ * M = 65536, N = 64, H = 1024 the terms in M are 0.54 GB against the 1 GB such an image would take, and 17 MB at H = 32.
+ * ORDER as above, the sums across query tiles (dU) and across episodes (dw1, db1, dw2, db2) included.  LABELS as above: a support row
+ * left out is written as a zero row of dfeats_s; a class without a support row has a zero prototype, so U[n,:] = b1.  A row of NaNs
+ * predicts class 0.
+ * B >= 1, 1 <= S <= 1024, Qn >= 1, B * Qn <= 65536, 2 <= N <= 64, F % 32 == 0, 32 <= F <= 2048, H % 32 == 0, 32 <= H <= 1024,
+ * loss_kind 0 or 1: FUMI_ENOTSUP otherwise; FUMI_EINVAL for a NULL required pointer or for one to five of the six gradient pointers;
+ * both before any launch, nothing is written. */
+int fumi_hip_relation_head_step(fumi_ws_t* ws, fumi_stream_t stream, int B, int S, int Qn, int N, int F, int H,
+        const float* feats_s, const int64_t* y_s, const float* feats_q, const int64_t* y_q, const float* w1, const float* b1,
+        const float* w2, const float* b2, int loss_kind, float grad_scale,
+        float* loss, float* correct, int64_t* preds, float* logits, float* hid_s, float* hid_q,
+        float* dfeats_s, float* dfeats_q, float* dw1, float* db1, float* dw2, float* db2);
 /* The ridge-regression few-shot head with a backward (csrc/ridgehead.hip): the closed-form base learner of R2-D2
  * and of MetaOptNet's ridge head, in the slot of fumi_hip_cos_proto_step.  params [2] = (rho, alpha) is read from DEVICE memory (both
  * are parameters the optimizer updates); lam = exp(rho) is the ridge weight, alpha the logit scale.  Per episode b, with X = feats_s[b]
